@@ -9,7 +9,7 @@ run before the timed region starts (resident in HBM); the CPU baseline leg draws
 shard by global env index with no data-path collective except the per-step reward/done all-gather the
 north star names (RCCL, async, off the critical path).  Rank 0 prints ONE JSON line.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--envs-per-gpu 4096] [--env KManipSoloArm]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--envs-per-gpu 4096] [--env KManipSoloArm] [--dump-outputs DIR]
 
 `--gpus N` with N > 1 and no RANK in the environment: this process starts N fresh rank processes (one per GPU,
 RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* set) BEFORE touching the GPU, waits for them and exits with their worst
@@ -36,6 +36,7 @@ sys.path.insert(0, ROOT)
 EPISODE = 64                      # MAX_EPISODE_STEPS, gym_kmanip/__init__.py:28
 HBM_PEAK_GBS = 8000.0             # MI355X_MICROARCH.md
 FP64_VECTOR_PEAK_TFLOPS = 78.6    # 256 CU x 4 SIMD x 16 lanes x 2 flop x 2.4 GHz
+DUMP_BUDGET_BYTES = 64 * 10**6    # --dump-outputs: all .npy files of all ranks together
 
 
 def parse_args(argv=None):
@@ -87,7 +88,15 @@ def parse_args(argv=None):
                     help="newton = MuJoCo default, what the reference runs; pgs = the north star's named solver (100 sweeps)")
     ap.add_argument("--no-variants", action="store_true", help="skip the secondary measurements (long window, phase-locked, PGS, chunked, seam, two handles, the other BASELINE configs)")
     ap.add_argument("--chunk", type=int, default=16, help="also time kmanip_step_chunk with this many control steps per launch (0: skip)")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (obs, reward, done, sim_time, and the depth / "
+                         "camera images when the step renders them) as DIR/<name>.npy in float32 / float64, %d MB at most in all: a "
+                         "larger output is a fixed seeded sample of its elements (DIR/manifest.json says which).  N > 1: every rank "
+                         "writes its own shard as <name>.rank<r>.npy" % (DUMP_BUDGET_BYTES // 10**6))
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 # --------------------------------------------------------------------------------------------------------------------
@@ -171,6 +180,36 @@ def kmanip_env_vars():
     """Every KMANIP_* variable set in this process's environment: several change the timed launch's shape (KMANIP_EPB,
     KMANIP_SPREAD*, KMANIP_COST_SORT, ...) though never its results -- the bench line records them (`config.kmanip_env`)."""
     return {k: v for k, v in sorted(os.environ.items()) if k.startswith("KMANIP_") and k != "KMANIP_BENCH_SPAWNED"}
+
+
+def dump_outputs(out_dir, arrays, rank=0, world=1, budget=DUMP_BUDGET_BYTES):
+    """--dump-outputs: write each device tensor of `arrays` (name -> tensor) as out_dir/<name>.npy -- float64 stays float64,
+    everything else becomes float32 -- plus out_dir/manifest.json.  An array larger than its share of `budget` (split evenly over
+    the arrays of all ranks) is written as a sample of its flattened elements: the indices are drawn with NumPy's seed 0 from
+    (element count, sample size) alone, so two builds run with the same arguments write the same elements."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    suffix = ".rank%d" % rank if world > 1 else ""
+    cap = budget // (len(arrays) * world) - 4096          # (4 KB for the .npy header)
+    manifest = {}
+    for name, t in arrays.items():
+        dtype = torch.float64 if t.dtype == torch.float64 else torch.float32
+        item = 8 if dtype == torch.float64 else 4
+        flat = t.detach().reshape(-1)
+        entry = {"shape": list(t.shape), "source_dtype": str(t.dtype).replace("torch.", ""), "sampled_elements": None}
+        if flat.numel() * item <= cap:
+            host = flat.to(dtype).cpu().numpy().reshape(tuple(t.shape))
+        else:
+            idx = np.sort(np.random.default_rng(0).choice(flat.numel(), cap // item, replace=False))
+            host = flat[torch.from_numpy(idx).to(flat.device)].to(dtype).cpu().numpy()
+            entry["sampled_elements"] = int(idx.size)
+            entry["sample"] = "flat element indices: np.sort(np.random.default_rng(0).choice(%d, %d, replace=False))" % (flat.numel(), idx.size)
+        np.save(os.path.join(out_dir, name + suffix + ".npy"), host)
+        entry["dtype"] = str(host.dtype)
+        manifest[name + suffix] = entry
+    with open(os.path.join(out_dir, "manifest%s.json" % suffix), "w") as f:
+        json.dump(manifest, f, indent=1, sort_keys=True)
 
 
 def free_port():
@@ -770,6 +809,14 @@ def run_rank(args):
             t = torch.tensor([dt], dtype=torch.float64, device="cuda")
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             dt = float(t.item())
+
+    if args.dump_outputs:
+        # what the last timed step returned, before the secondary measurements step this handle further
+        outs = {"obs": env.obs, "reward": env.reward, "done": env.done, "sim_time": env.sim_time}
+        if depth_buf is not None:
+            outs["depth_grip_r"] = depth_buf
+        outs.update(("camera_" + c, b) for c, b in rgb_bufs.items())
+        dump_outputs(args.dump_outputs, outs, rank, world)
 
     if rank == 0:
         version = env.L.kmanip_version().decode()

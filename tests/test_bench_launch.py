@@ -220,3 +220,61 @@ def test_timing_events_are_sampled_on_long_windows_only():
         assert bench.parse_args(["--time-every", "4"]).time_every == 4 and bench.parse_args([]).time_every == 0
     finally:
         bench.TIME_EVERY = old
+
+
+def test_steps_must_be_a_real_count():
+    import bench
+    assert bench.parse_args(["--steps", "7", "--warmup", "0"]).steps == 7
+    for bad in (["--steps", "0"], ["--steps", "-3"], ["--warmup", "-1"]):
+        with pytest.raises(SystemExit):
+            bench.parse_args(bad)
+
+
+def test_dump_outputs_writes_float_arrays_within_budget(tmp_path):
+    """--dump-outputs: float64 stays float64, uint8 / float32 become float32, small arrays are written whole, a large one as the
+    same seeded sample every time, and the files stay inside the budget (64 MB in the bench; a small budget here)."""
+    import numpy as np
+    import torch
+    import bench
+    g = torch.Generator().manual_seed(3)
+    obs = torch.rand((8, 5), dtype=torch.float64, generator=g)
+    done = torch.tensor([0, 1, 0, 0, 1, 0, 0, 1], dtype=torch.uint8)
+    cam = torch.randint(0, 256, (8, 48, 64, 3), dtype=torch.uint8, generator=g)
+    budget = 3 * (4096 + 16 * 1024)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), {"obs": obs, "done": done, "camera_head": cam}, budget=budget)
+    a, b = tmp_path / "a", tmp_path / "b"
+    assert sorted(p.name for p in a.iterdir()) == ["camera_head.npy", "done.npy", "manifest.json", "obs.npy"]
+    assert sum(p.stat().st_size for p in a.glob("*.npy")) <= budget
+    o, dn, c = (np.load(a / n) for n in ("obs.npy", "done.npy", "camera_head.npy"))
+    assert o.dtype == np.float64 and np.array_equal(o, obs.numpy())
+    assert dn.dtype == np.float32 and np.array_equal(dn, done.numpy().astype(np.float32))
+    man = json.load(open(a / "manifest.json"))
+    assert c.dtype == np.float32 and c.ndim == 1 and man["camera_head"]["sampled_elements"] == c.size < cam.numel()
+    assert man["camera_head"]["shape"] == [8, 48, 64, 3] and man["camera_head"]["source_dtype"] == "uint8" and man["obs"]["sampled_elements"] is None
+    idx = np.sort(np.random.default_rng(0).choice(cam.numel(), c.size, replace=False))
+    assert np.array_equal(c, cam.numpy().reshape(-1)[idx].astype(np.float32))
+    assert np.array_equal(c, np.load(b / "camera_head.npy"))              # the same elements on every run
+    bench.dump_outputs(str(tmp_path / "r"), {"obs": obs}, rank=1, world=2)
+    assert sorted(p.name for p in (tmp_path / "r").iterdir()) == ["manifest.rank1.json", "obs.rank1.npy"]
+
+
+@pytest.mark.gpu
+def test_dump_outputs_is_the_last_timed_step_and_repeats(tmp_path):
+    """Two runs with the same arguments dump the same arrays bit for bit; a run with 3 more timed steps leaves every env's
+    episode clock (sim_time = step in episode x CONTROL_TIMESTEP) exactly 3 steps further on: --steps is the count stepped."""
+    import numpy as np
+    from gym_kmanip_amd.model import CONTROL_TIMESTEP, MAX_EPISODE_STEPS
+    base = ["--envs-per-gpu", "256", "--warmup", "2", "--no-variants", "--no-cpu-baseline"]
+    dumps = {}
+    for tag, k in (("a", 5), ("b", 5), ("c", 8)):
+        r = _run(base + ["--steps", str(k), "--dump-outputs", str(tmp_path / tag)])
+        assert r.returncode == 0, r.stderr[-2000:]
+        assert json.loads(r.stdout.strip().splitlines()[-1])["steps"] == k
+        dumps[tag] = {p.name: np.load(p) for p in (tmp_path / tag).glob("*.npy")}
+    assert sorted(dumps["a"]) == ["done.npy", "obs.npy", "reward.npy", "sim_time.npy"]
+    for name, v in dumps["a"].items():
+        assert v.dtype in (np.float32, np.float64) and np.isfinite(v).all(), name
+        assert np.array_equal(v, dumps["b"][name]), name
+    step_a, step_c = (np.rint(dumps[t]["sim_time.npy"] / CONTROL_TIMESTEP).astype(np.int64) for t in ("a", "c"))
+    assert np.array_equal((step_c - step_a) % MAX_EPISODE_STEPS, np.full(256, 3)), (step_a[:8], step_c[:8])

@@ -3,10 +3,13 @@
 
 BUILD CONTAINER ONLY (needs /root/reference; nothing from it is copied -- the outputs are data: inputs + expected outputs).
     python tests/tools/make_golden_ref.py
+    python tests/tools/make_golden_ref.py --check      (regenerate a slice and compare it with the committed files)
 
 Files (all under tests/golden/):
   ref_spaces.json          for the eight registered ids: the kwargs the reference registers (__init__.py:244-483), the
                            observation / action spaces KManipEnv builds (env_base.py:115-190), info keys, camera list
+  ref_instances.json       for the eight registered ids: the reference's KManipEnv instance as env_sim.new sees it -- class,
+                           value and Python type of every attribute the sim reads, the attributes it lacks, the Dict spaces
   ref_run_<id>.npz         one rollout of the reference's KManipEnv.reset()/step() per id: per step the state before the
                            step, the flat float32 action, what before_step left (ctrl handed to set_control, qpos after the
                            IK's teleport, mocap goal pose, nfev/status of each least_squares call) and what k_step returned
@@ -107,6 +110,33 @@ def gen_spaces():
     consts["OBS_DTYPE"], consts["ACT_DTYPE"] = str(np.dtype(k.OBS_DTYPE)), str(np.dtype(k.ACT_DTYPE))
     with open(os.path.join(OUT, "ref_spaces.json"), "w") as f:
         json.dump(dict(envs=out, constants=consts), f, indent=1)       # (insertion order of the space Dicts is data: no sort_keys)
+    return out
+
+
+SEAM_ATTRS = ("mjcf_filename", "obs_list", "act_list", "q_pos_home", "q_len", "q_id_r_mask", "q_id_l_mask",
+              "ctrl_id_r_grip", "ctrl_id_l_grip", "seed")       # what env_sim.py:23-211 reads from gym_env (besides `cameras`)
+
+
+def gen_instances():
+    """The reference's own KManipEnv instance of each registered id, as env_sim.new(self) sees it: the class, the value AND the
+    Python type (tuple / list / ndarray + dtype / None) of every attribute the sim reads, which attributes it lacks, and its Dict
+    spaces in insertion order.  tests/test_seam_reference_object.py rebuilds a stand-in with exactly these types."""
+    refrun.install()
+    out = {}
+    for env_id in refrun.REGISTRY:
+        with quiet():
+            env = refrun.make_env(env_id)
+        attrs = {}
+        for a in SEAM_ATTRS:
+            v = getattr(env, a)
+            attrs[a] = dict(type=type(v).__name__, dtype=str(v.dtype) if isinstance(v, np.ndarray) else None, value=jsonable(v))
+        out[env_id] = dict(
+            cls="%s:%s" % (type(env).__module__, type(env).__name__), attrs=attrs,
+            absent=[a for a in ("env_id",) if not hasattr(env, a)],
+            action_space=[[n, list(s.shape), str(s.dtype)] for n, s in env.action_space.spaces.items()],
+            observation_space=[[n, list(s.shape), str(s.dtype)] for n, s in env.observation_space.spaces.items()])
+    with open(os.path.join(OUT, "ref_instances.json"), "w") as f:
+        json.dump(out, f, indent=1)
     return out
 
 
@@ -405,10 +435,49 @@ PLANS = {"KManipSoloArm": [64, 16], "KManipSoloArmQPos": [40], "KManipSoloArmVis
          "KManipDualArm": [64, 8], "KManipDualArmQPos": [40], "KManipDualArmVision": [2],
          "KManipTorso": [64, 8], "KManipTorsoVision": [2]}
 
+
+def check_committed():
+    """Staleness guard: regenerate a slice with the reference's Python (into a scratch directory) and compare it with the
+    committed fixtures.  Needs the reference checkout, so it is a tool and not part of the test suite."""
+    import tempfile
+    global OUT
+    golden, OUT = OUT, tempfile.mkdtemp()
+
+    def ref(name):
+        return np.load(os.path.join(golden, name))
+    try:
+        fresh = gen_ik("KManipSoloArm", n_cases=12)
+        old = ref("ref_ik_solo.npz")
+        for k in fresh:
+            assert np.array_equal(fresh[k], old[k][:12]), k
+        fresh = gen_run("KManipSoloArmQPos", [6], seed=101)
+        old = ref("ref_run_KManipSoloArmQPos.npz")
+        for k in ("action", "ctrl_set", "post_qpos", "obs", "reward"):
+            assert np.array_equal(fresh[k], old[k][:6]), k
+        # the reference's own logger tree and its scripted episode, regenerated (3 steps) against the committed 64-step run
+        tree, fresh = gen_h5_scripted("KManipSoloArm", nstep=3)
+        old_tree = json.load(open(os.path.join(golden, "ref_h5_tree_KManipSoloArm.json")))
+        assert tree["tree"] == old_tree["tree"] and tree["file"] == old_tree["file"]
+        old = ref("ref_scripted_KManipSoloArm.npz")
+        for k in ("raw_action", "action", "post_qpos", "reward", "h5/action"):
+            assert np.array_equal(fresh[k][:3], old[k][:3]), k
+        assert np.array_equal(fresh["success_reward"], old["success_reward"])
+        assert gen_instances() == json.load(open(os.path.join(golden, "ref_instances.json")))
+    finally:
+        import shutil
+        shutil.rmtree(OUT, ignore_errors=True)
+        OUT = golden
+    print("committed fixtures match the reference")
+
+
 if __name__ == "__main__":
+    if sys.argv[1:] == ["--check"]:
+        check_committed()
+        sys.exit(0)
     os.makedirs(OUT, exist_ok=True)
     sp = gen_spaces()
     print("ref_spaces.json:", list(sp))
+    print("ref_instances.json:", list(gen_instances()))
     for i, (env_id, plan) in enumerate(PLANS.items()):
         r = gen_run(env_id, plan, seed=100 + i)
         print("ref_run_%s: %d steps, mean nfev %s, contacts in %d steps" % (
