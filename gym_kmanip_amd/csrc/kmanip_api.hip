@@ -51,6 +51,11 @@ struct KHandle_ {
   unsigned disp_k = 0;
   int wave_slots = 0;           // entries of st.wave_clk (one per lane group of the step launch's grid)
   int last_epb = 0;             // envs per wave of the LAST step launch (a chunk launch always takes the full shape): what the slot -> env maps of kmanip_dbg_wave_clocks are rebuilt with
+  // per-env physics parameters (kmanip_set_env_params): allocated by the first call that needs them; st.envp / st.ep_range
+  // point at them while explicit values / ranges mode are in force
+  double* envp_buf = nullptr;       // [KM_EP_N][N]
+  double* ep_range_buf = nullptr;   // lo[KM_EP_N], hi[KM_EP_N]
+  int* ep_flag = nullptr;           // validation result of kmanip_set_env_params
   std::vector<void*> allocs;
 };
 
@@ -198,6 +203,32 @@ static int build_aux(const KModelDesc* d, KModelAux* x, std::string& err) {
 extern "C" {
 
 int kmanip_model_desc_size(void) { return (int)sizeof(KModelDesc); }
+
+// ---- per-env physics parameters (include/kmanip.h KM_EP_*)
+// robot part of trace(M(qpos0)), in the order model.py with_env_params restates (no contraction: the host rounds every operation)
+static double trace_robot_of(const KModelDesc& d) {
+#pragma clang fp contract(off)
+  const double nv = d.nlink + 6;
+  return d.meaninertia * nv - (3.0 * d.cube_mass + ((d.cube_inertia[0] + d.cube_inertia[1]) + d.cube_inertia[2]));
+}
+// the limits every parameter value must meet (the ranges' lo and hi as well)
+__host__ __device__ static inline bool ep_value_ok(int k, double v) {
+  if (!(v - v == 0.0)) return false;           // NaN or infinite (host and device alike)
+  return (k == KM_EP_CUBE_MASS || k == KM_EP_KP_SCALE) ? v > 0 : v >= 0;
+}
+__global__ void k_ep_validate(const double* __restrict__ p, int n, int* __restrict__ bad) {
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+    bool ok = true;
+    for (int k = 0; k < KM_EP_N; k++) ok = ok && ep_value_ok(k, p[(size_t)k * n + i]);
+    if (!ok) atomicOr(bad, 1);
+  }
+}
+__global__ void k_ep_fill(double* __restrict__ p, int n, double v0, double v1, double v2, double v3) {
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+    p[i] = v0; p[(size_t)n + i] = v1; p[2 * (size_t)n + i] = v2; p[3 * (size_t)n + i] = v3;
+  }
+}
+static int ep_grid(int n) { return (n + 255) / 256 < 1024 ? (n + 255) / 256 : 1024; }
 const char* kmanip_version(void) { return KM_VERSION; }
 
 int kmanip_create(const KModelDesc* desc, int num_envs, int device, uint64_t seed, int64_t env_id_offset, KHandle* out) {
@@ -210,6 +241,7 @@ int kmanip_create(const KModelDesc* desc, int num_envs, int device, uint64_t see
   KDeviceModel hm;
   hm.d = *desc;
   if (validate(desc, h->err) != 0 || build_aux(desc, &hm.x, h->err) != 0) { g_create_error = h->err; delete h; return -2; }
+  hm.trace_robot = trace_robot_of(*desc);
   int ndev = 0;
   hipError_t e = hipGetDeviceCount(&ndev);
   if (e != hipSuccess || ndev <= 0 || device >= ndev) {
@@ -671,6 +703,88 @@ int kmanip_select_reward_done_record(KHandle h, int index) {
   if (!h) return -1;
   if (index < 0 || index > 1 || !h->rd_rec[0]) { h->err = "kmanip_select_reward_done_record: index 0 / 1 of two bound buffers"; return -1; }
   h->rd_sel = index;
+  return 0;
+}
+
+// the compiled model's values (mass, tangential cube friction, cube frictionloss, kp scale 1) into p [KM_EP_N][N]
+static void ep_fill_model(KHandle h, double* p, hipStream_t stream) {
+  const KModelDesc& d = h->desc;
+  hipLaunchKernelGGL(k_ep_fill, dim3(ep_grid(h->num_envs)), dim3(256), 0, stream, p, h->num_envs, d.cube_mass, d.con_cube_friction[0],
+                     d.cube_frictionloss, 1.0);
+}
+static hipError_t ep_alloc(KHandle h) {
+  auto one = [&](void** p, size_t bytes) -> hipError_t {
+    if (*p) return hipSuccess;
+    hipError_t r = hipMalloc(p, bytes);
+    if (r == hipSuccess) h->allocs.push_back(*p);
+    return r;
+  };
+  hipError_t r = one((void**)&h->envp_buf, sizeof(double) * KM_EP_N * (size_t)h->num_envs);
+  if (r == hipSuccess) r = one((void**)&h->ep_range_buf, sizeof(double) * 2 * KM_EP_N);
+  if (r == hipSuccess) r = one((void**)&h->ep_flag, sizeof(int));
+  return r;
+}
+
+int kmanip_set_env_params(KHandle h, const double* params_dev, void* stream) {
+  if (!h) return -1;
+  KM_ENTER(h);
+  if (!params_dev) { h->st.envp = nullptr; h->st.ep_range = nullptr; return 0; }
+  hipStream_t s = (hipStream_t)stream;
+  HIPCHK(h, ep_alloc(h));
+  int bad = 0;
+  HIPCHK(h, hipMemsetAsync(h->ep_flag, 0, sizeof(int), s));
+  hipLaunchKernelGGL(k_ep_validate, dim3(ep_grid(h->num_envs)), dim3(256), 0, s, params_dev, h->num_envs, h->ep_flag);
+  HIPCHK(h, hipGetLastError());
+  HIPCHK(h, hipMemcpyAsync(&bad, h->ep_flag, sizeof(int), hipMemcpyDeviceToHost, s));
+  HIPCHK(h, hipStreamSynchronize(s));
+  if (bad) {
+    h->err = "kmanip_set_env_params: every env needs cube mass > 0, cube friction >= 0, cube frictionloss >= 0, kp scale > 0, all finite";
+    return -2;
+  }
+  // the parameter buffer may be read by a step in flight on any stream (as in kmanip_set_env_param_ranges)
+  HIPCHK(h, hipDeviceSynchronize());
+  HIPCHK(h, hipMemcpy(h->envp_buf, params_dev, sizeof(double) * KM_EP_N * (size_t)h->num_envs, hipMemcpyDeviceToDevice));
+  HIPCHK(h, hipDeviceSynchronize());
+  h->st.envp = h->envp_buf;
+  h->st.ep_range = nullptr;
+  return 0;
+}
+
+int kmanip_get_env_params(KHandle h, double* params_dev, void* stream) {
+  if (!h || !params_dev) { if (h) h->err = "kmanip_get_env_params: params_dev is NULL"; return -1; }
+  KM_ENTER(h);
+  hipStream_t s = (hipStream_t)stream;
+  if (h->st.envp) HIPCHK(h, hipMemcpyAsync(params_dev, h->st.envp, sizeof(double) * KM_EP_N * (size_t)h->num_envs, hipMemcpyDeviceToDevice, s));
+  else ep_fill_model(h, params_dev, s);
+  HIPCHK(h, hipGetLastError());
+  return 0;
+}
+
+int kmanip_set_env_param_ranges(KHandle h, const double* lo, const double* hi) {
+  if (!h) return -1;
+  if (!lo && !hi) { h->st.ep_range = nullptr; return 0; }
+  if (!lo || !hi) { h->err = "kmanip_set_env_param_ranges: lo and hi must both be NULL or both be set"; return -1; }
+  for (int k = 0; k < KM_EP_N; k++) {
+    if (!ep_value_ok(k, lo[k]) || !ep_value_ok(k, hi[k]) || lo[k] > hi[k]) {
+      h->err = "kmanip_set_env_param_ranges: parameter " + std::to_string(k) + " needs finite lo <= hi within its limits "
+               "(cube mass > 0, cube friction >= 0, cube frictionloss >= 0, kp scale > 0)";
+      return -2;
+    }
+  }
+  KM_ENTER(h);
+  HIPCHK(h, ep_alloc(h));
+  // the range buffer may be read by a step in flight on any stream
+  HIPCHK(h, hipDeviceSynchronize());
+  double r[2 * KM_EP_N];
+  for (int k = 0; k < KM_EP_N; k++) { r[k] = lo[k]; r[KM_EP_N + k] = hi[k]; }
+  HIPCHK(h, hipMemcpy(h->ep_range_buf, r, sizeof r, hipMemcpyHostToDevice));
+  if (!h->st.envp) {          // until an env's next reset it keeps the values in force: the compiled model's
+    ep_fill_model(h, h->envp_buf, nullptr);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipDeviceSynchronize());
+  }
+  h->st.envp = h->envp_buf;
+  h->st.ep_range = h->ep_range_buf;
   return 0;
 }
 

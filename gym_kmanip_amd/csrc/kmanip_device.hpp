@@ -46,6 +46,9 @@ struct KDeviceModel {
   KModelDesc d;
   KModelAux x;
   alignas(16) unsigned char staged[KM_LMODEL_MAX];
+  // robot part of trace(M(qpos0)) for the per-env meaninertia (kmanip_set_env_params): meaninertia * nv - (3 cube_mass +
+  // sum cube_inertia), evaluated on the host at create in that order (model.py with_env_params restates it)
+  double trace_robot;
 };
 
 typedef double real;
@@ -490,7 +493,8 @@ __device__ __host__ inline double u53(uint32_t hi, uint32_t lo) {
 // action_space.sample() of a Box(-1, 1, float32) component from 32 random bits: ((r >> 8) - 2^23) * 2^-23, exact in float32
 // (a 24-bit signed integer times a power of two), so the device and the CPU oracle produce identical bits
 __device__ __host__ inline float km_action_from_u32(uint32_t r) { return (float)((int32_t)(r >> 8) - 8388608) * (1.0f / 8388608.0f); }
-// counter word 3 of the action stream: the cube spawn uses 0 and 1 (reset_env), actions 0x10000 + 4 * step + block
+// counter word 3 of the action stream: the cube spawn uses 0 and 1 (reset_env), the per-env parameter draw of ranges mode
+// KM_EP_CTR3 + 0 and + 1 = 2 and 3 (kmanip.h), actions 0x10000 + 4 * step + block
 #define KM_ACT_CTR3(step, blk) (0x10000u + 4u * (uint32_t)(step) + (uint32_t)(blk))
 
 // Device state, struct-of-arrays over envs: element (k, env) of an [n_k, num_envs] array is at
@@ -534,6 +538,10 @@ struct KDeviceState {
   int32_t* disp_zero;
   int disp_cap;         // at most this many envs are dispatched as heavy (the grid is sized for it); the rest of them as light
   int disp_heavy_epb;   // heavy envs per wave (1 | 2 | 4)
+  // per-env physics parameters (kmanip_set_env_params): double[KM_EP_N][N], NULL = the compiled model (the default kernels);
+  // ep_range: device lo[KM_EP_N], hi[KM_EP_N] of ranges mode (every reset redraws the env's values), NULL = explicit values
+  double* envp;
+  const double* ep_range;
   double control_dt;  // n_sub_steps * timestep
   int num_envs;
   int64_t env_id_offset;

@@ -31,6 +31,21 @@
 //   PGS              : per-contact block form on the 4x4 Gram matrix (algebraically the same row order)
 #include "kmanip_ik_coop.hpp"
 #include <stdlib.h>
+// KM_VAR_PAR=1: the per-env physics parameter build of a variant (kmanip_set_env_params).  The Makefile
+// compiles this file a second time per variant with it; those kernels live in their own namespace and are launched only while a
+// handle has parameters; the default objects take none of the parameter code paths (same instruction counts, registers,
+// scratch and LDS as before).
+#ifndef KM_VAR_PAR
+#define KM_VAR_PAR 0
+#endif
+#if KM_VAR_PAR
+namespace km_envp {
+#define KM_K_STEP k_step_ep           // (kernel names of their own: profiles and tools/kernel_resources.py tell the builds apart)
+#define KM_K_RESET k_reset_ep
+#else
+#define KM_K_STEP k_step
+#define KM_K_RESET k_reset
+#endif
 // tree loops over link candidates (static addresses + a mask bit each): fully unrolled for the 10-link model, where all the
 // loads can be in flight together; the 20-link models sit at the 512-register limit and keep them rolled
 #define KM_TREE_UNROLL(NL) NL <= 10 ? NL : 1
@@ -61,6 +76,15 @@ template <int NL> struct Dim {
 // compile-time kind of contact slot c: 0 = table(plane) - cube corner, 1 = sphere - cube, 2 = table - sphere.  WHICH sphere sits
 // in a sphere slot is decided per sub-step by collide_parallel (Ws::slot_sph).
 template <int NL> __device__ __forceinline__ constexpr int slot_kind(int c) { return c < 4 ? 0 : (c < 4 + Dim<NL>::NSS ? 1 : 2); }
+
+// One env's physics parameters (KM_EP_*) and the constants derived from them (ep_derive), staged in LDS inside its Ws by the
+// KM_VAR_PAR kernels: they replace the wave-uniform reads of the same model quantities (the KM_EP_* accessors below Ws).
+template <int NL> struct EnvP {
+  real p[KM_EP_N];                // cube mass, cube friction, cube frictionloss, kp scale
+  real inertia[3];                // cube_inertia[k] * (mass / cube_mass)
+  real cubew[2], scale, cornerA;  // LModel::cubew / scale / cornerA of this env
+  real sphA[Dim<NL>::NSPH];       // LModel::sphA[0][*] (sphere on the cube) of this env
+};
 
 // Per-link model constants staged in LDS once per workgroup (lane-indexed reads stay on-chip); scalars
 // and small fixed arrays are read straight from the global KModelDesc with wave-uniform (scalar) loads.
@@ -108,7 +132,7 @@ struct ConRec {
   real f[6];       // edge forces
 };
 
-#define KM_WS_PAD(NL) ((NL) <= 10 ? 9 : 1)      // doubles of padding at the end of Ws (see the note on row strides in it)
+#define KM_WS_PAD(NL) ((NL) <= 10 ? (KM_VAR_PAR ? 24 : 9) : 1)      // doubles of padding at the end of Ws (see the note on row strides in it)
 template <int NL>
 struct Ws {
   static constexpr int NV = Dim<NL>::NV, NQ = Dim<NL>::NQ, NS = Dim<NL>::NS, NC = Dim<NL>::NC;
@@ -156,9 +180,36 @@ struct Ws {
   real c_pos[NC][3], c_frame[NC][9], c_dist[NC];
   int slot_sph[NC];        // sphere index held by each active sphere slot (4..NC-1)
   uint32_t slot_anc[NC];   // ... and the ancestor mask of that sphere's link (round 6: the constraint assembly read it through two more dependent loads)
+#if KM_VAR_PAR
+  EnvP<NL> ep;             // this env's physics parameters (per env, never per wave slot)
+#endif
   real pad_[KM_WS_PAD(NL)];
 };
 static_assert(KM_VAR_NL != 10 || KM_VAR_SOLVER != 1 || sizeof(Ws<KM_VAR_NL>) % 256 == 128, "Ws<10>: consecutive envs 128 bytes apart modulo the 256-byte bank row");
+
+// The model quantities an env's parameters change, as the kernels read them: the wave-uniform model values in the default build,
+// the env's own (Ws::ep) in the KM_VAR_PAR build.
+#if KM_VAR_PAR
+#define KM_EP_MASS(w, m) ((w).ep.p[KM_EP_CUBE_MASS])
+#define KM_EP_INERTIA(w, m, k) ((w).ep.inertia[k])
+#define KM_EP_FLOSS(w, m) ((w).ep.p[KM_EP_CUBE_FRICTIONLOSS])
+#define KM_EP_MU(w, m) ((w).ep.p[KM_EP_CUBE_FRICTION])
+#define KM_EP_FRIC_T(w, lm, pset) ((pset) ? (w).ep.p[KM_EP_CUBE_FRICTION] : (lm).fric[0][0])
+#define KM_EP_KP(w, lm, i) ((lm).kp[i] * (w).ep.p[KM_EP_KP_SCALE])
+#define KM_EP_CUBEW(w, lm, k) ((w).ep.cubew[k])
+#define KM_EP_SCALE(w, lm) ((w).ep.scale)
+#define KM_EP_SLOT_A(w, lm, kind, sp) ((kind) == 0 ? (w).ep.cornerA : ((kind) == 2 ? (lm).sphA[1][sp] : (w).ep.sphA[sp]))
+#else
+#define KM_EP_MASS(w, m) ((m)->cube_mass)
+#define KM_EP_INERTIA(w, m, k) ((m)->cube_inertia[k])
+#define KM_EP_FLOSS(w, m) ((m)->cube_frictionloss)
+#define KM_EP_MU(w, m) ((m)->con_cube_friction[0])
+#define KM_EP_FRIC_T(w, lm, pset) ((lm).fric[pset][0])
+#define KM_EP_KP(w, lm, i) ((lm).kp[i])
+#define KM_EP_CUBEW(w, lm, k) ((lm).cubew[k])
+#define KM_EP_SCALE(w, lm) ((lm).scale)
+#define KM_EP_SLOT_A(w, lm, kind, sp) ((kind) == 0 ? (lm).cornerA : (lm).sphA[(kind) == 2][sp])
+#endif
 
 // One-row groups (round 3): lane c < NC OWNS contact slot c for the Newton solve -- its regulariser, friction coefficients and
 // reference offsets live in that lane's registers, the slot's pyramid edges are evaluated there (all slots at once, one per
@@ -190,7 +241,7 @@ template <int NL> struct CReg {
 };
 
 #ifdef KM_PROFILE
-#if KM_VAR_NL == 10 && KM_VAR_SOLVER == 1
+#if KM_VAR_NL == 10 && KM_VAR_SOLVER == 1 && !KM_VAR_PAR
 extern "C" int kmanip_dbg_prof(unsigned long long* out, int reset) {
   if (out && hipMemcpyFromSymbol(out, HIP_SYMBOL(g_prof), sizeof(unsigned long long) * KM_NPH) != hipSuccess) return -1;
   if (reset) { unsigned long long z[KM_NPH] = {0}; if (hipMemcpyToSymbol(HIP_SYMBOL(g_prof), z, sizeof z) != hipSuccess) return -1; }
@@ -201,7 +252,7 @@ extern "C" int kmanip_dbg_prof_blocks(unsigned long long* out, int nblocks) {
   return hipMemcpyFromSymbol(out, HIP_SYMBOL(g_prof_blk), sizeof(unsigned long long) * KM_NPH * 4 * nblocks) == hipSuccess ? 0 : -1;
 }
 #endif
-#if KM_VAR_NL == 20 && KM_VAR_SOLVER == 1
+#if KM_VAR_NL == 20 && KM_VAR_SOLVER == 1 && !KM_VAR_PAR
 extern "C" int kmanip_dbg_prof20(unsigned long long* out, int reset) {          // the DualArm / Torso Newton object's accumulators
   if (out && hipMemcpyFromSymbol(out, HIP_SYMBOL(g_prof), sizeof(unsigned long long) * KM_NPH) != hipSuccess) return -1;
   if (reset) { unsigned long long z[KM_NPH] = {0}; if (hipMemcpyToSymbol(HIP_SYMBOL(g_prof), z, sizeof z) != hipSuccess) return -1; }
@@ -693,10 +744,10 @@ __device__ __forceinline__ void bias_bodies_parallel(Ws<NL>& w, const LModel<NL>
   } else if (sub == NL) {
     // cube (free joint, qvel = [v_world, w_body]): bias = [-m g, w x I w]
     real wv[3] = {w.qvel[NL + 3], w.qvel[NL + 4], w.qvel[NL + 5]};
-    real Iw[3] = {m->cube_inertia[0] * wv[0], m->cube_inertia[1] * wv[1], m->cube_inertia[2] * wv[2]}, t[3];
+    real Iw[3] = {KM_EP_INERTIA(w, m, 0) * wv[0], KM_EP_INERTIA(w, m, 1) * wv[1], KM_EP_INERTIA(w, m, 2) * wv[2]}, t[3];
     cross3(t, wv, Iw);
 #pragma unroll
-    for (int c = 0; c < 3; c++) { w.bias[NL + c] = -m->cube_mass * m->gravity[c]; w.bias[NL + 3 + c] = t[c]; }
+    for (int c = 0; c < 3; c++) { w.bias[NL + c] = -KM_EP_MASS(w, m) * m->gravity[c]; w.bias[NL + 3 + c] = t[c]; }
   }
 }
 
@@ -714,10 +765,10 @@ __device__ __forceinline__ void anc_sum3(uint32_t mask, const real* v, real* s) 
 template <int NL>
 __device__ __forceinline__ void cube_bias(Ws<NL>& w, const KModelDesc* m) {
   real wc[3] = {w.qvel[NL + 3], w.qvel[NL + 4], w.qvel[NL + 5]};
-  real Iw[3] = {m->cube_inertia[0] * wc[0], m->cube_inertia[1] * wc[1], m->cube_inertia[2] * wc[2]}, t[3];
+  real Iw[3] = {KM_EP_INERTIA(w, m, 0) * wc[0], KM_EP_INERTIA(w, m, 1) * wc[1], KM_EP_INERTIA(w, m, 2) * wc[2]}, t[3];
   cross3(t, wc, Iw);
 #pragma unroll
-  for (int c = 0; c < 3; c++) { w.bias[NL + c] = -m->cube_mass * m->gravity[c]; w.bias[NL + 3 + c] = t[c]; }
+  for (int c = 0; c < 3; c++) { w.bias[NL + c] = -KM_EP_MASS(w, m) * m->gravity[c]; w.bias[NL + 3 + c] = t[c]; }
 }
 // W = links per DPP row.  One-row groups: the row holds the whole robot (li = sub, base = 0, W = NL).  Two-row groups with a
 // block split (two-arm models): each row holds one block of the robot -- lane c of a row works on link li = base + c of ITS
@@ -1290,7 +1341,12 @@ __device__ __forceinline__ void build_constraints(Ws<NL>& w, const LModel<NL>& l
       const real* fr = cube ? m->con_cube_friction : m->con_def_friction;
       const real* sr = cube ? m->con_cube_solref : m->con_def_solref;
       const real* si = cube ? m->con_cube_solimp : m->con_def_solimp;
-      real mu[3] = {fr[0], fr[0], fr[1]};
+#if KM_VAR_PAR
+      const real fr0 = cube ? KM_EP_MU(w, m) : fr[0];
+#else
+      const real fr0 = fr[0];
+#endif
+      real mu[3] = {fr0, fr0, fr[1]};
       const real dist = w.c_dist[c];
       real imp = impedance_c(lm.imp[cube ? 1 : 0], dist), kk = lm.kb[cube ? 1 : 0][0], bb = lm.kb[cube ? 1 : 0][1];
       (void)sr; (void)si;
@@ -1305,7 +1361,7 @@ __device__ __forceinline__ void build_constraints(Ws<NL>& w, const LModel<NL>& l
 #pragma unroll
         for (int l = 0; l < 4; l++) Ge[l] = Gm[l][0] + sm * Gm[l][k];        // J_l . M^-1 (J_0 + sm J_k)^T
         const real Ad = Ge[0] + sm * Ge[k];
-        if (e == 0) R = 2 * fr[0] * fr[0] * fmax(MJ_MINVAL, (1 - imp) * frcp(imp) * (kind == 0 ? lm.cornerA : lm.sphA[kind == 2][w.slot_sph[c]]));
+        if (e == 0) R = 2 * fr0 * fr0 * fmax(MJ_MINVAL, (1 - imp) * frcp(imp) * KM_EP_SLOT_A(w, lm, kind, w.slot_sph[c]));
         const real vel = vb[0] + sm * vb[k];
         if (sub == 0) {
           rc.den[e] = Ad + R;
@@ -1345,7 +1401,7 @@ __device__ __forceinline__ real solve_accel(Ws<NL>& w, const LModel<NL>& lm, con
     real rhs = -w.bias[sub];
     if (actuation && sub < NL) {
       real c = fmin(fmax(w.ctrl[sub], lm.ctrlrange[sub][0]), lm.ctrlrange[sub][1]);
-      real force = lm.kp[sub] * c - lm.kp[sub] * w.qpos[sub];
+      real force = KM_EP_KP(w, lm, sub) * c - KM_EP_KP(w, lm, sub) * w.qpos[sub];
       if (lm.forcelimited[sub]) force = fmin(fmax(force, lm.forcerange[sub][0]), lm.forcerange[sub][1]);
       rhs += force;
     }
@@ -1361,12 +1417,12 @@ __device__ __forceinline__ real solve_accel(Ws<NL>& w, const LModel<NL>& lm, con
   const uint32_t act = w.cact;
   const real warm = sub < NV ? w.warm[sub] : 0.0;
   // ---- the cube's friction-loss row owned by this lane (registers only)
-  const bool my_row = sub >= NL && sub < NV && m->cube_frictionloss > 0;
+  const bool my_row = sub >= NL && sub < NV && KM_EP_FLOSS(w, m) > 0;
   real my_f = 0, my_aref = 0, my_R = 1, my_den = 1, my_inv = 0;
-  const real my_fl = m->cube_frictionloss;
+  const real my_fl = KM_EP_FLOSS(w, m);
   if (my_row) {
     real imp = lm.imp0[0], bb = lm.kb[0][1];
-    my_R = fmax(MJ_MINVAL, (1 - imp) * frcp(imp) * lm.cubew[sub < NL + 3 ? 0 : 1]);
+    my_R = fmax(MJ_MINVAL, (1 - imp) * frcp(imp) * KM_EP_CUBEW(w, lm, sub < NL + 3 ? 0 : 1));
     my_den = invm + my_R;
     my_inv = 1.0 / my_den;
     my_aref = -bb * w.qvel[sub];
@@ -1436,7 +1492,7 @@ __device__ __forceinline__ real solve_accel(Ws<NL>& w, const LModel<NL>& lm, con
   // M^-1, so the owning lanes update them locally and simultaneously -- identical to one after another,
   // and no cross-lane traffic.  A row on an arm dof needs one broadcast; a contact needs four DPP row
   // reductions (its basis projections u = J a), then its pyramid edges run on precomputed Gram rows.
-  const real scale = lm.scale;
+  const real scale = KM_EP_SCALE(w, lm);
   const int maxit = m->solver_iterations;
   const real tol = m->solver_tolerance;
   for (int iter = 0; iter < maxit; iter++) {
@@ -1696,7 +1752,7 @@ __device__ __forceinline__ void build_constraints_newton(Ws<NL>& w, const LModel
   // instead of one per input -- the phase was ~30 LDS round trips in a row with one wave per SIMD); the conditions select afterwards.
   const int si = sub < NL ? sub : NL - 1, sv = sub < NV ? sub : NV - 1, ck = ce >= 3 ? ce - 3 : 0;
   const int cs = sub < NC ? sub : NC - 1;                       // the contact slot this lane owns (slot lanes)
-  real dofw = lm.dofw[si], cubew0 = lm.cubew[0], cubew1 = lm.cubew[1], qvs = w.qvel[sv], kk0 = lm.kb[0][0], bb0 = lm.kb[0][1];
+  real dofw = lm.dofw[si], cubew0 = KM_EP_CUBEW(w, lm, 0), cubew1 = KM_EP_CUBEW(w, lm, 1), qvs = w.qvel[sv], kk0 = lm.kb[0][0], bb0 = lm.kb[0][1];
   real floss = lm.floss[si], imp00 = lm.imp0[0], qps = w.qpos[si], rlo = lm.range[si][0], rhi = lm.range[si][1], distc = w.c_dist[cs];
   real ax[3] = {w.k.axis[jl][0], w.k.axis[jl][1], w.k.axis[jl][2]}, xo[3] = {w.k.xpos[jl][0], w.k.xpos[jl][1], w.k.xpos[jl][2]};
   real col0 = w.k.cube_mat[ck], col1 = w.k.cube_mat[3 + ck], col2 = w.k.cube_mat[6 + ck], cpos[3] = {w.qpos[NL], w.qpos[NL + 1], w.qpos[NL + 2]};
@@ -1715,7 +1771,7 @@ __device__ __forceinline__ void build_constraints_newton(Ws<NL>& w, const LModel
     const real Ad = sub < NL ? dofw : (sub < NL + 3 ? cubew0 : cubew1);           // efc_diagApprox (qpos0 constants)
     const real qv = qvs;
     const real kk = kk0, bb = bb0;
-    const real fl = sub < NL ? floss : m->cube_frictionloss;
+    const real fl = sub < NL ? floss : KM_EP_FLOSS(w, m);
     if (fl > 0) {
       const real imp = imp00;
       cr.fl = fl; cr.Rf = fmax(MJ_MINVAL, (1 - imp) * frcp(imp) * Ad); cr.Df = frcp(cr.Rf); cr.areff = -bb * qv;
@@ -1784,8 +1840,8 @@ __device__ __forceinline__ void build_constraints_newton(Ws<NL>& w, const LModel
   // the slot lanes' solver constants: fetched now, while the projections below run (slot `sub` of a slot lane; clamped elsewhere)
   const int kindl = cs < 4 ? 0 : (cs < 4 + Dim<NL>::NSS ? 1 : 2), pset = kindl != 2 ? 1 : 0;
   const int spc = sps < 0 ? 0 : (sps >= NSPH ? NSPH - 1 : sps);            // (an inactive slot's sphere index is stale: clamped, never used)
-  real sA = kindl == 0 ? lm.cornerA : lm.sphA[kindl == 2][spc];            // efc_diagApprox of the first pyramid edge (qpos0 constant; no M^-1 product)
-  real mu_t = lm.fric[pset][0], mu_r = lm.fric[pset][1], kks = lm.kb[pset][0], bbs = lm.kb[pset][1];
+  real sA = KM_EP_SLOT_A(w, lm, kindl, spc);                               // efc_diagApprox of the first pyramid edge (qpos0 constant; no M^-1 product)
+  real mu_t = KM_EP_FRIC_T(w, lm, pset), mu_r = lm.fric[pset][1], kks = lm.kb[pset][0], bbs = lm.kb[pset][1];
   real i_d0 = lm.imp[pset].d0, i_dw = lm.imp[pset].dw, i_iw = lm.imp[pset].iw, i_mid = lm.imp[pset].mid, i_imid = lm.imp[pset].imid, i_i1 = lm.imp[pset].i1mid;
   int i_mode = lm.imp[pset].mode;
   const real qv = sub < NV ? qvs : 0.0;
@@ -2101,7 +2157,7 @@ __device__ __forceinline__ void newton_loop_sl(Ws<NL>& w, const LModel<NL>& lm, 
     slin = pr == KM_SUB_ARM ? (sub >= 4 + NSS && sub < NC) : sub < 4;
   };
   if (JOINT && two) enter(KM_SUB_ARM);
-  const real scale = lm.scale;
+  const real scale = KM_EP_SCALE(w, lm);
   const real tol = m->solver_tolerance;
   const int maxit = m->solver_iterations;
   pf.ph(40);       // (what a group waited for wave-mates that ran a loop it does not -- SIMD divergence -- lands here)
@@ -2424,7 +2480,7 @@ __device__ __forceinline__ real solve_newton(Ws<NL>& w, const LModel<NL>& lm, co
   // ---- actuation and smooth acceleration (as in the PGS path)
   // (round 6) the lane's inputs and its row of M^-1 in one batch in front of the exchange, the right-hand sides in one behind it
   const int si = sub < NL ? sub : NL - 1, sv = sub < NV ? sub : NV - 1;
-  real bia = w.bias[sv], ctl = w.ctrl[si], cr0 = lm.ctrlrange[si][0], cr1 = lm.ctrlrange[si][1], kpv = lm.kp[si], qps = w.qpos[si];
+  real bia = w.bias[sv], ctl = w.ctrl[si], cr0 = lm.ctrlrange[si][0], cr1 = lm.ctrlrange[si][1], kpv = KM_EP_KP(w, lm, si), qps = w.qpos[si];
   real fr0 = lm.forcerange[si][0], fr1 = lm.forcerange[si][1];
   int flim = lm.forcelimited[si];
   real mrow[NL];
@@ -2570,10 +2626,69 @@ __device__ __forceinline__ real lerp_unfused(real lo, real hi, real u) {
   return lo + p;
 }
 
-// initialize_episode (env_sim.py:23-36) + mj_forward without actuation (dm_control after_reset)
+#if KM_VAR_PAR
+// ---- per-env physics parameters.  ONE evaluation order for every derived constant, restated bit for bit by
+// model.py with_env_params (the mass-derived ones without contraction: the host rounds every operation); cornerA / sphA[0] are
+// build_lmodel's expressions, evaluated under the same contraction rules it is compiled with.
+__device__ __forceinline__ real ep_inertia(const KModelDesc* m, real mass, int k) {
+#pragma clang fp contract(off)
+  return m->cube_inertia[k] * (mass / m->cube_mass);
+}
+// cube_invweight0[1] = mean_k 1 / I_k, meaninertia = (trace_robot + 3 m + (I_0 + I_1 + I_2)) / nv (the compiled value while the mass is
+// the model's), as invweight0 in model.py sums them
+__device__ __forceinline__ void ep_mass_consts(const KDeviceModel* dm, real mass, const real (&I)[3], int nv, real& cw1, real& mi) {
+#pragma clang fp contract(off)
+  cw1 = ((1.0 / I[0] + 1.0 / I[1]) + 1.0 / I[2]) / 3.0;
+  mi = mass == dm->d.cube_mass ? dm->d.meaninertia : ((dm->trace_robot + 3.0 * mass) + ((I[0] + I[1]) + I[2])) / nv;
+}
+// this lane's cube diagonal of M^-1 (invm) for parameters p
+template <int NL>
+__device__ __forceinline__ real ep_invm(const KModelDesc* m, const real (&p)[KM_EP_N], int sub) {
+  if (sub < NL || sub >= Dim<NL>::NV) return 0;
+  return sub < NL + 3 ? 1.0 / p[KM_EP_CUBE_MASS] : 1.0 / ep_inertia(m, p[KM_EP_CUBE_MASS], sub - NL - 3);
+}
+// Ws::ep from the raw values p (every lane of the group holds the same p; lane 0 writes the scalars, lane s < NSPH sphA[s]).
+// The caller synchronises the group before the values are read.
+template <int NL>
+__device__ __forceinline__ void ep_derive(Ws<NL>& w, const KDeviceModel* dm, const real (&p)[KM_EP_N], int sub) {
+  const KModelDesc* m = &dm->d;
+  const real mass = p[KM_EP_CUBE_MASS], muc = p[KM_EP_CUBE_FRICTION];
+  const real cw = 1.0 / mass;
+  if (sub == 0) {
+    real I[3] = {ep_inertia(m, mass, 0), ep_inertia(m, mass, 1), ep_inertia(m, mass, 2)}, cw1, mi;
+    ep_mass_consts(dm, mass, I, NL + 6, cw1, mi);
+#pragma unroll
+    for (int k = 0; k < KM_EP_N; k++) w.ep.p[k] = p[k];
+#pragma unroll
+    for (int k = 0; k < 3; k++) w.ep.inertia[k] = I[k];
+    w.ep.cubew[0] = cw; w.ep.cubew[1] = cw1;
+    w.ep.scale = 1.0 / (mi * (NL + 6));
+    w.ep.cornerA = cw + muc * muc * cw;
+  }
+  if (sub < Dim<NL>::NSPH) {
+    const real lw = sub < m->nsphere ? m->body_invweight0[m->sphere_link[sub]][0] : 0.0;
+    w.ep.sphA[sub] = (cw + lw) + muc * muc * (cw + lw);
+  }
+}
+// the env's values in force (KDeviceState::envp) -> Ws::ep and the lane's invm
+template <int NL>
+__device__ __forceinline__ void ep_load(Ws<NL>& w, const KDeviceModel* dm, const KDeviceState& st, int env, int sub, real& invm) {
+  real p[KM_EP_N];
+#pragma unroll
+  for (int k = 0; k < KM_EP_N; k++) p[k] = st.envp[(size_t)k * st.num_envs + env];
+  ep_derive<NL>(w, dm, p, sub);
+  invm = ep_invm<NL>(&dm->d, p, sub);
+}
+#endif
+
+// initialize_episode (env_sim.py:23-36) + mj_forward without actuation (dm_control after_reset).  The KM_VAR_PAR build in ranges
+// mode first draws the env's parameters for the new episode (written back to KDeviceState::envp; invm follows them).
 template <int NL, int G, int SOLVER>
-__device__ __forceinline__ void reset_env(Ws<NL>& w, const LModel<NL>& lm, const KModelDesc* m, int sub, uint64_t seed,
-                                          int64_t genv, int episode, CReg<NL>& cr, real invm, Prof& pf) {
+__device__ __forceinline__ void reset_env(Ws<NL>& w, const LModel<NL>& lm, const KDeviceModel* dm, int sub, const KDeviceState& st,
+                                          int env, int episode, CReg<NL>& cr, real& invm, Prof& pf) {
+  const KModelDesc* m = &dm->d;
+  const uint64_t seed = st.seed;
+  const int64_t genv = st.env_id_offset + env;
   constexpr int NV = Dim<NL>::NV;
   if (sub < NV) { w.qvel[sub] = 0; w.warm[sub] = 0; }
   if (sub < NL) { w.qpos[sub] = lm.q_home[sub]; w.ctrl[sub] = lm.q_home[sub]; }
@@ -2591,6 +2706,25 @@ __device__ __forceinline__ void reset_env(Ws<NL>& w, const LModel<NL>& lm, const
     for (int c = 0; c < 4; c++) w.qpos[NL + 3 + c] = m->cube_quat0[c];
     w.bad = 0;
   }
+#if KM_VAR_PAR
+  if (st.ep_range) {
+    // p_k = lerp(lo_k, hi_k, u_k), u_k from counter word 3 = KM_EP_CTR3 + k / 2: words (0, 1) of the block for even k, (2, 3) for odd k
+    uint32_t key[2] = {(uint32_t)seed, (uint32_t)(seed >> 32)};
+    uint32_t ctr[4] = {(uint32_t)genv, (uint32_t)((uint64_t)genv >> 32), (uint32_t)episode, KM_EP_CTR3}, o[4], o2[4];
+    philox4x32_10(ctr, key, o);
+    ctr[3] = KM_EP_CTR3 + 1;
+    philox4x32_10(ctr, key, o2);
+    const real u[KM_EP_N] = {u53(o[0], o[1]), u53(o[2], o[3]), u53(o2[0], o2[1]), u53(o2[2], o2[3])};
+    real p[KM_EP_N];
+#pragma unroll
+    for (int k = 0; k < KM_EP_N; k++) {
+      p[k] = lerp_unfused(st.ep_range[k], st.ep_range[KM_EP_N + k], u[k]);
+      if (sub == 0) st.envp[(size_t)k * st.num_envs + env] = p[k];
+    }
+    ep_derive<NL>(w, dm, p, sub);
+    invm = ep_invm<NL>(m, p, sub);
+  }
+#endif
   GSYNC();
   step1_products<NL, G, SOLVER>(w, lm, m, sub, cr, invm, pf);
   real a = solve<NL, G, SOLVER>(w, lm, m, sub, 0, cr, invm, pf);
@@ -2740,7 +2874,7 @@ __device__ __forceinline__ real env_reward(Ws<NL>& w, const KModelDesc* m, int s
 // EPB = envs per single-wave workgroup (<= 64 / G).  Fewer envs per wave = more waves per SIMD: the kernel is
 // bound by LDS/dependent-issue latency, so waves of different envs hide each other's waits.
 template <int NL, int G, int SOLVER, int EPB, bool CHUNK>
-__global__ __launch_bounds__(64) void k_step(const KDeviceModel* __restrict__ dm, KDeviceState st, const float* __restrict__ act,
+__global__ __launch_bounds__(64) void KM_K_STEP(const KDeviceModel* __restrict__ dm, KDeviceState st, const float* __restrict__ act,
                                              double* __restrict__ obs, double* __restrict__ reward, uint8_t* __restrict__ done,
                                              int nchunk) {
   constexpr int NV = Dim<NL>::NV, NQ = Dim<NL>::NQ;
@@ -2796,8 +2930,10 @@ __global__ __launch_bounds__(64) void k_step(const KDeviceModel* __restrict__ dm
   stage_model<NL>(lm, dm);
   if (env < 0) return;                                 // whole group exits together
   Ws<NL>& w = ws[grp];
-  real invm = 0;                       // diagonal of M^-1 for the cube dof owned by this lane
+  real invm = 0;                       // diagonal of M^-1 for the cube dof owned by this lane (KM_VAR_PAR: set by ep_load below)
+#if !KM_VAR_PAR
   if (sub >= NL && sub < NV) invm = sub < NL + 3 ? 1.0 / m->cube_mass : 1.0 / m->cube_inertia[sub - NL - 3];
+#endif
   Prof pf;
   pf.start();
   const unsigned long long t_wave0 = st.wave_clk ? __builtin_amdgcn_s_memtime() : 0ull;
@@ -2807,6 +2943,9 @@ __global__ __launch_bounds__(64) void k_step(const KDeviceModel* __restrict__ dm
   { double* wp = reinterpret_cast<double*>(&w); for (int i = sub; i < (int)(sizeof(Ws<NL>) / 8); i += G) wp[i] = KM_DEBUG_NANFILL; GSYNC(); }
 #endif
   init_ws<NL>(w, sub);
+#if KM_VAR_PAR
+  ep_load<NL>(w, dm, st, env, sub, invm);       // (after the diagnostic poisoning above: Ws::ep is part of the workspace)
+#endif
   load_state<NL, G>(w, st, env, sub, fused);
   int step_idx = st.step_idx[env], episode = st.episode[env];
   const size_t NE = (size_t)st.num_envs;
@@ -2902,7 +3041,7 @@ __global__ __launch_bounds__(64) void k_step(const KDeviceModel* __restrict__ dm
     GSYNC();
     pf.ph(31);
     CReg<NL> cr;
-    reset_env<NL, G, SOLVER>(w, lm, m, sub, st.seed, st.env_id_offset + env, episode, cr, invm, pf);
+    reset_env<NL, G, SOLVER>(w, lm, dm, sub, st, env, episode, cr, invm, pf);
     write_obs<NL, G>(w, lm, m, sub, obs_row);
     pf.ph(32);
   }
@@ -2935,9 +3074,11 @@ __global__ __launch_bounds__(64) void k_step(const KDeviceModel* __restrict__ dm
 
 // KManipEnvSim.k_reset for the envs selected by mask (NULL = all)
 template <int NL, int G, int SOLVER, int EPB>
-__global__ __launch_bounds__(64) void k_reset(const KDeviceModel* __restrict__ dm, KDeviceState st,
+__global__ __launch_bounds__(64) void KM_K_RESET(const KDeviceModel* __restrict__ dm, KDeviceState st,
                                               const uint8_t* __restrict__ mask, double* __restrict__ obs) {
+#if !KM_VAR_PAR
   constexpr int NV = Dim<NL>::NV;
+#endif
   __shared__ Ws<NL> ws[EPB];
   __shared__ LModel<NL> lm;
   stage_model<NL>(lm, dm);
@@ -2949,12 +3090,16 @@ __global__ __launch_bounds__(64) void k_reset(const KDeviceModel* __restrict__ d
   Ws<NL>& w = ws[grp];
   CReg<NL> cr;
   real invm = 0;
+#if KM_VAR_PAR
+  ep_load<NL>(w, dm, st, env, sub, invm);
+#else
   if (sub >= NL && sub < NV) invm = sub < NL + 3 ? 1.0 / m->cube_mass : 1.0 / m->cube_inertia[sub - NL - 3];
+#endif
   int episode = st.episode[env] + 1;
   Prof pf;
   pf.start();
   init_ws<NL>(w, sub);
-  reset_env<NL, G, SOLVER>(w, lm, m, sub, st.seed, st.env_id_offset + env, episode, cr, invm, pf);
+  reset_env<NL, G, SOLVER>(w, lm, dm, sub, st, env, episode, cr, invm, pf);
   if (obs) write_obs<NL, G>(w, lm, m, sub, obs + (size_t)env * m->obs_dim);
   if (sub == 0) { st.step_idx[env] = 0; st.episode[env] = episode; st.contact_mask[env] = 0; if (st.sim_time) st.sim_time[env] = 0; }
   GSYNC();
@@ -2996,17 +3141,17 @@ __global__ __launch_bounds__(64) void k_observe(const KDeviceModel* __restrict__
 template <int NL, int G, int SOLVER, int EPB>
 static void launch_step_e(const KDeviceModel* dm, const KDeviceState& st, const float* act, double* obs, double* reward, uint8_t* done, int nchunk, hipStream_t stream) {
   if (nchunk > 1) {
-    if constexpr (EPB == 64 / G) hipLaunchKernelGGL((k_step<NL, G, SOLVER, EPB, true>), dim3((st.num_envs + EPB - 1) / EPB), dim3(64), 0, stream, dm, st, act, obs, reward, done, nchunk);
+    if constexpr (EPB == 64 / G) hipLaunchKernelGGL((KM_K_STEP<NL, G, SOLVER, EPB, true>), dim3((st.num_envs + EPB - 1) / EPB), dim3(64), 0, stream, dm, st, act, obs, reward, done, nchunk);
   } else {
     int grid = (st.num_envs + EPB - 1) / EPB;
     if (st.disp_in && st.disp_heavy_epb > 0)       // room for disp_cap heavy envs at disp_heavy_epb per wave next to the light ones at EPB per wave (surplus workgroups exit at once)
       grid = (st.disp_cap + st.disp_heavy_epb - 1) / st.disp_heavy_epb + (st.num_envs - st.disp_cap + EPB - 1) / EPB + 1;
-    hipLaunchKernelGGL((k_step<NL, G, SOLVER, EPB, false>), dim3(grid), dim3(64), 0, stream, dm, st, act, obs, reward, done, 1);
+    hipLaunchKernelGGL((KM_K_STEP<NL, G, SOLVER, EPB, false>), dim3(grid), dim3(64), 0, stream, dm, st, act, obs, reward, done, 1);
   }
 }
 template <int NL, int G, int SOLVER, int EPB>
 static void launch_reset_e(const KDeviceModel* dm, const KDeviceState& st, const uint8_t* mask, double* obs, hipStream_t stream) {
-  hipLaunchKernelGGL((k_reset<NL, G, SOLVER, EPB>), dim3((st.num_envs + EPB - 1) / EPB), dim3(64), 0, stream, dm, st, mask, obs);
+  hipLaunchKernelGGL((KM_K_RESET<NL, G, SOLVER, EPB>), dim3((st.num_envs + EPB - 1) / EPB), dim3(64), 0, stream, dm, st, mask, obs);
 }
 template <int NL, int G, int SOLVER>
 static void launch_step_t(const KDeviceModel* dm, const KDeviceState& st, const float* act, double* obs, double* reward, uint8_t* done, int nchunk, hipStream_t stream) {
@@ -3038,21 +3183,30 @@ static void launch_observe_t(const KDeviceModel* dm, const KDeviceState& st, dou
   constexpr int EPB = 64 / G;
   hipLaunchKernelGGL((k_observe<NL, G, EPB>), dim3((st.num_envs + EPB - 1) / EPB), dim3(64), 0, stream, dm, st, obs, reward);
 }
-// ---- one (NL, G, SOLVER) variant per translation unit (the Makefile compiles this file four times, in parallel)
+#if KM_VAR_PAR
+}  // namespace km_envp
+using namespace km_envp;
+#define KM_LAUNCH_STEP kmanip_launch_step_ep_
+#define KM_LAUNCH_RESET kmanip_launch_reset_ep_
+#else
+#define KM_LAUNCH_STEP kmanip_launch_step_
+#define KM_LAUNCH_RESET kmanip_launch_reset_
+#endif
+// ---- one (NL, G, SOLVER[, PAR]) variant per translation unit (the Makefile compiles this file eight times, in parallel)
 #ifndef KM_VAR_NL
 #error "compile with -DKM_VAR_NL=<10|20> -DKM_VAR_G=<16|32> -DKM_VAR_SOLVER=<0|1>"
 #endif
 #define KM_CAT4_(a, b, c, d) a##b##_##c##_##d
 #define KM_CAT4(a, b, c, d) KM_CAT4_(a, b, c, d)
-void KM_CAT4(kmanip_launch_step_, KM_VAR_NL, KM_VAR_G, KM_VAR_SOLVER)(const KDeviceModel* dm, const KDeviceState& st, const float* act,
+void KM_CAT4(KM_LAUNCH_STEP, KM_VAR_NL, KM_VAR_G, KM_VAR_SOLVER)(const KDeviceModel* dm, const KDeviceState& st, const float* act,
                                                                     double* obs, double* reward, uint8_t* done, int nchunk, hipStream_t stream) {
   launch_step_t<KM_VAR_NL, KM_VAR_G, KM_VAR_SOLVER>(dm, st, act, obs, reward, done, nchunk, stream);
 }
-void KM_CAT4(kmanip_launch_reset_, KM_VAR_NL, KM_VAR_G, KM_VAR_SOLVER)(const KDeviceModel* dm, const KDeviceState& st,
+void KM_CAT4(KM_LAUNCH_RESET, KM_VAR_NL, KM_VAR_G, KM_VAR_SOLVER)(const KDeviceModel* dm, const KDeviceState& st,
                                                                      const uint8_t* mask, double* obs, hipStream_t stream) {
   launch_reset_t<KM_VAR_NL, KM_VAR_G, KM_VAR_SOLVER>(dm, st, mask, obs, stream);
 }
-#if KM_VAR_SOLVER == 1      // (solver-independent: one copy per link-count class)
+#if KM_VAR_SOLVER == 1 && !KM_VAR_PAR      // (solver-independent: one copy per link-count class)
 void KM_CAT4(kmanip_launch_prepare_, KM_VAR_NL, KM_VAR_G, KM_VAR_SOLVER)(KDeviceModel* dm, hipStream_t stream) {
   hipLaunchKernelGGL((k_prepare_model<KM_VAR_NL>), dim3(1), dim3(64), 0, stream, dm);
 }

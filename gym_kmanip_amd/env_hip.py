@@ -19,7 +19,8 @@ from typing import Optional
 import numpy as np
 
 from . import lib as _libmod
-from .model import (CAMERAS, CONTROL_TIMESTEP, ENV_SPECS, KM_ACT_KEYS, KM_CAM_INDEX, CompiledModel, EnvSpec, compile_model)
+from .model import (CAMERAS, CONTROL_TIMESTEP, ENV_PARAMS, ENV_SPECS, KM_ACT_KEYS, KM_CAM_INDEX, CompiledModel, EnvSpec,
+                    compile_model, env_param_defaults)
 
 MJCF_TO_ASSET = {"_env_solo_arm.xml": "solo_arm", "_env_dual_arm.xml": "dual_arm", "_env_torso.xml": "torso"}
 
@@ -60,6 +61,8 @@ class KManipEnvHip:
         self.discount = torch.ones((n,), dtype=torch.float64, device=self.device)
         self.sim_time = torch.zeros((n,), dtype=torch.float64, device=self.device)
         self._check(self.L.kmanip_bind_sim_time(self.h, C.c_void_p(self.sim_time.data_ptr())), "kmanip_bind_sim_time")
+        self._ep_active = False          # per-env parameters in force (set_env_params / set_env_param_ranges)
+        self._ep_ranges = None           # (lo, hi) float64[KM_EP_N] of ranges mode, or None
 
     # ------------------------------------------------------------------ helpers
     def _check(self, rc, what):
@@ -363,13 +366,82 @@ class KManipEnvHip:
         self._check(self.L.kmanip_set_episode(self.h, ep.ctypes.data_as(C.POINTER(C.c_int32))), "kmanip_set_episode")
 
     def checkpoint(self):
-        """Complete restartable state: (qpos, qvel, ctrl, qacc_warmstart, step_idx, episode) as host arrays."""
-        return self.get_state() + (self.get_episode(),)
+        """Complete restartable state: (qpos, qvel, ctrl, qacc_warmstart, step_idx, episode, env_params) as host arrays;
+        env_params is None without per-env parameters, else (values float64[KM_EP_N, num_envs], lo, hi) -- lo / hi the
+        ranges of ranges mode or None."""
+        ep = None
+        if self._ep_active:
+            vals = np.stack([v.cpu().numpy() for v in self.get_env_params().values()])
+            lo, hi = (None, None) if self._ep_ranges is None else (self._ep_ranges[0].copy(), self._ep_ranges[1].copy())
+            ep = (vals, lo, hi)
+        return self.get_state() + (self.get_episode(), ep)
 
     def restore(self, ckpt):
-        qpos, qvel, ctrl, warm, step, episode = ckpt
+        qpos, qvel, ctrl, warm, step, episode = ckpt[:6]
         self.set_state(qpos, qvel, ctrl, warm, step)
         self.set_episode(episode)
+        if len(ckpt) > 6:
+            ep = ckpt[6]
+            if ep is None:
+                self.clear_env_params()
+            else:
+                vals, lo, hi = ep
+                self.set_env_params(**{name: vals[k] for k, name in enumerate(ENV_PARAMS)})
+                if lo is not None:
+                    self._set_ranges_raw(lo, hi)
+
+    # ------------------------------------------------------------------ per-env physics parameters (domain randomisation)
+    def set_env_params(self, **fields):
+        """Explicit per-env values (and ranges mode off): each of cube_mass, cube_friction, cube_frictionloss, kp_scale a
+        scalar or a [num_envs] tensor / array; unnamed fields keep the model's values.  Env e then behaves exactly like a
+        handle of model.with_env_params(cm, **values of e).  Bad values raise KManipError, leaving the handle unchanged."""
+        torch = _torch()
+        unknown = set(fields) - set(ENV_PARAMS)
+        if unknown:
+            raise ValueError("unknown env parameter(s) %s (known: %s)" % (sorted(unknown), ", ".join(ENV_PARAMS)))
+        base = env_param_defaults(self.cm)
+        p = torch.empty((len(ENV_PARAMS), self.num_envs), dtype=torch.float64, device=self.device)
+        for k, name in enumerate(ENV_PARAMS):
+            v = fields.get(name)
+            p[k] = base[name] if v is None else torch.as_tensor(v, dtype=torch.float64).to(self.device).expand(self.num_envs)
+        self._check(self.L.kmanip_set_env_params(self.h, C.c_void_p(p.data_ptr()), self._stream()), "kmanip_set_env_params")
+        self._ep_active, self._ep_ranges = True, None
+
+    def get_env_params(self):
+        """{name: float64[num_envs] device tensor} of the values in force (the drawn ones in ranges mode)."""
+        torch = _torch()
+        p = torch.empty((len(ENV_PARAMS), self.num_envs), dtype=torch.float64, device=self.device)
+        self._check(self.L.kmanip_get_env_params(self.h, C.c_void_p(p.data_ptr()), self._stream()), "kmanip_get_env_params")
+        return {name: p[k] for k, name in enumerate(ENV_PARAMS)}
+
+    def set_env_param_ranges(self, **ranges):
+        """Ranges mode: every reset of an env (k_reset or the auto-reset inside a step) draws each named parameter uniformly
+        from (lo, hi) for the new episode, from the seed's counter-based stream; unnamed parameters are pinned to the model's
+        value, lo == hi pins a value.  No argument turns ranges mode off (the values in force stay)."""
+        if not ranges:
+            self._check(self.L.kmanip_set_env_param_ranges(self.h, None, None), "kmanip_set_env_param_ranges")
+            self._ep_ranges = None
+            return
+        unknown = set(ranges) - set(ENV_PARAMS)
+        if unknown:
+            raise ValueError("unknown env parameter(s) %s (known: %s)" % (sorted(unknown), ", ".join(ENV_PARAMS)))
+        base = env_param_defaults(self.cm)
+        lo = np.array([base[n] for n in ENV_PARAMS]); hi = lo.copy()
+        for k, name in enumerate(ENV_PARAMS):
+            if name in ranges:
+                lo[k], hi[k] = (float(x) for x in ranges[name])
+        self._set_ranges_raw(lo, hi)
+
+    def _set_ranges_raw(self, lo, hi):
+        lo = np.ascontiguousarray(lo, dtype=np.float64); hi = np.ascontiguousarray(hi, dtype=np.float64)
+        ptr = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))
+        self._check(self.L.kmanip_set_env_param_ranges(self.h, ptr(lo), ptr(hi)), "kmanip_set_env_param_ranges")
+        self._ep_active, self._ep_ranges = True, (lo.copy(), hi.copy())
+
+    def clear_env_params(self):
+        """Back to the compiled model for every env (bit-identical to a handle that never had parameters)."""
+        self._check(self.L.kmanip_set_env_params(self.h, None, self._stream()), "kmanip_set_env_params")
+        self._ep_active, self._ep_ranges = False, None
 
     def set_state(self, qpos=None, qvel=None, ctrl=None, warm=None, step=None):
         def p(a, dt, t):

@@ -142,7 +142,7 @@ class KManipEnv(_EnvBase):
     def __init__(self, env_id: str = "KManipSoloArm", num_envs: int = 1, device: int = 0, seed: int = 0,
                  squeeze: bool = False, env_id_offset: int = 0, device_outputs: bool = False,
                  log_h5py: bool = False, log_prefix: str = "test", log_env_ids=None, log_backend=None,
-                 log_reference_layout: bool = False, log_h5py_module=None, **overrides):
+                 log_reference_layout: bool = False, log_h5py_module=None, domain_randomization=None, **overrides):
         spec: EnvSpec = ENV_SPECS[env_id]
         self.env_id = env_id
         self.seed = seed
@@ -176,6 +176,9 @@ class KManipEnv(_EnvBase):
         # backend seam, env_base.py:192-200
         self.env = env_hip.new(self, num_envs=num_envs, device=device, env_id_offset=env_id_offset,
                                auto_reset=False, **overrides)
+        # domain_randomization={name: (lo, hi)} (env_hip.ENV_PARAMS names): every reset redraws those physics parameters per env
+        if domain_randomization:
+            self.env.set_env_param_ranges(**domain_randomization)
         self.info: Dict[str, Any] = {
             "step": self.step_idx, "episode": self.episode_idx, "is_success": False, "q_keys": self.q_keys, "q_len": self.q_len,
             "a_len": self.action_len, "obs_list": self.obs_list, "act_list": self.act_list,

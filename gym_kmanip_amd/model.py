@@ -9,6 +9,7 @@ from the build-owned JSON written by tools/mjcf_extract.py.
 from __future__ import annotations
 
 import ctypes as C
+import dataclasses
 import json
 import math
 import os
@@ -434,3 +435,99 @@ def compile_model(env_id_or_spec, *, auto_reset: bool = True, touch_reward: bool
     return CompiledModel(spec=spec, asset=asset, desc=d, nlink=nl, nq=nl + 7, nv=nl + 6, nu=nl,
                          act_dim=col, obs_dim=2 * nl + 7, act_slices=act_slices,
                          obs_slices=obs_slices, cameras=cams)
+
+
+# ---- per-env physics parameters (include/kmanip.h KM_EP_*), in KM_EP_* order
+ENV_PARAMS = ("cube_mass", "cube_friction", "cube_frictionloss", "kp_scale")
+
+
+def env_param_defaults(cm: CompiledModel) -> Dict[str, float]:
+    """The compiled model's own value of every per-env parameter."""
+    d = cm.desc
+    return {"cube_mass": d.cube_mass, "cube_friction": d.con_cube_friction[0], "cube_frictionloss": d.cube_frictionloss,
+            "kp_scale": 1.0}
+
+
+def check_env_param(name: str, v) -> float:
+    """ValueError unless v is a finite value within the parameter's limits (mass and kp scale > 0, friction terms >= 0)."""
+    if name not in ENV_PARAMS:
+        raise ValueError("unknown env parameter %r (known: %s)" % (name, ", ".join(ENV_PARAMS)))
+    v = float(v)
+    positive = name in ("cube_mass", "kp_scale")
+    if not math.isfinite(v) or (v <= 0 if positive else v < 0):
+        raise ValueError("%s = %r: must be finite and %s 0" % (name, v, ">" if positive else ">="))
+    return v
+
+
+def trace_robot(d: "KModelDesc") -> float:
+    """Robot part of trace(M(qpos0)) as the library derives it at create (kmanip_api.hip trace_robot_of), same order."""
+    return d.meaninertia * float(d.nlink + 6) - (3.0 * d.cube_mass + ((d.cube_inertia[0] + d.cube_inertia[1]) + d.cube_inertia[2]))
+
+
+def with_env_params(cm: CompiledModel, cube_mass=None, cube_friction=None, cube_frictionloss=None,
+                    kp_scale=None) -> CompiledModel:
+    """The host definition of the per-env parameters: a copy of `cm` whose desc has the named fields and the constants derived
+    from them replaced, in the evaluation order the kernels use (kmanip_dyn.hip ep_derive) -- an env of a handle with
+    parameters p behaves exactly like a handle created from with_env_params(cm, **p).desc.
+      cube_mass          uniform-density box of unchanged size: cube_inertia[k] * (m / m0); cube_invweight0 = (1/m, mean 1/I_k);
+                         meaninertia = (trace_robot + 3 m + (I_0 + I_1 + I_2)) / nv (the compiled value while m == m0)
+      cube_friction      con_cube_friction[0] (torsional / rolling unchanged)
+      cube_frictionloss  the cube free joint's friction loss
+      kp_scale           every position servo's kp times the scale
+    Unnamed (None) fields keep the model's values; bad values raise ValueError."""
+    d0 = cm.desc
+    d = KModelDesc.from_buffer_copy(d0)
+    if cube_mass is not None:
+        m0, m = d0.cube_mass, check_env_param("cube_mass", cube_mass)
+        inertia = [d0.cube_inertia[k] * (m / m0) for k in range(3)]
+        d.cube_mass = m
+        for k in range(3):
+            d.cube_inertia[k] = inertia[k]
+        d.cube_invweight0[0] = 1.0 / m
+        d.cube_invweight0[1] = ((1.0 / inertia[0] + 1.0 / inertia[1]) + 1.0 / inertia[2]) / 3.0
+        if m != m0:
+            nv = d0.nlink + 6
+            d.meaninertia = ((trace_robot(d0) + 3.0 * m) + ((inertia[0] + inertia[1]) + inertia[2])) / nv
+    if cube_friction is not None:
+        d.con_cube_friction[0] = check_env_param("cube_friction", cube_friction)
+    if cube_frictionloss is not None:
+        d.cube_frictionloss = check_env_param("cube_frictionloss", cube_frictionloss)
+    if kp_scale is not None:
+        s = check_env_param("kp_scale", kp_scale)
+        for i in range(d0.nlink):
+            d.kp[i] = d0.kp[i] * s
+    return dataclasses.replace(cm, desc=d)
+
+
+def _philox4x32_10(ctr, key):
+    """Philox4x32-10 (Salmon et al. 2011) on uint32 words, as kmanip_device.hpp philox4x32_10 evaluates it."""
+    c0, c1, c2, c3 = (int(x) & 0xFFFFFFFF for x in ctr)
+    k0, k1 = (int(x) & 0xFFFFFFFF for x in key)
+    for _ in range(10):
+        p0, p1 = 0xD2511F53 * c0, 0xCD9E8D57 * c2
+        c0, c1, c2, c3 = ((p1 >> 32) ^ c1 ^ k0) & 0xFFFFFFFF, p1 & 0xFFFFFFFF, ((p0 >> 32) ^ c3 ^ k1) & 0xFFFFFFFF, p0 & 0xFFFFFFFF
+        k0, k1 = (k0 + 0x9E3779B9) & 0xFFFFFFFF, (k1 + 0xBB67AE85) & 0xFFFFFFFF
+    return np.array([c0, c1, c2, c3], dtype=np.uint32)
+
+
+def _u53(hi, lo):
+    return (float(int(hi) >> 5) * 67108864.0 + float(int(lo) >> 6)) / 9007199254740992.0
+
+
+KM_EP_CTR3 = 2      # include/kmanip.h: counter word 3 of the ranges-mode draw (words 2 and 3; the cube spawn uses 0 and 1)
+
+
+def draw_env_params(seed: int, genv: int, episode: int, lo, hi) -> np.ndarray:
+    """The values ranges mode draws at the reset that starts `episode` of global env `genv` (include/kmanip.h
+    kmanip_set_env_param_ranges): p_k = lo_k + (hi_k - lo_k) * u_k, product rounded before the sum, u_k from Philox4x32-10 with
+    key = seed and counter (genv lo, genv hi, episode, KM_EP_CTR3 + k // 2), words (0, 1) for even k and (2, 3) for odd k."""
+    key = (seed & 0xFFFFFFFF, (seed >> 32) & 0xFFFFFFFF)
+    g = int(genv) & 0xFFFFFFFFFFFFFFFF
+    out = np.zeros(len(ENV_PARAMS))
+    for blk in range(2):
+        o = _philox4x32_10((g & 0xFFFFFFFF, g >> 32, int(episode) & 0xFFFFFFFF, KM_EP_CTR3 + blk), key)
+        for j in range(2):
+            k = 2 * blk + j
+            u = _u53(o[2 * j], o[2 * j + 1])
+            out[k] = float(lo[k]) + (float(hi[k]) - float(lo[k])) * u
+    return out

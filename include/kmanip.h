@@ -371,6 +371,35 @@ KMANIP_API int kmanip_scripted_action(KHandle h, float* act_dev, void* stream);
  * reference never terminates early), so the next K actions can be laid out before stepping. */
 KMANIP_API int kmanip_sample_action(KHandle h, float* act_dev, int ahead, void* stream);
 
+/* Per-env physics parameters (domain randomisation).  Storage is double[KM_EP_N][num_envs], struct-of-arrays
+ * like the state: element (k, env) at k * num_envs + env.  Env e with parameters p behaves exactly like a handle whose KModelDesc is
+ * the compiled one with these fields and their derived constants replaced (gym_kmanip_amd/model.py with_env_params):
+ *   KM_EP_CUBE_MASS          cube mass m_e, kg; uniform-density box of unchanged size: cube_inertia[k] * (m_e / cube_mass),
+ *                            cube_invweight0 and meaninertia follow
+ *   KM_EP_CUBE_FRICTION      tangential friction of the pairs with the cube (con_cube_friction[0]); torsional / rolling unchanged
+ *   KM_EP_CUBE_FRICTIONLOSS  friction loss of the cube's free joint (its rows exist only while the value is > 0)
+ *   KM_EP_KP_SCALE           multiplier on every position servo's kp (ctrlrange / forcerange unchanged)
+ * Nothing else (geometry, gravity, spawn box, cameras) is per env. */
+enum { KM_EP_CUBE_MASS = 0, KM_EP_CUBE_FRICTION = 1, KM_EP_CUBE_FRICTIONLOSS = 2, KM_EP_KP_SCALE = 3, KM_EP_N = 4 };
+
+/* Explicit values: params_dev DEVICE double[KM_EP_N][num_envs], read once `stream` has produced it; switches ranges mode off.
+ * Synchronous: returns after the whole device is idle and the values are copied (a step in flight on any stream finishes first).  The values are
+ * validated on the device first (mass > 0, friction >= 0, frictionloss >= 0, kp_scale > 0, all finite; one flag read back per
+ * call, never per step): a bad value returns nonzero and leaves the handle unchanged.  params_dev == NULL returns to the compiled
+ * model: the default kernels, bit-identical to a handle that never had parameters. */
+KMANIP_API int kmanip_set_env_params(KHandle h, const double* params_dev, void* stream);
+/* The values in force into DEVICE double[KM_EP_N][num_envs] on `stream` (the compiled model's when none are set); in ranges mode,
+ * after a reset, the values drawn for the env's current episode. */
+KMANIP_API int kmanip_get_env_params(KHandle h, double* params_dev, void* stream);
+/* Ranges mode: lo / hi HOST double[KM_EP_N].  From then on every reset of env e -- kmanip_reset's mask or the auto-reset inside
+ * kmanip_step / kmanip_step_chunk -- draws p_k = lo[k] + (hi[k] - lo[k]) * u_k (product rounded before the sum), u_k a 53-bit
+ * uniform from Philox4x32-10 keyed by the seed with counter (global env id lo, hi, episode, KM_EP_CTR3 + k / 2): words (0, 1)
+ * of the block for even k, (2, 3) for odd k; `episode` is the one the reset's cube spawn uses.  lo == hi pins a parameter.  Envs
+ * keep their current values until their next reset.  lo > hi or a value outside the limits above is refused (handle unchanged);
+ * NULL, NULL turns ranges mode off and keeps the values in force.  Synchronous. */
+#define KM_EP_CTR3 2u
+KMANIP_API int kmanip_set_env_param_ranges(KHandle h, const double* lo, const double* hi);
+
 KMANIP_API int kmanip_num_envs(KHandle h);
 KMANIP_API const char* kmanip_last_error(KHandle h);   /* h may be NULL: error of the last failed create */
 KMANIP_API const char* kmanip_version(void);
