@@ -40,16 +40,14 @@ struct KHandle_ {
   int step_cam = -1, step_h = 0, step_w = 0;
   float* step_depth = nullptr;
   bool ik_unfused = false;      // KMANIP_IK_UNFUSED=1: before_step as its own launch (A/B timing only)
+  int ik_ppb = 0;               // KMANIP_IK_PPB: problems per workgroup of that launch (A/B), 0 = chosen from the width
+  int epb_forced = 0;           // KMANIP_EPB = 1 | 2 | 4: envs per wave of the step / reset launches (diagnostics), 0 = km_pick_epb's choice
   // wave slots in predicted-cost order (k_sort_envs) for launches of several residency rounds; KMANIP_COST_SORT=0 / 1 overrides
   int32_t* slot_env = nullptr;
   bool cost_sort = false;
   KCostWeights cost_w{18, 1, 2000, 0, 0, 100};     // work units per: IK evaluation, Newton work unit, collider near the cube; bin width
-  // heavy-first dispatch (KDeviceState::disp_*): three rotating tables, the step counter that rotates them
   uint8_t* spread_flags[2] = {nullptr, nullptr};   // SPREAD (KDeviceState::spread_*): the two flag arrays, rotated by every single-step launch
   unsigned spread_k = 0;
-  int32_t* disp_tab[3] = {nullptr, nullptr, nullptr};
-  unsigned disp_k = 0;
-  int wave_slots = 0;           // entries of st.wave_clk (one per lane group of the step launch's grid)
   int last_epb = 0;             // envs per wave of the LAST step launch (a chunk launch always takes the full shape): what the slot -> env maps of kmanip_dbg_wave_clocks are rebuilt with
   // per-env physics parameters (kmanip_set_env_params): allocated by the first call that needs them; st.envp / st.ep_range
   // point at them while explicit values / ranges mode are in force
@@ -281,6 +279,8 @@ int kmanip_create(const KModelDesc* desc, int num_envs, int device, uint64_t see
   h->st.rd_rec = nullptr;
   h->st.control_dt = desc->n_sub_steps * desc->timestep;
   { const char* e = getenv("KMANIP_IK_UNFUSED"); h->ik_unfused = e && e[0] == '1'; }
+  if (const char* e = getenv("KMANIP_IK_PPB")) h->ik_ppb = atoi(e);
+  if (const char* e = getenv("KMANIP_EPB")) { const int v = atoi(e); if (v == 1 || v == 2 || v == 4) h->epb_forced = v; }
   h->st.slot_env = nullptr;
   h->st.wave_clk = nullptr;
   h->st.spread_in = nullptr; h->st.spread_out = nullptr;
@@ -289,8 +289,19 @@ int kmanip_create(const KModelDesc* desc, int num_envs, int device, uint64_t see
   // the two-arm sort at 2.5-3 cm on the DualArm (3.91 -> 3.97 M) and flat on the Torso (4.86 / 4.85 / 4.83 M at 1.5 / 2.5 / 4 cm)
   h->st.near_margin = nl > 10 ? 0.025 : 0.015;
   if (const char* e = getenv("KMANIP_NEAR_MARGIN")) { const double v = atof(e); if (v >= 0 && v < 1) h->st.near_margin = v; }
-  h->st.disp_in = nullptr; h->st.disp_out = nullptr; h->st.disp_zero = nullptr; h->st.disp_cap = 0; h->st.disp_heavy_epb = 1;
-  h->wave_slots = num_envs;
+  {
+    // more waves than SIMD slots (1024) at two envs per wave: the two-arm models (their kernels carry the work counters the
+    // order is predicted from; the single-arm kernel ships without them -- KMANIP_COST_SORT=1 still sorts it by its IK counts)
+    h->cost_sort = nl > 10 && num_envs > 2048;
+    if (const char* e = getenv("KMANIP_COST_SORT")) h->cost_sort = e[0] == '1';
+    if (const char* e = getenv("KMANIP_COST_W")) {       // diagnostic: "ik,work,near-cube,armtab,cubetab,binwidth"
+      KCostWeights w = h->cost_w;
+      // (negative weights would make a cost negative; the kernel clamps the bin, and they are refused here)
+      if (sscanf(e, "%d,%d,%d,%d,%d,%d", &w.ik, &w.work, &w.coupled, &w.armtab, &w.cubetab, &w.binw) == 6 && w.binw > 0 &&
+          w.ik >= 0 && w.work >= 0 && w.coupled >= 0 && w.armtab >= 0 && w.cubetab >= 0) h->cost_w = w;
+      else { g_create_error = "kmanip_create: KMANIP_COST_W must be six comma-separated integers >= 0 with a bin width > 0"; kmanip_destroy(h); return -2; }
+    }
+  }
   {
     // Which envs share a wave (the single-arm Newton kernel at widths whose launch is about one residency round of multi-env waves).
     // Every step notes which envs end it with a collider on or within 1.5 cm of the cube ("heavy": 12 % of the envs, 99 % of the
@@ -305,59 +316,17 @@ int kmanip_create(const KModelDesc* desc, int num_envs, int device, uint64_t see
     //    sit together in the later waves.  k_step 0.5896 -> 0.5690 ms at 4096 envs (heavy-only flags 0.5751, + table bit 0.5716),
     //    0.5361 -> 0.5302 ms at 2048 (profiles/r05_spread_dispatch.txt).  A permutation INSIDE each block whatever the flags
     //    say: the cache lines a block touches are those of the identity map (a first version dealt from launch-wide lists filled by
-    //    atomics in completion order: 0.5853 ms, HBM traffic 5.6 -> 17 MB a launch).
-    //  * HEAVY-FIRST with variable occupancy (experiment, KMANIP_HEAVY_DISPATCH=1 KMANIP_HEAVY_EPB=1|2|4|0, KMANIP_HEAVY_CAP = most
-    //    envs dispatched as heavy, default num_envs / 16): launch-wide lists (KDeviceState::disp_*), heavy envs first and
-    //    KMANIP_HEAVY_EPB to a wave (0: the list-based spread).  Loses (profiles/r05_heavy_dispatch.txt): a coupled env
-    //    alone in a wave ends after 1.0-1.2 M cycles against 1.4-1.5 M in a four-env wave, but 12 % flagged envs are 35 % more waves
-    //    than SIMD slots, whose late starters end last.
-    //  * KMANIP_HEAVY_DISPATCH=0: neither; the identity map.
+    //    atomics in completion order: 0.5853 ms, HBM traffic 5.6 -> 17 MB a launch; a heavy-first dispatch with a wave to each heavy
+    //    env lost too: DESIGN.md 3.2).
+    //  * the cost sort (above) or KMANIP_SPREAD=0: the sorted slot order (a map of its own) / the identity map.
     const bool single_newton = nl == 10 && desc->solver == KM_SOLVER_NEWTON;
-    bool spread = single_newton && num_envs >= 2048 && num_envs % 64 == 0 && !getenv("KMANIP_HEAVY_DISPATCH");
+    bool spread = single_newton && num_envs >= 2048 && num_envs % 64 == 0 && !h->cost_sort;
     if (const char* e = getenv("KMANIP_SPREAD")) spread = spread && e[0] == '1';
-    if (const char* e = getenv("KMANIP_COST_SORT")) if (e[0] == '1') spread = false;      // (the sorted slot order is a map of its own)
     if (spread) for (int t = 0; t < 2; t++) CR(dalloc((void**)&h->spread_flags[t], (size_t)num_envs));
-    h->st.spread_table = 3;
-    if (const char* e = getenv("KMANIP_SPREAD_TABLE")) h->st.spread_table = atoi(e);
-    bool on = false;
-    int hepb = 1;
-    if (const char* e = getenv("KMANIP_HEAVY_DISPATCH")) on = single_newton && num_envs >= 2048 && e[0] == '1';
-    if (on) {
-      int cap = num_envs / 16 > 64 ? num_envs / 16 : 64;
-      if (const char* e = getenv("KMANIP_HEAVY_CAP")) { const int v = atoi(e); if (v > 0) cap = v; }
-      if (const char* e = getenv("KMANIP_HEAVY_EPB")) { const int v = atoi(e); if (v == 0 || v == 1 || v == 2 || v == 4) hepb = v; }
-      if (hepb == 0) {                 // SPREAD: at most one heavy env per wave, every wave of the plain grid can take one
-        const int waves = num_envs / (num_envs >= 4096 ? 4 : 2);
-        if (!getenv("KMANIP_HEAVY_CAP") || cap > waves) cap = waves;
-      }
-      if (cap > num_envs) cap = num_envs;
-      h->st.disp_cap = cap; h->st.disp_heavy_epb = hepb;
-      std::vector<int32_t> init(KM_DISP_HDR + N, 0);
-      init[1] = num_envs;                                   // table 0: nobody heavy, the light list is the identity
-      for (int i = 0; i < num_envs; i++) init[KM_DISP_HDR + i] = i;
-      for (int t = 0; t < 3; t++) {
-        CR(dalloc((void**)&h->disp_tab[t], sizeof(int32_t) * (KM_DISP_HDR + N)));
-        if (t == 0) CR(hipMemcpy(h->disp_tab[0], init.data(), sizeof(int32_t) * (KM_DISP_HDR + N), hipMemcpyHostToDevice));
-      }
-      if (hepb > 0) h->wave_slots = 4 * (cap + num_envs + 4);      // (an upper bound of 4 lane groups x the grid of any launch shape; SPREAD keeps the plain grid)
-    }
   }
-  if (const char* e = getenv("KMANIP_WAVE_CLOCKS")) if (e[0] == '1') CR(dalloc((void**)&h->st.wave_clk, sizeof(unsigned long long) * h->wave_slots));
+  if (const char* e = getenv("KMANIP_WAVE_CLOCKS")) if (e[0] == '1') CR(dalloc((void**)&h->st.wave_clk, sizeof(unsigned long long) * N));
   CR(dalloc((void**)&h->slot_env, sizeof(int32_t) * N));
   CR(dalloc((void**)&h->st.work, sizeof(int32_t) * N));
-  {
-    // more waves than SIMD slots (1024) at two envs per wave: the two-arm models (their kernels carry the work counters the
-    // order is predicted from; the single-arm kernel ships without them -- KMANIP_COST_SORT=1 still sorts it by its IK counts)
-    h->cost_sort = nl > 10 && num_envs > 2048;
-    if (const char* e = getenv("KMANIP_COST_SORT")) h->cost_sort = e[0] == '1';
-    if (const char* e = getenv("KMANIP_COST_W")) {       // diagnostic: "ik,work,near-cube,armtab,cubetab,binwidth"
-      KCostWeights w = h->cost_w;
-      // (negative weights would make a cost negative; the kernel clamps the bin, and they are refused here)
-      if (sscanf(e, "%d,%d,%d,%d,%d,%d", &w.ik, &w.work, &w.coupled, &w.armtab, &w.cubetab, &w.binw) == 6 && w.binw > 0 &&
-          w.ik >= 0 && w.work >= 0 && w.coupled >= 0 && w.armtab >= 0 && w.cubetab >= 0) h->cost_w = w;
-      else { g_create_error = "kmanip_create: KMANIP_COST_W must be six comma-separated integers >= 0 with a bin width > 0"; kmanip_destroy(h); return -2; }
-    }
-  }
   // the initialisation above ran on the null stream; the caller's (non-blocking) streams must not start before it
   CR(hipDeviceSynchronize());
 #undef CR
@@ -379,40 +348,27 @@ int kmanip_num_envs(KHandle h) { return h ? h->num_envs : 0; }
 int kmanip_reset(KHandle h, const uint8_t* mask_dev, double* obs_dev, void* stream) {
   if (!h) return -1;
   KM_ENTER(h);
-  kmanip_launch_reset(h->dmodel, h->desc, h->st, mask_dev, 0, obs_dev, (hipStream_t)stream);
+  kmanip_launch_reset(h->dmodel, h->desc, h->st, mask_dev, 0, obs_dev, km_pick_epb(h->num_envs, h->desc.nlink <= 10 ? 4 : 2, h->epb_forced),
+                      (hipStream_t)stream);
   HIPCHK(h, hipGetLastError());
   return 0;
 }
 
 // Diagnostics (include/kmanip_debug.h, not part of the boundary; KMANIP_WAVE_CLOCKS=1 at create): per wave slot, the ticks its wave spent in the last
-// k_step and the env it held -- HOST arrays of kmanip_dbg_wave_slots(h) entries --, and every env's work counter (num_envs entries).  Synchronous.
+// k_step and the env it held, and every env's work counter -- HOST arrays of num_envs entries each.  Synchronous.
 int kmanip_dbg_wave_clocks(KHandle h, unsigned long long* clk, int32_t* slot_env, int32_t* work) {
   if (!h) return -1;
   if (clk && !h->st.wave_clk) { h->err = "kmanip_dbg_wave_clocks: clk needs KMANIP_WAVE_CLOCKS=1 at create"; return -1; }
   KM_ENTER(h);
   HIPCHK(h, hipDeviceSynchronize());
   const size_t N = (size_t)h->num_envs;
-  if (clk) HIPCHK(h, hipMemcpy(clk, h->st.wave_clk, sizeof(unsigned long long) * h->wave_slots, hipMemcpyDeviceToHost));
+  if (clk) HIPCHK(h, hipMemcpy(clk, h->st.wave_clk, sizeof(unsigned long long) * N, hipMemcpyDeviceToHost));
   if (slot_env) {
-    if (h->disp_tab[0]) {
-      // heavy-first dispatch: rebuild the LAST launch's slot -> env map (4 slots per workgroup, -1 = empty lane group) from its table
-      std::vector<int32_t> tab(KM_DISP_HDR + N);
-      HIPCHK(h, hipMemcpy(tab.data(), h->disp_tab[(h->disp_k + 2) % 3], sizeof(int32_t) * (KM_DISP_HDR + N), hipMemcpyDeviceToHost));
-      const int epb = h->last_epb ? h->last_epb : km_step_epb(h->num_envs, 4, 1), hepb = h->st.disp_heavy_epb;
-      const int nh = tab[0] < h->st.disp_cap ? tab[0] : h->st.disp_cap, nhw = hepb ? (nh + hepb - 1) / hepb : 0;
-      for (int sl = 0; sl < h->wave_slots; sl++) {
-        const int b = sl / epb, grp = sl % epb;
-        int idx = -1;
-        if (hepb == 0) { const int i = b < nh ? (grp == 0 ? b : nh + (epb - 1) * b + grp - 1) : epb * b + grp; if (i < (int)N) idx = i; }
-        else if (b < nhw) { if (grp < hepb && b * hepb + grp < nh) idx = b * hepb + grp; }
-        else { const int i = nh + (b - nhw) * epb + grp; if (i < (int)N) idx = i; }
-        slot_env[sl] = idx >= 0 ? tab[KM_DISP_HDR + idx] : -1;
-      }
-    } else if (h->spread_flags[0]) {
+    if (h->spread_flags[0]) {
       // SPREAD: the LAST launch's map from the flags it read (slot = wave index in slot space x envs per wave + lane group)
       std::vector<uint8_t> fl(N);
       HIPCHK(h, hipMemcpy(fl.data(), h->spread_flags[(h->spread_k + 1) & 1], N, hipMemcpyDeviceToHost));
-      const int epb = h->last_epb ? h->last_epb : km_step_epb(h->num_envs, 4, 1);      // (a chunk launch at 2048 envs runs four envs per wave, a step two)
+      const int epb = h->last_epb ? h->last_epb : km_step_epb(h->num_envs, 4, 1, h->epb_forced);      // (a chunk launch at 2048 envs runs four envs per wave, a step two)
       for (size_t blk = 0; blk < N / 64; blk++) {
         unsigned long long M = 0, S1 = 0, S2 = 0;
         for (int i = 0; i < 64; i++) {
@@ -428,8 +384,6 @@ int kmanip_dbg_wave_clocks(KHandle h, unsigned long long* clk, int32_t* slot_env
   if (work) HIPCHK(h, hipMemcpy(work, h->st.work, sizeof(int32_t) * N, hipMemcpyDeviceToHost));
   return 0;
 }
-// number of entries of kmanip_dbg_wave_clocks' clk / slot_env arrays (num_envs, or more with the heavy-first dispatch)
-int kmanip_dbg_wave_slots(KHandle h) { return h ? h->wave_slots : 0; }
 
 int kmanip_observe(KHandle h, double* obs_dev, double* reward_dev, void* stream) {
   if (!h) { g_create_error = "kmanip_observe: null handle"; return -1; }
@@ -455,7 +409,7 @@ static int step_impl(KHandle h, int nchunk, const float* act_dev, double* obs_de
   if (split && nchunk != 1) { h->err = "kmanip_step_chunk needs the fused path (unset KMANIP_IK_UNFUSED)"; return -1; }
   if (split) {
     if (tm) HIPCHK(h, hipEventRecord(ev[0], s));
-    kmanip_launch_ik_coop(h->dmodel, h->desc, h->st, act_dev, s);
+    kmanip_launch_ik_coop(h->dmodel, h->desc, h->st, act_dev, h->ik_ppb, s);
   }
   h->st.slot_env = nullptr;
   if (h->cost_sort) {                        // (one small launch: counting sort of the envs by their last step's diagnostics)
@@ -467,14 +421,9 @@ static int step_impl(KHandle h, int nchunk, const float* act_dev, double* obs_de
     h->st.spread_in = h->spread_flags[h->spread_k & 1]; h->st.spread_out = h->spread_flags[(h->spread_k + 1) & 1];
     h->spread_k++;
   }
-  h->st.disp_in = nullptr; h->st.disp_out = nullptr; h->st.disp_zero = nullptr;
-  if (h->disp_tab[0] && nchunk == 1) {       // heavy-first dispatch: this launch reads table k, fills k + 1, clears the counters of k + 2
-    h->st.disp_in = h->disp_tab[h->disp_k % 3]; h->st.disp_out = h->disp_tab[(h->disp_k + 1) % 3]; h->st.disp_zero = h->disp_tab[(h->disp_k + 2) % 3];
-    h->disp_k++;
-  }
-  h->last_epb = km_step_epb(h->num_envs, h->desc.nlink <= 10 ? 4 : 2, nchunk);
+  h->last_epb = km_step_epb(h->num_envs, h->desc.nlink <= 10 ? 4 : 2, nchunk, h->epb_forced);
   if (tm) HIPCHK(h, hipEventRecord(ev[1], s));        // (fused path: two events per step, each costs the stream a barrier packet)
-  kmanip_launch_step(h->dmodel, h->desc, h->st, split ? nullptr : act_dev, obs_dev, reward_dev, done_dev, nchunk, s);
+  kmanip_launch_step(h->dmodel, h->desc, h->st, split ? nullptr : act_dev, obs_dev, reward_dev, done_dev, nchunk, h->last_epb, s);
   if (tm) HIPCHK(h, hipEventRecord(ev[2], s));
   const bool render = h->step_depth && nchunk == 1;
   if (render)                             // the observation's camera branch (env_sim.py:140-145) of the state just produced

@@ -499,7 +499,6 @@ __device__ __host__ inline float km_action_from_u32(uint32_t r) { return (float)
 
 // Device state, struct-of-arrays over envs: element (k, env) of an [n_k, num_envs] array is at
 // k * num_envs + env, so a wave reading component k for consecutive envs is fully coalesced.
-#define KM_DISP_HDR 4
 struct KDeviceState {
   double* qpos;       // [nq][N]
   double* qvel;       // [nv][N]
@@ -516,14 +515,6 @@ struct KDeviceState {
   int32_t* work;      // [N] Newton work units of the env's last control step (two-arm kernels; 0 otherwise): k_sort_envs' predictor
   unsigned long long* wave_clk;   // [N] or NULL (KMANIP_WAVE_CLOCKS=1, diagnostics): s_memtime ticks the wave that held slot s spent in k_step
   const int32_t* slot_env;   // [N] or NULL: env handled by wave slot s (k_sort_envs: predicted-cost order, heaviest first); NULL = identity
-  // Heavy-first dispatch with variable wave occupancy (round 5; single-arm Newton kernel, launches of one residency round).
-  // A dispatch table is int32[KM_DISP_HDR + N]: [0] = envs registered as HEAVY, [1] = as light, then the env list -- heavy envs
-  // from the front in arrival order, everybody else from the back.  k_step reads disp_in (NULL: classic slot mapping): workgroups
-  // [0, ceil(nh / disp_heavy_epb)) take disp_heavy_epb heavy envs each (1: a heavy env has a wave to itself), the following ones
-  // EPB light envs each; at its end every env registers itself in disp_out for the NEXT launch (heavy = a collider on or within
-  // KM_NEAR_MARGIN of the cube: the coupled Newton loop is on or about to start), and workgroup 0 clears the counters of disp_zero
-  // (the table after next).  Three tables rotate on the host; any partition of the env ids is a valid table, and an env's bits
-  // depend neither on its slot nor on its wave-mates.  (The round-5 EXPERIMENT, KMANIP_HEAVY_DISPATCH=1; the product is SPREAD, below.)
   // SPREAD (the default of the single-arm launches of two or four envs per wave; kmanip_api.hip): one byte per env -- bit 0 "heavy at
   // the end of its last step", bits 1-2 a cost score of the others (spread_pick) -- written by every step into spread_out and read by the
   // next launch from spread_in.  A wave looks at the 64 flags of ITS block of 64 consecutive envs (three ballots) and deals the block's
@@ -532,12 +523,6 @@ struct KDeviceState {
   double near_margin;   // "near the cube" for the heavy flag / the sort's proximity bit (KM_NEAR_MARGIN; KMANIP_NEAR_MARGIN, A/B)
   const uint8_t* spread_in;
   uint8_t* spread_out;
-  int spread_table;     // which score the flags carry (KMANIP_SPREAD_TABLE, A/B): 3 = both bits (default), 2 = both as one class, 1 = the table bit, 0 = none
-  const int32_t* disp_in;
-  int32_t* disp_out;
-  int32_t* disp_zero;
-  int disp_cap;         // at most this many envs are dispatched as heavy (the grid is sized for it); the rest of them as light
-  int disp_heavy_epb;   // heavy envs per wave (1 | 2 | 4)
   // per-env physics parameters (kmanip_set_env_params): double[KM_EP_N][N], NULL = the compiled model (the default kernels);
   // ep_range: device lo[KM_EP_N], hi[KM_EP_N] of ranges mode (every reset redraws the env's values), NULL = explicit values
   double* envp;
@@ -550,7 +535,8 @@ struct KDeviceState {
 
 // fills dm->staged (device memory) for the model's link-count class; kmanip_create, once
 void kmanip_launch_prepare_model(KDeviceModel* dm, const KModelDesc& hd, hipStream_t stream);
-void kmanip_launch_ik_coop(const KDeviceModel* dm, const KModelDesc& hd, const KDeviceState& st, const float* act,
+// ppb: problems per workgroup (KMANIP_IK_PPB, A/B), 0 = chosen from the launch width
+void kmanip_launch_ik_coop(const KDeviceModel* dm, const KModelDesc& hd, const KDeviceState& st, const float* act, int ppb,
                            hipStream_t stream);
 void kmanip_launch_ik_coop_standalone(const KDeviceModel* dm, const KModelDesc& hd, int arm, int n, double* qpos_env_major,
                                       const double* goal_pos, const double* goal_quat, double* q_out, int32_t* nfev,
@@ -559,10 +545,11 @@ void kmanip_launch_ik_eval_coop(const KDeviceModel* dm, const KModelDesc& hd, in
                                 const double* goal_pos, const double* goal_quat, double* res, double* jac, hipStream_t stream);
 // act != NULL: the decode + IK of before_step run inside k_step (product path); NULL: they already ran
 // nchunk > 1 (act != NULL only): that many control steps per launch, act / obs / reward / done laid out [nchunk][num_envs][..]
+// epb: envs per wave (km_step_epb / km_pick_epb)
 void kmanip_launch_step(const KDeviceModel* dm, const KModelDesc& hd, const KDeviceState& st, const float* act, double* obs,
-                        double* reward, uint8_t* done, int nchunk, hipStream_t stream);
+                        double* reward, uint8_t* done, int nchunk, int epb, hipStream_t stream);
 void kmanip_launch_reset(const KDeviceModel* dm, const KModelDesc& hd, const KDeviceState& st, const uint8_t* mask,
-                         int use_done_bits, double* obs, hipStream_t stream);
+                         int use_done_bits, double* obs, int epb, hipStream_t stream);
 void kmanip_launch_observe(const KDeviceModel* dm, const KModelDesc& hd, const KDeviceState& st, double* obs, double* reward,
                            hipStream_t stream);
 void kmanip_launch_render_depth(const KDeviceModel* dm, const KDeviceState& st, int cam, int height, int width, float* depth,
@@ -571,18 +558,17 @@ void kmanip_launch_render_depth(const KDeviceModel* dm, const KDeviceState& st, 
 struct KRenderJobs { int n; int cam[KM_MAX_CAMS], height[KM_MAX_CAMS], width[KM_MAX_CAMS]; uint8_t* rgb[KM_MAX_CAMS]; };
 void kmanip_launch_render_rgb(const KDeviceModel* dm, const KDeviceState& st, const KRenderJobs& jobs, hipStream_t stream);
 // envs per workgroup (= per wave) of a step / reset launch: as many waves as the chip has SIMD slots for, but no more lanes idle than
-// needed; the chunked kernel exists for the full shape only.  Shared by the launchers (kmanip_dyn.hip) and by the host code that
-// has to know the LAST launch's shape (kmanip_api.hip: the slot -> env maps of kmanip_dbg_wave_clocks).
+// needed; the chunked kernel exists for the full shape only.  kmanip_api.hip picks it and passes it to the launchers, and rebuilds
+// the LAST launch's slot -> env maps (kmanip_dbg_wave_clocks) from the same value.
+// forced: the handle's KMANIP_EPB (1 | 2 | 4; diagnostics: tests exercise every launch shape), 0 = this choice
 #define KM_TARGET_WAVES 1024   // 256 CUs x 4 SIMDs: below this many workgroups, fewer envs per wave fills more SIMDs
-static inline int km_pick_epb(int num_envs, int max_epb) {
-  const char* e = getenv("KMANIP_EPB");              // diagnostic override (tests exercise every launch shape)
-  const int forced = e ? atoi(e) : 0;
+static inline int km_pick_epb(int num_envs, int max_epb, int forced) {
   if (forced > 0) return forced < max_epb ? forced : max_epb;
   int epb = max_epb;
   while (epb > 1 && (num_envs + epb - 1) / epb < KM_TARGET_WAVES) epb >>= 1;
   return epb;
 }
-static inline int km_step_epb(int num_envs, int max_epb, int nchunk) { return nchunk > 1 ? max_epb : km_pick_epb(num_envs, max_epb); }
+static inline int km_step_epb(int num_envs, int max_epb, int nchunk, int forced) { return nchunk > 1 ? max_epb : km_pick_epb(num_envs, max_epb, forced); }
 // slot_env[s] = the env wave slot s handles, envs ordered by the cost their LAST step predicts, heaviest first (LPT dispatch)
 struct KCostWeights { int ik, work, coupled, armtab, cubetab, binw; };
 void kmanip_launch_sort_envs(const KDeviceState& st, int32_t* slot_env, const KCostWeights& w, hipStream_t stream);

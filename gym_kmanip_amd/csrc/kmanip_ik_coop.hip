@@ -40,18 +40,17 @@ __global__ void k_prepare_coop(const KDeviceModel* __restrict__ dm, KDeviceState
   st.qpos_ik[i] = st.qpos[i];
 }
 
-void kmanip_launch_ik_coop(const KDeviceModel* dm, const KModelDesc& hd, const KDeviceState& st, const float* act,
+void kmanip_launch_ik_coop(const KDeviceModel* dm, const KModelDesc& hd, const KDeviceState& st, const float* act, int ppb,
                            hipStream_t stream) {
   int n0 = st.num_envs * hd.nlink;
   hipLaunchKernelGGL(k_prepare_coop, dim3((n0 + 255) / 256), dim3(256), 0, stream, dm, st);
   int narm_slots = (hd.arm_present[1]) ? 2 : 1;
   int nprob = st.num_envs * narm_slots;
   int nik = hd.arm_nq[0] ? hd.arm_nq[0] : hd.arm_nq[1];
-  static int forced = -1;
-  if (forced < 0) { const char* e = getenv("KMANIP_IK_PPB"); forced = e ? atoi(e) : 0; }
-  int ppb = PPW;
-  if (forced > 0) ppb = forced;
-  else while (ppb > 2 && (nprob + ppb - 1) / ppb < 1024) ppb >>= 1;   // 1024 = SIMDs on the chip
+  if (ppb <= 0) {
+    ppb = PPW;
+    while (ppb > 2 && (nprob + ppb - 1) / ppb < 1024) ppb >>= 1;   // 1024 = SIMDs on the chip
+  }
 #define KM_IK_LAUNCH(NN, PP) hipLaunchKernelGGL((k_before_step_coop<NN, PP>), dim3((nprob + PP - 1) / PP), dim3(64), 0, stream, dm, st, act, nprob)
   if (nik == 7) { if (ppb >= 4) KM_IK_LAUNCH(7, 4); else KM_IK_LAUNCH(7, 2); }
   else { if (ppb >= 4) KM_IK_LAUNCH(6, 4); else KM_IK_LAUNCH(6, 2); }

@@ -212,9 +212,13 @@ KMANIP_API int kmanip_create(const KModelDesc* desc, int num_envs, int device, u
  * tests compare shards, launch shapes and orders bit for bit).  A step is ONE launch of single-wave workgroups holding 4 (10-link
  * models) or 2 (20-link models) envs each.  When a two-arm handle has more waves than the GPU has SIMD slots (more than 2048 envs),
  * kmanip_step first orders the envs by the cost their last step predicts and dispatches the longest waves first (k_sort_envs, one
- * small extra launch).  Diagnostic environment variables, read at create: KMANIP_COST_SORT=0/1 (force that order
- * off / on), KMANIP_COST_W (its weights), KMANIP_EPB (envs per wave), KMANIP_IK_UNFUSED=1 (before_step as its own launch),
- * KMANIP_NO_BLOCK_SPLIT=1 (two-arm inertia as one block), KMANIP_WAVE_CLOCKS=1 (per-wave cycle counts for tests/tools/wave_times.py).
+ * small extra launch).  A single-arm Newton handle of 2048 or more envs (a multiple of 64) chooses every wave's
+ * envs so that no wave holds two predicted to be heavy (SPREAD).  Diagnostic environment variables, each read once
+ * by kmanip_create: KMANIP_SPREAD=0 (the identity map instead of SPREAD), KMANIP_COST_SORT=0/1 (force
+ * the cost order off / on), KMANIP_COST_W (its weights), KMANIP_NEAR_MARGIN (what counts as near the cube for both),
+ * KMANIP_EPB=1/2/4 (envs per wave), KMANIP_IK_UNFUSED=1 (before_step as its own launch), KMANIP_IK_PPB (problems per workgroup of
+ * that launch), KMANIP_NO_BLOCK_SPLIT=1 (two-arm inertia as one block), KMANIP_WAVE_CLOCKS=1 (per-wave cycle counts for
+ * tests/tools/wave_times.py).
  * Throughput note: one batch's launch ends with its slowest wave and leaves about half the SIMD time idle; handles are
  * independent and every entry point takes the caller's stream, so two or more batches kept in flight on different streams fill
  * it (gym_kmanip_amd/pipeline.py). */

@@ -104,6 +104,19 @@ def test_asm_phase_mix_charges_an_instruction_to_the_phase_that_called_it(tmp_pa
         "    }",
         "  }",
         "}"]) + "\n")
+    # a second phase file: step1_products of kmanip_dyn_env.hpp (line 6 of kmanip_dyn.hip is another call) calls kmanip_dyn_tree.hpp
+    (tmp_path / "kmanip_dyn_tree.hpp").write_text("\n".join([
+        "__device__ __forceinline__ void invert_mass_blocks(int s) {",              # 1
+        "  x = 1 / x;",                                                              # 2
+        "}"]) + "\n")
+    (tmp_path / "kmanip_dyn_env.hpp").write_text("\n".join([
+        "// kmanip_dyn_env.hpp",                                                     # 1
+        "",                                                                          # 2
+        "",                                                                          # 3
+        "__device__ __forceinline__ void step1_products(int s) {",                   # 4
+        "  fk_parallel<NL, G>(w, lm, sub);",                                         # 5
+        "  invert_mass_blocks<NL, G>(w, sub, cr, split, pf);",                       # 6
+        "}"]) + "\n")
     lst = tmp_path / "k.s"
     lst.write_text("\n".join([
         "_Z6k_stepTEST:",
@@ -120,6 +133,8 @@ def test_asm_phase_mix_charges_an_instruction_to_the_phase_that_called_it(tmp_pa
         "\tv_fma_f64 v[0:1], v[0:1], v[2:3], v[4:5]",
         "\t.loc\t2 2 3 ; ./kmanip_ik_coop.hpp:2:3 @[ kmanip_dyn.hip:9:3 ]",                          # the IK's set-up
         "\tv_accvgpr_read_b32 v7, a3",
+        "\t.loc\t3 2 3 ; ./kmanip_dyn_tree.hpp:2:3 @[ ./kmanip_dyn_env.hpp:6:3 @[ kmanip_dyn.hip:10:3 ] ]",  # helper <- invert_mass (a header)
+        "\tv_rcp_f64_e32 v[8:9], v[0:1]",
         "other_kernel:",
         "\tv_mul_f64 v[0:1], v[0:1], 2.0"]) + "\n")
     out = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "asm_phase_mix.py"), str(lst), "k_stepTEST", "--src=%s" % src,
@@ -130,10 +145,11 @@ def test_asm_phase_mix_charges_an_instruction_to_the_phase_that_called_it(tmp_pa
         if "|" in ln and not ln.startswith(("phase", "TOTAL", "SUM")):
             name = ln.split("|")[0].rsplit(None, 1)[0].strip()
             rows.setdefault(name, ln)
-    assert set(rows) >= {"fk", "build_constraints", "integrate", "IK: per trial point", "IK: trf set-up"}, out.stdout
+    assert set(rows) >= {"fk", "build_constraints", "integrate", "IK: per trial point", "IK: trf set-up", "invert_mass"}, out.stdout
     cols = lambda name: [int(x) for x in rows[name].split("|")[1].split()]
     # classes: f64 mov dppmov sel agpr lane cmp valu lds vmem salu nop wait br
     assert cols("fk")[:3] == [1, 0, 1] and cols("build_constraints")[3] == 1 and cols("build_constraints")[8] == 1 and cols("build_constraints")[12] == 1
     assert cols("integrate")[0] == 1 and cols("IK: per trial point")[0] == 1 and cols("IK: trf set-up")[4] == 1
+    assert cols("invert_mass")[0] == 1 and cols("build_constraints")[0] == 0
     assert "TOTAL" in out.stdout and "other_kernel" not in out.stdout
     assert "VALU instructions per wave and control step, estimated: 29" in out.stdout        # fk (2 VALU) x 10 + trial (1) x 9

@@ -54,7 +54,9 @@ def func_ranges(src):
 
 
 here = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "gym_kmanip_amd", "csrc")
-for fname in ("kmanip_dyn.hip", "kmanip_ik_coop.hpp", "kmanip_device.hpp"):
+FILES = ("kmanip_dyn.hip", "kmanip_dyn_ws.hpp", "kmanip_dyn_tree.hpp", "kmanip_dyn_constraints.hpp", "kmanip_dyn_newton.hpp",
+         "kmanip_dyn_env.hpp", "kmanip_ik_coop.hpp", "kmanip_device.hpp")
+for fname in FILES:
     st = func_ranges(os.path.join(here, fname))
     agg = collections.Counter()
     for (f, l), c in counts.items():

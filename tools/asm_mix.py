@@ -85,7 +85,9 @@ here = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "gym_kmani
 cols = ["f64", "mov", "dppmov", "sel", "agpr", "lane", "perm", "cmp64", "cmp", "valu", "lds", "vmem", "salu", "br", "nop", "wait"]
 tot = collections.Counter()
 agg = collections.defaultdict(collections.Counter)
-for fname in ("kmanip_dyn.hip", "kmanip_ik_coop.hpp", "kmanip_device.hpp"):
+FILES = ("kmanip_dyn.hip", "kmanip_dyn_ws.hpp", "kmanip_dyn_tree.hpp", "kmanip_dyn_constraints.hpp", "kmanip_dyn_newton.hpp",
+         "kmanip_dyn_env.hpp", "kmanip_ik_coop.hpp", "kmanip_device.hpp")
+for fname in FILES:
     st = func_ranges(os.path.join(here, fname))
     for (f, l), c in counts.items():
         if f != fname:
@@ -99,7 +101,7 @@ for fname in ("kmanip_dyn.hip", "kmanip_ik_coop.hpp", "kmanip_device.hpp"):
         agg[name].update(c)
         tot.update(c)
 for (f, l), c in counts.items():
-    if f not in ("kmanip_dyn.hip", "kmanip_ik_coop.hpp", "kmanip_device.hpp"):
+    if f not in FILES:
         agg["<" + f + ">"].update(c)
         tot.update(c)
 print("%-28s %6s | " % ("function", "total") + " ".join("%6s" % c for c in cols))

@@ -8,6 +8,9 @@ solve / integrate / tail ...), refined by the call site in step1_products, solve
 at its pf.ph() stamps: H build | factorisation | solves | line-search set-up | line search | evaluation).  Helpers inlined
 everywhere (dppfma*, gsum_n, frcp, ...) are thereby charged to the phase that called them, which per-function tables cannot do.
 
+The phases live in kmanip_dyn.hip and the kmanip_dyn_*.hpp headers it includes (any kmanip_dyn*.hip / kmanip_dyn*.hpp next to --src);
+each frame's line is looked up in its own file.
+
 Usage: tools/asm_phase_mix.py <listing.s> <kernel-symbol-substring> [--src gym_kmanip_amd/csrc/kmanip_dyn.hip] [--weights k=v,...]
 """
 import collections
@@ -17,6 +20,7 @@ import sys
 
 CLASSES = ["f64", "mov", "dppmov", "sel", "agpr", "lane", "cmp", "valu", "lds", "vmem", "salu", "nop", "wait", "br"]
 VALU = ["f64", "mov", "dppmov", "sel", "agpr", "lane", "cmp", "valu"]
+DYN_FILE = re.compile(r"^kmanip_dyn[A-Za-z0-9_]*\.(?:hip|hpp)$")      # the files of the step kernel's phases
 
 
 def klass(op, s):
@@ -59,14 +63,15 @@ def newton_stamps(src):
     return out
 
 
-def phase_of(chain, src, stamps, fn_of):
-    """chain: [(file, line)] innermost first.  Returns the phase name."""
-    frames = [(f, l) for f, l in reversed(chain) if f == "kmanip_dyn.hip"]           # outermost first
+def phase_of(chain, srcs):
+    """chain: [(file, line)] innermost first; srcs: {file: Source}.  Returns the phase name."""
+    frames = [(f, l) for f, l in reversed(chain) if f in srcs]           # outermost first
     top = None
     loop = None
     for f, l in frames:
-        text = src[l - 1] if 0 < l <= len(src) else ""
-        fn = fn_of(l)
+        src = srcs[f]
+        text = src.lines[l - 1] if 0 < l <= len(src.lines) else ""
+        fn = src.fn_of(l)
         if fn == "k_step":
             if "coop_before_step" in text:
                 # refined by where in coop_trf (kmanip_ik_coop.hpp) the instruction sits: set-up | once per outer iteration
@@ -104,7 +109,7 @@ def phase_of(chain, src, stamps, fn_of):
         if fn == "newton_loop_sl" and loop:
             # stamps in source order: 9 (after H build), 10 (after factorisation; several sites), 11 (after the solves / the plain
             # direction), 12 (after ls set-up), 13 (after the line search), 14 (after the evaluation)
-            s9, s10, s11, s12, s13, s14 = (stamps[k] for k in (9, 10, 11, 12, 13, 14))
+            s9, s10, s11, s12, s13, s14 = (src.stamps[k] for k in (9, 10, 11, 12, 13, 14))
             if l <= min(s11): sub = "plain direction / entry"
             elif l <= max(s9): sub = "H build"
             elif l <= max(s10): sub = "factorisation"
@@ -133,31 +138,40 @@ def ik_lines(path):
               trial_end=next(i for i, l in enumerate(src, 1) if i > lo and "pf->ph(37)" in l))
 
 
+class Source:
+    """one file of the step kernel: its lines, newton_loop_sl's stamps in it and its line -> function map"""
+
+    def __init__(self, path):
+        self.lines = open(path).read().split("\n")
+        self.stamps = newton_stamps(self.lines)
+        # function of a source line: the nearest preceding "__device__ ... name(" / "__global__ ... name(" definition
+        self.starts = []
+        for i, ln in enumerate(self.lines, 1):
+            if not re.match(r"^(?:__device__|__global__|static)\b", ln) or ln.startswith("static_assert") or ln.rstrip().endswith(";"):
+                continue
+            names = [n for n in re.findall(r"\b([A-Za-z_0-9]+)\s*\(", ln) if n not in ("__launch_bounds__", "__attribute__")]
+            if names:
+                self.starts.append((i, names[0]))
+
+    def fn_of(self, line):
+        name = None
+        for i, n in self.starts:
+            if i > line:
+                break
+            name = n
+        return name
+
+
 def main():
     args = [a for a in sys.argv[1:] if not a.startswith("--")]
     path, sym = args[0], args[1]
     opt = dict(a[2:].split("=", 1) if "=" in a else (a[2:], "1") for a in sys.argv[1:] if a.startswith("--"))
     here = os.path.dirname(os.path.abspath(__file__))
     src_path = opt.get("src", os.path.join(here, "..", "gym_kmanip_amd", "csrc", "kmanip_dyn.hip"))
-    src = open(src_path).read().split("\n")
-    stamps = newton_stamps(src)
-    ik_lines(os.path.join(os.path.dirname(src_path), "kmanip_ik_coop.hpp"))
-    # function of a source line: the nearest preceding "__device__ ... name(" / "__global__ ... name(" definition
-    starts = []
-    for i, ln in enumerate(src, 1):
-        if not re.match(r"^(?:__device__|__global__|static)\b", ln) or ln.startswith("static_assert") or ln.rstrip().endswith(";"):
-            continue
-        names = [n for n in re.findall(r"\b([A-Za-z_0-9]+)\s*\(", ln) if n not in ("__launch_bounds__", "__attribute__")]
-        if names:
-            starts.append((i, names[0]))
-
-    def fn_of(line):
-        name = None
-        for i, n in starts:
-            if i > line:
-                break
-            name = n
-        return name
+    src_dir = os.path.dirname(os.path.abspath(src_path))
+    srcs = {f: Source(os.path.join(src_dir, f)) for f in sorted(os.listdir(src_dir)) if DYN_FILE.match(f)}
+    srcs.setdefault(os.path.basename(src_path), Source(src_path))
+    ik_lines(os.path.join(src_dir, "kmanip_ik_coop.hpp"))
 
     counts = collections.defaultdict(collections.Counter)
     inside = False
@@ -176,7 +190,7 @@ def main():
         if not s or s.startswith((".", ";", "//")) or s.endswith(":"):
             continue
         op = s.split()[0]
-        ph = phase_of(chain or [], src, stamps, fn_of)
+        ph = phase_of(chain or [], srcs)
         counts[ph][klass(op, s)] += 1
 
     weights = {}
