@@ -54,6 +54,14 @@ struct KHandle_ {
   double* envp_buf = nullptr;       // [KM_EP_N][N]
   double* ep_range_buf = nullptr;   // lo[KM_EP_N], hi[KM_EP_N]
   int* ep_flag = nullptr;           // validation result of kmanip_set_env_params
+  // per-env visual parameters (kmanip_set_visual_params): `vis` is what the render launchers get (all NULL:
+  // the default kernels); vis.vp points at vp_buf while explicit values are in force, vis.range at vp_range_buf in ranges mode
+  KVisArgs vis{};
+  double* vp_buf = nullptr;         // [KM_VP_N][N]
+  double* vp_range_buf = nullptr;   // lo[KM_VP_N], hi[KM_VP_N]
+  int* vp_flag = nullptr;           // validation result of kmanip_set_visual_params
+  int32_t* ep_snap[2] = {nullptr, nullptr};   // the episode counters a snapshot took in ranges mode (a render of that slot draws from them)
+  bool ep_snap_ok[2] = {false, false};
   std::vector<void*> allocs;
 };
 
@@ -227,6 +235,35 @@ __global__ void k_ep_fill(double* __restrict__ p, int n, double v0, double v1, d
   }
 }
 static int ep_grid(int n) { return (n + 255) / 256 < 1024 ? (n + 255) / 256 : 1024; }
+
+// ---- per-env visual parameters (include/kmanip.h KM_VP_*)
+__host__ __device__ static inline double vp_default(int k) {
+  if (k < KM_VP_TABLE_RGB) return k == KM_VP_CUBE_RGB ? 1.0 : 0.0;                 // cube 1 0 0
+  if (k < KM_VP_ROBOT_RGB) return 0.2;                                             // table .2 .2 .2
+  if (k < KM_VP_BACKGROUND_RGB) return 0.647059;                                   // finger spheres
+  if (k < KM_VP_AMBIENT) return 0.0;                                               // background black
+  if (k == KM_VP_AMBIENT || k == KM_VP_HEADLIGHT) return 0.4;
+  if (k == KM_VP_DIRECTIONAL) return 1.0;
+  return 0.0;                                                                      // camera offset
+}
+// the limits every value must meet (the ranges' lo and hi as well): colours in [0, 1], light terms >= 0, |offset| <= 0.25 m, finite
+__host__ __device__ static inline bool vp_value_ok(int k, double v) {
+  if (!(v - v == 0.0)) return false;           // NaN or infinite
+  if (k < KM_VP_AMBIENT) return v >= 0.0 && v <= 1.0;
+  if (k < KM_VP_CAM_OFFSET) return v >= 0.0;
+  return v >= -0.25 && v <= 0.25;
+}
+__global__ void k_vp_validate(const double* __restrict__ p, int n, int* __restrict__ bad) {
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+    bool ok = true;
+    for (int k = 0; k < KM_VP_N; k++) ok = ok && vp_value_ok(k, p[(size_t)k * n + i]);
+    if (!ok) atomicOr(bad, 1);
+  }
+}
+__global__ void k_vp_fill_defaults(double* __restrict__ p, int n) {
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x)
+    for (int k = 0; k < KM_VP_N; k++) p[(size_t)k * n + i] = vp_default(k);
+}
 const char* kmanip_version(void) { return KM_VERSION; }
 
 int kmanip_create(const KModelDesc* desc, int num_envs, int device, uint64_t seed, int64_t env_id_offset, KHandle* out) {
@@ -393,6 +430,14 @@ int kmanip_observe(KHandle h, double* obs_dev, double* reward_dev, void* stream)
   return 0;
 }
 
+// the render launchers' visual inputs for a render of source `src` (-1 live state, 0 / 1 a snapshot): in ranges mode the draw
+// uses the episode counters of that source (a snapshot taken before ranges mode was on has none: the live ones)
+static KVisArgs vis_args(KHandle h, int src) {
+  KVisArgs v = h->vis;
+  if (v.range) v.episode = (src >= 0 && h->ep_snap_ok[src]) ? h->ep_snap[src] : h->st.episode;
+  return v;
+}
+
 static int step_impl(KHandle h, int nchunk, const float* act_dev, double* obs_dev, double* reward_dev, uint8_t* done_dev, void* stream) {
   if (!h) { g_create_error = "kmanip_step: null handle"; return -1; }
   if (!act_dev || !obs_dev || !reward_dev || !done_dev) { h->err = "kmanip_step: null buffer"; return -1; }
@@ -427,7 +472,7 @@ static int step_impl(KHandle h, int nchunk, const float* act_dev, double* obs_de
   if (tm) HIPCHK(h, hipEventRecord(ev[2], s));
   const bool render = h->step_depth && nchunk == 1;
   if (render)                             // the observation's camera branch (env_sim.py:140-145) of the state just produced
-    kmanip_launch_render_depth(h->dmodel, h->st, h->step_cam, h->step_h, h->step_w, h->step_depth, s);
+    kmanip_launch_render_depth(h->dmodel, h->st, h->step_cam, h->step_h, h->step_w, h->step_depth, vis_args(h, -1), s);
   if (tm) {
     if (render) HIPCHK(h, hipEventRecord(ev[3], s));
     h->ev_render[h->timed_steps] = render;
@@ -452,7 +497,7 @@ int kmanip_render_depth(KHandle h, int cam, int height, int width, float* depth_
   KM_ENTER(h);
   KDeviceState st = h->st;
   if (h->render_src >= 0) st.qpos = h->qpos_snap[h->render_src];
-  kmanip_launch_render_depth(h->dmodel, st, cam, height, width, depth_dev, (hipStream_t)stream);
+  kmanip_launch_render_depth(h->dmodel, st, cam, height, width, depth_dev, vis_args(h, h->render_src), (hipStream_t)stream);
   HIPCHK(h, hipGetLastError());
   return 0;
 }
@@ -469,6 +514,18 @@ int kmanip_snapshot_render_state(KHandle h, int slot, void* stream) {
     h->qpos_snap[slot] = (double*)p;
   }
   HIPCHK(h, hipMemcpyAsync(h->qpos_snap[slot], h->st.qpos, bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+  // visual ranges mode: the draw of the snapshot's images uses the episode of the snapshot's step, not of a later auto-reset
+  h->ep_snap_ok[slot] = false;
+  if (h->vis.range) {
+    if (!h->ep_snap[slot]) {
+      void* p = nullptr;
+      HIPCHK(h, hipMalloc(&p, sizeof(int32_t) * (size_t)h->num_envs));
+      h->allocs.push_back(p);
+      h->ep_snap[slot] = (int32_t*)p;
+    }
+    HIPCHK(h, hipMemcpyAsync(h->ep_snap[slot], h->st.episode, sizeof(int32_t) * (size_t)h->num_envs, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    h->ep_snap_ok[slot] = true;
+  }
   return 0;
 }
 
@@ -494,7 +551,7 @@ int kmanip_render_rgb_multi(KHandle h, int ncam, const int* cams, const int* hei
   KM_ENTER(h);
   KDeviceState st = h->st;
   if (h->render_src >= 0) st.qpos = h->qpos_snap[h->render_src];
-  kmanip_launch_render_rgb(h->dmodel, st, jobs, (hipStream_t)stream);
+  kmanip_launch_render_rgb(h->dmodel, st, jobs, vis_args(h, h->render_src), (hipStream_t)stream);
   // kernel timing (kmanip_enable_timing): the camera observations rendered right after a timed step are that step's render leg --
   // its start is the event the step recorded after k_step, so the render costs the stream ONE more event, not a pair around it
   // (a render of a SNAPSHOT runs behind the steps, on a stream of its own: it is no leg of the step's stream)
@@ -734,6 +791,87 @@ int kmanip_set_env_param_ranges(KHandle h, const double* lo, const double* hi) {
   }
   h->st.envp = h->envp_buf;
   h->st.ep_range = h->ep_range_buf;
+  return 0;
+}
+
+static hipError_t vp_alloc(KHandle h) {
+  auto one = [&](void** p, size_t bytes) -> hipError_t {
+    if (*p) return hipSuccess;
+    hipError_t r = hipMalloc(p, bytes);
+    if (r == hipSuccess) h->allocs.push_back(*p);
+    return r;
+  };
+  hipError_t r = one((void**)&h->vp_buf, sizeof(double) * KM_VP_N * (size_t)h->num_envs);
+  if (r == hipSuccess) r = one((void**)&h->vp_range_buf, sizeof(double) * 2 * KM_VP_N);
+  if (r == hipSuccess) r = one((void**)&h->vp_flag, sizeof(int));
+  return r;
+}
+
+int kmanip_set_visual_params(KHandle h, const double* params_dev, void* stream) {
+  if (!h) return -1;
+  KM_ENTER(h);
+  // a render in flight on any stream may read the buffers: every change waits for the device
+  if (!params_dev) { HIPCHK(h, hipDeviceSynchronize()); h->vis = KVisArgs{}; return 0; }
+  hipStream_t s = (hipStream_t)stream;
+  HIPCHK(h, vp_alloc(h));
+  int bad = 0;
+  HIPCHK(h, hipMemsetAsync(h->vp_flag, 0, sizeof(int), s));
+  hipLaunchKernelGGL(k_vp_validate, dim3(ep_grid(h->num_envs)), dim3(256), 0, s, params_dev, h->num_envs, h->vp_flag);
+  HIPCHK(h, hipGetLastError());
+  HIPCHK(h, hipMemcpyAsync(&bad, h->vp_flag, sizeof(int), hipMemcpyDeviceToHost, s));
+  HIPCHK(h, hipStreamSynchronize(s));
+  if (bad) {
+    h->err = "kmanip_set_visual_params: every env needs colours in [0, 1], finite light terms >= 0 and camera offsets within +-0.25 m";
+    return -2;
+  }
+  HIPCHK(h, hipDeviceSynchronize());
+  HIPCHK(h, hipMemcpy(h->vp_buf, params_dev, sizeof(double) * KM_VP_N * (size_t)h->num_envs, hipMemcpyDeviceToDevice));
+  HIPCHK(h, hipDeviceSynchronize());
+  h->vis = KVisArgs{h->vp_buf, nullptr, nullptr};
+  return 0;
+}
+
+int kmanip_get_visual_params(KHandle h, double* params_dev, void* stream) {
+  if (!h || !params_dev) { if (h) h->err = "kmanip_get_visual_params: params_dev is NULL"; return -1; }
+  KM_ENTER(h);
+  hipStream_t s = (hipStream_t)stream;
+  if (h->vis.range) kmanip_launch_vp_draw(h->st, vis_args(h, -1), params_dev, s);
+  else if (h->vis.vp) HIPCHK(h, hipMemcpyAsync(params_dev, h->vis.vp, sizeof(double) * KM_VP_N * (size_t)h->num_envs, hipMemcpyDeviceToDevice, s));
+  else hipLaunchKernelGGL(k_vp_fill_defaults, dim3(ep_grid(h->num_envs)), dim3(256), 0, s, params_dev, h->num_envs);
+  HIPCHK(h, hipGetLastError());
+  return 0;
+}
+
+int kmanip_set_visual_param_ranges(KHandle h, const double* lo, const double* hi) {
+  if (!h) return -1;
+  if (!lo && !hi) {
+    if (!h->vis.range) return 0;
+    // ranges mode off: every env keeps its current episode's draw, as explicit values
+    KM_ENTER(h);
+    HIPCHK(h, hipDeviceSynchronize());
+    kmanip_launch_vp_draw(h->st, vis_args(h, -1), h->vp_buf, nullptr);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipDeviceSynchronize());
+    h->vis = KVisArgs{h->vp_buf, nullptr, nullptr};
+    return 0;
+  }
+  if (!lo || !hi) { h->err = "kmanip_set_visual_param_ranges: lo and hi must both be NULL or both be set"; return -1; }
+  for (int k = 0; k < KM_VP_N; k++) {
+    if (!vp_value_ok(k, lo[k]) || !vp_value_ok(k, hi[k]) || lo[k] > hi[k]) {
+      h->err = "kmanip_set_visual_param_ranges: parameter " + std::to_string(k) + " needs finite lo <= hi within its limits "
+               "(colours in [0, 1], light terms >= 0, camera offsets within +-0.25 m)";
+      return -2;
+    }
+  }
+  KM_ENTER(h);
+  HIPCHK(h, vp_alloc(h));
+  HIPCHK(h, hipDeviceSynchronize());
+  double r[2 * KM_VP_N];
+  for (int k = 0; k < KM_VP_N; k++) { r[k] = lo[k]; r[KM_VP_N + k] = hi[k]; }
+  HIPCHK(h, hipMemcpy(h->vp_range_buf, r, sizeof r, hipMemcpyHostToDevice));
+  HIPCHK(h, hipDeviceSynchronize());
+  h->vis = KVisArgs{nullptr, h->vp_range_buf, nullptr};
+  h->ep_snap_ok[0] = h->ep_snap_ok[1] = false;
   return 0;
 }
 

@@ -494,8 +494,28 @@ __device__ __host__ inline double u53(uint32_t hi, uint32_t lo) {
 // (a 24-bit signed integer times a power of two), so the device and the CPU oracle produce identical bits
 __device__ __host__ inline float km_action_from_u32(uint32_t r) { return (float)((int32_t)(r >> 8) - 8388608) * (1.0f / 8388608.0f); }
 // counter word 3 of the action stream: the cube spawn uses 0 and 1 (reset_env), the per-env parameter draw of ranges mode
-// KM_EP_CTR3 + 0 and + 1 = 2 and 3 (kmanip.h), actions 0x10000 + 4 * step + block
+// KM_EP_CTR3 + 0 and + 1 = 2 and 3 (kmanip.h), the visual parameter draw KM_VP_CTR3 + 0 .. 8 = 0x100 .. 0x108 (km_vp_draw_pair),
+// actions 0x10000 + 4 * step + block
 #define KM_ACT_CTR3(step, blk) (0x10000u + 4u * (uint32_t)(step) + (uint32_t)(blk))
+
+// Visual parameters of ranges mode (include/kmanip.h kmanip_set_visual_param_ranges): values 2j and 2j + 1 of global env genv in
+// `episode`, lo + (hi - lo) * u with the product rounded before the sum; u from words (0, 1) and (2, 3) of the Philox block with
+// counter word 3 = KM_VP_CTR3 + j.  range = lo[KM_VP_N], hi[KM_VP_N].  The render kernels and kmanip_get_visual_params both call it.
+__device__ __host__ inline void km_vp_draw_pair(uint64_t seed, int64_t genv, int32_t episode, int j, const double* range, double* out) {
+#pragma clang fp contract(off)
+  const uint32_t key[2] = {(uint32_t)seed, (uint32_t)(seed >> 32)};
+  const uint32_t ctr[4] = {(uint32_t)genv, (uint32_t)((uint64_t)genv >> 32), (uint32_t)episode, KM_VP_CTR3 + (uint32_t)j};
+  uint32_t o[4];
+  philox4x32_10(ctr, key, o);
+  const double u0 = u53(o[0], o[1]), u1 = u53(o[2], o[3]);
+  const int k = 2 * j;
+  const double p0 = (range[KM_VP_N + k] - range[k]) * u0;
+  out[0] = range[k] + p0;
+  if (k + 1 < KM_VP_N) {
+    const double p1 = (range[KM_VP_N + k + 1] - range[k + 1]) * u1;
+    out[1] = range[k + 1] + p1;
+  }
+}
 
 // Device state, struct-of-arrays over envs: element (k, env) of an [n_k, num_envs] array is at
 // k * num_envs + env, so a wave reading component k for consecutive envs is fully coalesced.
@@ -552,11 +572,20 @@ void kmanip_launch_reset(const KDeviceModel* dm, const KModelDesc& hd, const KDe
                          int use_done_bits, double* obs, int epb, hipStream_t stream);
 void kmanip_launch_observe(const KDeviceModel* dm, const KModelDesc& hd, const KDeviceState& st, double* obs, double* reward,
                            hipStream_t stream);
+// The render launchers' visual inputs (kmanip_set_visual_params / _ranges), a kernel argument of the VIS
+// kernels only -- never a KDeviceState field: the step kernels' argument stays as it is.  All NULL: the default kernels.
+//   vp       explicit values double[KM_VP_N][N], read at the render's launch
+//   range    lo[KM_VP_N], hi[KM_VP_N] of ranges mode (vp is then NULL): the kernel draws env e's values from episode[e]
+//   episode  the counters the draw uses: the live state's, or the copy a snapshot took (kmanip_snapshot_render_state)
+struct KVisArgs { const double* vp; const double* range; const int32_t* episode; };
+__host__ __device__ inline bool km_vis_on(const KVisArgs& v) { return v.vp != nullptr || v.range != nullptr; }
 void kmanip_launch_render_depth(const KDeviceModel* dm, const KDeviceState& st, int cam, int height, int width, float* depth,
-                                hipStream_t stream);
+                                const KVisArgs& vis, hipStream_t stream);
 // up to KM_MAX_CAMS camera images of every env in ONE launch (grid = envs x jobs): the *Vision observation
 struct KRenderJobs { int n; int cam[KM_MAX_CAMS], height[KM_MAX_CAMS], width[KM_MAX_CAMS]; uint8_t* rgb[KM_MAX_CAMS]; };
-void kmanip_launch_render_rgb(const KDeviceModel* dm, const KDeviceState& st, const KRenderJobs& jobs, hipStream_t stream);
+void kmanip_launch_render_rgb(const KDeviceModel* dm, const KDeviceState& st, const KRenderJobs& jobs, const KVisArgs& vis, hipStream_t stream);
+// ranges mode's values of every env's current episode into out double[KM_VP_N][N] (kmanip_get_visual_params)
+void kmanip_launch_vp_draw(const KDeviceState& st, const KVisArgs& vis, double* out, hipStream_t stream);
 // envs per workgroup (= per wave) of a step / reset launch: as many waves as the chip has SIMD slots for, but no more lanes idle than
 // needed; the chunked kernel exists for the full shape only.  kmanip_api.hip picks it and passes it to the launchers, and rebuilds
 // the LAST launch's slot -> env maps (kmanip_dbg_wave_clocks) from the same value.

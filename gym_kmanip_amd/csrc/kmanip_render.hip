@@ -26,6 +26,11 @@
 //     operations (most of a head / top image); (3) a lane shades FOUR consecutive pixels of a row and stores their 12 bytes as
 //     three dwords (768 contiguous bytes per wave-instruction group); (4) the per-ray divides of the slab and plane tests are
 //     v_rcp_f32 on quantities that are linear in the pixel coordinates.
+// Visual parameters (kmanip_set_visual_params / _ranges): every kernel has a VIS instantiation with one more
+// argument (KVisArgs), launched only while the handle has visual parameters; VIS = false is the default kernel, unchanged.  In the
+// VIS build a few lanes of the second wave load the env's KM_VP_N values (or evaluate their Philox draw) into LDS while the FK
+// loads are in flight; lane 0 adds the camera offset when it builds the camera frame, and the RGB kernel shades with the env's
+// colours and light terms (RgbVis).
 #include "kmanip_device.hpp"
 #include <stdlib.h>
 
@@ -44,7 +49,24 @@ struct RenderPre { int sl, cl, tl; real sp[3], cp[3], tp[3], tanhalf; };
 // Round 6: every global read of the set-up is issued at the top and waited for once -- the joint angle (HBM), the link's constants
 // and its jump table for all four rounds (L2): read where they were used, each round's `jump[k][i]` cost another L2 round trip
 // behind a barrier, and a launch whose 2048 workgroups all start together hides none of it (the 64 x 64 depth render: 8 of 39 us).
-__device__ __forceinline__ void render_fk(const KDeviceModel* dm, const KDeviceState& st, int env, int cam, RenderScene* sc, RenderPre& pre) {
+// lanes KM_VP_LANE0 .. of the VIS kernels: the env's visual parameters into vsv[KM_VP_N] (LDS), explicit values one per lane, the
+// ranges draw one Philox block (two values) per lane
+#define KM_VP_LANE0 96
+__device__ __forceinline__ void render_vis_setup(const KDeviceState& st, const KVisArgs& va, int env, int i, double* vsv) {
+  const int j = i - KM_VP_LANE0;
+  if (va.range) {
+    if (j >= 0 && j < (KM_VP_N + 1) / 2) {
+      double o[2];
+      km_vp_draw_pair(st.seed, st.env_id_offset + env, va.episode[env], j, va.range, o);
+      vsv[2 * j] = o[0];
+      if (2 * j + 1 < KM_VP_N) vsv[2 * j + 1] = o[1];
+    }
+  } else if (j >= 0 && j < KM_VP_N) vsv[j] = va.vp[(size_t)j * st.num_envs + env];
+}
+
+template <bool VIS>
+__device__ __forceinline__ void render_fk(const KDeviceModel* dm, const KDeviceState& st, int env, int cam, RenderScene* sc, RenderPre& pre,
+                                          const KVisArgs& va, double* vsv) {
   const KModelDesc* m = &dm->d;
   const int nl = m->nlink, NE = st.num_envs, i = threadIdx.x;
   const bool on = i < nl;
@@ -73,6 +95,7 @@ __device__ __forceinline__ void render_fk(const KDeviceModel* dm, const KDeviceS
   for (int k = 0; k < 4; k++) ja[k] = dm->x.jump[k][ii];
   const int rounds = dm->x.fk_rounds;
   km_pin(Rl); km_pin(p); km_pin(q, cube_c); km_pin_i(jt); km_pin_i(ja[0], ja[1]); km_pin_i(ja[2], ja[3]); km_pin(pre.sp); km_pin_i(pre.sl);
+  if constexpr (VIS) render_vis_setup(st, va, env, i, vsv);     // (read by lane 0 and the scene set-up after the FK's barriers)
   if (i < 7) sc->cube_q[i] = cube_c;
   if (on) {
     if (jt == KM_JNT_SLIDE) {
@@ -121,8 +144,11 @@ __device__ __forceinline__ void render_fk(const KDeviceModel* dm, const KDeviceS
 }
 
 // Per-env scene after the FK: lane 0 builds the camera frame (mj_camlight, targetbody) and the cube pose, lanes 64.. one sphere
-// centre each (another wave: in parallel with lane 0).  Caller synchronises afterwards.
-__device__ __forceinline__ void render_camera(const KDeviceModel* dm, const KDeviceState& st, int env, int cam, int height, RenderScene* sc, const RenderPre& pre) {
+// centre each (another wave: in parallel with lane 0).  Caller synchronises afterwards.  VIS: the camera sits at cam_pos + the env's
+// KM_VP_CAM_OFFSET (in cam_link's frame), exactly where a model with that cam_pos puts it (model.py with_visual_params).
+template <bool VIS>
+__device__ __forceinline__ void render_camera(const KDeviceModel* dm, const KDeviceState& st, int env, int cam, int height, RenderScene* sc, const RenderPre& pre,
+                                              const double* vsv) {
   const KModelDesc* m = &dm->d;
   const int t = threadIdx.x;
   if (t == 0) {
@@ -130,6 +156,7 @@ __device__ __forceinline__ void render_camera(const KDeviceModel* dm, const KDev
     const int cl = pre.cl, tl = pre.tl;
     real co[3], to[3], v[3];
     real cp[3] = {pre.cp[0], pre.cp[1], pre.cp[2]};
+    if constexpr (VIS) { for (int c = 0; c < 3; c++) cp[c] += vsv[KM_VP_CAM_OFFSET + c]; }
     real tp[3] = {pre.tp[0], pre.tp[1], pre.tp[2]};
     if (cl < 0) { co[0] = cp[0]; co[1] = cp[1]; co[2] = cp[2]; }
     else { mat_vec3(v, sc->xmat[cl], cp); co[0] = sc->xpos[cl][0] + v[0]; co[1] = sc->xpos[cl][1] + v[1]; co[2] = sc->xpos[cl][2] + v[2]; }
@@ -169,6 +196,14 @@ struct RgbScene {              // float32 view of the scene for the pixel loop, 
   int box[1 + KM_RGB_MAXSPH][4];   // screen-space bounding rectangle of the cube [0] and of every visible sphere: r0, r1, c0, c1 (inclusive)
   float tab_L;                 // directional-light sum on the table's normal
 };
+// the env's colours and light terms, float32, for the VIS pixel loop (a separate LDS object: the default kernel's layout stays as it is)
+struct RgbVis {
+  float col[3][3];             // material colour [mat - 1][channel]: table, cube, robot
+  float k255[3];               // 255 x table colour: the table-only quads' per-channel factor
+  uint32_t bg;                 // background pixel r | g << 8 | b << 16
+  uint32_t bgw[3];             // four background pixels as the three dwords of a quad
+  float amb, hl, ds;           // ambient, headlight diffuse, 0.3 x directional scale
+};
 // pixel (row, col) of the world point P; false if it is not safely in front of the camera
 __device__ __forceinline__ bool rgb_project(const RenderScene& sc, const real* P, int height, int width, real& row, real& col) {
   const real pc[3] = {P[0] - sc.cam_o[0], P[1] - sc.cam_o[1], P[2] - sc.cam_o[2]};
@@ -184,7 +219,9 @@ __device__ __forceinline__ bool rgb_project(const RenderScene& sc, const real* P
 // constants and rectangle), lanes 12-15 one table edge each, lane 16 the camera / cube-frame scalars; lane 0 then folds the corners
 // into the cube's rectangle and the rectangles into their union.
 struct RgbTmp { real row[8], col[8]; int ok[8]; };
-__device__ __forceinline__ void rgb_scene(const KDeviceModel* dm, const RenderScene& sc, int height, int width, RgbScene* g, RgbTmp* tmp, int t) {
+template <bool VIS>
+__device__ __forceinline__ void rgb_scene(const KDeviceModel* dm, const RenderScene& sc, int height, int width, RgbScene* g, RgbTmp* tmp, int t,
+                                          RgbVis* gv, const double* vsv) {
   const KModelDesc* m = &dm->d;
   // bounding rectangles, one per object (an object that is not safely in front of the camera gets the whole image): the cube's
   // eight corners; a sphere's centre +- a conservative projected radius
@@ -244,6 +281,20 @@ __device__ __forceinline__ void rgb_scene(const KDeviceModel* dm, const RenderSc
     for (int c = 0; c < 9; c++) g->R[c] = (float)sc.cube_R[c];
     g->nsph = dm->x.nvis;
     g->tab_L = 0.3f * (0.57735026919f + 0.57735026919f + 0.70710678119f);    // sum_l max(0, L_l . (0,0,1)), scene.xml:11-13
+    if constexpr (VIS) g->tab_L = (float)vsv[KM_VP_DIRECTIONAL] * g->tab_L;
+  } else if (VIS && t == 17) {
+    // material order of rgb_pixel's `mat`: 1 table, 2 cube, 3 robot
+    const int base[3] = {KM_VP_TABLE_RGB, KM_VP_CUBE_RGB, KM_VP_ROBOT_RGB};
+    for (int m2 = 0; m2 < 3; m2++)
+      for (int c = 0; c < 3; c++) gv->col[m2][c] = (float)vsv[base[m2] + c];
+    for (int c = 0; c < 3; c++) gv->k255[c] = (float)(255.0 * vsv[KM_VP_TABLE_RGB + c]);
+    uint32_t b[3];
+    for (int c = 0; c < 3; c++) b[c] = (uint32_t)floor(255.0 * vsv[KM_VP_BACKGROUND_RGB + c] + 0.5);
+    gv->bg = b[0] | (b[1] << 8) | (b[2] << 16);
+    gv->bgw[0] = b[0] | (b[1] << 8) | (b[2] << 16) | (b[0] << 24);
+    gv->bgw[1] = b[1] | (b[2] << 8) | (b[0] << 16) | (b[1] << 24);
+    gv->bgw[2] = b[2] | (b[0] << 8) | (b[1] << 16) | (b[2] << 24);
+    gv->amb = (float)vsv[KM_VP_AMBIENT]; gv->hl = (float)vsv[KM_VP_HEADLIGHT]; gv->ds = (float)vsv[KM_VP_DIRECTIONAL] * 0.3f;
   }
   __syncthreads();
   if (t == 0) {
@@ -272,11 +323,18 @@ __device__ __forceinline__ void rgb_scene(const KDeviceModel* dm, const RenderSc
 // every wave ran both paths -- 0.155 ms against round 3's 0.089; dropped.)
 struct DepthScene { real ol[3], DX[3], DY[3], DZ[3]; real oc[KM_RENDER_MAXVIS][3], cc[KM_RENDER_MAXVIS]; int nvis; };
 
-template <bool COLFIXED>      // COLFIXED: blockDim.x is a whole number of image rows (the launcher knows)
+// COLFIXED: blockDim.x is a whole number of image rows (the launcher knows).  VIS = false: the default kernel (no VA);
+// VIS = true: VA = KVisArgs, one more argument, and the camera offset applied
+template <bool COLFIXED, bool VIS, class... VA>
 __global__ __launch_bounds__(256, 4) void k_render_depth(const KDeviceModel* __restrict__ dm, KDeviceState st, int cam, int height, int width,
-                                                      float* __restrict__ depth) {
+                                                      float* __restrict__ depth, VA... vargs) {
+  static_assert(sizeof...(VA) == (VIS ? 1 : 0), "the VIS kernel takes one KVisArgs, the default kernel none");
   __shared__ RenderScene sc;
   __shared__ DepthScene ds;
+  __shared__ double vsv_[KM_VP_N];           // (VIS only: the default kernel never references it)
+  KVisArgs va{};
+  double* vsv = nullptr;
+  if constexpr (VIS) { ((va = vargs), ...); vsv = vsv_; }
   const KModelDesc* m = &dm->d;
   const int env = blockIdx.x;
   // model scalars of the pixel loop: wave-uniform reads, issued in front of the set-up (they used to start after its last barrier)
@@ -284,8 +342,8 @@ __global__ __launch_bounds__(256, 4) void k_render_depth(const KDeviceModel* __r
   const real rx0 = m->table_rect[0], rx1 = m->table_rect[1], ry0 = m->table_rect[2], ry1 = m->table_rect[3];
   const real hf0 = m->cube_half[0], hf1 = m->cube_half[1], hf2 = m->cube_half[2];
   RenderPre pre;
-  render_fk(dm, st, env, cam, &sc, pre);
-  render_camera(dm, st, env, cam, height, &sc, pre);
+  render_fk<VIS>(dm, st, env, cam, &sc, pre, va, vsv);
+  render_camera<VIS>(dm, st, env, cam, height, &sc, pre, vsv);
   __syncthreads();
   if (threadIdx.x < 4) {
     // ray origin and basis in the cube frame, one vector per lane
@@ -466,7 +524,8 @@ __device__ __forceinline__ void rgb_table_span(const RgbScene& g, float dy, floa
   }
 }
 
-__device__ __forceinline__ uint32_t rgb_pixel(const RgbScene& g, float dx, float dy, uint32_t objs, bool tab) {
+template <bool VIS>
+__device__ __forceinline__ uint32_t rgb_pixel(const RgbScene& g, const RgbVis* gv, float dx, float dy, uint32_t objs, bool tab) {
   const float dz = g.X[2] * dx + g.Y[2] * dy - g.Z[2];
   const float dd = dx * dx + dy * dy + 1.0f;                   // |d|^2: the camera axes are orthonormal
   float best = g.zfar;
@@ -513,9 +572,25 @@ __device__ __forceinline__ uint32_t rgb_pixel(const RgbScene& g, float dx, float
       }
     }
   }
-  if (mat == 0) return 0u;
+  if constexpr (VIS) {
+    if (mat == 0) return gv->bg;
+  } else {
+    if (mat == 0) return 0u;
+  }
   const float rs = __builtin_amdgcn_rsqf(dd);
   float I;
+  if constexpr (VIS) {
+    // the env's light terms (at their defaults these are the default kernel's operations on the same values)
+    if (mat == 1) I = gv->amb + gv->hl * fmaxf(0.0f, -dz * rs) + g.tab_L;
+    else {
+      const float r3 = 0.57735026919f, r2 = 0.70710678119f;
+      I = gv->amb + gv->hl * fmaxf(0.0f, -(n0 * d0 + n1 * d1 + n2 * dz) * rs)
+          + gv->ds * (fmaxf(0.0f, (-n0 - n1 + n2) * r3) + fmaxf(0.0f, (n0 - n1 + n2) * r3) + fmaxf(0.0f, (n1 + n2) * r2));
+    }
+    I = fminf(I, 1.0f) * 255.0f;
+    const float* col = gv->col[mat - 1];
+    return (uint32_t)(col[0] * I + 0.5f) | ((uint32_t)(col[1] * I + 0.5f) << 8) | ((uint32_t)(col[2] * I + 0.5f) << 16);
+  }
   if (mat == 1) I = 0.4f + 0.4f * fmaxf(0.0f, -dz * rs) + g.tab_L;
   else {
     const float r3 = 0.57735026919f, r2 = 0.70710678119f;
@@ -530,18 +605,27 @@ __device__ __forceinline__ uint32_t rgb_pixel(const RgbScene& g, float dx, float
 }
 
 // grid = envs x jobs: blockIdx.y picks the camera / resolution / output buffer (all the cameras of a *Vision observation in one launch)
-__global__ __launch_bounds__(256) void k_render_rgb(const KDeviceModel* __restrict__ dm, KDeviceState st, KRenderJobs jobs) {
+// VIS = false: the default kernel (no VA); VIS = true: VA = KVisArgs, one more argument, the env's colours / lights / camera offset
+template <bool VIS, class... VA>
+__global__ __launch_bounds__(256) void k_render_rgb(const KDeviceModel* __restrict__ dm, KDeviceState st, KRenderJobs jobs, VA... vargs) {
+  static_assert(sizeof...(VA) == (VIS ? 1 : 0), "the VIS kernel takes one KVisArgs, the default kernel none");
   __shared__ RenderScene sc;
-  __shared__ RgbScene g;
+  __shared__ alignas(8) RgbScene g;     // (a kernel template's LDS objects keep their declared alignment: 8 is what the default had)
   __shared__ RgbTmp tmp;
+  __shared__ RgbVis gv_;                     // (VIS only: the default kernel never references these two)
+  __shared__ double vsv_[KM_VP_N];
+  KVisArgs va{};
+  RgbVis* gv = nullptr;
+  double* vsv = nullptr;
+  if constexpr (VIS) { ((va = vargs), ...); gv = &gv_; vsv = vsv_; }
   const int env = blockIdx.x, job = blockIdx.y;
   const int cam = jobs.cam[job], height = jobs.height[job], width = jobs.width[job];
   uint8_t* __restrict__ rgb = jobs.rgb[job];
   RenderPre pre;
-  render_fk(dm, st, env, cam, &sc, pre);
-  render_camera(dm, st, env, cam, height, &sc, pre);
+  render_fk<VIS>(dm, st, env, cam, &sc, pre, va, vsv);
+  render_camera<VIS>(dm, st, env, cam, height, &sc, pre, vsv);
   __syncthreads();
-  rgb_scene(dm, sc, height, width, &g, &tmp, threadIdx.x);
+  rgb_scene<VIS>(dm, sc, height, width, &g, &tmp, threadIdx.x, gv, vsv);
   __syncthreads();
   const int npix = height * width;
   const float hw = 0.5f * width, hh = 0.5f * height, inv_f = g.inv_f;
@@ -559,8 +643,19 @@ __global__ __launch_bounds__(256) void k_render_rgb(const KDeviceModel* __restri
     // s = sign(tz - o_z), the hit test 0 < (tz - o_z) / dz < zfar is  s dz > |tz - o_z| / zfar, and the Lambert term
     // 0.4 max(0, -dz / |d|) is clamp(s dz * rsq(|d|^2) * (-0.4 s)).  ~14 operations a pixel, one of them transcendental
     const float k0 = g.tz - g.o[2], sg = k0 < 0.0f ? -1.0f : 1.0f, thr = k0 != 0.0f ? fabsf(k0) / g.zfar : INFINITY;
-    const float Xzs = sg * g.X[2], Yzs = sg * g.Y[2], Zzs = sg * g.Z[2], lam = -0.4f * sg, c1 = 0.4f + g.tab_L;
+    const float Xzs = sg * g.X[2], Yzs = sg * g.Y[2], Zzs = sg * g.Z[2];
+    const float lam = VIS ? -gv->hl * sg : -0.4f * sg, c1 = VIS ? gv->amb + g.tab_L : 0.4f + g.tab_L;
     const int nobj = g.nsph;
+    // VIS: the table's three channel factors and the background's packed dwords, wave-uniform
+    float kr = 0, kg = 0, kb = 0;
+    uint32_t bg0 = 0, bg1 = 0, bg2 = 0;
+    if constexpr (VIS) {
+      kr = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, gv->k255[0])));
+      kg = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, gv->k255[1])));
+      kb = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, gv->k255[2])));
+      bg0 = __builtin_amdgcn_readfirstlane(gv->bgw[0]); bg1 = __builtin_amdgcn_readfirstlane(gv->bgw[1]);
+      bg2 = __builtin_amdgcn_readfirstlane(gv->bgw[2]);
+    }
     // Round 5: the loop was bound by instruction issue, not by its stores (~95 instructions a quad: 0.38 of its 0.45 ms).  A lane
     // keeps its image row while the block walks the tile columns, so the row's table span (20 instructions) and its ray constants
     // are computed once per tile ROW; and a quad that lies wholly inside the span and above the horizon -- nearly all of them --
@@ -587,10 +682,39 @@ __global__ __launch_bounds__(256) void k_render_rgb(const KDeviceModel* __restri
           objs |= (uint32_t)(r >= g.box[o][0] && r <= g.box[o][1] && c + 3 >= g.box[o][2] && c <= g.box[o][3]) << o;
         uint32_t px[4];
 #pragma unroll
-        for (int i = 0; i < 4; i++) { const float dx = (c + i + 0.5f - hw) * inv_f; px[i] = rgb_pixel(g, dx, dy, objs, dx > lo && dx < hi); }
+        for (int i = 0; i < 4; i++) { const float dx = (c + i + 0.5f - hw) * inv_f; px[i] = rgb_pixel<VIS>(g, gv, dx, dy, objs, dx > lo && dx < hi); }
         w0 = px[0] | (px[1] << 24); w1 = (px[1] >> 8) | (px[2] << 16); w2 = (px[2] >> 16) | (px[3] << 8);
       } else if (!(dx0 + 3.0f * inv_f > lo && dx0 < hi)) {
-        w0 = 0; w1 = 0; w2 = 0;                                                        // beside the table: background
+        if constexpr (VIS) { w0 = bg0; w1 = bg1; w2 = bg2; }
+        else { w0 = 0; w1 = 0; w2 = 0; }                                               // beside the table: background
+      } else if constexpr (VIS) {
+        // per-env table colour: three channel values a pixel (one FMA and one conversion each, the default's rounding), packed
+        // r | g << 8 | b << 16 and the quad's three dwords cut from the four packed pixels with one v_perm each
+        // (the same two cases as the default below: the whole quad is table, or each pixel is tested)
+        uint32_t px[4];
+        auto shade = [&](float dx, float& sdz) {
+          sdz = Xzs * dx + rz;
+          const float dd = dx * dx + rd;
+          const float a = __builtin_amdgcn_fmed3f(sdz * __builtin_amdgcn_rsqf(dd) * lam, 0.0f, 1.0f);
+          const float I = __builtin_amdgcn_fmed3f(a + c1, 0.0f, 1.0f);
+          return (uint32_t)(I * kr + 0.5f) | ((uint32_t)(I * kg + 0.5f) << 8) | ((uint32_t)(I * kb + 0.5f) << 16);
+        };
+        if (row_ok && dx0 > lo && dx0 + 3.0f * inv_f < hi) {
+#pragma unroll
+          for (int i = 0; i < 4; i++) { float sdz; px[i] = shade(dx0 + (float)i * inv_f, sdz); }
+        } else {
+          const uint32_t bgp = bg0 & 0xFFFFFFu;
+#pragma unroll
+          for (int i = 0; i < 4; i++) {
+            const float dx = (c + i + 0.5f - hw) * inv_f;
+            float sdz;
+            const uint32_t v = shade(dx, sdz);
+            px[i] = (sdz > thr && dx > lo && dx < hi) ? v : bgp;
+          }
+        }
+        w0 = __builtin_amdgcn_perm(px[1], px[0], 0x04020100u);                       // r0 g0 b0 r1
+        w1 = __builtin_amdgcn_perm(px[2], px[1], 0x05040201u);                       // g1 b1 r2 g2
+        w2 = __builtin_amdgcn_perm(px[3], px[2], 0x06050402u);                       // b2 r3 g3 b3
       } else {
         uint32_t v[4];
         if (row_ok && dx0 > lo && dx0 + 3.0f * inv_f < hi) {                  // the whole quad is table: no per-pixel tests
@@ -625,18 +749,42 @@ __global__ __launch_bounds__(256) void k_render_rgb(const KDeviceModel* __restri
       for (int o = 0; o <= g.nsph; o++)
         objs |= (uint32_t)(r >= g.box[o][0] && r <= g.box[o][1] && c >= g.box[o][2] && c <= g.box[o][3]) << o;
       const float dx = (c + 0.5f - hw) * inv_f, dy = -(r + 0.5f - hh) * inv_f;
-      const uint32_t v = rgb_pixel(g, dx, dy, objs, rgb_over_table(g, dx, dy));
+      const uint32_t v = rgb_pixel<VIS>(g, gv, dx, dy, objs, rgb_over_table(g, dx, dy));
       out[3 * (size_t)p] = (uint8_t)v; out[3 * (size_t)p + 1] = (uint8_t)(v >> 8); out[3 * (size_t)p + 2] = (uint8_t)(v >> 16);
     }
   }
 }
 
-void kmanip_launch_render_depth(const KDeviceModel* dm, const KDeviceState& st, int cam, int height, int width, float* depth,
-                                hipStream_t stream) {
-  // 128 lanes per env: two waves -- 2048 envs x 2 waves fill the chip's 4096 wave slots (120 registers: four waves per SIMD) in one round
-  if (width > 0 && 128 % width == 0 && (height * width) % 128 == 0) hipLaunchKernelGGL(k_render_depth<true>, dim3(st.num_envs), dim3(128), 0, stream, dm, st, cam, height, width, depth);
-  else hipLaunchKernelGGL(k_render_depth<false>, dim3(st.num_envs), dim3(128), 0, stream, dm, st, cam, height, width, depth);
+// ranges mode's values of every env's current episode (kmanip_get_visual_params): the draw the VIS kernels evaluate
+__global__ void k_vp_draw(uint64_t seed, int64_t env_id_offset, int n, KVisArgs va, double* __restrict__ out) {
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n * ((KM_VP_N + 1) / 2); i += gridDim.x * blockDim.x) {
+    const int env = i % n, j = i / n;
+    double o[2];
+    km_vp_draw_pair(seed, env_id_offset + env, va.episode[env], j, va.range, o);
+    out[(size_t)(2 * j) * n + env] = o[0];
+    if (2 * j + 1 < KM_VP_N) out[(size_t)(2 * j + 1) * n + env] = o[1];
+  }
 }
-void kmanip_launch_render_rgb(const KDeviceModel* dm, const KDeviceState& st, const KRenderJobs& jobs, hipStream_t stream) {
-  hipLaunchKernelGGL(k_render_rgb, dim3(st.num_envs, jobs.n), dim3(256), 0, stream, dm, st, jobs);
+void kmanip_launch_vp_draw(const KDeviceState& st, const KVisArgs& vis, double* out, hipStream_t stream) {
+  const int n = st.num_envs, tot = n * ((KM_VP_N + 1) / 2), grid = (tot + 255) / 256 < 1024 ? (tot + 255) / 256 : 1024;
+  hipLaunchKernelGGL(k_vp_draw, dim3(grid), dim3(256), 0, stream, st.seed, st.env_id_offset, n, vis, out);
+}
+
+void kmanip_launch_render_depth(const KDeviceModel* dm, const KDeviceState& st, int cam, int height, int width, float* depth,
+                                const KVisArgs& vis, hipStream_t stream) {
+  // 128 lanes per env: two waves -- 2048 envs x 2 waves fill the chip's 4096 wave slots (120 registers: four waves per SIMD) in one round
+  const dim3 grid(st.num_envs), block(128);
+  const bool colfixed = width > 0 && 128 % width == 0 && (height * width) % 128 == 0;
+  if (km_vis_on(vis)) {
+    if (colfixed) k_render_depth<true, true, KVisArgs><<<grid, block, 0, stream>>>(dm, st, cam, height, width, depth, vis);
+    else k_render_depth<false, true, KVisArgs><<<grid, block, 0, stream>>>(dm, st, cam, height, width, depth, vis);
+  } else {
+    if (colfixed) k_render_depth<true, false><<<grid, block, 0, stream>>>(dm, st, cam, height, width, depth);
+    else k_render_depth<false, false><<<grid, block, 0, stream>>>(dm, st, cam, height, width, depth);
+  }
+}
+void kmanip_launch_render_rgb(const KDeviceModel* dm, const KDeviceState& st, const KRenderJobs& jobs, const KVisArgs& vis, hipStream_t stream) {
+  const dim3 grid(st.num_envs, jobs.n), block(256);
+  if (km_vis_on(vis)) k_render_rgb<true, KVisArgs><<<grid, block, 0, stream>>>(dm, st, jobs, vis);
+  else k_render_rgb<false><<<grid, block, 0, stream>>>(dm, st, jobs);
 }

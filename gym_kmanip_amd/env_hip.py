@@ -19,8 +19,9 @@ from typing import Optional
 import numpy as np
 
 from . import lib as _libmod
-from .model import (CAMERAS, CONTROL_TIMESTEP, ENV_PARAMS, ENV_SPECS, KM_ACT_KEYS, KM_CAM_INDEX, CompiledModel, EnvSpec,
-                    compile_model, env_param_defaults)
+from .model import (CAMERAS, CONTROL_TIMESTEP, ENV_PARAMS, ENV_SPECS, KM_ACT_KEYS, KM_CAM_INDEX, KM_VP_N, VISUAL_PARAMS,
+                    CompiledModel, EnvSpec, check_visual_param, compile_model, env_param_defaults, visual_param_defaults,
+                    visual_param_vector)
 
 MJCF_TO_ASSET = {"_env_solo_arm.xml": "solo_arm", "_env_dual_arm.xml": "dual_arm", "_env_torso.xml": "torso"}
 
@@ -63,6 +64,8 @@ class KManipEnvHip:
         self._check(self.L.kmanip_bind_sim_time(self.h, C.c_void_p(self.sim_time.data_ptr())), "kmanip_bind_sim_time")
         self._ep_active = False          # per-env parameters in force (set_env_params / set_env_param_ranges)
         self._ep_ranges = None           # (lo, hi) float64[KM_EP_N] of ranges mode, or None
+        self._vp_active = False          # per-env visual parameters in force (set_visual_params / set_visual_param_ranges)
+        self._vp_ranges = None           # (lo, hi) float64[KM_VP_N] of visual ranges mode, or None
 
     # ------------------------------------------------------------------ helpers
     def _check(self, rc, what):
@@ -366,15 +369,22 @@ class KManipEnvHip:
         self._check(self.L.kmanip_set_episode(self.h, ep.ctypes.data_as(C.POINTER(C.c_int32))), "kmanip_set_episode")
 
     def checkpoint(self):
-        """Complete restartable state: (qpos, qvel, ctrl, qacc_warmstart, step_idx, episode, env_params) as host arrays;
-        env_params is None without per-env parameters, else (values float64[KM_EP_N, num_envs], lo, hi) -- lo / hi the
-        ranges of ranges mode or None."""
+        """Complete restartable state: (qpos, qvel, ctrl, qacc_warmstart, step_idx, episode, env_params, visual_params) as host
+        arrays; env_params is None without per-env parameters, else (values float64[KM_EP_N, num_envs], lo, hi) -- lo / hi the
+        ranges of ranges mode or None; visual_params likewise: None, or (values float64[KM_VP_N, num_envs] or None, lo, hi) --
+        explicit values, or the ranges (the draw is a function of seed and episode, both restored with the state)."""
         ep = None
         if self._ep_active:
             vals = np.stack([v.cpu().numpy() for v in self.get_env_params().values()])
             lo, hi = (None, None) if self._ep_ranges is None else (self._ep_ranges[0].copy(), self._ep_ranges[1].copy())
             ep = (vals, lo, hi)
-        return self.get_state() + (self.get_episode(), ep)
+        vp = None
+        if self._vp_active:
+            if self._vp_ranges is None:
+                vp = (self._get_visual_raw().cpu().numpy(), None, None)
+            else:
+                vp = (None, self._vp_ranges[0].copy(), self._vp_ranges[1].copy())
+        return self.get_state() + (self.get_episode(), ep, vp)
 
     def restore(self, ckpt):
         qpos, qvel, ctrl, warm, step, episode = ckpt[:6]
@@ -389,6 +399,14 @@ class KManipEnvHip:
                 self.set_env_params(**{name: vals[k] for k, name in enumerate(ENV_PARAMS)})
                 if lo is not None:
                     self._set_ranges_raw(lo, hi)
+        if len(ckpt) > 7:
+            vp = ckpt[7]
+            if vp is None:
+                self.clear_visual_params()
+            elif vp[0] is not None:
+                self._set_visual_raw(_torch().as_tensor(np.ascontiguousarray(vp[0], dtype=np.float64)).to(self.device))
+            else:
+                self._set_visual_ranges_raw(vp[1], vp[2])
 
     # ------------------------------------------------------------------ per-env physics parameters (domain randomisation)
     def set_env_params(self, **fields):
@@ -442,6 +460,84 @@ class KManipEnvHip:
         """Back to the compiled model for every env (bit-identical to a handle that never had parameters)."""
         self._check(self.L.kmanip_set_env_params(self.h, None, self._stream()), "kmanip_set_env_params")
         self._ep_active, self._ep_ranges = False, None
+
+    # ------------------------------------------------------------------ per-env visual parameters (camera renders)
+    def set_visual_params(self, **fields):
+        """Explicit per-env visual values (and visual ranges mode off): cube_rgb, table_rgb, robot_rgb, background_rgb and
+        camera_offset as [num_envs, 3] or a broadcast (3,); ambient, headlight and directional as [num_envs] or a scalar.  Unnamed
+        fields keep their defaults (model.visual_param_defaults).  Names, shapes and limits (colours in [0, 1], light terms >= 0,
+        |camera offset| <= 0.25 m, finite) are checked before the library is called; the renders then use the env's values."""
+        torch = _torch()
+        unknown = set(fields) - set(VISUAL_PARAMS)
+        if unknown:
+            raise ValueError("unknown visual parameter(s) %s (known: %s)" % (sorted(unknown), ", ".join(VISUAL_PARAMS)))
+        n = self.num_envs
+        rows = {}
+        for name, v in fields.items():
+            k, m = VISUAL_PARAMS[name]
+            a = check_visual_param(name, v.cpu().numpy() if hasattr(v, "cpu") else v)
+            if m == 3 and a.shape not in ((3,), (n, 3)):
+                raise ValueError("%s: expected shape (3,) or (%d, 3), got %s" % (name, n, a.shape))
+            if m == 1 and a.shape not in ((), (n,)):
+                raise ValueError("%s: expected a scalar or shape (%d,), got %s" % (name, n, a.shape))
+            rows[name] = np.broadcast_to(a, (n, 3) if m == 3 else (n,))
+        p = np.empty((KM_VP_N, n))
+        p[:] = visual_param_vector({})[:, None]
+        for name, a in rows.items():
+            k, m = VISUAL_PARAMS[name]
+            p[k:k + m] = a.T if m == 3 else a[None]
+        self._set_visual_raw(torch.from_numpy(p).to(self.device))
+
+    def _set_visual_raw(self, p):
+        p = p.to(dtype=_torch().float64).contiguous()
+        self._check(self.L.kmanip_set_visual_params(self.h, C.c_void_p(p.data_ptr()), self._stream()), "kmanip_set_visual_params")
+        self._vp_active, self._vp_ranges = True, None
+
+    def _get_visual_raw(self):
+        p = _torch().empty((KM_VP_N, self.num_envs), dtype=_torch().float64, device=self.device)
+        self._check(self.L.kmanip_get_visual_params(self.h, C.c_void_p(p.data_ptr()), self._stream()), "kmanip_get_visual_params")
+        return p
+
+    def get_visual_params(self):
+        """{name: float64 device tensor [num_envs, 3] or [num_envs]} of the values in force: the defaults when none are set, the
+        draw of every env's current episode in ranges mode."""
+        p = self._get_visual_raw()
+        return {name: (p[k:k + m].T if m == 3 else p[k]) for name, (k, m) in VISUAL_PARAMS.items()}
+
+    def set_visual_param_ranges(self, **ranges):
+        """Visual ranges mode: each named parameter (name=(lo, hi), lo / hi scalars or 3-vectors for the rgb / offset fields) is
+        drawn per env and episode from the seed's counter-based stream; every reset redraws.  Unnamed parameters stay at their
+        defaults.  No argument turns ranges mode off, keeping every env's current draw as explicit values."""
+        if not ranges:
+            self._check(self.L.kmanip_set_visual_param_ranges(self.h, None, None), "kmanip_set_visual_param_ranges")
+            self._vp_ranges = None
+            return
+        unknown = set(ranges) - set(VISUAL_PARAMS)
+        if unknown:
+            raise ValueError("unknown visual parameter(s) %s (known: %s)" % (sorted(unknown), ", ".join(VISUAL_PARAMS)))
+        lo, hi = visual_param_vector({}), visual_param_vector({})
+        for name, r in ranges.items():
+            k, m = VISUAL_PARAMS[name]
+            if len(r) != 2:
+                raise ValueError("%s: expected (lo, hi)" % name)
+            a, b = (check_visual_param(name, x) for x in r)
+            if a.shape not in ((), (m,)) or b.shape not in ((), (m,)) or (m == 1 and (a.shape or b.shape)):
+                raise ValueError("%s: lo / hi must be scalars%s" % (name, " or 3-vectors" if m == 3 else ""))
+            if (a > b).any():
+                raise ValueError("%s: lo > hi" % name)
+            lo[k:k + m], hi[k:k + m] = a, b
+        self._set_visual_ranges_raw(lo, hi)
+
+    def _set_visual_ranges_raw(self, lo, hi):
+        lo = np.ascontiguousarray(lo, dtype=np.float64); hi = np.ascontiguousarray(hi, dtype=np.float64)
+        ptr = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))
+        self._check(self.L.kmanip_set_visual_param_ranges(self.h, ptr(lo), ptr(hi)), "kmanip_set_visual_param_ranges")
+        self._vp_active, self._vp_ranges = True, (lo.copy(), hi.copy())
+
+    def clear_visual_params(self):
+        """Back to the default render kernels for every env (bit-identical to a handle that never had visual parameters)."""
+        self._check(self.L.kmanip_set_visual_params(self.h, None, self._stream()), "kmanip_set_visual_params")
+        self._vp_active, self._vp_ranges = False, None
 
     def set_state(self, qpos=None, qvel=None, ctrl=None, warm=None, step=None):
         def p(a, dt, t):

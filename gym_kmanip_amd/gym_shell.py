@@ -142,7 +142,8 @@ class KManipEnv(_EnvBase):
     def __init__(self, env_id: str = "KManipSoloArm", num_envs: int = 1, device: int = 0, seed: int = 0,
                  squeeze: bool = False, env_id_offset: int = 0, device_outputs: bool = False,
                  log_h5py: bool = False, log_prefix: str = "test", log_env_ids=None, log_backend=None,
-                 log_reference_layout: bool = False, log_h5py_module=None, domain_randomization=None, **overrides):
+                 log_reference_layout: bool = False, log_h5py_module=None, domain_randomization=None, visual_randomization=None,
+                 **overrides):
         spec: EnvSpec = ENV_SPECS[env_id]
         self.env_id = env_id
         self.seed = seed
@@ -179,6 +180,9 @@ class KManipEnv(_EnvBase):
         # domain_randomization={name: (lo, hi)} (env_hip.ENV_PARAMS names): every reset redraws those physics parameters per env
         if domain_randomization:
             self.env.set_env_param_ranges(**domain_randomization)
+        # visual_randomization={name: (lo, hi)} (model.VISUAL_PARAMS names): colours, lights and camera offset per env and episode
+        if visual_randomization:
+            self.env.set_visual_param_ranges(**visual_randomization)
         self.info: Dict[str, Any] = {
             "step": self.step_idx, "episode": self.episode_idx, "is_success": False, "q_keys": self.q_keys, "q_len": self.q_len,
             "a_len": self.action_len, "obs_list": self.obs_list, "act_list": self.act_list,

@@ -20,7 +20,7 @@ _lib = None
 EXPORTS = [
     "kmanip_model_desc_size", "kmanip_create", "kmanip_reset", "kmanip_step", "kmanip_step_chunk", "kmanip_get_state",
     "kmanip_set_state", "kmanip_get_episode", "kmanip_set_episode", "kmanip_get_counters", "kmanip_bind_sim_time", "kmanip_bind_reward_done_record", "kmanip_select_reward_done_record", "kmanip_observe", "kmanip_set_seed", "kmanip_get_diag", "kmanip_timing_summary", "kmanip_enable_timing", "kmanip_ik", "kmanip_ik_eval",
-    "kmanip_render_depth", "kmanip_render_rgb", "kmanip_render_rgb_multi", "kmanip_snapshot_render_state", "kmanip_set_render_source", "kmanip_bind_step_depth", "kmanip_scripted_action", "kmanip_sample_action", "kmanip_set_env_params", "kmanip_get_env_params", "kmanip_set_env_param_ranges", "kmanip_num_envs", "kmanip_last_error", "kmanip_version", "kmanip_destroy",
+    "kmanip_render_depth", "kmanip_render_rgb", "kmanip_render_rgb_multi", "kmanip_snapshot_render_state", "kmanip_set_render_source", "kmanip_bind_step_depth", "kmanip_scripted_action", "kmanip_sample_action", "kmanip_set_env_params", "kmanip_get_env_params", "kmanip_set_env_param_ranges", "kmanip_set_visual_params", "kmanip_get_visual_params", "kmanip_set_visual_param_ranges", "kmanip_num_envs", "kmanip_last_error", "kmanip_version", "kmanip_destroy",
 ]
 
 
@@ -89,6 +89,9 @@ def load():
     lib.kmanip_set_env_params.argtypes = [vp, vp, vp]
     lib.kmanip_get_env_params.argtypes = [vp, vp, vp]
     lib.kmanip_set_env_param_ranges.argtypes = [vp, f64p, f64p]
+    lib.kmanip_set_visual_params.argtypes = [vp, vp, vp]
+    lib.kmanip_get_visual_params.argtypes = [vp, vp, vp]
+    lib.kmanip_set_visual_param_ranges.argtypes = [vp, f64p, f64p]
     lib.kmanip_num_envs.argtypes = [vp]
     lib.kmanip_last_error.argtypes = [vp]
     lib.kmanip_last_error.restype = C.c_char_p

@@ -531,3 +531,84 @@ def draw_env_params(seed: int, genv: int, episode: int, lo, hi) -> np.ndarray:
             u = _u53(o[2 * j], o[2 * j + 1])
             out[k] = float(lo[k]) + (float(hi[k]) - float(lo[k])) * u
     return out
+
+
+# ---- per-env visual parameters of the camera renders (include/kmanip.h KM_VP_*)
+# name -> (first index in the KM_VP_N values, number of components)
+VISUAL_PARAMS = {"cube_rgb": (0, 3), "table_rgb": (3, 3), "robot_rgb": (6, 3), "background_rgb": (9, 3), "ambient": (12, 1),
+                 "headlight": (13, 1), "directional": (14, 1), "camera_offset": (15, 3)}
+KM_VP_N = 18
+KM_VP_CTR3 = 0x100  # include/kmanip.h: counter word 3 of the visual draw is KM_VP_CTR3 + k // 2 (disjoint from spawn, KM_EP_CTR3, actions)
+VP_MAX_CAM_OFFSET = 0.25
+
+
+def visual_param_defaults() -> Dict[str, object]:
+    """The values every env renders with when none are set (the default kernels' constants)."""
+    return {"cube_rgb": (1.0, 0.0, 0.0), "table_rgb": (0.2, 0.2, 0.2), "robot_rgb": (0.647059, 0.647059, 0.647059),
+            "background_rgb": (0.0, 0.0, 0.0), "ambient": 0.4, "headlight": 0.4, "directional": 1.0,
+            "camera_offset": (0.0, 0.0, 0.0)}
+
+
+def visual_param_vector(values: Dict[str, object]) -> np.ndarray:
+    """float64[KM_VP_N] of named per-env values (unnamed ones at their defaults), in KM_VP_* order."""
+    out = np.zeros(KM_VP_N)
+    full = dict(visual_param_defaults())
+    full.update(values)
+    for name, (k, n) in VISUAL_PARAMS.items():
+        out[k:k + n] = np.broadcast_to(np.asarray(full[name], dtype=np.float64), (n,)) if n > 1 else float(full[name])
+    return out
+
+
+def check_visual_param(name: str, v) -> np.ndarray:
+    """ValueError unless every component of v is finite and within the parameter's limits: colours in [0, 1], light terms >= 0,
+    |camera offset| <= 0.25 m.  Returns v as a float64 array."""
+    if name not in VISUAL_PARAMS:
+        raise ValueError("unknown visual parameter %r (known: %s)" % (name, ", ".join(VISUAL_PARAMS)))
+    a = np.asarray(v, dtype=np.float64)
+    if not np.isfinite(a).all():
+        raise ValueError("%s: values must be finite" % name)
+    if name.endswith("_rgb"):
+        ok, what = ((a >= 0) & (a <= 1)).all(), "in [0, 1]"
+    elif name == "camera_offset":
+        ok, what = (np.abs(a) <= VP_MAX_CAM_OFFSET).all(), "within +-%g m" % VP_MAX_CAM_OFFSET
+    else:
+        ok, what = (a >= 0).all(), ">= 0"
+    if not ok:
+        raise ValueError("%s: values must be %s" % (name, what))
+    return a
+
+
+def with_visual_params(cm: CompiledModel, camera_offset=None, **others) -> CompiledModel:
+    """The host definition of the per-env camera offset: a copy of `cm` whose desc has cam_pos[c] + camera_offset for every
+    present camera c (in cam_link's frame; world frame for top / head).  An env with offset o renders what a handle of
+    with_visual_params(cm, camera_offset=o).desc renders.  Colours and light terms are not part of KModelDesc: they may be named
+    (and are validated) but change nothing here."""
+    for name, v in others.items():
+        check_visual_param(name, v)
+    d = KModelDesc.from_buffer_copy(cm.desc)
+    if camera_offset is not None:
+        o = check_visual_param("camera_offset", camera_offset)
+        if o.shape != (3,):
+            raise ValueError("camera_offset: expected 3 components, got shape %s" % (o.shape,))
+        for c in range(KM_MAX_CAMS):
+            if d.cam_present[c]:
+                for k in range(3):
+                    d.cam_pos[c][k] = d.cam_pos[c][k] + float(o[k])
+    return dataclasses.replace(cm, desc=d)
+
+
+def draw_visual_params(seed: int, genv: int, episode: int, lo, hi) -> np.ndarray:
+    """The values ranges mode gives global env `genv` in `episode` (include/kmanip.h kmanip_set_visual_param_ranges): value k is
+    lo_k + (hi_k - lo_k) * u_k, product rounded before the sum, u_k from Philox4x32-10 with key = seed and counter
+    (genv lo, genv hi, episode, KM_VP_CTR3 + k // 2), words (0, 1) for even k and (2, 3) for odd k."""
+    key = (seed & 0xFFFFFFFF, (seed >> 32) & 0xFFFFFFFF)
+    g = int(genv) & 0xFFFFFFFFFFFFFFFF
+    out = np.zeros(KM_VP_N)
+    for blk in range((KM_VP_N + 1) // 2):
+        o = _philox4x32_10((g & 0xFFFFFFFF, g >> 32, int(episode) & 0xFFFFFFFF, KM_VP_CTR3 + blk), key)
+        for j in range(2):
+            k = 2 * blk + j
+            if k < KM_VP_N:
+                u = _u53(o[2 * j], o[2 * j + 1])
+                out[k] = float(lo[k]) + (float(hi[k]) - float(lo[k])) * u
+    return out

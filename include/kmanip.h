@@ -342,8 +342,9 @@ KMANIP_API int kmanip_render_rgb_multi(KHandle h, int ncam, const int* cams, con
                             void* stream);
 
 /* Rendering BEHIND the steps (a data-generation loop whose policy does not look at the images: the reference's scripted heuristic,
- * examples/2_synthetic_data.py:28-41, logs them and acts on the state).  A render reads nothing of the state but qpos:
- * kmanip_snapshot_render_state copies qpos into snapshot `slot` (0 or 1) on `stream` -- the step's stream, after the step whose
+ * examples/2_synthetic_data.py:28-41, logs them and acts on the state).  A render reads nothing of the state but qpos (and, in
+ * visual ranges mode, the episode counters the colour / light / camera draw uses: kmanip_set_visual_param_ranges):
+ * kmanip_snapshot_render_state copies them into snapshot `slot` (0 or 1) on `stream` -- the step's stream, after the step whose
  * images are wanted -- and kmanip_set_render_source(h, slot) makes the kmanip_render_* calls that follow read that copy
  * (-1: the live state again, the default; host-side switch, not stream-ordered).  The caller can then issue the render on a
  * SECOND stream while the next kmanip_step runs on the first: the render's workgroups take the SIMDs the step's early-finishing
@@ -403,6 +404,47 @@ KMANIP_API int kmanip_get_env_params(KHandle h, double* params_dev, void* stream
  * NULL, NULL turns ranges mode off and keeps the values in force.  Synchronous. */
 #define KM_EP_CTR3 2u
 KMANIP_API int kmanip_set_env_param_ranges(KHandle h, const double* lo, const double* hi);
+
+/* Per-env visual parameters (visual domain randomisation of the camera renders).  Storage is
+ * double[KM_VP_N][num_envs], struct-of-arrays like KM_EP_*: element (k, env) at k * num_envs + env.
+ *   index  name                  default        meaning
+ *   0-2    KM_VP_CUBE_RGB        1 0 0          cube material colour
+ *   3-5    KM_VP_TABLE_RGB       .2 .2 .2       table colour
+ *   6-8    KM_VP_ROBOT_RGB       .647059 x 3    the visible finger spheres
+ *   9-11   KM_VP_BACKGROUND_RGB  0 0 0          pixels whose ray hits nothing
+ *   12     KM_VP_AMBIENT         0.4            headlight ambient
+ *   13     KM_VP_HEADLIGHT       0.4            headlight diffuse
+ *   14     KM_VP_DIRECTIONAL     1.0            scale on the three 0.3 directional lights
+ *   15-17  KM_VP_CAM_OFFSET      0 0 0          metres, added to cam_pos[c] of every camera, in cam_link's frame (world for
+ *                                               top / head); the camera keeps tracking its target body
+ * Object pixel of material m: round_half_up(255 I rgb_m[ch]) with
+ *   I = min(1, ambient + headlight max(0, -n.d) + directional sum_l 0.3 max(0, n.L_l))  (d the unit ray direction);
+ * background pixel: round_half_up(255 bg[ch]).  Env e with offset o renders what a model whose cam_pos is shifted by o renders
+ * (gym_kmanip_amd/model.py with_visual_params); depth images use the offset and ignore colours and lights.  Physics, observations,
+ * rewards and done bytes never depend on these values.  Limits: colours in [0, 1], light terms finite and >= 0, |offset
+ * component| <= 0.25 m. */
+enum {
+  KM_VP_CUBE_RGB = 0, KM_VP_TABLE_RGB = 3, KM_VP_ROBOT_RGB = 6, KM_VP_BACKGROUND_RGB = 9, KM_VP_AMBIENT = 12, KM_VP_HEADLIGHT = 13,
+  KM_VP_DIRECTIONAL = 14, KM_VP_CAM_OFFSET = 15, KM_VP_N = 18
+};
+/* Explicit values: params_dev DEVICE double[KM_VP_N][num_envs], read once `stream` has produced it; switches ranges mode off.
+ * Validated on the device (one flag read back per call); a bad value returns nonzero and leaves the handle unchanged.
+ * Synchronous (the whole device is idle when it returns).  The values are read when a render LAUNCHES: a render behind the steps
+ * (kmanip_snapshot_render_state) uses the values in force at its launch.  params_dev == NULL returns to the default kernels,
+ * bit-identical to a handle that never had visual parameters. */
+KMANIP_API int kmanip_set_visual_params(KHandle h, const double* params_dev, void* stream);
+/* The values in force into DEVICE double[KM_VP_N][num_envs] on `stream`: the defaults above when none are set; in ranges mode
+ * the draw of every env's current episode. */
+KMANIP_API int kmanip_get_visual_params(KHandle h, double* params_dev, void* stream);
+/* Ranges mode: lo / hi HOST double[KM_VP_N].  Value k of env e in episode p is lo[k] + (hi[k] - lo[k]) * u_k (product rounded
+ * before the sum), u_k a 53-bit uniform from Philox4x32-10 keyed by the seed with counter (global env id lo, hi, p,
+ * KM_VP_CTR3 + k / 2): words (0, 1) of the block for even k, (2, 3) for odd k.  The renders evaluate the draw from the episode
+ * counter, so every reset redraws and kmanip_set_seed / kmanip_set_episode move the draw as they move the cube spawn; in ranges
+ * mode kmanip_snapshot_render_state copies the episode counters with qpos, and a render of that snapshot draws from the copy.
+ * lo > hi or a value outside the limits above is refused (handle unchanged).  NULL, NULL turns ranges mode off and keeps the
+ * values of every env's current episode as explicit values.  Synchronous. */
+#define KM_VP_CTR3 0x100u
+KMANIP_API int kmanip_set_visual_param_ranges(KHandle h, const double* lo, const double* hi);
 
 KMANIP_API int kmanip_num_envs(KHandle h);
 KMANIP_API const char* kmanip_last_error(KHandle h);   /* h may be NULL: error of the last failed create */
