@@ -1,7 +1,7 @@
 // kmanip_api.hip -- host side of the C ABI declared in include/kmanip.h.
-// Owns the device model, the struct-of-arrays env state and the launch sequence of one control step:
-//   k_prepare (ctrl float32 round trip, qpos_ik = qpos)  ->  k_before_step_coop (decode + IK)  ->  k_step (physics,
-//   reward, obs, done, auto-reset).  No CPU fallback exists: every entry point fails loudly without a HIP device.
+// Owns the device model, the struct-of-arrays env state and the launch sequence of one control step: ONE k_step launch
+//   (before_step's decode + IK, physics, reward, obs, done, auto-reset), preceded by k_sort_envs when the cost sort is on.
+//   No CPU fallback exists: every entry point fails loudly without a HIP device.
 #include <hip/hip_runtime.h>
 
 #include <cstdio>
@@ -25,8 +25,8 @@ struct KHandle_ {
   int device = 0;
   int num_envs = 0;
   std::string err;
-  std::vector<hipEvent_t> ev;   // 4 events per timed step
-  std::vector<char> ev_render;  // the step rendered in the step (its fourth event was recorded)
+  std::vector<hipEvent_t> ev;   // 3 events per timed step: before k_step, after k_step, after the render
+  std::vector<char> ev_render;  // the step rendered in the step (its third event was recorded)
   bool timing = false;
   int timing_every = 1;         // events around every timing_every-th step (the argument of kmanip_enable_timing)
   long timing_count = 0;
@@ -39,8 +39,6 @@ struct KHandle_ {
   // render target bound to the step (BASELINE config 5: "depth render in the step"): kmanip_step then also renders
   int step_cam = -1, step_h = 0, step_w = 0;
   float* step_depth = nullptr;
-  bool ik_unfused = false;      // KMANIP_IK_UNFUSED=1: before_step as its own launch (A/B timing only)
-  int ik_ppb = 0;               // KMANIP_IK_PPB: problems per workgroup of that launch (A/B), 0 = chosen from the width
   int epb_forced = 0;           // KMANIP_EPB = 1 | 2 | 4: envs per wave of the step / reset launches (diagnostics), 0 = km_pick_epb's choice
   // wave slots in predicted-cost order (k_sort_envs) for launches of several residency rounds; KMANIP_COST_SORT=0 / 1 overrides
   int32_t* slot_env = nullptr;
@@ -301,7 +299,6 @@ int kmanip_create(const KModelDesc* desc, int num_envs, int device, uint64_t see
   CR(dalloc((void**)&h->st.qvel, sizeof(double) * nv * N));
   CR(dalloc((void**)&h->st.ctrl, sizeof(double) * nl * N));
   CR(dalloc((void**)&h->st.warm, sizeof(double) * nv * N));
-  CR(dalloc((void**)&h->st.qpos_ik, sizeof(double) * nl * N));
   CR(dalloc((void**)&h->st.step_idx, sizeof(int32_t) * N));
   CR(dalloc((void**)&h->st.episode, sizeof(int32_t) * N));
   CR(dalloc((void**)&h->st.contact_mask, sizeof(uint32_t) * N));
@@ -315,8 +312,6 @@ int kmanip_create(const KModelDesc* desc, int num_envs, int device, uint64_t see
   h->st.sim_time = nullptr;
   h->st.rd_rec = nullptr;
   h->st.control_dt = desc->n_sub_steps * desc->timestep;
-  { const char* e = getenv("KMANIP_IK_UNFUSED"); h->ik_unfused = e && e[0] == '1'; }
-  if (const char* e = getenv("KMANIP_IK_PPB")) h->ik_ppb = atoi(e);
   if (const char* e = getenv("KMANIP_EPB")) { const int v = atoi(e); if (v == 1 || v == 2 || v == 4) h->epb_forced = v; }
   h->st.slot_env = nullptr;
   h->st.wave_clk = nullptr;
@@ -325,19 +320,11 @@ int kmanip_create(const KModelDesc* desc, int num_envs, int device, uint64_t see
   // (profiles/r05_near_margin.txt): the single-arm launch is best at 1.5 cm (7.18 M; 1 cm 7.17, 2.5 cm 7.14, 0 = in contact only 7.01);
   // the two-arm sort at 2.5-3 cm on the DualArm (3.91 -> 3.97 M) and flat on the Torso (4.86 / 4.85 / 4.83 M at 1.5 / 2.5 / 4 cm)
   h->st.near_margin = nl > 10 ? 0.025 : 0.015;
-  if (const char* e = getenv("KMANIP_NEAR_MARGIN")) { const double v = atof(e); if (v >= 0 && v < 1) h->st.near_margin = v; }
   {
     // more waves than SIMD slots (1024) at two envs per wave: the two-arm models (their kernels carry the work counters the
     // order is predicted from; the single-arm kernel ships without them -- KMANIP_COST_SORT=1 still sorts it by its IK counts)
     h->cost_sort = nl > 10 && num_envs > 2048;
     if (const char* e = getenv("KMANIP_COST_SORT")) h->cost_sort = e[0] == '1';
-    if (const char* e = getenv("KMANIP_COST_W")) {       // diagnostic: "ik,work,near-cube,armtab,cubetab,binwidth"
-      KCostWeights w = h->cost_w;
-      // (negative weights would make a cost negative; the kernel clamps the bin, and they are refused here)
-      if (sscanf(e, "%d,%d,%d,%d,%d,%d", &w.ik, &w.work, &w.coupled, &w.armtab, &w.cubetab, &w.binw) == 6 && w.binw > 0 &&
-          w.ik >= 0 && w.work >= 0 && w.coupled >= 0 && w.armtab >= 0 && w.cubetab >= 0) h->cost_w = w;
-      else { g_create_error = "kmanip_create: KMANIP_COST_W must be six comma-separated integers >= 0 with a bin width > 0"; kmanip_destroy(h); return -2; }
-    }
   }
   {
     // Which envs share a wave (the single-arm Newton kernel at widths whose launch is about one residency round of multi-env waves).
@@ -385,7 +372,7 @@ int kmanip_num_envs(KHandle h) { return h ? h->num_envs : 0; }
 int kmanip_reset(KHandle h, const uint8_t* mask_dev, double* obs_dev, void* stream) {
   if (!h) return -1;
   KM_ENTER(h);
-  kmanip_launch_reset(h->dmodel, h->desc, h->st, mask_dev, 0, obs_dev, km_pick_epb(h->num_envs, h->desc.nlink <= 10 ? 4 : 2, h->epb_forced),
+  kmanip_launch_reset(h->dmodel, h->desc, h->st, mask_dev, obs_dev, km_pick_epb(h->num_envs, h->desc.nlink <= 10 ? 4 : 2, h->epb_forced),
                       (hipStream_t)stream);
   HIPCHK(h, hipGetLastError());
   return 0;
@@ -445,17 +432,11 @@ static int step_impl(KHandle h, int nchunk, const float* act_dev, double* obs_de
   hipStream_t s = (hipStream_t)stream;
   const bool tm = h->timing && (h->timing_count++ % h->timing_every) == 0 && h->timed_steps < KM_TIMING_SLOTS;
   h->last_step_timed = tm;
-  hipEvent_t* ev = tm ? &h->ev[4 * (size_t)h->timed_steps] : nullptr;
-  // product path: ONE launch, before_step (decode + IK) fused into k_step so that no device-wide barrier sits between
-  // an env's IK and its physics; the split launches remain for A/B timing (KMANIP_IK_UNFUSED=1)
-  const bool split = h->ik_unfused;
+  hipEvent_t* ev = tm ? &h->ev[3 * (size_t)h->timed_steps] : nullptr;
+  // ONE launch: before_step (decode + IK) runs inside k_step, so that no device-wide barrier sits between an env's IK and
+  // its physics
   h->st.rd_rec = nullptr;
   if (nchunk == 1 && h->rd_rec[0]) h->st.rd_rec = h->rd_rec[h->rd_sel];     // (the CALLER alternates: kmanip_select_reward_done_record)
-  if (split && nchunk != 1) { h->err = "kmanip_step_chunk needs the fused path (unset KMANIP_IK_UNFUSED)"; return -1; }
-  if (split) {
-    if (tm) HIPCHK(h, hipEventRecord(ev[0], s));
-    kmanip_launch_ik_coop(h->dmodel, h->desc, h->st, act_dev, h->ik_ppb, s);
-  }
   h->st.slot_env = nullptr;
   if (h->cost_sort) {                        // (one small launch: counting sort of the envs by their last step's diagnostics)
     kmanip_launch_sort_envs(h->st, h->slot_env, h->cost_w, s);
@@ -467,14 +448,14 @@ static int step_impl(KHandle h, int nchunk, const float* act_dev, double* obs_de
     h->spread_k++;
   }
   h->last_epb = km_step_epb(h->num_envs, h->desc.nlink <= 10 ? 4 : 2, nchunk, h->epb_forced);
-  if (tm) HIPCHK(h, hipEventRecord(ev[1], s));        // (fused path: two events per step, each costs the stream a barrier packet)
-  kmanip_launch_step(h->dmodel, h->desc, h->st, split ? nullptr : act_dev, obs_dev, reward_dev, done_dev, nchunk, h->last_epb, s);
-  if (tm) HIPCHK(h, hipEventRecord(ev[2], s));
+  if (tm) HIPCHK(h, hipEventRecord(ev[0], s));        // (two events per step, each costs the stream a barrier packet)
+  kmanip_launch_step(h->dmodel, h->desc, h->st, act_dev, obs_dev, reward_dev, done_dev, nchunk, h->last_epb, s);
+  if (tm) HIPCHK(h, hipEventRecord(ev[1], s));
   const bool render = h->step_depth && nchunk == 1;
   if (render)                             // the observation's camera branch (env_sim.py:140-145) of the state just produced
     kmanip_launch_render_depth(h->dmodel, h->st, h->step_cam, h->step_h, h->step_w, h->step_depth, vis_args(h, -1), s);
   if (tm) {
-    if (render) HIPCHK(h, hipEventRecord(ev[3], s));
+    if (render) HIPCHK(h, hipEventRecord(ev[2], s));
     h->ev_render[h->timed_steps] = render;
     h->timed_steps++;
   }
@@ -556,7 +537,7 @@ int kmanip_render_rgb_multi(KHandle h, int ncam, const int* cams, const int* hei
   // its start is the event the step recorded after k_step, so the render costs the stream ONE more event, not a pair around it
   // (a render of a SNAPSHOT runs behind the steps, on a stream of its own: it is no leg of the step's stream)
   if (h->timing && h->render_src < 0 && h->last_step_timed && h->timed_steps > 0 && !h->ev_render[h->timed_steps - 1]) {
-    HIPCHK(h, hipEventRecord(h->ev[4 * (size_t)(h->timed_steps - 1) + 3], (hipStream_t)stream));
+    HIPCHK(h, hipEventRecord(h->ev[3 * (size_t)(h->timed_steps - 1) + 2], (hipStream_t)stream));
     h->ev_render[h->timed_steps - 1] = 1;
   }
   HIPCHK(h, hipGetLastError());
@@ -599,7 +580,7 @@ int kmanip_enable_timing(KHandle h, int enable) {
   if (!h) return -1;
   KM_ENTER(h);
   if (enable && h->ev.empty()) {
-    h->ev.resize(4 * KM_TIMING_SLOTS, nullptr);
+    h->ev.resize(3 * KM_TIMING_SLOTS, nullptr);
     h->ev_render.assign(KM_TIMING_SLOTS, 0);
     for (auto& e : h->ev) HIPCHK(h, hipEventCreate(&e));
   }
@@ -613,17 +594,16 @@ int kmanip_timing_summary(KHandle h, double* ik_ms_sum, double* dyn_ms_sum, doub
   if (!h) return -1;
   KM_ENTER(h);
   HIPCHK(h, hipDeviceSynchronize());
-  double a = 0, b = 0, c = 0;
+  double dyn = 0, ren = 0;
   for (int k = 0; k < h->timed_steps; k++) {
-    float m1 = 0, m2 = 0, m3 = 0;
-    if (h->ik_unfused) HIPCHK(h, hipEventElapsedTime(&m1, h->ev[4 * k], h->ev[4 * k + 1]));
-    HIPCHK(h, hipEventElapsedTime(&m2, h->ev[4 * k + 1], h->ev[4 * k + 2]));
-    if (h->ev_render[k]) HIPCHK(h, hipEventElapsedTime(&m3, h->ev[4 * k + 2], h->ev[4 * k + 3]));
-    a += m1; b += m2; c += m3;
+    float md = 0, mr = 0;
+    HIPCHK(h, hipEventElapsedTime(&md, h->ev[3 * k], h->ev[3 * k + 1]));
+    if (h->ev_render[k]) HIPCHK(h, hipEventElapsedTime(&mr, h->ev[3 * k + 1], h->ev[3 * k + 2]));
+    dyn += md; ren += mr;
   }
-  if (ik_ms_sum) *ik_ms_sum = a;
-  if (dyn_ms_sum) *dyn_ms_sum = b;
-  if (render_ms_sum) *render_ms_sum = c;
+  if (ik_ms_sum) *ik_ms_sum = 0;      // (before_step runs inside k_step: its time is part of dyn_ms_sum)
+  if (dyn_ms_sum) *dyn_ms_sum = dyn;
+  if (render_ms_sum) *render_ms_sum = ren;
   if (nsteps) *nsteps = h->timed_steps;
   h->timed_steps = 0;
   return 0;

@@ -524,7 +524,6 @@ struct KDeviceState {
   double* qvel;       // [nv][N]
   double* ctrl;       // [nu][N]
   double* warm;       // [nv][N]  qacc_warmstart
-  double* qpos_ik;    // [nl][N]  robot qpos after the IK's last evaluation (teleport, ik_mujoco.py:34,67)
   int32_t* step_idx;  // [N]
   int32_t* episode;   // [N]
   uint32_t* contact_mask;  // [N]
@@ -540,7 +539,6 @@ struct KDeviceState {
   // next launch from spread_in.  A wave looks at the 64 flags of ITS block of 64 consecutive envs (three ballots) and deals the block's
   // envs to the block's waves so that no wave holds two heavy ones and a heavy env's wave-mates are the block's plainest envs: a
   // permutation inside the block, whatever the flags are -- the block's cache lines are the ones the identity map touches.
-  double near_margin;   // "near the cube" for the heavy flag / the sort's proximity bit (KM_NEAR_MARGIN; KMANIP_NEAR_MARGIN, A/B)
   const uint8_t* spread_in;
   uint8_t* spread_out;
   // per-env physics parameters (kmanip_set_env_params): double[KM_EP_N][N], NULL = the compiled model (the default kernels);
@@ -548,6 +546,7 @@ struct KDeviceState {
   double* envp;
   const double* ep_range;
   double control_dt;  // n_sub_steps * timestep
+  double near_margin;   // "near the cube" for the heavy flag / the sort's proximity bit (KM_NEAR_MARGIN; kmanip_create sets it)
   int num_envs;
   int64_t env_id_offset;
   uint64_t seed;
@@ -555,21 +554,18 @@ struct KDeviceState {
 
 // fills dm->staged (device memory) for the model's link-count class; kmanip_create, once
 void kmanip_launch_prepare_model(KDeviceModel* dm, const KModelDesc& hd, hipStream_t stream);
-// ppb: problems per workgroup (KMANIP_IK_PPB, A/B), 0 = chosen from the launch width
-void kmanip_launch_ik_coop(const KDeviceModel* dm, const KModelDesc& hd, const KDeviceState& st, const float* act, int ppb,
-                           hipStream_t stream);
 void kmanip_launch_ik_coop_standalone(const KDeviceModel* dm, const KModelDesc& hd, int arm, int n, double* qpos_env_major,
                                       const double* goal_pos, const double* goal_quat, double* q_out, int32_t* nfev,
                                       int32_t* status, hipStream_t stream);
 void kmanip_launch_ik_eval_coop(const KDeviceModel* dm, const KModelDesc& hd, int arm, int n, const double* qpos_env_major,
                                 const double* goal_pos, const double* goal_quat, double* res, double* jac, hipStream_t stream);
-// act != NULL: the decode + IK of before_step run inside k_step (product path); NULL: they already ran
-// nchunk > 1 (act != NULL only): that many control steps per launch, act / obs / reward / done laid out [nchunk][num_envs][..]
+// act (required): the actions that before_step (decode + IK) turns into ctrl inside k_step
+// nchunk > 1: that many control steps per launch, act / obs / reward / done laid out [nchunk][num_envs][..]
 // epb: envs per wave (km_step_epb / km_pick_epb)
 void kmanip_launch_step(const KDeviceModel* dm, const KModelDesc& hd, const KDeviceState& st, const float* act, double* obs,
                         double* reward, uint8_t* done, int nchunk, int epb, hipStream_t stream);
-void kmanip_launch_reset(const KDeviceModel* dm, const KModelDesc& hd, const KDeviceState& st, const uint8_t* mask,
-                         int use_done_bits, double* obs, int epb, hipStream_t stream);
+void kmanip_launch_reset(const KDeviceModel* dm, const KModelDesc& hd, const KDeviceState& st, const uint8_t* mask, double* obs,
+                         int epb, hipStream_t stream);
 void kmanip_launch_observe(const KDeviceModel* dm, const KModelDesc& hd, const KDeviceState& st, double* obs, double* reward,
                            hipStream_t stream);
 // The render launchers' visual inputs (kmanip_set_visual_params / _ranges), a kernel argument of the VIS

@@ -28,9 +28,8 @@ void kmanip_launch_step(const KDeviceModel* dm, const KModelDesc& hd, const KDev
   if (hd.nlink <= 10) { if (newton) kmanip_launch_step_10_16_1(dm, st, act, obs, reward, done, nchunk, epb, stream); else kmanip_launch_step_10_16_0(dm, st, act, obs, reward, done, nchunk, epb, stream); }
   else { if (newton) kmanip_launch_step_20_32_1(dm, st, act, obs, reward, done, nchunk, epb, stream); else kmanip_launch_step_20_32_0(dm, st, act, obs, reward, done, nchunk, epb, stream); }
 }
-void kmanip_launch_reset(const KDeviceModel* dm, const KModelDesc& hd, const KDeviceState& st, const uint8_t* mask,
-                         int use_done_bits, double* obs, int epb, hipStream_t stream) {
-  (void)use_done_bits;
+void kmanip_launch_reset(const KDeviceModel* dm, const KModelDesc& hd, const KDeviceState& st, const uint8_t* mask, double* obs,
+                         int epb, hipStream_t stream) {
   const bool newton = hd.solver == KM_SOLVER_NEWTON;
   if (st.envp) {
     if (hd.nlink <= 10) { if (newton) kmanip_launch_reset_ep_10_16_1(dm, st, mask, obs, epb, stream); else kmanip_launch_reset_ep_10_16_0(dm, st, mask, obs, epb, stream); }

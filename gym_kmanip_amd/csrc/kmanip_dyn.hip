@@ -113,7 +113,6 @@ __global__ __launch_bounds__(64) void KM_K_STEP(const KDeviceModel* __restrict__
   pf.start();
   const unsigned long long t_wave0 = st.wave_clk ? __builtin_amdgcn_s_memtime() : 0ull;
   const unsigned long long r_wave0 = st.wave_clk ? __builtin_amdgcn_s_memrealtime() : 0ull;
-  const bool fused = act != nullptr;
 #ifdef KM_DEBUG_NANFILL   // diagnostic build (-DKM_DEBUG_NANFILL=<value>): poison the workspace, so that a read of LDS this launch did not write shows
   { double* wp = reinterpret_cast<double*>(&w); for (int i = sub; i < (int)(sizeof(Ws<NL>) / 8); i += G) wp[i] = KM_DEBUG_NANFILL; GSYNC(); }
 #endif
@@ -121,7 +120,7 @@ __global__ __launch_bounds__(64) void KM_K_STEP(const KDeviceModel* __restrict__
 #if KM_VAR_PAR
   ep_load<NL>(w, dm, st, env, sub, invm);       // (after the diagnostic poisoning above: Ws::ep is part of the workspace)
 #endif
-  load_state<NL, G>(w, st, env, sub, fused);
+  load_state<NL, G>(w, st, env, sub);
   int step_idx = st.step_idx[env], episode = st.episode[env];
   const size_t NE = (size_t)st.num_envs;
   GSYNC();
@@ -132,31 +131,29 @@ __global__ __launch_bounds__(64) void KM_K_STEP(const KDeviceModel* __restrict__
   const int nsteps = CHUNK ? nchunk : 1;      // (the single-step kernel keeps its register allocation: no outer loop)
   int spread_next = 0;                        // this env's SPREAD flag for the next launch (the state it ENDS the step in)
   for (int kc = 0; kc < nsteps; kc++) {
-  if (fused) {
-    if (kc > 0) {
-      // what load_state does for the first step: ctrl <- float32(ctrl) (env_sim.py:40), qpos_ik <- qpos
-      if (sub < NL) { w.ctrl[sub] = (real)(float)w.ctrl[sub]; w.qpos_ik[sub] = w.qpos[sub]; }
-      if (sub == 0) { w.bad = 0; w.work = 0; }
-      GSYNC();
-    }
-    // ---- KManipTask.before_step: 8 lanes per arm, one arm per 16-lane DPP row of the group (lanes 0-7 of row 0: right arm;
-    // of row 1, in the two-row groups: left arm), the rest idle.
-    // Fused here so that an env whose IK needs many evaluations delays only its own wave, not the whole batch.
-    // (chunk kernels: the lane index is made opaque once per control step, like the dof index per sub-step below -- otherwise the
-    // IK's per-lane chain constants, invariant across the steps of a chunk, are hoisted out of the chunk loop and kept alive
-    // through the physics: the two-arm chunk kernels sat at the 512-register cap with 268 / 116 bytes of scratch)
-    int subk = sub;
-    if constexpr (CHUNK) asm volatile("" : "+v"(subk));
-    const int arm = subk / GS;
-    if (subk % GS < GI && arm < KM_MAX_ARMS && (NL > 10 || arm == 0) && m->arm_present[arm]) {
-      LdsIO<NL> io{w, st, env};
-      const float* arow = act + ((size_t)kc * NE + env) * m->act_dim;
-      if (m->arm_nq[arm] == 7) coop_before_step<7>(dm, arm, subk % GS, arow, io, &pf);
-      else coop_before_step<6>(dm, arm, subk % GS, arow, io, &pf);
-    }
+  if (kc > 0) {
+    // what load_state does for the first step: ctrl <- float32(ctrl) (env_sim.py:40), qpos_ik <- qpos
+    if (sub < NL) { w.ctrl[sub] = (real)(float)w.ctrl[sub]; w.qpos_ik[sub] = w.qpos[sub]; }
+    if (sub == 0) { w.bad = 0; w.work = 0; }
     GSYNC();
-    pf.ph(30);
   }
+  // ---- KManipTask.before_step: 8 lanes per arm, one arm per 16-lane DPP row of the group (lanes 0-7 of row 0: right arm;
+  // of row 1, in the two-row groups: left arm), the rest idle.
+  // Fused here so that an env whose IK needs many evaluations delays only its own wave, not the whole batch.
+  // (chunk kernels: the lane index is made opaque once per control step, like the dof index per sub-step below -- otherwise the
+  // IK's per-lane chain constants, invariant across the steps of a chunk, are hoisted out of the chunk loop and kept alive
+  // through the physics: the two-arm chunk kernels sat at the 512-register cap with 268 / 116 bytes of scratch)
+  int subk = sub;
+  if constexpr (CHUNK) asm volatile("" : "+v"(subk));
+  const int arm = subk / GS;
+  if (subk % GS < GI && arm < KM_MAX_ARMS && (NL > 10 || arm == 0) && m->arm_present[arm]) {
+    LdsIO<NL> io{w, st, env};
+    const float* arow = act + ((size_t)kc * NE + env) * m->act_dim;
+    if (m->arm_nq[arm] == 7) coop_before_step<7>(dm, arm, subk % GS, arow, io, &pf);
+    else coop_before_step<6>(dm, arm, subk % GS, arow, io, &pf);
+  }
+  GSYNC();
+  pf.ph(30);
   int bad = 0;
   spread_next = 0;
   const int nsub = m->n_sub_steps;
@@ -283,7 +280,7 @@ __global__ __launch_bounds__(64) void k_observe(const KDeviceModel* __restrict__
   if (grp >= EPB || env >= st.num_envs) return;
   Ws<NL>& w = ws[grp];
   init_ws<NL>(w, sub);
-  load_state<NL, G>(w, st, env, sub, false);
+  load_state<NL, G>(w, st, env, sub);
   GSYNC();
   // a state restored from a diverged checkpoint: what k_step reports for such an env -- zero observation and reward, no contacts
   // (the kinematics of a non-finite state would put garbage into the mask the diagnostics and the next cost sort read)

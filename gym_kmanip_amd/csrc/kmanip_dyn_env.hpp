@@ -228,38 +228,27 @@ template <int NL>
 __device__ __forceinline__ void init_ws(Ws<NL>& w, int sub) {
   if (sub < Dim<NL>::NC) { w.c_pos[sub][0] = 0; w.c_pos[sub][1] = 0; w.c_pos[sub][2] = 0; w.c_dist[sub] = 0; }
 }
-// fused = before_step runs in this kernel: ctrl <- float32(ctrl) (env_sim.py:40) and qpos_ik <- qpos here
+// the env's state -> LDS, with the start of before_step: ctrl <- float32(ctrl) (env_sim.py:40) and qpos_ik <- qpos
 template <int NL, int G>
-__device__ __forceinline__ void load_state(Ws<NL>& w, const KDeviceState& st, int env, int sub, bool fused) {
+__device__ __forceinline__ void load_state(Ws<NL>& w, const KDeviceState& st, int env, int sub) {
   constexpr int NV = Dim<NL>::NV, NQ = Dim<NL>::NQ;
   const int NE = st.num_envs;
   // (round 6) every column read of the env's state issued before the first is waited for: as loops, each HBM read was waited for
   // on its own (five to six round trips at the start of every wave)
   constexpr int KQ = (NQ + G - 1) / G, KV = (NV + G - 1) / G, KL = (NL + G - 1) / G;
-  real q[KQ], v[KV], wm[KV], c[KL], qi[KL];
+  real q[KQ], v[KV], wm[KV], c[KL];
 #pragma unroll
   for (int k = 0; k < KQ; k++) { const int i = sub + G * k; q[k] = st.qpos[(size_t)(i < NQ ? i : NQ - 1) * NE + env]; }
 #pragma unroll
   for (int k = 0; k < KV; k++) { const int i = sub + G * k, ic = i < NV ? i : NV - 1; v[k] = st.qvel[(size_t)ic * NE + env]; wm[k] = st.warm[(size_t)ic * NE + env]; }
 #pragma unroll
-  for (int k = 0; k < KL; k++) {
-    const int i = sub + G * k, ic = i < NL ? i : NL - 1;
-    c[k] = st.ctrl[(size_t)ic * NE + env];
-    qi[k] = 0.0;
-    if (!fused) qi[k] = st.qpos_ik[(size_t)ic * NE + env];      // (wave-uniform: the split-launch path only)
-  }
+  for (int k = 0; k < KL; k++) { const int i = sub + G * k; c[k] = st.ctrl[(size_t)(i < NL ? i : NL - 1) * NE + env]; }
 #pragma unroll
-  for (int k = 0; k < KQ; k++) { const int i = sub + G * k; if (i < NQ) { w.qpos[i] = q[k]; if (fused && i < NL) w.qpos_ik[i] = q[k]; } }
+  for (int k = 0; k < KQ; k++) { const int i = sub + G * k; if (i < NQ) { w.qpos[i] = q[k]; if (i < NL) w.qpos_ik[i] = q[k]; } }
 #pragma unroll
   for (int k = 0; k < KV; k++) { const int i = sub + G * k; if (i < NV) { w.qvel[i] = v[k]; w.warm[i] = wm[k]; } }
 #pragma unroll
-  for (int k = 0; k < KL; k++) {
-    const int i = sub + G * k;
-    if (i < NL) {
-      w.ctrl[i] = fused ? (real)(float)c[k] : c[k];
-      if (!fused) w.qpos_ik[i] = qi[k];
-    }
-  }
+  for (int k = 0; k < KL; k++) { const int i = sub + G * k; if (i < NL) w.ctrl[i] = (real)(float)c[k]; }
   if (sub == 0) { w.bad = 0; w.work = 0; }
 }
 template <int NL> struct LdsIO {

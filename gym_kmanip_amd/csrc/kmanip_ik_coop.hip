@@ -1,61 +1,6 @@
-// kmanip_ik_coop.hip -- stand-alone launches of the cooperative decode + IK device code (kmanip_ik_coop.hpp):
-// the batched ik() entry point used by parity tests and the unfused before_step kernel kept for A/B runs.
+// kmanip_ik_coop.hip -- stand-alone launches of the cooperative IK device code (kmanip_ik_coop.hpp): the batched ik() and
+// ik_res / ik_jac entry points of the parity tests.  The product path runs before_step (decode + IK) inside k_step (kmanip_dyn.hip).
 #include "kmanip_ik_coop.hpp"
-#include <stdlib.h>
-
-// ---------------------------------------------------------------------------------------------
-// before_step for every env, stand-alone launch (A/B path: KMANIP_IK_UNFUSED=1; the product path runs the same
-// device code inside k_step): 8 lanes per (env, arm) problem
-struct GlobalIO {
-  KDeviceState st; int env;
-  __device__ __forceinline__ real qpos(int i) const { return st.qpos[(size_t)i * st.num_envs + env]; }
-  __device__ __forceinline__ void set_ctrl(int i, real v) { st.ctrl[(size_t)i * st.num_envs + env] = v; }
-  __device__ __forceinline__ void set_qpos_ik(int i, real v) { st.qpos_ik[(size_t)i * st.num_envs + env] = v; }
-  __device__ __forceinline__ void set_diag(int arm, int nfev, int status) {
-    st.ik_nfev[(size_t)arm * st.num_envs + env] = nfev; st.ik_status[(size_t)arm * st.num_envs + env] = status;
-  }
-};
-// PPB = problems per single-wave workgroup (<= PPW): the kernel needs > 256 registers, i.e. one wave per SIMD, so a
-// batch with fewer than 1024 full waves is spread over more, emptier waves (less lock-step divergence too).
-template <int N, int PPB>
-__global__ __launch_bounds__(64) void k_before_step_coop(const KDeviceModel* __restrict__ dm, KDeviceState st,
-                                                         const float* __restrict__ act, int nprob) {
-  const KModelDesc* m = &dm->d;
-  const int NE = st.num_envs;
-  const int slot = threadIdx.x / GS, c = threadIdx.x % GS;
-  const int prob = blockIdx.x * PPB + slot;
-  if (c >= GI || slot >= PPB || prob >= nprob) return;      // whole problem exits together (lanes 8..15 of a row stay idle)
-  const int env = prob % NE, arm = prob / NE;
-  if (!m->arm_present[arm]) return;
-  GlobalIO io{st, env};
-  Prof pf;
-  coop_before_step<N>(dm, arm, c, act + (size_t)env * m->act_dim, io, &pf);
-}
-
-__global__ void k_prepare_coop(const KDeviceModel* __restrict__ dm, KDeviceState st) {
-  const int NE = st.num_envs, nl = dm->d.nlink;
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= NE * nl) return;
-  st.ctrl[i] = f32r_c(st.ctrl[i]);
-  st.qpos_ik[i] = st.qpos[i];
-}
-
-void kmanip_launch_ik_coop(const KDeviceModel* dm, const KModelDesc& hd, const KDeviceState& st, const float* act, int ppb,
-                           hipStream_t stream) {
-  int n0 = st.num_envs * hd.nlink;
-  hipLaunchKernelGGL(k_prepare_coop, dim3((n0 + 255) / 256), dim3(256), 0, stream, dm, st);
-  int narm_slots = (hd.arm_present[1]) ? 2 : 1;
-  int nprob = st.num_envs * narm_slots;
-  int nik = hd.arm_nq[0] ? hd.arm_nq[0] : hd.arm_nq[1];
-  if (ppb <= 0) {
-    ppb = PPW;
-    while (ppb > 2 && (nprob + ppb - 1) / ppb < 1024) ppb >>= 1;   // 1024 = SIMDs on the chip
-  }
-#define KM_IK_LAUNCH(NN, PP) hipLaunchKernelGGL((k_before_step_coop<NN, PP>), dim3((nprob + PP - 1) / PP), dim3(64), 0, stream, dm, st, act, nprob)
-  if (nik == 7) { if (ppb >= 4) KM_IK_LAUNCH(7, 4); else KM_IK_LAUNCH(7, 2); }
-  else { if (ppb >= 4) KM_IK_LAUNCH(6, 4); else KM_IK_LAUNCH(6, 2); }
-#undef KM_IK_LAUNCH
-}
 
 // standalone batched ik() for parity tests: qpos env-major [n][nq] (mutated like the reference)
 template <int N>

@@ -634,8 +634,8 @@ __device__ __forceinline__ real f32r_c(real x) { return (real)(float)x; }
 
 // ---------------------------------------------------------------------------------------------
 // KManipTask.before_step (env_sim.py:38-108) for ONE (env, arm) problem on its 8 lanes: grip decode, EE-delta decode
-// + IK, or the joint-delta modes.  IO abstracts where the env's state lives (global SoA columns for the
-// stand-alone kernel, the LDS workspace when fused into k_step):
+// + IK, or the joint-delta modes, inside k_step.  IO is where the env's state lives: LdsIO (kmanip_dyn_env.hpp), the LDS
+// workspace, implements
 //   real IO::qpos(int i); void IO::set_ctrl(int i, real v); void IO::set_qpos_ik(int i, real v); void IO::set_diag(int arm, int nfev, int status)
 template <int N, class IO>
 __device__ __forceinline__ void coop_before_step(const KDeviceModel* dm, int arm, int c, const float* a, IO& io, Prof* pf) {

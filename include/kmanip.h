@@ -215,10 +215,8 @@ KMANIP_API int kmanip_create(const KModelDesc* desc, int num_envs, int device, u
  * small extra launch).  A single-arm Newton handle of 2048 or more envs (a multiple of 64) chooses every wave's
  * envs so that no wave holds two predicted to be heavy (SPREAD).  Diagnostic environment variables, each read once
  * by kmanip_create: KMANIP_SPREAD=0 (the identity map instead of SPREAD), KMANIP_COST_SORT=0/1 (force
- * the cost order off / on), KMANIP_COST_W (its weights), KMANIP_NEAR_MARGIN (what counts as near the cube for both),
- * KMANIP_EPB=1/2/4 (envs per wave), KMANIP_IK_UNFUSED=1 (before_step as its own launch), KMANIP_IK_PPB (problems per workgroup of
- * that launch), KMANIP_NO_BLOCK_SPLIT=1 (two-arm inertia as one block), KMANIP_WAVE_CLOCKS=1 (per-wave cycle counts for
- * tests/tools/wave_times.py).
+ * the cost order off / on), KMANIP_EPB=1/2/4 (envs per wave), KMANIP_NO_BLOCK_SPLIT=1 (two-arm inertia as one block),
+ * KMANIP_WAVE_CLOCKS=1 (per-wave cycle counts for tests/tools/wave_times.py).
  * Throughput note: one batch's launch ends with its slowest wave and leaves about half the SIMD time idle; handles are
  * independent and every entry point takes the caller's stream, so two or more batches kept in flight on different streams fill
  * it (gym_kmanip_amd/pipeline.py). */
@@ -291,12 +289,12 @@ KMANIP_API int kmanip_set_seed(KHandle h, uint64_t seed, int restart_episodes);
 KMANIP_API int kmanip_get_diag(KHandle h, uint32_t* contact_mask, int32_t* ik_nfev, int32_t* ik_status);
 
 /* Kernel timing with HIP events recorded on the launch stream (bench.py roofline leg).  While enabled, every kmanip_step
- * records an event before and after k_step, one more after the bound in-step render (or after the first kmanip_render_rgb[_multi]
- * call that follows the step: the camera observations of a *Vision id), and -- only on the KMANIP_IK_UNFUSED=1 A/B
- * path -- one before its stand-alone decode/IK launches (an event record costs the stream about 5 us, so the product path takes
- * the two it needs), into a ring of `KM_TIMING_SLOTS` steps.  kmanip_timing_summary synchronises the device and returns the
- * summed durations in milliseconds of the three legs (stand-alone IK: 0 on the product path; k_step; the step's render:
- * kmanip_bind_step_depth's or the RGB render called after the step, 0 without one) over the recorded steps, then clears the ring.  Any output pointer may be NULL.
+ * records an event before and after k_step and one more after the bound in-step render (or after the first kmanip_render_rgb[_multi]
+ * call that follows the step: the camera observations of a *Vision id), into a ring of `KM_TIMING_SLOTS` steps (an event record
+ * costs the stream about 5 us).  kmanip_timing_summary synchronises the device and returns the summed durations in milliseconds of
+ * k_step and of the step's render (kmanip_bind_step_depth's or the RGB render called after the step, 0 without one) over the
+ * recorded steps, then clears the ring.  *ik_ms_sum is always 0: before_step runs inside k_step, and the argument is kept for ABI
+ * compatibility.  Any output pointer may be NULL.
  * `enable` = k > 1 records every k-th step only (the first step after the call, then every k-th): the events' own cost -- the ~5 us
  * above, 1 % of a 4096-env step -- then falls on one step in k, and the averages are over the sampled steps (`*nsteps` = their count). */
 #define KM_TIMING_SLOTS 1024

@@ -484,40 +484,6 @@ def test_render_depth_config5_size():
     e.k_close(); f.k_close()
 
 
-@pytest.mark.parametrize("env", ["KManipSoloArm", "KManipTorso"])
-def test_fused_and_split_launches_agree(env, monkeypatch):
-    """The product path runs before_step inside k_step; KMANIP_IK_UNFUSED=1 keeps it as separate launches.  Same device
-    code on the same inputs => bit-identical state/obs/reward."""
-    torch = _torch()
-    from gym_kmanip_amd import env_hip
-    from gym_kmanip_amd.lib import KManipError
-    n = 96
-    cm = compile_model(env)
-    envs = {}
-    for name, var in (("fused", None), ("split", "KMANIP_IK_UNFUSED")):
-        monkeypatch.delenv("KMANIP_IK_UNFUSED", raising=False)
-        if var:
-            monkeypatch.setenv(var, "1")
-        envs[name] = env_hip.KManipEnvHip(cm, num_envs=n, seed=9)      # the switch is read at kmanip_create
-    monkeypatch.delenv("KMANIP_IK_UNFUSED", raising=False)
-    gen = torch.Generator(device="cuda"); gen.manual_seed(4)
-    for e in envs.values():
-        e.k_reset()
-    for k in range(70):                                                    # crosses the 64-step auto-reset
-        act = torch.rand((n, cm.act_dim), generator=gen, device="cuda") * 2 - 1
-        for e in envs.values():
-            e.step_flat(act)
-        f, s = envs["fused"], envs["split"]
-        assert torch.equal(f.obs, s.obs) and torch.equal(f.reward, s.reward) and torch.equal(f.done, s.done), k
-    for x, y in zip(envs["fused"].get_state(), envs["split"].get_state()):
-        assert np.array_equal(x, y)
-    df, ds = envs["fused"].get_diag(), envs["split"].get_diag()
-    for x, y in zip(df, ds):
-        assert np.array_equal(x, y)
-    for e in envs.values():
-        e.k_close()
-
-
 @pytest.mark.parametrize("env,n,epb", [("KManipSoloArm", 1, None), ("KManipSoloArm", 5, None), ("KManipSoloArm", 37, "1"),
                                        ("KManipSoloArm", 37, "2"), ("KManipSoloArm", 300, None),
                                        ("KManipDualArm", 3, None), ("KManipDualArm", 21, "1"), ("KManipTorso", 21, "1"), ("KManipTorso", 33, None)])
