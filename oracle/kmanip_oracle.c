@@ -1642,8 +1642,11 @@ int ko_constraint_rows(const KModelDesc* m, const double* qpos, const double* qv
  * (H/2)/tan(fovy/2); depth = distance along the optical axis, clipped to [znear, zfar] (no hit = zfar). */
 /* shared by the depth and the RGB render: rgb != NULL selects Lambert shading (cube rgba 1 0 0, table .2 .2 .2: scene.xml:15,20;
  * headlight ambient 0.4 + MuJoCo's default headlight diffuse 0.4 at the camera, three directional lights of diffuse 0.3:
- * scene.xml:8-13; no specular / shadows / fog; background black) */
-static void render_any(const KModelDesc* m, const double* qpos, int cam, int H, int W, float* out, uint8_t* rgb) {
+ * scene.xml:8-13; no specular / shadows / fog; background black).  vis != NULL (RGB only): an env's visual parameters,
+ * double[KM_VP_N] as kmanip_set_visual_params lays out one env's column -- the material and background colours, the ambient and
+ * headlight terms and the scale on the directional lights; a background pixel is round(255 bg).  Its camera offset is not read
+ * here: it is the desc's cam_pos (gym_kmanip_amd/model.py with_visual_params) */
+static void render_any(const KModelDesc* m, const double* qpos, int cam, int H, int W, float* out, uint8_t* rgb, const double* vis) {
   Kin k;
   kinematics(m, qpos, &k);
   int cl = m->cam_link[cam], tl = m->cam_target_link[cam];
@@ -1666,7 +1669,15 @@ static void render_any(const KModelDesc* m, const double* qpos, int cam, int H, 
   }
   const double r3 = 0.57735026918962576451, r2 = 0.70710678118654752440;
   const double L[3][3] = {{-r3, -r3, r3}, {r3, -r3, r3}, {0, r2, r2}};
-  const double col[4][3] = {{0, 0, 0}, {0.2, 0.2, 0.2}, {1, 0, 0}, {0.647059, 0.647059, 0.647059}};
+  double col[4][3] = {{0, 0, 0}, {0.2, 0.2, 0.2}, {1, 0, 0}, {0.647059, 0.647059, 0.647059}};
+  double amb = 0.4, hl = 0.4, dl_scale = 0.3;
+  if (vis) {
+    for (int q = 0; q < 3; q++) {
+      col[0][q] = vis[KM_VP_BACKGROUND_RGB + q]; col[1][q] = vis[KM_VP_TABLE_RGB + q];
+      col[2][q] = vis[KM_VP_CUBE_RGB + q]; col[3][q] = vis[KM_VP_ROBOT_RGB + q];
+    }
+    amb = vis[KM_VP_AMBIENT]; hl = vis[KM_VP_HEADLIGHT]; dl_scale = 0.3 * vis[KM_VP_DIRECTIONAL];
+  }
   for (int r = 0; r < H; r++) for (int c = 0; c < W; c++) {
     double dx = (c + 0.5 - 0.5 * W) / f, dy = -(r + 0.5 - 0.5 * H) / f;
     double d[3] = {x[0] * dx + y[0] * dy - z[0], x[1] * dx + y[1] * dy - z[1], x[2] * dx + y[2] * dy - z[2]};
@@ -1713,13 +1724,16 @@ static void render_any(const KModelDesc* m, const double* qpos, int cam, int H, 
       double I = 0;
       if (mat) {
         double head = fmax(0.0, -dot3(nrm, d) / sqrt(dot3(d, d)));
-        I = 0.4 + 0.4 * head;
-        for (int l = 0; l < 3; l++) I += 0.3 * fmax(0.0, dot3(nrm, L[l]));
+        I = amb + hl * head;
+        for (int l = 0; l < 3; l++) I += dl_scale * fmax(0.0, dot3(nrm, L[l]));
         I = fmin(I, 1.0);
       }
-      for (int q = 0; q < 3; q++) rgb[(r * W + c) * 3 + q] = (uint8_t)(255.0 * col[mat][q] * I + 0.5);
+      for (int q = 0; q < 3; q++) rgb[(r * W + c) * 3 + q] = (uint8_t)((mat ? 255.0 * col[mat][q] * I : 255.0 * col[0][q]) + 0.5);
     }
   }
 }
-void ko_render_depth(const KModelDesc* m, const double* qpos, int cam, int H, int W, float* out) { render_any(m, qpos, cam, H, W, out, NULL); }
-void ko_render_rgb(const KModelDesc* m, const double* qpos, int cam, int H, int W, uint8_t* rgb) { render_any(m, qpos, cam, H, W, NULL, rgb); }
+void ko_render_depth(const KModelDesc* m, const double* qpos, int cam, int H, int W, float* out) { render_any(m, qpos, cam, H, W, out, NULL, NULL); }
+void ko_render_rgb(const KModelDesc* m, const double* qpos, int cam, int H, int W, uint8_t* rgb) { render_any(m, qpos, cam, H, W, NULL, rgb, NULL); }
+void ko_render_rgb_vis(const KModelDesc* m, const double* qpos, int cam, int H, int W, const double* vis, uint8_t* rgb) {
+  render_any(m, qpos, cam, H, W, NULL, rgb, vis);
+}

@@ -232,9 +232,14 @@ class Oracle:
         self.L.ko_render_depth(C.byref(self.desc), _p(_f64(qpos)), cam, h, w, _p(out, C.c_float))
         return out
 
-    def render_rgb(self, qpos, cam=0, h=40, w=60):
+    def render_rgb(self, qpos, cam=0, h=40, w=60, vis=None):
+        """vis: one env's visual parameters (float64[KM_VP_N], model.visual_param_vector) for the colours and lights; the camera
+        offset among them is not read -- it is the desc's (model.with_visual_params)."""
         out = np.zeros((h, w, 3), dtype=np.uint8)
-        self.L.ko_render_rgb(C.byref(self.desc), _p(_f64(qpos)), cam, h, w, _p(out, C.c_uint8))
+        if vis is None:
+            self.L.ko_render_rgb(C.byref(self.desc), _p(_f64(qpos)), cam, h, w, _p(out, C.c_uint8))
+        else:
+            self.L.ko_render_rgb_vis(C.byref(self.desc), _p(_f64(qpos)), cam, h, w, _p(_f64(vis)), _p(out, C.c_uint8))
         return out
 
     def scripted_eer_pos(self, qpos):
