@@ -204,6 +204,26 @@ static int build_aux(const KModelDesc* d, KModelAux* x, std::string& err) {
   return 0;
 }
 
+// The arm of every sphere (KDeviceModel::sphere_arm; model.py sphere_arm restates it): sphere s belongs to arm a when its link is an
+// ancestor-or-self of the arm's site link or of one of its gripper links.  Exactly one arm per sphere in every reference model.
+// No desc is refused over this (kmanip_create accepts what it accepted before the labels): a sphere on several chains gets the
+// lowest of those arms, one on none gets arm 0, as model.sphere_arm does without strict=True.
+static void build_sphere_arm(const KModelDesc* d, uint8_t* out) {
+  memset(out, 0, KM_MAX_SPHERES);
+  for (int s = 0; s < d->nsphere; s++) {
+    int found = -1;
+    for (int a = 0; a < KM_MAX_ARMS && found < 0; a++) {
+      if (!d->arm_present[a]) continue;
+      const int leaf[3] = {d->arm_site_link[a], d->arm_grip_id[a][0], d->arm_grip_id[a][1]};
+      bool on = false;
+      for (int k = 0; k < 3 && !on; k++)
+        for (int j = leaf[k]; j >= 0 && j < d->nlink && !on; j = d->link_parent[j]) on = j == d->sphere_link[s];
+      if (on) found = a;
+    }
+    out[s] = (uint8_t)(found < 0 ? 0 : found);
+  }
+}
+
 extern "C" {
 
 int kmanip_model_desc_size(void) { return (int)sizeof(KModelDesc); }
@@ -275,6 +295,7 @@ int kmanip_create(const KModelDesc* desc, int num_envs, int device, uint64_t see
   hm.d = *desc;
   if (validate(desc, h->err) != 0 || build_aux(desc, &hm.x, h->err) != 0) { g_create_error = h->err; delete h; return -2; }
   hm.trace_robot = trace_robot_of(*desc);
+  build_sphere_arm(desc, hm.sphere_arm);
   int ndev = 0;
   hipError_t e = hipGetDeviceCount(&ndev);
   if (e != hipSuccess || ndev <= 0 || device >= ndev) {
@@ -546,6 +567,42 @@ int kmanip_render_rgb_multi(KHandle h, int ncam, const int* cams, const int* hei
 
 int kmanip_render_rgb(KHandle h, int cam, int height, int width, uint8_t* rgb_dev, void* stream) {
   return kmanip_render_rgb_multi(h, 1, &cam, &height, &width, &rgb_dev, stream);
+}
+
+int kmanip_render_labels_multi(KHandle h, int ncam, const int* cams, const int* heights, const int* widths, uint8_t* const* rgb_dev,
+                               uint8_t* const* seg_dev, void* stream) {
+  if (!h) { g_create_error = "kmanip_render_labels: null handle"; return -1; }
+  if (ncam <= 0 || ncam > KM_MAX_CAMS || !cams || !heights || !widths || (!rgb_dev && !seg_dev)) { h->err = "kmanip_render_labels: bad arguments"; return -1; }
+  KLabelJobs jobs;
+  jobs.n = ncam;
+  int nrgb = 0, nseg = 0;
+  for (int i = 0; i < ncam; i++) {
+    uint8_t* const r = rgb_dev ? rgb_dev[i] : nullptr;
+    uint8_t* const g = seg_dev ? seg_dev[i] : nullptr;
+    if (!r && !g) { h->err = "kmanip_render_labels: a job needs rgb_dev[i] or seg_dev[i]"; return -1; }
+    if (cams[i] < 0 || cams[i] >= KM_MAX_CAMS || heights[i] <= 0 || widths[i] <= 0) { h->err = "kmanip_render_labels: bad arguments"; return -1; }
+    if (!h->desc.cam_present[cams[i]]) { h->err = "kmanip_render_labels: this model has no such camera"; return -1; }
+    jobs.cam[i] = cams[i]; jobs.height[i] = heights[i]; jobs.width[i] = widths[i]; jobs.rgb[i] = r; jobs.seg[i] = g;
+    nrgb += r != nullptr; nseg += g != nullptr;
+  }
+  // no label wanted anywhere: this is the RGB render
+  if (nseg == 0) return kmanip_render_rgb_multi(h, ncam, cams, heights, widths, rgb_dev, stream);
+  KM_ENTER(h);
+  KDeviceState st = h->st;
+  if (h->render_src >= 0) st.qpos = h->qpos_snap[h->render_src];
+  // labels only in every job: the kernel that does not shade; anything else: the one that writes what each job asks for
+  kmanip_launch_render_labels(h->dmodel, st, jobs, nrgb > 0, vis_args(h, h->render_src), (hipStream_t)stream);
+  // (kmanip_enable_timing: the render after the step, as in kmanip_render_rgb_multi)
+  if (h->timing && h->render_src < 0 && h->last_step_timed && h->timed_steps > 0 && !h->ev_render[h->timed_steps - 1]) {
+    HIPCHK(h, hipEventRecord(h->ev[3 * (size_t)(h->timed_steps - 1) + 2], (hipStream_t)stream));
+    h->ev_render[h->timed_steps - 1] = 1;
+  }
+  HIPCHK(h, hipGetLastError());
+  return 0;
+}
+
+int kmanip_render_seg(KHandle h, int cam, int height, int width, uint8_t* seg_dev, void* stream) {
+  return kmanip_render_labels_multi(h, 1, &cam, &height, &width, nullptr, &seg_dev, stream);
 }
 
 int kmanip_bind_step_depth(KHandle h, int cam, int height, int width, float* depth_dev) {

@@ -49,6 +49,9 @@ struct KDeviceModel {
   // robot part of trace(M(qpos0)) for the per-env meaninertia (kmanip_set_env_params): meaninertia * nv - (3 cube_mass +
   // sum cube_inertia), evaluated on the host at create in that order (model.py with_env_params restates it)
   double trace_robot;
+  // camera renders, per sphere: the arm (0 right, 1 left) whose kinematic chain carries the sphere -- the robot classes of the label
+  // render (KM_SEG_ROBOT_R + arm).  Appended here and not to KModelAux, so that no byte the other kernels address moves
+  uint8_t sphere_arm[KM_MAX_SPHERES];
 };
 
 typedef double real;
@@ -579,6 +582,9 @@ void kmanip_launch_render_depth(const KDeviceModel* dm, const KDeviceState& st, 
                                 const KVisArgs& vis, hipStream_t stream);
 // up to KM_MAX_CAMS camera images of every env in ONE launch (grid = envs x jobs): the *Vision observation
 struct KRenderJobs { int n; int cam[KM_MAX_CAMS], height[KM_MAX_CAMS], width[KM_MAX_CAMS]; uint8_t* rgb[KM_MAX_CAMS]; };
+// the label render's jobs: seg[i] uint8 [num_envs, height, width], rgb[i] as KRenderJobs'; either may be NULL, not both
+struct KLabelJobs { int n; int cam[KM_MAX_CAMS], height[KM_MAX_CAMS], width[KM_MAX_CAMS]; uint8_t* rgb[KM_MAX_CAMS]; uint8_t* seg[KM_MAX_CAMS]; };
+void kmanip_launch_render_labels(const KDeviceModel* dm, const KDeviceState& st, const KLabelJobs& jobs, bool rgb, const KVisArgs& vis, hipStream_t stream);
 void kmanip_launch_render_rgb(const KDeviceModel* dm, const KDeviceState& st, const KRenderJobs& jobs, const KVisArgs& vis, hipStream_t stream);
 // ranges mode's values of every env's current episode into out double[KM_VP_N][N] (kmanip_get_visual_params)
 void kmanip_launch_vp_draw(const KDeviceState& st, const KVisArgs& vis, double* out, hipStream_t stream);

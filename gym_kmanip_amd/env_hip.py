@@ -251,13 +251,33 @@ class KManipEnvHip:
                     "kmanip_render_rgb")
         return out
 
-    def render_cameras(self, cams=None, out=None):
+    def render_seg(self, cam="top", height=None, width=None, out=None):
+        """uint8 segmentation labels [num_envs, height, width] of the camera's ray cast (kmanip_render_seg): KM_SEG_* values --
+        0 background, 1 table, 2 cube, 3 / 4 the right / left arm's finger spheres.  Size defaults as in render_rgb."""
+        torch = _torch()
+        ci = self._cam_index(cam)
+        spec = CAMERAS[getattr(cam, "name", cam)]
+        height = spec.h if height is None else height
+        width = spec.w if width is None else width
+        if out is None:
+            out = torch.empty((self.num_envs, height, width), dtype=torch.uint8, device=self.device)
+        else:
+            self._check_buf(out, (self.num_envs, height, width), torch.uint8, "segmentation")
+        self._check(self.L.kmanip_render_seg(self.h, ci, height, width, C.c_void_p(out.data_ptr()), self._stream()),
+                    "kmanip_render_seg")
+        return out
+
+    def render_cameras(self, cams=None, out=None, segmentation: bool = False):
         """Every camera of the observation (default: this id's `cameras`, head first) at its reference resolution in ONE launch
-        (kmanip_render_rgb_multi): {name: uint8 [num_envs, h, w, 3]}.  `out` = such a dict of buffers to fill."""
+        (kmanip_render_rgb_multi): {name: uint8 [num_envs, h, w, 3]}.  `out` = such a dict of buffers to fill.
+        segmentation=True: the same launch (kmanip_render_labels_multi) also fills "segmentation/<name>": uint8 [num_envs, h, w]
+        labels (render_seg); `out` may supply those buffers too."""
         torch = _torch()
         names = [getattr(c, "name", c) for c in (self.cm.cameras if cams is None else cams)]
         if not names:
             return {}
+        if segmentation:
+            return self._render_cameras_labels(names, out)
         bufs = {}
         for nm in names:
             spec = CAMERAS[nm]
@@ -273,6 +293,28 @@ class KManipEnvHip:
         ww = (C.c_int32 * n)(*[CAMERAS[nm].w for nm in names])
         pp = (C.c_void_p * n)(*[bufs[nm].data_ptr() for nm in names])
         self._check(self.L.kmanip_render_rgb_multi(self.h, n, ci, hh, ww, pp, self._stream()), "kmanip_render_rgb_multi")
+        return bufs
+
+    def _render_cameras_labels(self, names, out):
+        torch = _torch()
+        bufs = {}
+        for prefix, tail, what in (("", (3,), "rgb"), ("segmentation/", (), "segmentation")):
+            for nm in names:
+                spec = CAMERAS[nm]
+                shape = (self.num_envs, spec.h, spec.w) + tail
+                t = None if out is None else out.get(prefix + nm)
+                if t is None:
+                    t = torch.empty(shape, dtype=torch.uint8, device=self.device)
+                else:
+                    self._check_buf(t, shape, torch.uint8, what)
+                bufs[prefix + nm] = t
+        n = len(names)
+        ci = (C.c_int32 * n)(*[self._cam_index(nm) for nm in names])
+        hh = (C.c_int32 * n)(*[CAMERAS[nm].h for nm in names])
+        ww = (C.c_int32 * n)(*[CAMERAS[nm].w for nm in names])
+        pp = (C.c_void_p * n)(*[bufs[nm].data_ptr() for nm in names])
+        ss = (C.c_void_p * n)(*[bufs["segmentation/" + nm].data_ptr() for nm in names])
+        self._check(self.L.kmanip_render_labels_multi(self.h, n, ci, hh, ww, pp, ss, self._stream()), "kmanip_render_labels_multi")
         return bufs
 
     def snapshot_render_state(self, slot: int):

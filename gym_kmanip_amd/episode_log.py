@@ -138,24 +138,40 @@ class EpisodeLogger:
         self.qvel = torch.zeros((T, num_envs, q_len), dtype=torch.float32, device=device)
         self.action = torch.zeros((T, num_envs, self.log_a_len), dtype=torch.float32, device=device)
         self.cams = {}                 # name -> (Cam, ring uint8 [T, len(env_ids), h, w, c])
+        self.labels = {}               # name -> ring uint8 [T, len(env_ids), h, w]: segmentation labels (cam(..., labels=True))
         self._frames_due = set()       # rows logged with images_later=True whose frames have not arrived
         self._sel = torch.as_tensor(self.env_ids, dtype=torch.long, device=device)
         self.t = 0
         self.episode = 0
         self.cpu_time0 = None          # info["cpu_time"] of the episode's reset (env_base.py:226)
 
-    def cam(self, cam) -> None:
+    def cam(self, cam, labels: bool = False) -> None:
         """log_h5py.cam (:36-46): register a camera -- its metadata group and a uint8 image dataset per episode.  Frames of
-        the selected envs only are kept (a 480x640 head frame is 0.9 MB per env and step)."""
+        the selected envs only are kept (a 480x640 head frame is 0.9 MB per env and step).  labels=True: every step also brings
+        the camera's segmentation labels (`step(..., labels=)`), written as `observations/segmentation/<name> [T, h, w] uint8`;
+        the reference's tree has no such node, so not together with reference_action_quirk."""
         torch = self.torch
+        if labels and self.quirk:
+            raise ValueError("segmentation labels are logged in the default layout only: the reference's tree has no such node")
         ring = torch.zeros((MAX_EPISODE_STEPS, len(self.env_ids), cam.h, cam.w, cam.c), dtype=torch.uint8, device=self.device)
         self.cams[cam.name] = (cam, ring)
+        if labels:
+            self.labels[cam.name] = torch.zeros((MAX_EPISODE_STEPS, len(self.env_ids), cam.h, cam.w), dtype=torch.uint8, device=self.device)
 
-    def step(self, act_flat, obs_q_pos, obs_q_vel, images: Optional[Dict[str, Any]] = None, images_later: bool = False) -> int:
+    def step(self, act_flat, obs_q_pos, obs_q_vel, images: Optional[Dict[str, Any]] = None, images_later: bool = False,
+             labels: Optional[Dict[str, Any]] = None) -> int:
         """Append one control step (log_h5py.step): device-to-device copies only.  `images`: camera name -> uint8
         [num_envs, h, w, 3] (e.g. KManipEnvHip.render_rgb) for every registered camera.  images_later: the frames of this step
         are still being rendered (pipeline.RenderBehind): hand them to `late_images(t, images)` with the returned row index t
-        before end_episode().  Returns t."""
+        before end_episode().  `labels`: "segmentation/<name>" -> uint8 [num_envs, h, w] for every camera registered with
+        labels=True (they may also sit in `images` under that key, as RenderBehind(segmentation=True).images() returns them).
+        With images_later the labels come later too, in late_images' dict: labels= together with it is a ValueError.  Returns t."""
+        if labels and self.quirk:
+            raise ValueError("segmentation labels are logged in the default layout only: the reference's tree has no such node")
+        if labels and images_later:
+            raise ValueError("labels= with images_later=True: a row's labels arrive with its frames, through late_images()")
+        if labels:
+            images = dict(images or {}, **labels)
         if self.t >= MAX_EPISODE_STEPS:
             raise RuntimeError("episode longer than MAX_EPISODE_STEPS: call end_episode() at the TimeLimit boundary")
         if self.t == 0 and self.cpu_time0 is None:
@@ -180,6 +196,11 @@ class EpisodeLogger:
                 raise KeyError("no frame for registered camera %r in this step" % name)
             img = images[name] if name in images else images[cam.log_name]
             ring[t].copy_(img.index_select(0, self._sel))
+        for name, ring in self.labels.items():
+            key = "segmentation/" + name
+            if images is None or key not in images:
+                raise KeyError("no segmentation labels for registered camera %r in this step" % name)
+            ring[t].copy_(images[key].index_select(0, self._sel))
 
     def late_images(self, t: int, images: Dict[str, Any]) -> None:
         """The frames of row t, logged with `step(..., images_later=True)` (copies on the CURRENT stream: call it after
@@ -213,6 +234,7 @@ class EpisodeLogger:
         self.episode += 1
         qpos = self.qpos.cpu().numpy(); qvel = self.qvel.cpu().numpy(); action = self.action.cpu().numpy()
         frames = {name: ring.cpu().numpy() for name, (cam, ring) in self.cams.items()}
+        segs = {name: ring.cpu().numpy() for name, ring in self.labels.items()}
         Tree = _H5Tree if self.backend == "h5py" else _NpzTree
         paths = []
         for k, e in enumerate(self.env_ids):
@@ -228,10 +250,15 @@ class EpisodeLogger:
                 tree.group_attrs("metadata/" + cam.log_name, {"resolution": [cam.w, cam.h], "focal_length": cam.fl,
                                                               "principal_point": cam.pp})
                 tree.dataset("/observations/images/" + cam.name, frames[name][:, k], chunks=(1, cam.h, cam.w, cam.c))
+            for name in self.labels:                                                 # (not in the reference: DESIGN.md section 13)
+                cam = self.cams[name][0]
+                tree.dataset("/observations/segmentation/" + name, segs[name][:, k], chunks=(1, cam.h, cam.w))
             paths.append(tree.close())
         self.t = 0
         self.cpu_time0 = None
         self.qpos.zero_(); self.qvel.zero_(); self.action.zero_()
         for _, ring in self.cams.values():
+            ring.zero_()
+        for ring in self.labels.values():
             ring.zero_()
         return paths

@@ -4,9 +4,11 @@ overwritten by the unit vector from the right end effector to the cube) for a wh
 the policy is a kernel (`kmanip_scripted_action`), the step takes its device action matrix, the logger's rings are device
 tensors.  A *Vision id also logs its camera frames (the reference's log_h5py.cam / step): the heuristic acts on the state, so
 the frames of step t are rendered BEHIND the steps (pipeline.RenderBehind: a qpos snapshot and a second stream) and reach the
-logger while step t + 1 runs -- `--render-in-sequence` renders them before the next step instead.
+logger while step t + 1 runs -- `--render-in-sequence` renders them before the next step instead.  `--segmentation` logs the
+per-pixel class labels of every frame next to it (`observations/segmentation/<camera>`), rendered by the frames' own launch.
 
     python -m gym_kmanip_amd.examples.synthetic_data [--env KManipSoloArm] [--num-envs 4096] [--episodes 10] [--log-envs 0 1 2 3]
+                                                     [--segmentation]
 """
 import argparse
 import os
@@ -25,6 +27,7 @@ def main(argv=None):
     ap.add_argument("--log-envs", type=int, nargs="*", default=[0, 1, 2, 3])
     ap.add_argument("--log-dir", default=os.path.join(os.getcwd(), "data", "sim_synth"))
     ap.add_argument("--render-in-sequence", action="store_true", help="*Vision ids: render every step's frames before the next step starts")
+    ap.add_argument("--segmentation", action="store_true", help="*Vision ids: also log uint8 class labels per pixel (KM_SEG_*)")
     args = ap.parse_args(argv)
     import torch
     os.makedirs(args.log_dir, exist_ok=True)
@@ -35,8 +38,8 @@ def main(argv=None):
     from gym_kmanip_amd.model import CAMERAS
     from gym_kmanip_amd.pipeline import RenderBehind
     for name in env.cm.cameras:                                                  # (none unless the id is a *Vision one)
-        log.cam(CAMERAS[name])
-    behind = RenderBehind(env) if (env.cm.cameras and not args.render_in_sequence) else None
+        log.cam(CAMERAS[name], labels=args.segmentation)
+    behind = RenderBehind(env, segmentation=args.segmentation) if (env.cm.cameras and not args.render_in_sequence) else None
     gen = torch.Generator(device=env.obs.device); gen.manual_seed(0)
     t0 = time.time()
     closest = None
@@ -53,7 +56,7 @@ def main(argv=None):
                     log.late_images(due[1], behind.images(due[0]))               # the previous step's frames have had a whole step
                 due = (k, log.step(act, env.obs[:, :q], env.obs[:, q:2 * q], images_later=True))
             else:
-                log.step(act, env.obs[:, :q], env.obs[:, q:2 * q], images=env.render_cameras() if env.cm.cameras else None)
+                log.step(act, env.obs[:, :q], env.obs[:, q:2 * q], images=env.render_cameras(segmentation=args.segmentation) if env.cm.cameras else None)
         if due is not None:
             log.late_images(due[1], behind.images(due[0]))
         paths = log.end_episode()

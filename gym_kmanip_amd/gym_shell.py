@@ -26,7 +26,7 @@ from typing import Any, Dict
 import numpy as np
 
 from . import env_hip
-from .model import (CAMERAS, ENV_SPECS, MAX_EPISODE_STEPS, REWARD_SUCCESS_THRESHOLD, KM_DONE_DIVERGED, EnvSpec, load_asset)
+from .model import (CAMERAS, ENV_SPECS, KM_SEG_N, MAX_EPISODE_STEPS, REWARD_SUCCESS_THRESHOLD, KM_DONE_DIVERGED, EnvSpec, load_asset)
 
 OBS_DTYPE = np.float64   # __init__.py:50
 ACT_DTYPE = np.float32   # __init__.py:51
@@ -93,9 +93,11 @@ INFO_KEYS = ("step", "episode", "is_success", "q_keys", "q_len", "a_len", "obs_l
              "sim_time", "cpu_time", "reward", "terminated")
 
 
-def spaces_for(env_id: str):
+def spaces_for(env_id: str, segmentation: bool = False):
     """{"observation": OrderedDict, "action": OrderedDict} of Boxes for a registered id: the Dict spaces KManipEnv.__init__
-    builds (env_base.py:115-190) -- same keys, insertion order (== flat column order of the action matrix), shapes, dtypes, bounds."""
+    builds (env_base.py:115-190) -- same keys, insertion order (== flat column order of the action matrix), shapes, dtypes, bounds.
+    segmentation=True (not in the reference): "segmentation/<cam>" label Boxes (0 .. KM_SEG_N - 1, (h, w), uint8) after the
+    "camera/<cam>" keys."""
     spec: EnvSpec = ENV_SPECS[env_id]
     q_len = len(spec.q_pos_home)
     od = OrderedDict()
@@ -111,6 +113,11 @@ def spaces_for(env_id: str):
         if "camera" in o:
             cam = CAMERAS[o.split("/")[-1]]
             od[cam.log_name] = _box(cam.low, cam.high, (cam.h, cam.w, 3), cam.dtype)
+    if segmentation:
+        for o in spec.obs_list:
+            if "camera" in o:
+                cam = CAMERAS[o.split("/")[-1]]
+                od["segmentation/" + cam.name] = _box(0, KM_SEG_N - 1, (cam.h, cam.w), np.uint8)
     ad = OrderedDict()
     for key in ["eel_pos", "eel_orn", "eer_pos", "eer_orn"]:
         if key in spec.act_list:
@@ -143,7 +150,7 @@ class KManipEnv(_EnvBase):
                  squeeze: bool = False, env_id_offset: int = 0, device_outputs: bool = False,
                  log_h5py: bool = False, log_prefix: str = "test", log_env_ids=None, log_backend=None,
                  log_reference_layout: bool = False, log_h5py_module=None, domain_randomization=None, visual_randomization=None,
-                 **overrides):
+                 segmentation: bool = False, **overrides):
         spec: EnvSpec = ENV_SPECS[env_id]
         self.env_id = env_id
         self.seed = seed
@@ -165,8 +172,12 @@ class KManipEnv(_EnvBase):
         self.act_list = list(spec.act_list)
         # env_base.py:110-113: the Cam records of the "camera/<name>" observation keys
         self.cameras = [CAMERAS[o.split("/")[-1]] for o in self.obs_list if "camera" in o]
+        # segmentation=True: a "segmentation/<cam>" label image after the camera keys, rendered by the cameras' own launch
+        self.segmentation = bool(segmentation) and bool(self.cameras)
+        if self.segmentation and log_h5py and log_reference_layout:
+            raise ValueError("the reference's log tree has no segmentation node: use the default layout with segmentation=True")
         # observation / action spaces, env_base.py:115-190
-        sp = spaces_for(env_id)
+        sp = spaces_for(env_id, segmentation=self.segmentation)
         self.observation_space = _dict(sp["observation"])
         self.action_space = _dict(sp["action"])
         self.action_len = len(sp["action"])
@@ -177,6 +188,8 @@ class KManipEnv(_EnvBase):
         # backend seam, env_base.py:192-200
         self.env = env_hip.new(self, num_envs=num_envs, device=device, env_id_offset=env_id_offset,
                                auto_reset=False, **overrides)
+        if self.segmentation:                       # (after the backend read the reference's obs_list)
+            self.obs_list = self.obs_list + ["segmentation/" + cam.name for cam in self.cameras]
         # domain_randomization={name: (lo, hi)} (env_hip.ENV_PARAMS names): every reset redraws those physics parameters per env
         if domain_randomization:
             self.env.set_env_param_ranges(**domain_randomization)
@@ -203,14 +216,15 @@ class KManipEnv(_EnvBase):
                                         grip_r_col=None if grip is None else grip.start,
                                         reference_action_quirk=log_reference_layout, h5py_module=log_h5py_module)
             for cam in self.cameras:                                                 # env_base.py:233-234
-                self.logger.cam(cam)
+                self.logger.cam(cam, labels=self.segmentation)
 
     def _log_step(self, action, obs_dev):
         """env_base.py:255-257: append this step's action / q_pos / q_vel (and camera frames) to the episode's rings."""
         act = self.env.last_act                                                 # the flat row k_step packed and ran on
         q = self.q_len
         frames = {cam.name: obs_dev[cam.log_name] for cam in self.cameras} or None
-        self.logger.step(act, self.env.obs[:, :q], self.env.obs[:, q:2 * q], images=frames)
+        labels = {"segmentation/" + cam.name: obs_dev["segmentation/" + cam.name] for cam in self.cameras} if self.segmentation else None
+        self.logger.step(act, self.env.obs[:, :q], self.env.obs[:, q:2 * q], images=frames, labels=labels)
 
     def _log_flush(self):
         if self.logger is not None and self.logger.t > 0:
@@ -222,9 +236,12 @@ class KManipEnv(_EnvBase):
         launch: kmanip_render_rgb_multi), in obs_list order."""
         obs = OrderedDict((k, v) for k, v in state_obs.items() if k in self.obs_list)
         if self.cameras:
-            imgs = self.env.render_cameras(self.cameras)
+            imgs = self.env.render_cameras(self.cameras, segmentation=True) if self.segmentation else self.env.render_cameras(self.cameras)
             for cam in self.cameras:
                 obs[cam.log_name] = imgs[cam.name]
+            if self.segmentation:
+                for cam in self.cameras:
+                    obs["segmentation/" + cam.name] = imgs["segmentation/" + cam.name]
         self._obs_dev = obs
         if self.device_outputs:
             return obs

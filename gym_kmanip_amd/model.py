@@ -612,3 +612,35 @@ def draw_visual_params(seed: int, genv: int, episode: int, lo, hi) -> np.ndarray
                 u = _u53(o[2 * j], o[2 * j + 1])
                 out[k] = float(lo[k]) + (float(hi[k]) - float(lo[k])) * u
     return out
+
+
+# ---- segmentation labels of the camera renders (include/kmanip.h KM_SEG_*)
+KM_SEG_BACKGROUND, KM_SEG_TABLE, KM_SEG_CUBE, KM_SEG_ROBOT_R, KM_SEG_ROBOT_L, KM_SEG_N = 0, 1, 2, 3, 4, 5
+SEG_CLASSES = ("background", "table", "cube", "robot_r", "robot_l")
+
+
+def sphere_arm(cm: CompiledModel, strict: bool = False) -> list:
+    """The arm (0 right, 1 left) of every collision sphere, as kmanip_create computes it for the label render: sphere s belongs to
+    arm a when sphere_link[s] is an ancestor-or-self of arm_site_link[a] or of one of arm_grip_id[a][*], walking link_parent.
+    That names exactly one arm for every sphere of the reference models.  For any other desc kmanip_create refuses nothing: a
+    sphere on several chains gets the lowest of those arms and one on none gets arm 0, and so does this function; strict=True
+    raises ValueError for such a sphere instead."""
+    d = cm.desc
+    out = []
+    for s in range(d.nsphere):
+        arms = []
+        for a in range(KM_MAX_ARMS):
+            if not d.arm_present[a]:
+                continue
+            chain = set()
+            for leaf in (d.arm_site_link[a], d.arm_grip_id[a][0], d.arm_grip_id[a][1]):
+                j = leaf
+                while 0 <= j < d.nlink:
+                    chain.add(j)
+                    j = d.link_parent[j]
+            if d.sphere_link[s] in chain:
+                arms.append(a)
+        if strict and len(arms) != 1:
+            raise ValueError("sphere %d lies on the chains of arms %s, expected exactly one" % (s, arms))
+        out.append(arms[0] if arms else 0)
+    return out

@@ -145,11 +145,14 @@ class RenderBehind:
     read from a stream images() never saw, shows torn or newer images: clone what has to live longer.
     """
 
-    def __init__(self, env, cams=None, depth=None):
+    def __init__(self, env, cams=None, depth=None, segmentation: bool = False):
         """cams: RGB cameras (default: the env id's camera observations; [] for none).  depth: (camera, height, width) of a float32
-        depth image rendered with them (BASELINE config 5's 64 x 64 gripper image), under the key "depth"."""
+        depth image rendered with them (BASELINE config 5's 64 x 64 gripper image), under the key "depth".  segmentation: the
+        image sets also carry "segmentation/<name>" uint8 [n, h, w] labels of every RGB camera, rendered from the same snapshot by
+        the same launch (KManipEnvHip.render_cameras(segmentation=True)), under the same ordering contract."""
         torch = _torch()
         self.torch, self.env, self.cams, self.depth = torch, env, cams, depth
+        self.segmentation = bool(segmentation)
         self.k = 0
         self.stream = torch.cuda.Stream(device=env.device)
         self.bufs = [self._render(None), self._render(None)]                      # two image sets (allocated by a first render each)
@@ -159,7 +162,12 @@ class RenderBehind:
         self._readers = [set(), set()]            # streams images() handed set s to since its last render
 
     def _render(self, out):
-        bufs = dict(self.env.render_cameras(self.cams, out=out)) if (self.cams is None or len(self.cams)) else {}
+        if not (self.cams is None or len(self.cams)):
+            bufs = {}
+        elif self.segmentation:
+            bufs = dict(self.env.render_cameras(self.cams, out=out, segmentation=True))
+        else:
+            bufs = dict(self.env.render_cameras(self.cams, out=out))
         if self.depth is not None:
             cam, h, w = self.depth
             bufs["depth"] = self.env.render_depth(cam, h, w, out=None if out is None else out["depth"])

@@ -290,7 +290,7 @@ KMANIP_API int kmanip_get_diag(KHandle h, uint32_t* contact_mask, int32_t* ik_nf
 
 /* Kernel timing with HIP events recorded on the launch stream (bench.py roofline leg).  While enabled, every kmanip_step
  * records an event before and after k_step and one more after the bound in-step render (or after the first kmanip_render_rgb[_multi]
- * call that follows the step: the camera observations of a *Vision id), into a ring of `KM_TIMING_SLOTS` steps (an event record
+ * / kmanip_render_labels_multi call that follows the step: the camera observations of a *Vision id), into a ring of `KM_TIMING_SLOTS` steps (an event record
  * costs the stream about 5 us).  kmanip_timing_summary synchronises the device and returns the summed durations in milliseconds of
  * k_step and of the step's render (kmanip_bind_step_depth's or the RGB render called after the step, 0 without one) over the
  * recorded steps, then clears the ring.  *ik_ms_sum is always 0: before_step runs inside k_step, and the argument is kept for ABI
@@ -338,6 +338,20 @@ KMANIP_API int kmanip_render_rgb(KHandle h, int cam, int height, int width, uint
  * rgb_dev are HOST arrays of ncam entries; rgb_dev[i] is device memory uint8[num_envs, heights[i], widths[i], 3]. */
 KMANIP_API int kmanip_render_rgb_multi(KHandle h, int ncam, const int* cams, const int* heights, const int* widths, uint8_t* const* rgb_dev,
                             void* stream);
+
+/* Per-pixel segmentation labels of the same ray cast: the class of what the pixel's ray hits first.
+ * 0..2 are the ray caster's materials; a robot pixel carries the arm of the finger sphere that was hit (sphere s belongs to arm a
+ * when sphere_link[s] is an ancestor-or-self of arm_site_link[a] or of one of arm_grip_id[a][*]; gym_kmanip_amd/model.py
+ * sphere_arm).  A label depends on geometry only: colours and lights (KM_VP_*) never change it, the per-env camera offset moves it
+ * exactly as it moves the RGB image. */
+enum { KM_SEG_BACKGROUND = 0, KM_SEG_TABLE = 1, KM_SEG_CUBE = 2, KM_SEG_ROBOT_R = 3, KM_SEG_ROBOT_L = 4, KM_SEG_N = 5 };
+/* ncam jobs in ONE launch.  seg_dev[i]: device uint8[num_envs, heights[i], widths[i]] (KM_SEG_* values) or NULL;
+ * rgb_dev[i]: device uint8[num_envs, heights[i], widths[i], 3] or NULL; rgb_dev itself may be NULL (labels only).  A job with
+ * neither is an error.  The RGB bytes are those kmanip_render_rgb_multi writes.  Snapshots (kmanip_set_render_source), visual
+ * parameters and kmanip_enable_timing are honoured as by kmanip_render_rgb_multi. */
+KMANIP_API int kmanip_render_labels_multi(KHandle h, int ncam, const int* cams, const int* heights, const int* widths,
+                               uint8_t* const* rgb_dev, uint8_t* const* seg_dev, void* stream);
+KMANIP_API int kmanip_render_seg(KHandle h, int cam, int height, int width, uint8_t* seg_dev, void* stream);   /* one camera, labels only */
 
 /* Rendering BEHIND the steps (a data-generation loop whose policy does not look at the images: the reference's scripted heuristic,
  * examples/2_synthetic_data.py:28-41, logs them and acts on the state).  A render reads nothing of the state but qpos (and, in
