@@ -14,7 +14,7 @@
 
 #include "kmanip_device.hpp"
 
-#define KM_VERSION "kmanip-hip 0.30 (gfx950, f64)"
+#define KM_VERSION "kmanip-hip 0.31 (gfx950, f64)"
 
 static thread_local std::string g_create_error;
 
@@ -60,6 +60,10 @@ struct KHandle_ {
   int* vp_flag = nullptr;           // validation result of kmanip_set_visual_params
   int32_t* ep_snap[2] = {nullptr, nullptr};   // the episode counters a snapshot took in ranges mode (a render of that slot draws from them)
   bool ep_snap_ok[2] = {false, false};
+  // link capsules of the RGB / label renders (kmanip_set_render_links): the list in force and its device copy,
+  // an argument of k_render_links; empty = the default kernels
+  std::vector<KLinkCapsule> links;
+  KLinkCapsule* links_buf = nullptr;   // [KM_MAX_LINK_CAPSULES], allocated by the first call that sets a list
   std::vector<void*> allocs;
 };
 
@@ -553,7 +557,14 @@ int kmanip_render_rgb_multi(KHandle h, int ncam, const int* cams, const int* hei
   KM_ENTER(h);
   KDeviceState st = h->st;
   if (h->render_src >= 0) st.qpos = h->qpos_snap[h->render_src];
-  kmanip_launch_render_rgb(h->dmodel, st, jobs, vis_args(h, h->render_src), (hipStream_t)stream);
+  if (!h->links.empty()) {
+    // link capsules: the kernel that draws them, with no label output
+    KLabelJobs lj{};
+    lj.n = ncam;
+    for (int i = 0; i < ncam; i++) { lj.cam[i] = jobs.cam[i]; lj.height[i] = jobs.height[i]; lj.width[i] = jobs.width[i]; lj.rgb[i] = jobs.rgb[i]; lj.seg[i] = nullptr; }
+    kmanip_launch_render_links(h->dmodel, st, lj, true, KLinkArgs{h->links_buf, (int)h->links.size()}, vis_args(h, h->render_src), (hipStream_t)stream);
+  } else
+    kmanip_launch_render_rgb(h->dmodel, st, jobs, vis_args(h, h->render_src), (hipStream_t)stream);
   // kernel timing (kmanip_enable_timing): the camera observations rendered right after a timed step are that step's render leg --
   // its start is the event the step recorded after k_step, so the render costs the stream ONE more event, not a pair around it
   // (a render of a SNAPSHOT runs behind the steps, on a stream of its own: it is no leg of the step's stream)
@@ -591,7 +602,10 @@ int kmanip_render_labels_multi(KHandle h, int ncam, const int* cams, const int* 
   KDeviceState st = h->st;
   if (h->render_src >= 0) st.qpos = h->qpos_snap[h->render_src];
   // labels only in every job: the kernel that does not shade; anything else: the one that writes what each job asks for
-  kmanip_launch_render_labels(h->dmodel, st, jobs, nrgb > 0, vis_args(h, h->render_src), (hipStream_t)stream);
+  if (!h->links.empty())
+    kmanip_launch_render_links(h->dmodel, st, jobs, nrgb > 0, KLinkArgs{h->links_buf, (int)h->links.size()}, vis_args(h, h->render_src), (hipStream_t)stream);
+  else
+    kmanip_launch_render_labels(h->dmodel, st, jobs, nrgb > 0, vis_args(h, h->render_src), (hipStream_t)stream);
   // (kmanip_enable_timing: the render after the step, as in kmanip_render_rgb_multi)
   if (h->timing && h->render_src < 0 && h->last_step_timed && h->timed_steps > 0 && !h->ev_render[h->timed_steps - 1]) {
     HIPCHK(h, hipEventRecord(h->ev[3 * (size_t)(h->timed_steps - 1) + 2], (hipStream_t)stream));
@@ -603,6 +617,46 @@ int kmanip_render_labels_multi(KHandle h, int ncam, const int* cams, const int* 
 
 int kmanip_render_seg(KHandle h, int cam, int height, int width, uint8_t* seg_dev, void* stream) {
   return kmanip_render_labels_multi(h, 1, &cam, &height, &width, nullptr, &seg_dev, stream);
+}
+
+int kmanip_set_render_links(KHandle h, int n, const KLinkCapsule* caps) {
+  if (!h) { g_create_error = "kmanip_set_render_links: null handle"; return -1; }
+  if (n < 0 || n > KM_MAX_LINK_CAPSULES) { h->err = "kmanip_set_render_links: n must be 0 .. " + std::to_string(KM_MAX_LINK_CAPSULES); return -1; }
+  if (n > 0 && !caps) { h->err = "kmanip_set_render_links: caps is NULL with n > 0"; return -1; }
+  auto finite = [](double v) { return v - v == 0.0; };
+  for (int k = 0; k < n; k++) {
+    const KLinkCapsule& c = caps[k];
+    const char* what = nullptr;
+    if (c.link < 0 || c.link >= h->desc.nlink) what = "link out of range";
+    else if (c.label != KM_SEG_ROBOT_R && c.label != KM_SEG_ROBOT_L) what = "label must be KM_SEG_ROBOT_R or KM_SEG_ROBOT_L";
+    else if (!finite(c.radius) || !(c.radius > 0)) what = "radius must be finite and > 0";
+    else for (int q = 0; q < 3; q++) if (!finite(c.p0[q]) || !finite(c.seg[q])) what = "p0 and seg must be finite";
+    if (what) { h->err = "kmanip_set_render_links: capsule " + std::to_string(k) + ": " + what; return -2; }
+  }
+  KM_ENTER(h);
+  // a render in flight on any stream may read the list: every change waits for the device
+  HIPCHK(h, hipDeviceSynchronize());
+  if (n == 0) { h->links.clear(); return 0; }
+  if (!h->links_buf) {
+    void* p = nullptr;
+    HIPCHK(h, hipMalloc(&p, sizeof(KLinkCapsule) * KM_MAX_LINK_CAPSULES));
+    h->allocs.push_back(p);
+    h->links_buf = (KLinkCapsule*)p;
+  }
+  std::vector<KLinkCapsule> list(caps, caps + n);
+  for (auto& c : list) c.pad_ = 0;
+  HIPCHK(h, hipMemcpy(h->links_buf, list.data(), sizeof(KLinkCapsule) * n, hipMemcpyHostToDevice));
+  HIPCHK(h, hipDeviceSynchronize());
+  h->links.swap(list);
+  return 0;
+}
+
+int kmanip_get_render_links(KHandle h, int* n, KLinkCapsule* caps) {
+  if (!h) { g_create_error = "kmanip_get_render_links: null handle"; return -1; }
+  if (!n) { h->err = "kmanip_get_render_links: n is NULL"; return -1; }
+  *n = (int)h->links.size();
+  if (caps) for (size_t k = 0; k < h->links.size(); k++) caps[k] = h->links[k];
+  return 0;
 }
 
 int kmanip_bind_step_depth(KHandle h, int cam, int height, int width, float* depth_dev) {

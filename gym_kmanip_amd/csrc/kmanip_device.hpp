@@ -586,6 +586,11 @@ struct KRenderJobs { int n; int cam[KM_MAX_CAMS], height[KM_MAX_CAMS], width[KM_
 struct KLabelJobs { int n; int cam[KM_MAX_CAMS], height[KM_MAX_CAMS], width[KM_MAX_CAMS]; uint8_t* rgb[KM_MAX_CAMS]; uint8_t* seg[KM_MAX_CAMS]; };
 void kmanip_launch_render_labels(const KDeviceModel* dm, const KDeviceState& st, const KLabelJobs& jobs, bool rgb, const KVisArgs& vis, hipStream_t stream);
 void kmanip_launch_render_rgb(const KDeviceModel* dm, const KDeviceState& st, const KRenderJobs& jobs, const KVisArgs& vis, hipStream_t stream);
+// link capsules (kmanip_set_render_links; kmanip_render_links.hip): the handle's device copy of the list, an argument of its own --
+// no field of KDeviceModel / KDeviceState moves.  rgb: some job has an rgb pointer (else labels only); a job's seg may be NULL
+struct KLinkArgs { const KLinkCapsule* caps; int n; };
+void kmanip_launch_render_links(const KDeviceModel* dm, const KDeviceState& st, const KLabelJobs& jobs, bool rgb, const KLinkArgs& links, const KVisArgs& vis,
+                                hipStream_t stream);
 // ranges mode's values of every env's current episode into out double[KM_VP_N][N] (kmanip_get_visual_params)
 void kmanip_launch_vp_draw(const KDeviceState& st, const KVisArgs& vis, double* out, hipStream_t stream);
 // envs per workgroup (= per wave) of a step / reset launch: as many waves as the chip has SIMD slots for, but no more lanes idle than

@@ -20,8 +20,8 @@ import numpy as np
 
 from . import lib as _libmod
 from .model import (CAMERAS, CONTROL_TIMESTEP, ENV_PARAMS, ENV_SPECS, KM_ACT_KEYS, KM_CAM_INDEX, KM_VP_N, VISUAL_PARAMS,
-                    CompiledModel, EnvSpec, check_visual_param, compile_model, env_param_defaults, visual_param_defaults,
-                    visual_param_vector)
+                    CompiledModel, EnvSpec, check_link_capsules, check_visual_param, compile_model, env_param_defaults,
+                    link_capsules, visual_param_defaults, visual_param_vector)
 
 MJCF_TO_ASSET = {"_env_solo_arm.xml": "solo_arm", "_env_dual_arm.xml": "dual_arm", "_env_torso.xml": "torso"}
 
@@ -253,7 +253,8 @@ class KManipEnvHip:
 
     def render_seg(self, cam="top", height=None, width=None, out=None):
         """uint8 segmentation labels [num_envs, height, width] of the camera's ray cast (kmanip_render_seg): KM_SEG_* values --
-        0 background, 1 table, 2 cube, 3 / 4 the right / left arm's finger spheres.  Size defaults as in render_rgb."""
+        0 background, 1 table, 2 cube, 3 / 4 the right / left arm's finger spheres and, while a capsule list is set
+        (set_render_links), that arm's link capsules.  Size defaults as in render_rgb."""
         torch = _torch()
         ci = self._cam_index(cam)
         spec = CAMERAS[getattr(cam, "name", cam)]
@@ -316,6 +317,34 @@ class KManipEnvHip:
         ss = (C.c_void_p * n)(*[bufs["segmentation/" + nm].data_ptr() for nm in names])
         self._check(self.L.kmanip_render_labels_multi(self.h, n, ci, hh, ww, pp, ss, self._stream()), "kmanip_render_labels_multi")
         return bufs
+
+    def set_render_links(self, caps=True):
+        """Draw the arm links as capsules in every RGB and label render of this handle (kmanip_set_render_links; depth renders
+        never draw them).  True: the model's default list (model.link_capsules); a list of dicts with the fields of KLinkCapsule
+        (link, label, cam_mask, p0, seg, radius) or of tuples in that order: that list; None / False / an empty list: no
+        capsules, the default kernels again.  Synchronous.  A bad list raises and leaves the list in force unchanged."""
+        if caps is None or caps is False:
+            caps = []
+        elif caps is True:
+            caps = link_capsules(self.cm)
+        try:
+            caps = check_link_capsules(self.cm, caps)
+        except ValueError as e:
+            raise _libmod.KManipError("set_render_links: %s" % e) from None
+        arr = (_libmod.KLinkCapsule * max(len(caps), 1))()
+        for a, c in zip(arr, caps):
+            a.link, a.label, a.cam_mask, a.radius = c["link"], c["label"], c["cam_mask"], c["radius"]
+            a.p0[:] = c["p0"]
+            a.seg[:] = c["seg"]
+        self._check(self.L.kmanip_set_render_links(self.h, len(caps), arr if caps else None), "kmanip_set_render_links")
+
+    def get_render_links(self) -> list:
+        """The capsule list in force (kmanip_get_render_links), as set_render_links takes it; [] without one."""
+        arr = (_libmod.KLinkCapsule * _libmod.KM_MAX_LINK_CAPSULES)()
+        n = C.c_int(0)
+        self._check(self.L.kmanip_get_render_links(self.h, C.byref(n), arr), "kmanip_get_render_links")
+        return [{"link": a.link, "label": a.label, "cam_mask": a.cam_mask, "p0": tuple(a.p0), "seg": tuple(a.seg), "radius": a.radius}
+                for a in arr[:n.value]]
 
     def snapshot_render_state(self, slot: int):
         """Copy qpos -- all a render reads of the state -- into snapshot `slot` (0 / 1) on the current stream

@@ -6,9 +6,10 @@ tensors.  A *Vision id also logs its camera frames (the reference's log_h5py.cam
 the frames of step t are rendered BEHIND the steps (pipeline.RenderBehind: a qpos snapshot and a second stream) and reach the
 logger while step t + 1 runs -- `--render-in-sequence` renders them before the next step instead.  `--segmentation` logs the
 per-pixel class labels of every frame next to it (`observations/segmentation/<camera>`), rendered by the frames' own launch.
+`--links` draws the arm links as capsules in the frames and the labels (KManipEnvHip.set_render_links).
 
     python -m gym_kmanip_amd.examples.synthetic_data [--env KManipSoloArm] [--num-envs 4096] [--episodes 10] [--log-envs 0 1 2 3]
-                                                     [--segmentation]
+                                                     [--segmentation] [--links]
 """
 import argparse
 import os
@@ -28,10 +29,13 @@ def main(argv=None):
     ap.add_argument("--log-dir", default=os.path.join(os.getcwd(), "data", "sim_synth"))
     ap.add_argument("--render-in-sequence", action="store_true", help="*Vision ids: render every step's frames before the next step starts")
     ap.add_argument("--segmentation", action="store_true", help="*Vision ids: also log uint8 class labels per pixel (KM_SEG_*)")
+    ap.add_argument("--links", action="store_true", help="*Vision ids: draw the arm links as capsules in the frames and labels (set_render_links)")
     args = ap.parse_args(argv)
     import torch
     os.makedirs(args.log_dir, exist_ok=True)
     env = env_hip.make(args.env, num_envs=args.num_envs, auto_reset=False)
+    if args.links and env.cm.cameras:
+        env.set_render_links(True)                                               # the frames and labels show the arm, not only the finger tips
     q = env.cm.nlink
     log = EpisodeLogger(args.log_dir, args.num_envs, q, env.cm.act_dim, device=env.obs.device, env_ids=args.log_envs,
                         info={"sim": True, "env": args.env, "policy": "toward-cube heuristic"})

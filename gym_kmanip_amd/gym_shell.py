@@ -150,7 +150,7 @@ class KManipEnv(_EnvBase):
                  squeeze: bool = False, env_id_offset: int = 0, device_outputs: bool = False,
                  log_h5py: bool = False, log_prefix: str = "test", log_env_ids=None, log_backend=None,
                  log_reference_layout: bool = False, log_h5py_module=None, domain_randomization=None, visual_randomization=None,
-                 segmentation: bool = False, **overrides):
+                 segmentation: bool = False, render_links: bool = False, **overrides):
         spec: EnvSpec = ENV_SPECS[env_id]
         self.env_id = env_id
         self.seed = seed
@@ -190,6 +190,10 @@ class KManipEnv(_EnvBase):
                                auto_reset=False, **overrides)
         if self.segmentation:                       # (after the backend read the reference's obs_list)
             self.obs_list = self.obs_list + ["segmentation/" + cam.name for cam in self.cameras]
+        # render_links=True: the camera images (and labels) draw the arm links as capsules (model.link_capsules); spaces and keys unchanged
+        self.render_links = bool(render_links)
+        if self.render_links:
+            self.env.set_render_links(True)
         # domain_randomization={name: (lo, hi)} (env_hip.ENV_PARAMS names): every reset redraws those physics parameters per env
         if domain_randomization:
             self.env.set_env_param_ranges(**domain_randomization)

@@ -644,3 +644,90 @@ def sphere_arm(cm: CompiledModel, strict: bool = False) -> list:
             raise ValueError("sphere %d lies on the chains of arms %s, expected exactly one" % (s, arms))
         out.append(arms[0] if arms else 0)
     return out
+
+
+# ---- link capsules of the RGB / label renders (include/kmanip.h KLinkCapsule)
+KM_MAX_LINK_CAPSULES = 24
+
+
+def link_arm(cm: CompiledModel) -> Dict[int, int]:
+    """{link: arm} for every link on an arm's chain -- sphere_arm's rule: an ancestor-or-self of arm_site_link[a] or of one of
+    arm_grip_id[a][*]; a link on several chains belongs to the lowest of those arms.  Links on no chain are absent."""
+    d = cm.desc
+    out: Dict[int, int] = {}
+    for a in range(KM_MAX_ARMS):
+        if not d.arm_present[a]:
+            continue
+        for leaf in (d.arm_site_link[a], d.arm_grip_id[a][0], d.arm_grip_id[a][1]):
+            j = leaf
+            while 0 <= j < d.nlink:
+                out.setdefault(j, a)
+                j = d.link_parent[j]
+    return out
+
+
+def link_capsules(cm: CompiledModel, radius: float = 0.03) -> list:
+    """The default capsule list of kmanip_set_render_links, as dicts with the fields of KLinkCapsule (link, label, cam_mask, p0,
+    seg, radius), in this order:
+      joint-to-joint capsules -- for every link j whose parent p >= 0, both on an arm's chain (link_arm): one capsule on p from
+        its origin to link_pos[j], of `radius` (0.03 m: the collision housings already in the model);
+      finger capsules -- for every visible sphere s: one capsule on sphere_link[s] from its origin to sphere_pos[s], of
+        sphere_radius[s].
+    label = KM_SEG_ROBOT_R + the chain's arm.  cam_mask = every present camera, minus camera c for capsules whose link is
+    cam_link[c] or link_parent[cam_link[c]]: a gripper camera sits 5 cm from its link's joint origin and looks through it."""
+    d = cm.desc
+    la = link_arm(cm)
+    present = 0
+    for c in range(KM_MAX_CAMS):
+        if d.cam_present[c]:
+            present |= 1 << c
+
+    def mask(link):
+        m = present
+        for c in range(KM_MAX_CAMS):
+            cl = d.cam_link[c]
+            if d.cam_present[c] and cl >= 0 and link in (cl, d.link_parent[cl]):
+                m &= ~(1 << c)
+        return m
+
+    def cap(link, seg, rad):
+        return {"link": int(link), "label": KM_SEG_ROBOT_R + la[link], "cam_mask": mask(link), "p0": (0.0, 0.0, 0.0),
+                "seg": tuple(float(x) for x in seg), "radius": float(rad)}
+    caps = []
+    for j in range(d.nlink):
+        p = d.link_parent[j]
+        if p >= 0 and p in la and j in la:
+            caps.append(cap(p, d.link_pos[j], radius))
+    for s in range(d.nsphere):
+        if d.sphere_visible[s] and d.sphere_link[s] in la:
+            caps.append(cap(d.sphere_link[s], d.sphere_pos[s], d.sphere_radius[s]))
+    if len(caps) > KM_MAX_LINK_CAPSULES:
+        raise ValueError("%d capsules: kmanip_set_render_links takes at most %d" % (len(caps), KM_MAX_LINK_CAPSULES))
+    return caps
+
+
+def check_link_capsules(cm: CompiledModel, caps) -> list:
+    """kmanip_set_render_links' validation on the host: a list of dicts (or (link, label, cam_mask, p0, seg, radius) tuples) ->
+    a list of dicts; ValueError for more than KM_MAX_LINK_CAPSULES entries, a link out of range, a label other than the two robot
+    classes, a radius that is not finite and > 0, or a p0 / seg that is not finite."""
+    keys = ("link", "label", "cam_mask", "p0", "seg", "radius")
+    out = []
+    caps = list(caps)
+    if len(caps) > KM_MAX_LINK_CAPSULES:
+        raise ValueError("%d capsules: at most %d" % (len(caps), KM_MAX_LINK_CAPSULES))
+    for k, c in enumerate(caps):
+        c = dict(c) if isinstance(c, dict) else dict(zip(keys, c))
+        if set(c) != set(keys):
+            raise ValueError("capsule %d: expected the fields %s" % (k, ", ".join(keys)))
+        p0, seg = np.asarray(c["p0"], dtype=np.float64), np.asarray(c["seg"], dtype=np.float64)
+        if not 0 <= int(c["link"]) < cm.desc.nlink:
+            raise ValueError("capsule %d: link out of range" % k)
+        if int(c["label"]) not in (KM_SEG_ROBOT_R, KM_SEG_ROBOT_L):
+            raise ValueError("capsule %d: label must be KM_SEG_ROBOT_R or KM_SEG_ROBOT_L" % k)
+        if not (np.isfinite(c["radius"]) and c["radius"] > 0):
+            raise ValueError("capsule %d: radius must be finite and > 0" % k)
+        if p0.shape != (3,) or seg.shape != (3,) or not (np.isfinite(p0).all() and np.isfinite(seg).all()):
+            raise ValueError("capsule %d: p0 and seg must be 3 finite numbers" % k)
+        out.append({"link": int(c["link"]), "label": int(c["label"]), "cam_mask": int(c["cam_mask"]) & 0xFFFFFFFF,
+                    "p0": tuple(float(x) for x in p0), "seg": tuple(float(x) for x in seg), "radius": float(c["radius"])})
+    return out

@@ -326,7 +326,7 @@ KMANIP_API int kmanip_ik_eval(KHandle h, int arm, int n, const double* qpos, con
  * (env_sim.py:140-145) for the gripper cameras, as BASELINE.json config 5 defines it: a height x width
  * float32 DEPTH image (metres along the optical axis) of every env's current state.
  * depth_dev: float[num_envs, height, width] device memory owned by the caller. */
-KMANIP_API int kmanip_render_depth(KHandle h, int cam, int height, int width, float* depth_dev, void* stream);
+KMANIP_API int kmanip_render_depth(KHandle h, int cam, int height, int width, float* depth_dev, void* stream);   /* (never draws link capsules) */
 
 /* The same cameras as uint8 RGB, what dm_control's physics.render(height, width, camera_id) returns for the camera
  * observations of the *Vision env ids (env_sim.py:140-145; shapes env_base.py:140-146, cameras __init__.py:157-161) and for
@@ -342,7 +342,7 @@ KMANIP_API int kmanip_render_rgb_multi(KHandle h, int ncam, const int* cams, con
 /* Per-pixel segmentation labels of the same ray cast: the class of what the pixel's ray hits first.
  * 0..2 are the ray caster's materials; a robot pixel carries the arm of the finger sphere that was hit (sphere s belongs to arm a
  * when sphere_link[s] is an ancestor-or-self of arm_site_link[a] or of one of arm_grip_id[a][*]; gym_kmanip_amd/model.py
- * sphere_arm).  A label depends on geometry only: colours and lights (KM_VP_*) never change it, the per-env camera offset moves it
+ * sphere_arm) or, while the handle has link capsules (kmanip_set_render_links), the `label` of the capsule that was hit.  A label depends on geometry only: colours and lights (KM_VP_*) never change it, the per-env camera offset moves it
  * exactly as it moves the RGB image. */
 enum { KM_SEG_BACKGROUND = 0, KM_SEG_TABLE = 1, KM_SEG_CUBE = 2, KM_SEG_ROBOT_R = 3, KM_SEG_ROBOT_L = 4, KM_SEG_N = 5 };
 /* ncam jobs in ONE launch.  seg_dev[i]: device uint8[num_envs, heights[i], widths[i]] (KM_SEG_* values) or NULL;
@@ -352,6 +352,33 @@ enum { KM_SEG_BACKGROUND = 0, KM_SEG_TABLE = 1, KM_SEG_CUBE = 2, KM_SEG_ROBOT_R 
 KMANIP_API int kmanip_render_labels_multi(KHandle h, int ncam, const int* cams, const int* heights, const int* widths,
                                uint8_t* const* rgb_dev, uint8_t* const* seg_dev, void* stream);
 KMANIP_API int kmanip_render_seg(KHandle h, int cam, int height, int width, uint8_t* seg_dev, void* stream);   /* one camera, labels only */
+
+/* Link capsules: an opt-in, per-handle list of capsules -- a segment fixed in a link's frame, with a
+ * radius -- that the RGB and label renders draw as robot material (KM_VP_ROBOT_RGB, shaded like the finger spheres, under the
+ * env's light terms and camera offset) and label with `label`.  While a handle has a list, kmanip_render_rgb[_multi],
+ * kmanip_render_seg and kmanip_render_labels_multi launch k_render_links instead of k_render_rgb / k_render_labels; snapshots,
+ * visual parameters and kmanip_enable_timing's render leg are honoured as before.  With no list (the default) every launch is
+ * exactly what it was: the same kernels, the same bytes.  Objects are tested in the order table, cube, spheres, capsules in
+ * list order, and a later object wins only where it is strictly nearer.  Only a ray's entry point counts: a camera inside a
+ * capsule sees through it, as it does through a sphere.  DEPTH IS NOT COVERED: kmanip_render_depth and kmanip_bind_step_depth
+ * keep drawing the scene without capsules.  The capsules are drawn only; the physics never reads them.
+ * gym_kmanip_amd/model.py link_capsules builds the default list (joint-to-joint capsules along both arms plus the fingers). */
+#define KM_MAX_LINK_CAPSULES 24
+typedef struct KLinkCapsule {
+  int32_t  link;      /* 0 .. nlink-1: the frame p0 / seg are given in                      */
+  int32_t  label;     /* KM_SEG_ROBOT_R or KM_SEG_ROBOT_L: what a pixel of it is labelled   */
+  uint32_t cam_mask;  /* bit KM_CAM_*: drawn by that camera                                 */
+  int32_t  pad_;
+  double   p0[3], seg[3];   /* axis from p0 to p0 + seg, link frame; seg = 0 is a sphere    */
+  double   radius;          /* metres, > 0                                                  */
+} KLinkCapsule;
+/* caps: HOST array of n entries; n = 0 or caps == NULL with n = 0: no list (the default kernels again).  Validated first
+ * (0 <= n <= KM_MAX_LINK_CAPSULES, link in range, label KM_SEG_ROBOT_R / _L, radius finite and > 0, p0 and seg finite): a bad list
+ * returns nonzero, sets kmanip_last_error and leaves the handle as it was.  Synchronous (the whole device is idle when it
+ * returns); the list is read when a render LAUNCHES. */
+KMANIP_API int kmanip_set_render_links(KHandle h, int n, const KLinkCapsule* caps);
+/* The list in force: *n entries into caps, a HOST array with room for KM_MAX_LINK_CAPSULES (caps may be NULL: the count only). */
+KMANIP_API int kmanip_get_render_links(KHandle h, int* n, KLinkCapsule* caps);
 
 /* Rendering BEHIND the steps (a data-generation loop whose policy does not look at the images: the reference's scripted heuristic,
  * examples/2_synthetic_data.py:28-41, logs them and acts on the state).  A render reads nothing of the state but qpos (and, in
@@ -422,7 +449,7 @@ KMANIP_API int kmanip_set_env_param_ranges(KHandle h, const double* lo, const do
  *   index  name                  default        meaning
  *   0-2    KM_VP_CUBE_RGB        1 0 0          cube material colour
  *   3-5    KM_VP_TABLE_RGB       .2 .2 .2       table colour
- *   6-8    KM_VP_ROBOT_RGB       .647059 x 3    the visible finger spheres
+ *   6-8    KM_VP_ROBOT_RGB       .647059 x 3    the visible finger spheres and the link capsules (kmanip_set_render_links)
  *   9-11   KM_VP_BACKGROUND_RGB  0 0 0          pixels whose ray hits nothing
  *   12     KM_VP_AMBIENT         0.4            headlight ambient
  *   13     KM_VP_HEADLIGHT       0.4            headlight diffuse

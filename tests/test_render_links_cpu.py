@@ -1,0 +1,227 @@
+"""Link capsules of the camera renders, host side (no GPU): the reference the GPU tests are held to (tests/tools/link_oracle.py)
+against the CPU oracle, the default capsule list of model.link_capsules, and properties of the reference with that list."""
+import os
+import sys
+
+import numpy as np
+import pytest
+
+from conftest import ROOT
+from gym_kmanip_amd import model as M
+from gym_kmanip_amd.model import KM_CAM_INDEX, KM_SEG_ROBOT_L, KM_SEG_ROBOT_R, compile_model, visual_param_vector
+
+sys.path.insert(0, os.path.join(ROOT, "tests", "tools"))
+from link_oracle import LinkOracle  # noqa: E402
+
+SHAPES = [(37, 42), (68, 100), (20, 4)]
+_STATES = {}
+
+
+def _states(env, n=6, steps=12):
+    """qpos of n oracle envs after `steps` random steps (computed once per env id and shared)."""
+    if env not in _STATES:
+        from oracle.oracle import Oracle
+        cm = compile_model(env)
+        o = Oracle(cm, n, seed=6)
+        o.reset()
+        for _ in range(steps):
+            o.step(o.sample_action())
+        _STATES[env] = (cm, o.get_state()[0])
+    return _STATES[env]
+
+
+def _cams(cm):
+    return [name for name, ci in KM_CAM_INDEX.items() if cm.desc.cam_present[ci]]
+
+
+def _vis(e):
+    rng = np.random.default_rng(100 + e)
+    return visual_param_vector({"cube_rgb": rng.uniform(0, 1, 3), "table_rgb": rng.uniform(0, 1, 3), "robot_rgb": rng.uniform(0, 1, 3),
+                                "background_rgb": rng.uniform(0, 1, 3), "ambient": rng.uniform(0.1, 0.5),
+                                "headlight": rng.uniform(0, 0.6), "directional": rng.uniform(0, 1.2)})
+
+
+# ------------------------------------------------------------------------------------------------ 1. the reference is the oracle
+@pytest.mark.parametrize("vis", ["default", "explicit"])
+@pytest.mark.parametrize("env", ["KManipSoloArm", "KManipTorso"])
+def test_reference_without_capsules_is_the_oracle(env, vis):
+    """With no capsules the reference's RGB bytes equal Oracle.render_rgb's: every camera, three shapes, 6 envs, default and
+    explicit colours and lights -- and with a per-env camera offset (the desc's cam_pos)."""
+    from oracle.oracle import Oracle
+    cm, qpos = _states(env)
+    orc, ref = Oracle(cm, 1), LinkOracle(cm)
+    for cam in _cams(cm):
+        ci = KM_CAM_INDEX[cam]
+        for h, w in SHAPES:
+            for e in range(len(qpos)):
+                v = _vis(e) if vis == "explicit" else None
+                want = orc.render_rgb(qpos[e], ci, h, w, vis=v)
+                got, lab, capmask = ref.render(qpos[e], ci, h, w, (), v)
+                assert np.array_equal(got, want), (cam, h, w, e, int((got != want).any(-1).sum()))
+                assert not capmask.any() and lab.max() <= KM_SEG_ROBOT_L
+    off = np.array([0.03, -0.02, 0.04])
+    cmo = M.with_visual_params(cm, camera_offset=off)
+    orc, ref = Oracle(cmo, 1), LinkOracle(cm, camera_offset=off)
+    for cam in _cams(cm):
+        want = orc.render_rgb(qpos[0], KM_CAM_INDEX[cam], 37, 42)
+        assert np.array_equal(ref.rgb(qpos[0], KM_CAM_INDEX[cam], 37, 42), want), cam
+        assert not np.array_equal(LinkOracle(cm).rgb(qpos[0], KM_CAM_INDEX[cam], 37, 42), want), cam
+
+
+def test_reference_labels_without_capsules_are_the_label_oracles():
+    """... and its labels, robot classes folded to 3, are tests/tools/label_oracle.py's; its arm split agrees too."""
+    from label_oracle import LabelOracle
+    cm, qpos = _states("KManipTorso")
+    lo, ref = LabelOracle(cm), LinkOracle(cm)
+    seen = set()
+    for cam in _cams(cm):
+        ci = KM_CAM_INDEX[cam]
+        for e in range(3):
+            lab = ref.labels(qpos[e], ci, 37, 42)
+            assert np.array_equal(np.minimum(lab, 3), lo.labels(qpos[e], ci, 37, 42)), (cam, e)
+            for arm in (0, 1):
+                assert np.array_equal(np.minimum(ref.labels(qpos[e], ci, 37, 42, arm=arm), 3), lo.arm_labels(qpos[e], ci, 37, 42, arm))
+            seen |= set(np.unique(lab).tolist())
+    assert {0, 1, 2} <= seen and seen & {3, 4}
+
+
+# ------------------------------------------------------------------------------------------------ 2. the default list
+@pytest.mark.parametrize("env,count", [("KManipSoloArm", 10), ("KManipDualArm", 20), ("KManipTorso", 20)])
+def test_default_capsule_list(env, count):
+    """model.link_capsules: 10 / 20 / 20 entries, joint-to-joint capsules first and finger capsules last; labels follow
+    sphere_arm's chains; the masks hide exactly the camera link's and its parent's capsules from that camera (three per gripper
+    camera); every entry passes kmanip_set_render_links' rules."""
+    cm = compile_model(env)
+    d = cm.desc
+    caps = M.link_capsules(cm)
+    assert len(caps) == count <= M.KM_MAX_LINK_CAPSULES
+    assert M.check_link_capsules(cm, caps) == caps
+    la = M.link_arm(cm)
+    # the chains are sphere_arm's: every sphere's link is on its arm's chain
+    for s, a in enumerate(M.sphere_arm(cm, strict=True)):
+        assert la[d.sphere_link[s]] == a
+    if env == "KManipTorso":
+        assert 0 not in la and 1 not in la                      # the torso's own links are on no arm's chain
+    nvis = sum(1 for s in range(d.nsphere) if d.sphere_visible[s])
+    joints, fingers = caps[:count - nvis], caps[count - nvis:]
+    pairs = [(d.link_parent[j], j) for j in range(d.nlink) if d.link_parent[j] >= 0 and d.link_parent[j] in la and j in la]
+    assert [c["link"] for c in joints] == [p for p, _ in pairs]
+    for c, (p, j) in zip(joints, pairs):
+        assert c["seg"] == tuple(d.link_pos[j]) and c["p0"] == (0.0, 0.0, 0.0) and c["radius"] == 0.03
+    vis_s = [s for s in range(d.nsphere) if d.sphere_visible[s]]
+    for c, s in zip(fingers, vis_s):
+        assert c["link"] == d.sphere_link[s] and c["seg"] == tuple(d.sphere_pos[s]) and c["radius"] == d.sphere_radius[s]
+    present = sum(1 << c for c in range(M.KM_MAX_CAMS) if d.cam_present[c])
+    for c in caps:
+        assert c["label"] == KM_SEG_ROBOT_R + la[c["link"]] and c["label"] in (KM_SEG_ROBOT_R, KM_SEG_ROBOT_L)
+        assert 0 <= c["link"] < d.nlink and np.isfinite(c["radius"]) and c["radius"] > 0
+        assert np.isfinite(c["p0"]).all() and np.isfinite(c["seg"]).all()
+        hidden = {k for k in range(M.KM_MAX_CAMS) if d.cam_present[k] and d.cam_link[k] >= 0
+                  and c["link"] in (d.cam_link[k], d.link_parent[d.cam_link[k]])}
+        assert c["cam_mask"] == present & ~sum(1 << k for k in hidden)
+    for k in range(M.KM_MAX_CAMS):
+        if d.cam_present[k] and d.cam_link[k] >= 0:
+            assert sum(1 for c in caps if not c["cam_mask"] >> k & 1) == 3, k
+    if env != "KManipSoloArm":
+        assert {c["label"] for c in caps} == {KM_SEG_ROBOT_R, KM_SEG_ROBOT_L}
+    assert len(M.link_capsules(cm, radius=0.02)) == count and M.link_capsules(cm, radius=0.02)[0]["radius"] == 0.02
+
+
+def test_capsule_list_validation_on_the_host():
+    cm = compile_model("KManipSoloArm")
+    good = M.link_capsules(cm)
+    as_tuples = [(c["link"], c["label"], c["cam_mask"], c["p0"], c["seg"], c["radius"]) for c in good]
+    assert M.check_link_capsules(cm, as_tuples) == good
+    for bad in (dict(good[0], link=10), dict(good[0], link=-1), dict(good[0], label=2), dict(good[0], radius=0.0),
+                dict(good[0], radius=float("nan")), dict(good[0], seg=(0.0, float("nan"), 0.0)), dict(good[0], p0=(0.0, float("inf"), 0.0))):
+        with pytest.raises(ValueError):
+            M.check_link_capsules(cm, [bad])
+    with pytest.raises(ValueError):
+        M.check_link_capsules(cm, good * 3)
+
+
+# ------------------------------------------------------------------------------------------------ 3. the reference with the list
+@pytest.mark.parametrize("env", ["KManipSoloArm", "KManipDualArm", "KManipTorso"])
+def test_reference_with_the_default_list(env):
+    """A gripper image is not all robot (the cam_mask rule: without it every pixel is); head and top images at 37 x 42 contain
+    capsule pixels in every env; capsules only add robot pixels; both arms' labels occur where there are two arms."""
+    cm, qpos = _states(env)
+    caps = M.link_capsules(cm)
+    ref = LinkOracle(cm)
+    labels = set()
+    for cam in _cams(cm):
+        ci = KM_CAM_INDEX[cam]
+        for e in range(len(qpos)):
+            _, lab0, _ = ref.render(qpos[e], ci, 37, 42)
+            rgb, lab, capmask = ref.render(qpos[e], ci, 37, 42, caps)
+            robot = lab >= KM_SEG_ROBOT_R
+            assert np.array_equal(lab[~capmask], lab0[~capmask]) and robot[capmask].all()
+            labels |= set(np.unique(lab[capmask]).tolist())
+            if cam.startswith("grip"):
+                assert robot.mean() < 0.6, (cam, e, float(robot.mean()))
+                assert len(np.unique(lab)) >= 2, (cam, e)
+                unmasked = [dict(c, cam_mask=15) for c in caps]
+                if e == 0 and env != "KManipTorso":
+                    assert (ref.labels(qpos[e], ci, 37, 42, unmasked) >= KM_SEG_ROBOT_R).all(), cam
+            else:
+                assert capmask.sum() > 0, (cam, e)
+    assert labels == ({KM_SEG_ROBOT_R} if env == "KManipSoloArm" else {KM_SEG_ROBOT_R, KM_SEG_ROBOT_L})
+
+
+def test_hiding_a_capsule_changes_only_that_cameras_image():
+    cm, qpos = _states("KManipTorso")
+    caps = M.link_capsules(cm)
+    ref = LinkOracle(cm)
+    head, top = KM_CAM_INDEX["head"], KM_CAM_INDEX["top"]
+    base = {c: ref.render(qpos[0], c, 37, 42, caps) for c in (head, top)}
+    # the capsule with the most head pixels of its own
+    own = [int((ref.labels(qpos[0], head, 37, 42, caps[:k] + caps[k + 1:]) != base[head][1]).sum()) for k in range(len(caps))]
+    k = int(np.argmax(own))
+    assert own[k] > 0
+    hidden = [dict(c, cam_mask=c["cam_mask"] & ~(1 << head)) if i == k else c for i, c in enumerate(caps)]
+    assert not np.array_equal(ref.render(qpos[0], head, 37, 42, hidden)[1], base[head][1])
+    assert np.array_equal(ref.render(qpos[0], head, 37, 42, hidden)[1], ref.labels(qpos[0], head, 37, 42, caps[:k] + caps[k + 1:]))
+    for a, b in zip(ref.render(qpos[0], top, 37, 42, hidden), base[top]):
+        assert np.array_equal(a, b)
+
+
+def test_a_zero_length_capsule_is_its_sphere():
+    """seg = 0 at a finger sphere's position with its radius: the same image, byte for byte (an earlier object keeps a tie)."""
+    cm, qpos = _states("KManipSoloArm")
+    d = cm.desc
+    ref = LinkOracle(cm)
+    s = next(s for s in range(d.nsphere) if d.sphere_visible[s])
+    cap = {"link": d.sphere_link[s], "label": KM_SEG_ROBOT_R, "cam_mask": 15, "p0": tuple(d.sphere_pos[s]), "seg": (0.0, 0.0, 0.0),
+           "radius": d.sphere_radius[s]}
+    for cam in _cams(cm):
+        a, b = ref.render(qpos[1], KM_CAM_INDEX[cam], 40, 60), ref.render(qpos[1], KM_CAM_INDEX[cam], 40, 60, [cap])
+        assert np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1]), cam
+
+
+# ------------------------------------------------------------------------------------------------ 4. the library
+def test_link_kernel_resources_and_exports():
+    """The four k_render_links instantiations (VIS x RGB) exist and none spills to scratch; the existing render kernels keep their
+    instantiation counts; the two new entry points are declared and exported."""
+    import subprocess
+    from gym_kmanip_amd import lib as klib
+    if not os.path.exists(klib.LIB_PATH):
+        klib.build()
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "kernel_resources.py"), klib.LIB_PATH, "render"],
+                         capture_output=True, text=True, check=True).stdout
+    res = {}
+    for line in out.splitlines():
+        f = line.split()
+        res[f[0]] = {f[i]: int(f[i + 1]) for i in range(1, len(f) - 1, 2) if f[i + 1].isdigit()}
+    links = {(vis, rgb): v for k, v in res.items() for vis in (0, 1) for rgb in (0, 1)
+             if k.startswith("_Z14k_render_linksILb%dELb%dE" % (vis, rgb))}
+    assert len(links) == 4 and sum(k.startswith("_Z14k_render_links") for k in res) == 4, sorted(res)
+    for key, v in links.items():
+        print("k_render_links<VIS=%d, RGB=%d>" % key, v)
+        assert v["scratch"] == 0 and v["vgpr"] <= 168, (key, v)                 # (168 VGPR: three waves per SIMD)
+    assert sum(k.startswith("_Z15k_render_labels") for k in res) == 4 and sum(k.startswith("_Z12k_render_rgbILb") for k in res) == 2
+    hdr = open(os.path.join(ROOT, "include", "kmanip.h")).read()
+    for name in ("kmanip_set_render_links", "kmanip_get_render_links"):
+        assert name + "(" in hdr and name in klib.EXPORTS and hasattr(klib.load(), name)
+    assert "#define KM_MAX_LINK_CAPSULES %d" % M.KM_MAX_LINK_CAPSULES in hdr
+    import ctypes as C
+    assert C.sizeof(klib.KLinkCapsule) == 72 and klib.KM_MAX_LINK_CAPSULES == M.KM_MAX_LINK_CAPSULES
