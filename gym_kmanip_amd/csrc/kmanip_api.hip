@@ -14,7 +14,7 @@
 
 #include "kmanip_device.hpp"
 
-#define KM_VERSION "kmanip-hip 0.31 (gfx950, f64)"
+#define KM_VERSION "kmanip-hip 0.32 (gfx950, f64)"
 
 static thread_local std::string g_create_error;
 
@@ -64,6 +64,8 @@ struct KHandle_ {
   // an argument of k_render_links; empty = the default kernels
   std::vector<KLinkCapsule> links;
   KLinkCapsule* links_buf = nullptr;   // [KM_MAX_LINK_CAPSULES], allocated by the first call that sets a list
+  // kmanip_set_depth_links: while on AND the list is not empty the depth renders launch k_render_depth_links
+  bool depth_links = false;
   std::vector<void*> allocs;
 };
 
@@ -477,8 +479,13 @@ static int step_impl(KHandle h, int nchunk, const float* act_dev, double* obs_de
   kmanip_launch_step(h->dmodel, h->desc, h->st, act_dev, obs_dev, reward_dev, done_dev, nchunk, h->last_epb, s);
   if (tm) HIPCHK(h, hipEventRecord(ev[1], s));
   const bool render = h->step_depth && nchunk == 1;
-  if (render)                             // the observation's camera branch (env_sim.py:140-145) of the state just produced
-    kmanip_launch_render_depth(h->dmodel, h->st, h->step_cam, h->step_h, h->step_w, h->step_depth, vis_args(h, -1), s);
+  if (render) {                           // the observation's camera branch (env_sim.py:140-145) of the state just produced
+    if (h->depth_links && !h->links.empty())
+      kmanip_launch_render_depth_links(h->dmodel, h->st, h->step_cam, h->step_h, h->step_w, h->step_depth, KLinkArgs{h->links_buf, (int)h->links.size()},
+                                       vis_args(h, -1), s);
+    else
+      kmanip_launch_render_depth(h->dmodel, h->st, h->step_cam, h->step_h, h->step_w, h->step_depth, vis_args(h, -1), s);
+  }
   if (tm) {
     if (render) HIPCHK(h, hipEventRecord(ev[2], s));
     h->ev_render[h->timed_steps] = render;
@@ -503,7 +510,11 @@ int kmanip_render_depth(KHandle h, int cam, int height, int width, float* depth_
   KM_ENTER(h);
   KDeviceState st = h->st;
   if (h->render_src >= 0) st.qpos = h->qpos_snap[h->render_src];
-  kmanip_launch_render_depth(h->dmodel, st, cam, height, width, depth_dev, vis_args(h, h->render_src), (hipStream_t)stream);
+  if (h->depth_links && !h->links.empty())
+    kmanip_launch_render_depth_links(h->dmodel, st, cam, height, width, depth_dev, KLinkArgs{h->links_buf, (int)h->links.size()}, vis_args(h, h->render_src),
+                                     (hipStream_t)stream);
+  else
+    kmanip_launch_render_depth(h->dmodel, st, cam, height, width, depth_dev, vis_args(h, h->render_src), (hipStream_t)stream);
   HIPCHK(h, hipGetLastError());
   return 0;
 }
@@ -656,6 +667,22 @@ int kmanip_get_render_links(KHandle h, int* n, KLinkCapsule* caps) {
   if (!n) { h->err = "kmanip_get_render_links: n is NULL"; return -1; }
   *n = (int)h->links.size();
   if (caps) for (size_t k = 0; k < h->links.size(); k++) caps[k] = h->links[k];
+  return 0;
+}
+
+int kmanip_set_depth_links(KHandle h, int on) {
+  if (!h) { g_create_error = "kmanip_set_depth_links: null handle"; return -1; }
+  KM_ENTER(h);
+  // like a change of the list: a render in flight keeps what it was launched with, and the device is idle when this returns
+  HIPCHK(h, hipDeviceSynchronize());
+  h->depth_links = on != 0;
+  return 0;
+}
+
+int kmanip_get_depth_links(KHandle h, int* on) {
+  if (!h) { g_create_error = "kmanip_get_depth_links: null handle"; return -1; }
+  if (!on) { h->err = "kmanip_get_depth_links: on is NULL"; return -1; }
+  *on = h->depth_links ? 1 : 0;
   return 0;
 }
 

@@ -591,6 +591,10 @@ void kmanip_launch_render_rgb(const KDeviceModel* dm, const KDeviceState& st, co
 struct KLinkArgs { const KLinkCapsule* caps; int n; };
 void kmanip_launch_render_links(const KDeviceModel* dm, const KDeviceState& st, const KLabelJobs& jobs, bool rgb, const KLinkArgs& links, const KVisArgs& vis,
                                 hipStream_t stream);
+// the depth render with the same list drawn (kmanip_set_depth_links; kmanip_render_depth_links.hip): kmanip_launch_render_depth's
+// arguments and its COLFIXED rule, plus the list
+void kmanip_launch_render_depth_links(const KDeviceModel* dm, const KDeviceState& st, int cam, int height, int width, float* depth,
+                                      const KLinkArgs& links, const KVisArgs& vis, hipStream_t stream);
 // ranges mode's values of every env's current episode into out double[KM_VP_N][N] (kmanip_get_visual_params)
 void kmanip_launch_vp_draw(const KDeviceState& st, const KVisArgs& vis, double* out, hipStream_t stream);
 // envs per workgroup (= per wave) of a step / reset launch: as many waves as the chip has SIMD slots for, but no more lanes idle than

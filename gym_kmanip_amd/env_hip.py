@@ -224,7 +224,8 @@ class KManipEnvHip:
 
     def render_depth(self, cam="grip_r", height: int = 64, width: int = 64, out=None):
         """float32 depth image [num_envs, height, width] (metres along the optical axis) of every env's current state
-        -- BASELINE.json config 5's observation (camera branch of env_sim.py:140-145)."""
+        -- BASELINE.json config 5's observation (camera branch of env_sim.py:140-145).  Draws the link capsules of
+        set_render_links only while set_depth_links is on."""
         torch = _torch()
         ci = self._cam_index(cam)
         if out is None:
@@ -320,7 +321,7 @@ class KManipEnvHip:
 
     def set_render_links(self, caps=True):
         """Draw the arm links as capsules in every RGB and label render of this handle (kmanip_set_render_links; depth renders
-        never draw them).  True: the model's default list (model.link_capsules); a list of dicts with the fields of KLinkCapsule
+        draw them only after set_depth_links).  True: the model's default list (model.link_capsules); a list of dicts with the fields of KLinkCapsule
         (link, label, cam_mask, p0, seg, radius) or of tuples in that order: that list; None / False / an empty list: no
         capsules, the default kernels again.  Synchronous.  A bad list raises and leaves the list in force unchanged."""
         if caps is None or caps is False:
@@ -346,6 +347,19 @@ class KManipEnvHip:
         return [{"link": a.link, "label": a.label, "cam_mask": a.cam_mask, "p0": tuple(a.p0), "seg": tuple(a.seg), "radius": a.radius}
                 for a in arr[:n.value]]
 
+    def set_depth_links(self, on=True):
+        """render_depth and the in-step render of bind_step_depth draw the capsule list of set_render_links too
+        (kmanip_set_depth_links): the float64 depth ray cast with the capsules, so that depth, RGB and labels show one scene.
+        A flag of its own, off by default and kept across changes of the list; with the flag off or no list set the depth
+        renders are exactly the default ones.  Synchronous."""
+        self._check(self.L.kmanip_set_depth_links(self.h, 1 if on else 0), "kmanip_set_depth_links")
+
+    def get_depth_links(self) -> bool:
+        """Whether depth renders draw the capsule list (kmanip_get_depth_links)."""
+        on = C.c_int(0)
+        self._check(self.L.kmanip_get_depth_links(self.h, C.byref(on)), "kmanip_get_depth_links")
+        return bool(on.value)
+
     def snapshot_render_state(self, slot: int):
         """Copy qpos -- all a render reads of the state -- into snapshot `slot` (0 / 1) on the current stream
         (kmanip_snapshot_render_state); `set_render_source(slot)` then points the render_* calls at it."""
@@ -357,7 +371,8 @@ class KManipEnvHip:
 
     def bind_step_depth(self, cam="grip_r", height: int = 64, width: int = 64, out=None):
         """BASELINE config 5: every step_flat / k_step from now on also renders `cam` into the returned buffer
-        (float32 [num_envs, height, width]), in the same C call.  bind_step_depth(None) unbinds."""
+        (float32 [num_envs, height, width]), in the same C call.  bind_step_depth(None) unbinds.  With set_depth_links on and a
+        capsule list set, that render draws the capsules, as render_depth does."""
         torch = _torch()
         if cam is None:
             self._check(self.L.kmanip_bind_step_depth(self.h, 0, 0, 0, None), "kmanip_bind_step_depth")

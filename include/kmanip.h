@@ -326,7 +326,7 @@ KMANIP_API int kmanip_ik_eval(KHandle h, int arm, int n, const double* qpos, con
  * (env_sim.py:140-145) for the gripper cameras, as BASELINE.json config 5 defines it: a height x width
  * float32 DEPTH image (metres along the optical axis) of every env's current state.
  * depth_dev: float[num_envs, height, width] device memory owned by the caller. */
-KMANIP_API int kmanip_render_depth(KHandle h, int cam, int height, int width, float* depth_dev, void* stream);   /* (never draws link capsules) */
+KMANIP_API int kmanip_render_depth(KHandle h, int cam, int height, int width, float* depth_dev, void* stream);   /* (link capsules: only after kmanip_set_depth_links) */
 
 /* The same cameras as uint8 RGB, what dm_control's physics.render(height, width, camera_id) returns for the camera
  * observations of the *Vision env ids (env_sim.py:140-145; shapes env_base.py:140-146, cameras __init__.py:157-161) and for
@@ -360,8 +360,8 @@ KMANIP_API int kmanip_render_seg(KHandle h, int cam, int height, int width, uint
  * visual parameters and kmanip_enable_timing's render leg are honoured as before.  With no list (the default) every launch is
  * exactly what it was: the same kernels, the same bytes.  Objects are tested in the order table, cube, spheres, capsules in
  * list order, and a later object wins only where it is strictly nearer.  Only a ray's entry point counts: a camera inside a
- * capsule sees through it, as it does through a sphere.  DEPTH IS NOT COVERED: kmanip_render_depth and kmanip_bind_step_depth
- * keep drawing the scene without capsules.  The capsules are drawn only; the physics never reads them.
+ * capsule sees through it, as it does through a sphere.  Depth is a switch of its own: kmanip_render_depth and kmanip_bind_step_depth
+ * draw the scene without capsules until kmanip_set_depth_links turns them on.  The capsules are drawn only; the physics never reads them.
  * gym_kmanip_amd/model.py link_capsules builds the default list (joint-to-joint capsules along both arms plus the fingers). */
 #define KM_MAX_LINK_CAPSULES 24
 typedef struct KLinkCapsule {
@@ -380,6 +380,16 @@ KMANIP_API int kmanip_set_render_links(KHandle h, int n, const KLinkCapsule* cap
 /* The list in force: *n entries into caps, a HOST array with room for KM_MAX_LINK_CAPSULES (caps may be NULL: the count only). */
 KMANIP_API int kmanip_get_render_links(KHandle h, int* n, KLinkCapsule* caps);
 
+/* Depth renders draw the handle's capsule list too (default 0: they never do).  A per-handle flag, separate
+ * from the list and surviving its changes: while it is on AND the list is not empty, kmanip_render_depth and the in-step render of
+ * kmanip_bind_step_depth launch k_render_depth_links -- the float64 depth ray cast with the capsules tested after the spheres, in
+ * list order, by the ray test above in float64; `label` is ignored, cam_mask honoured -- and otherwise exactly what they launch
+ * without it: the same kernels, the same bytes.  Snapshots, both visual-parameter modes (the per-env camera offset and its episode
+ * draw) and kmanip_enable_timing's render leg are honoured as kmanip_render_depth honours them.  Synchronous, like
+ * kmanip_set_render_links; the flag and the list are read when a render LAUNCHES. */
+KMANIP_API int kmanip_set_depth_links(KHandle h, int on);
+KMANIP_API int kmanip_get_depth_links(KHandle h, int* on);
+
 /* Rendering BEHIND the steps (a data-generation loop whose policy does not look at the images: the reference's scripted heuristic,
  * examples/2_synthetic_data.py:28-41, logs them and acts on the state).  A render reads nothing of the state but qpos (and, in
  * visual ranges mode, the episode counters the colour / light / camera draw uses: kmanip_set_visual_param_ranges):
@@ -395,7 +405,8 @@ KMANIP_API int kmanip_set_render_source(KHandle h, int slot);
 
 /* BASELINE config 5 ("64x64 gripper-cam depth render in the step"): bind a caller-owned device buffer
  * float[num_envs, height, width]; every kmanip_step then ends by rendering camera `cam` of the state it produced into it,
- * on the step's stream (one C call per control step).  depth_dev == NULL unbinds. */
+ * on the step's stream (one C call per control step).  depth_dev == NULL unbinds.  The render draws the handle's link capsules
+ * while kmanip_set_depth_links is on and a list is set, as kmanip_render_depth does. */
 KMANIP_API int kmanip_bind_step_depth(KHandle h, int cam, int height, int width, float* depth_dev);
 
 /* The scripted data-generation policy of reference examples/2_synthetic_data.py:28-41, for every env, on device:
