@@ -14,7 +14,7 @@
 
 #include "kmanip_device.hpp"
 
-#define KM_VERSION "kmanip-hip 0.32 (gfx950, f64)"
+#define KM_VERSION "kmanip-hip 0.33 (gfx950, f64)"
 
 static thread_local std::string g_create_error;
 
@@ -515,6 +515,35 @@ int kmanip_render_depth(KHandle h, int cam, int height, int width, float* depth_
                                      (hipStream_t)stream);
   else
     kmanip_launch_render_depth(h->dmodel, st, cam, height, width, depth_dev, vis_args(h, h->render_src), (hipStream_t)stream);
+  HIPCHK(h, hipGetLastError());
+  return 0;
+}
+
+int kmanip_get_camera_poses(KHandle h, int cam, double* pose_dev, void* stream) {
+  if (!h) { g_create_error = "kmanip_get_camera_poses: null handle"; return -1; }
+  if (!pose_dev) { h->err = "kmanip_get_camera_poses: pose_dev is NULL"; return -1; }
+  if (cam < 0 || cam >= KM_MAX_CAMS || !h->desc.cam_present[cam]) { h->err = "kmanip_get_camera_poses: this model has no such camera"; return -1; }
+  KM_ENTER(h);
+  KDeviceState st = h->st;
+  if (h->render_src >= 0) st.qpos = h->qpos_snap[h->render_src];
+  kmanip_launch_camera_poses(h->dmodel, st, cam, pose_dev, vis_args(h, h->render_src), (hipStream_t)stream);
+  HIPCHK(h, hipGetLastError());
+  return 0;
+}
+
+int kmanip_render_points(KHandle h, int cam, int height, int width, int frame, float* xyz_dev, float* depth_dev, void* stream) {
+  if (!h) { g_create_error = "kmanip_render_points: null handle"; return -1; }
+  if (!xyz_dev) { h->err = "kmanip_render_points: xyz_dev is NULL"; return -1; }
+  if (cam < 0 || cam >= KM_MAX_CAMS || !h->desc.cam_present[cam]) { h->err = "kmanip_render_points: this model has no such camera"; return -1; }
+  if (height <= 0 || width <= 0) { h->err = "kmanip_render_points: height and width must be positive"; return -1; }
+  if (frame != KM_POINTS_CAMERA && frame != KM_POINTS_WORLD) { h->err = "kmanip_render_points: frame must be KM_POINTS_CAMERA or KM_POINTS_WORLD"; return -1; }
+  KM_ENTER(h);
+  KDeviceState st = h->st;
+  if (h->render_src >= 0) st.qpos = h->qpos_snap[h->render_src];
+  // the scene kmanip_render_depth draws on this handle now: the capsule list only while the depth flag is on
+  const KLinkArgs links = h->depth_links && !h->links.empty() ? KLinkArgs{h->links_buf, (int)h->links.size()} : KLinkArgs{nullptr, 0};
+  kmanip_launch_render_points(h->dmodel, st, cam, height, width, frame == KM_POINTS_WORLD, xyz_dev, depth_dev, links, vis_args(h, h->render_src),
+                              (hipStream_t)stream);
   HIPCHK(h, hipGetLastError());
   return 0;
 }

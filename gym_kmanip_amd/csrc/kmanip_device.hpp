@@ -595,6 +595,12 @@ void kmanip_launch_render_links(const KDeviceModel* dm, const KDeviceState& st, 
 // arguments and its COLFIXED rule, plus the list
 void kmanip_launch_render_depth_links(const KDeviceModel* dm, const KDeviceState& st, int cam, int height, int width, float* depth,
                                       const KLinkArgs& links, const KVisArgs& vis, hipStream_t stream);
+// camera geometry out of the library (kmanip_render_points.hip): camera `cam`'s pose of every env into pose
+// double[N][12]; the depth ray cast with the points stored (xyz float[N][h][w][3], depth float[N][h][w] or NULL; world: 0 camera
+// frame, 1 world frame; links.n == 0: the scene without capsules), under kmanip_launch_render_depth's COLFIXED rule
+void kmanip_launch_camera_poses(const KDeviceModel* dm, const KDeviceState& st, int cam, double* pose, const KVisArgs& vis, hipStream_t stream);
+void kmanip_launch_render_points(const KDeviceModel* dm, const KDeviceState& st, int cam, int height, int width, int world, float* xyz, float* depth,
+                                 const KLinkArgs& links, const KVisArgs& vis, hipStream_t stream);
 // ranges mode's values of every env's current episode into out double[KM_VP_N][N] (kmanip_get_visual_params)
 void kmanip_launch_vp_draw(const KDeviceState& st, const KVisArgs& vis, double* out, hipStream_t stream);
 // envs per workgroup (= per wave) of a step / reset launch: as many waves as the chip has SIMD slots for, but no more lanes idle than

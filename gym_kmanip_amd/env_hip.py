@@ -20,7 +20,7 @@ import numpy as np
 
 from . import lib as _libmod
 from .model import (CAMERAS, CONTROL_TIMESTEP, ENV_PARAMS, ENV_SPECS, KM_ACT_KEYS, KM_CAM_INDEX, KM_VP_N, VISUAL_PARAMS,
-                    CompiledModel, EnvSpec, check_link_capsules, check_visual_param, compile_model, env_param_defaults,
+                    CompiledModel, EnvSpec, camera_intrinsics, check_link_capsules, check_visual_param, compile_model, env_param_defaults,
                     link_capsules, visual_param_defaults, visual_param_vector)
 
 MJCF_TO_ASSET = {"_env_solo_arm.xml": "solo_arm", "_env_dual_arm.xml": "dual_arm", "_env_torso.xml": "torso"}
@@ -318,6 +318,56 @@ class KManipEnvHip:
         ss = (C.c_void_p * n)(*[bufs["segmentation/" + nm].data_ptr() for nm in names])
         self._check(self.L.kmanip_render_labels_multi(self.h, n, ci, hh, ww, pp, ss, self._stream()), "kmanip_render_labels_multi")
         return bufs
+
+    def camera_poses(self, cam="head", out=None):
+        """Camera `cam`'s pose in every env (kmanip_get_camera_poses): {"pos": [n, 3], "mat": [n, 3, 3]} float64 device tensors,
+        views of one [n, 12] buffer (`out`, if given).  MuJoCo's cam_xpos / cam_xmat as the renders build them: the COLUMNS of
+        `mat` are the camera's x (right), y (up) and z axes in the world frame, and the camera looks along -z; a camera-frame
+        point p_c of render_points is the world point pos + mat @ p_c.  Follows set_render_source and the per-env camera offset
+        of the visual parameters as render_depth does."""
+        torch = _torch()
+        ci = self._cam_index(cam)
+        if out is None:
+            out = torch.empty((self.num_envs, 12), dtype=torch.float64, device=self.device)
+        else:
+            self._check_buf(out, (self.num_envs, 12), torch.float64, "camera poses")
+        self._check(self.L.kmanip_get_camera_poses(self.h, ci, C.c_void_p(out.data_ptr()), self._stream()), "kmanip_get_camera_poses")
+        return {"pos": out[:, :3], "mat": out[:, 3:].view(self.num_envs, 3, 3)}
+
+    def camera_intrinsics(self, cam="head", height=None, width=None) -> dict:
+        """Pinhole intrinsics of a height x width image of `cam` (default: the camera's reference resolution), host arithmetic
+        from the compiled model (model.camera_intrinsics): {"f", "cx", "cy", "fovy"} with f = (height / 2) / tan(fovy / 2) in
+        pixels, cx = width / 2, cy = height / 2, fovy in degrees.  Pixel convention of every render here: pixel (r, c) is the ray
+        through the pixel's centre, dx = (c + 0.5 - cx) / f to the right and dy = -(r + 0.5 - cy) / f upwards, direction
+        x dx + y dy - z in the camera's axes (camera_poses); a depth D (render_depth: metres along the optical axis) is the
+        camera-frame point (D dx, D dy, -D)."""
+        self._cam_index(cam)
+        try:
+            return camera_intrinsics(self.cm, cam, height, width)
+        except ValueError as e:
+            raise _libmod.KManipError(str(e)) from None
+
+    def render_points(self, cam="grip_r", height: int = 64, width: int = 64, frame="world", out=None, depth_out=None):
+        """Point cloud float32 [num_envs, height, width, 3] of the camera's depth image (kmanip_render_points): the
+        back-projection of what render_depth draws on this handle now (the link capsules only while set_depth_links is on), by
+        the same float64 ray cast, in the "world" frame or the "camera" frame (camera_intrinsics has the pixel convention,
+        camera_poses the frame).  depth_out: a float32 [num_envs, height, width] tensor that the same launch fills with the
+        depth image.  A pixel without a hit is the point on the far plane: mask with depth >= cm.desc.cam_zfar."""
+        torch = _torch()
+        ci = self._cam_index(cam)
+        if frame not in _libmod.KM_POINTS_FRAMES:
+            raise _libmod.KManipError("render_points: frame must be 'world' or 'camera', got %r" % (frame,))
+        if out is None:
+            out = torch.empty((self.num_envs, height, width, 3), dtype=torch.float32, device=self.device)
+        else:
+            self._check_buf(out, (self.num_envs, height, width, 3), torch.float32, "points")
+        dp = None
+        if depth_out is not None:
+            self._check_buf(depth_out, (self.num_envs, height, width), torch.float32, "depth")
+            dp = C.c_void_p(depth_out.data_ptr())
+        self._check(self.L.kmanip_render_points(self.h, ci, height, width, _libmod.KM_POINTS_FRAMES[frame], C.c_void_p(out.data_ptr()), dp,
+                                                self._stream()), "kmanip_render_points")
+        return out
 
     def set_render_links(self, caps=True):
         """Draw the arm links as capsules in every RGB and label render of this handle (kmanip_set_render_links; depth renders

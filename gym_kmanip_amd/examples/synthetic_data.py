@@ -7,13 +7,18 @@ the frames of step t are rendered BEHIND the steps (pipeline.RenderBehind: a qpo
 logger while step t + 1 runs -- `--render-in-sequence` renders them before the next step instead.  `--segmentation` logs the
 per-pixel class labels of every frame next to it (`observations/segmentation/<camera>`), rendered by the frames' own launch.
 `--links` draws the arm links as capsules in the frames and the labels (KManipEnvHip.set_render_links).
+`--points` (any id) logs one world-frame point cloud of the right gripper camera per step (KManipEnvHip.render_points: float32
+[h, w, 3], the back-projection of the camera's depth image; with `--links` the capsules are in it) for the logged envs, one
+`points_grip_r_<episode>.npy` [steps, envs, h, w, 3] per episode next to the episode files.
 
     python -m gym_kmanip_amd.examples.synthetic_data [--env KManipSoloArm] [--num-envs 4096] [--episodes 10] [--log-envs 0 1 2 3]
-                                                     [--segmentation] [--links]
+                                                     [--segmentation] [--links] [--points]
 """
 import argparse
 import os
 import time
+
+import numpy as np
 
 from gym_kmanip_amd import env_hip
 from gym_kmanip_amd.episode_log import EpisodeLogger
@@ -30,12 +35,14 @@ def main(argv=None):
     ap.add_argument("--render-in-sequence", action="store_true", help="*Vision ids: render every step's frames before the next step starts")
     ap.add_argument("--segmentation", action="store_true", help="*Vision ids: also log uint8 class labels per pixel (KM_SEG_*)")
     ap.add_argument("--links", action="store_true", help="*Vision ids: draw the arm links as capsules in the frames and labels (set_render_links)")
+    ap.add_argument("--points", action="store_true", help="log a world-frame point cloud of the right gripper camera per step (render_points)")
     args = ap.parse_args(argv)
     import torch
     os.makedirs(args.log_dir, exist_ok=True)
     env = env_hip.make(args.env, num_envs=args.num_envs, auto_reset=False)
-    if args.links and env.cm.cameras:
+    if args.links and (env.cm.cameras or args.points):
         env.set_render_links(True)                                               # the frames and labels show the arm, not only the finger tips
+        env.set_depth_links(args.points)                                         # ... and so does the point cloud's depth ray cast
     q = env.cm.nlink
     log = EpisodeLogger(args.log_dir, args.num_envs, q, env.cm.act_dim, device=env.obs.device, env_ids=args.log_envs,
                         info={"sim": True, "env": args.env, "policy": "toward-cube heuristic"})
@@ -43,7 +50,18 @@ def main(argv=None):
     from gym_kmanip_amd.pipeline import RenderBehind
     for name in env.cm.cameras:                                                  # (none unless the id is a *Vision one)
         log.cam(CAMERAS[name], labels=args.segmentation)
-    behind = RenderBehind(env, segmentation=args.segmentation) if (env.cm.cameras and not args.render_in_sequence) else None
+    pts = ("grip_r", CAMERAS["grip_r"].h, CAMERAS["grip_r"].w, "world") if args.points else None
+    sel = torch.as_tensor(args.log_envs, dtype=torch.long, device=env.obs.device)
+    pts_ring = torch.zeros((MAX_EPISODE_STEPS, len(args.log_envs), pts[1], pts[2], 3), dtype=torch.float32, device=env.obs.device) if pts else None
+    behind = (RenderBehind(env, segmentation=args.segmentation, points=pts)
+              if ((env.cm.cameras or pts) and not args.render_in_sequence) else None)
+
+    def late(due):                                                               # the frames (and the point cloud) of an earlier step
+        imgs = behind.images(due[0])
+        if env.cm.cameras:
+            log.late_images(due[1], imgs)
+        if pts:
+            pts_ring[due[1]].copy_(imgs["points"].index_select(0, sel))
     gen = torch.Generator(device=env.obs.device); gen.manual_seed(0)
     t0 = time.time()
     closest = None
@@ -57,13 +75,17 @@ def main(argv=None):
             if behind is not None:
                 k = behind.after_step()                                          # this step's frames: rendering from now on
                 if due is not None:
-                    log.late_images(due[1], behind.images(due[0]))               # the previous step's frames have had a whole step
-                due = (k, log.step(act, env.obs[:, :q], env.obs[:, q:2 * q], images_later=True))
+                    late(due)                                                    # the previous step's frames have had a whole step
+                due = (k, log.step(act, env.obs[:, :q], env.obs[:, q:2 * q], images_later=bool(env.cm.cameras)))
             else:
-                log.step(act, env.obs[:, :q], env.obs[:, q:2 * q], images=env.render_cameras(segmentation=args.segmentation) if env.cm.cameras else None)
+                t = log.step(act, env.obs[:, :q], env.obs[:, q:2 * q], images=env.render_cameras(segmentation=args.segmentation) if env.cm.cameras else None)
+                if pts:
+                    pts_ring[t].copy_(env.render_points(*pts[:3], frame=pts[3]).index_select(0, sel))
         if due is not None:
-            log.late_images(due[1], behind.images(due[0]))
+            late(due)
         paths = log.end_episode()
+        if pts:
+            np.save(os.path.join(args.log_dir, "points_grip_r_%04d.npy" % ep), pts_ring.cpu().numpy())
         closest = float(env.reward.max())
     torch.cuda.synchronize()
     dt = time.time() - t0

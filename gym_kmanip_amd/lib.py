@@ -20,7 +20,7 @@ _lib = None
 EXPORTS = [
     "kmanip_model_desc_size", "kmanip_create", "kmanip_reset", "kmanip_step", "kmanip_step_chunk", "kmanip_get_state",
     "kmanip_set_state", "kmanip_get_episode", "kmanip_set_episode", "kmanip_get_counters", "kmanip_bind_sim_time", "kmanip_bind_reward_done_record", "kmanip_select_reward_done_record", "kmanip_observe", "kmanip_set_seed", "kmanip_get_diag", "kmanip_timing_summary", "kmanip_enable_timing", "kmanip_ik", "kmanip_ik_eval",
-    "kmanip_render_depth", "kmanip_render_rgb", "kmanip_render_rgb_multi", "kmanip_render_labels_multi", "kmanip_render_seg", "kmanip_set_render_links", "kmanip_get_render_links", "kmanip_set_depth_links", "kmanip_get_depth_links", "kmanip_snapshot_render_state", "kmanip_set_render_source", "kmanip_bind_step_depth", "kmanip_scripted_action", "kmanip_sample_action", "kmanip_set_env_params", "kmanip_get_env_params", "kmanip_set_env_param_ranges", "kmanip_set_visual_params", "kmanip_get_visual_params", "kmanip_set_visual_param_ranges", "kmanip_num_envs", "kmanip_last_error", "kmanip_version", "kmanip_destroy",
+    "kmanip_render_depth", "kmanip_render_rgb", "kmanip_render_rgb_multi", "kmanip_render_labels_multi", "kmanip_render_seg", "kmanip_set_render_links", "kmanip_get_render_links", "kmanip_set_depth_links", "kmanip_get_depth_links", "kmanip_get_camera_poses", "kmanip_render_points", "kmanip_snapshot_render_state", "kmanip_set_render_source", "kmanip_bind_step_depth", "kmanip_scripted_action", "kmanip_sample_action", "kmanip_set_env_params", "kmanip_get_env_params", "kmanip_set_env_param_ranges", "kmanip_set_visual_params", "kmanip_get_visual_params", "kmanip_set_visual_param_ranges", "kmanip_num_envs", "kmanip_last_error", "kmanip_version", "kmanip_destroy",
 ]
 
 
@@ -39,6 +39,7 @@ class KLinkCapsule(C.Structure):
 
 
 KM_MAX_LINK_CAPSULES = 24
+KM_POINTS_FRAMES = {"camera": 0, "world": 1}     # include/kmanip.h KM_POINTS_CAMERA / KM_POINTS_WORLD
 
 
 def build(force: bool = False) -> str:
@@ -96,6 +97,8 @@ def load():
     lib.kmanip_get_render_links.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(KLinkCapsule)]
     lib.kmanip_set_depth_links.argtypes = [vp, C.c_int]
     lib.kmanip_get_depth_links.argtypes = [vp, C.POINTER(C.c_int)]
+    lib.kmanip_get_camera_poses.argtypes = [vp, C.c_int, vp, vp]
+    lib.kmanip_render_points.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp]
     lib.kmanip_snapshot_render_state.argtypes = [vp, C.c_int, vp]
     lib.kmanip_set_render_source.argtypes = [vp, C.c_int]
     lib.kmanip_bind_step_depth.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp]

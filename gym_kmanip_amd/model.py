@@ -666,6 +666,24 @@ def link_arm(cm: CompiledModel) -> Dict[int, int]:
     return out
 
 
+def camera_intrinsics(cm: CompiledModel, cam, height=None, width=None) -> dict:
+    """Pinhole intrinsics of a height x width image of camera `cam` (a name or a Cam; default size: the camera's reference
+    resolution): {"f", "cx", "cy", "fovy"} with f = (height / 2) / tan(fovy / 2) in pixels (square pixels), cx = width / 2,
+    cy = height / 2, fovy in degrees.  Pixel convention of every render of the library: pixel (r, c) is the ray through the pixel's
+    centre, dx = (c + 0.5 - cx) / f to the right and dy = -(r + 0.5 - cy) / f upwards (rows run down, the camera's y axis up), with
+    direction x dx + y dy - z in the camera's axes; a depth D (metres along the optical axis) is the camera-frame point
+    (D dx, D dy, -D)."""
+    name = getattr(cam, "name", cam)
+    if name not in KM_CAM_INDEX or not cm.desc.cam_present[KM_CAM_INDEX[name]]:
+        raise ValueError("no camera %r in this model" % (name,))
+    height = CAMERAS[name].h if height is None else int(height)
+    width = CAMERAS[name].w if width is None else int(width)
+    if height < 1 or width < 1:
+        raise ValueError("camera_intrinsics: height and width must be positive")
+    fovy = float(cm.desc.cam_fovy[KM_CAM_INDEX[name]])
+    return {"f": 0.5 * height / math.tan(0.5 * fovy * (math.pi / 180.0)), "cx": 0.5 * width, "cy": 0.5 * height, "fovy": fovy}
+
+
 def link_capsules(cm: CompiledModel, radius: float = 0.03) -> list:
     """The default capsule list of kmanip_set_render_links, as dicts with the fields of KLinkCapsule (link, label, cam_mask, p0,
     seg, radius), in this order:

@@ -145,13 +145,17 @@ class RenderBehind:
     read from a stream images() never saw, shows torn or newer images: clone what has to live longer.
     """
 
-    def __init__(self, env, cams=None, depth=None, segmentation: bool = False):
+    def __init__(self, env, cams=None, depth=None, segmentation: bool = False, points=None):
         """cams: RGB cameras (default: the env id's camera observations; [] for none).  depth: (camera, height, width) of a float32
         depth image rendered with them (BASELINE config 5's 64 x 64 gripper image), under the key "depth".  segmentation: the
         image sets also carry "segmentation/<name>" uint8 [n, h, w] labels of every RGB camera, rendered from the same snapshot by
-        the same launch (KManipEnvHip.render_cameras(segmentation=True)), under the same ordering contract."""
+        the same launch (KManipEnvHip.render_cameras(segmentation=True)), under the same ordering contract.  points: (camera, height,
+        width) or (camera, height, width, frame) of a float32 [n, h, w, 3] point cloud (KManipEnvHip.render_points; frame "world",
+        the default, or "camera"), under the key "points"; if `depth` names the same camera and shape, the depth image comes from
+        that launch too, not from a second ray cast."""
         torch = _torch()
         self.torch, self.env, self.cams, self.depth = torch, env, cams, depth
+        self.points = None if points is None else (tuple(points) + ("world",))[:4]
         self.segmentation = bool(segmentation)
         self.k = 0
         self.stream = torch.cuda.Stream(device=env.device)
@@ -168,9 +172,17 @@ class RenderBehind:
             bufs = dict(self.env.render_cameras(self.cams, out=out, segmentation=True))
         else:
             bufs = dict(self.env.render_cameras(self.cams, out=out))
-        if self.depth is not None:
+        shared = self.points is not None and self.depth is not None and tuple(self.depth) == self.points[:3]
+        if self.depth is not None and not shared:
             cam, h, w = self.depth
             bufs["depth"] = self.env.render_depth(cam, h, w, out=None if out is None else out["depth"])
+        if self.points is not None:
+            cam, h, w, frame = self.points
+            if shared:                                # one ray cast: the depth image is the launch's second output
+                bufs["depth"] = (self.torch.empty((self.env.num_envs, h, w), dtype=self.torch.float32, device=self.env.device)
+                                 if out is None else out["depth"])
+            bufs["points"] = self.env.render_points(cam, h, w, frame=frame, out=None if out is None else out["points"],
+                                                    depth_out=bufs.get("depth") if shared else None)
         return bufs
 
     def after_step(self):

@@ -390,6 +390,29 @@ KMANIP_API int kmanip_get_render_links(KHandle h, int* n, KLinkCapsule* caps);
 KMANIP_API int kmanip_set_depth_links(KHandle h, int on);
 KMANIP_API int kmanip_get_depth_links(KHandle h, int* on);
 
+/* Camera geometry.  MuJoCo's data.cam_xpos / cam_xmat of camera `cam`, per env, as the renders build it:
+ * pose_dev DEVICE double[num_envs, 12] = origin (3), then the 3x3 row-major matrix whose COLUMNS are the camera's x (right),
+ * y (up), z (the camera looks along -z) axes in the world frame.  Honours kmanip_set_render_source (a snapshot's qpos and, in
+ * visual ranges mode, its episode counters) and the per-env camera offset in both visual-parameter modes, exactly as
+ * kmanip_render_depth does.  Asynchronous on `stream`. */
+KMANIP_API int kmanip_get_camera_poses(KHandle h, int cam, double* pose_dev, void* stream);
+
+/* The point cloud of a depth image: the back-projection of what kmanip_render_depth draws on this handle at this moment (the
+ * surrogate scene, plus the capsule list while kmanip_set_depth_links is on and the list is not empty), by the same float64 ray
+ * cast.  Pixel (r, c) of a height x width image has the ray direction d = x dx + y dy - z in the camera's axes, with
+ * dx = (c + 0.5 - width/2) / f, dy = -(r + 0.5 - height/2) / f, f = (height/2) / tan(fovy/2); D is the pixel's depth in float64 (the
+ * nearest hit along the optical axis, clipped to [cam_znear, cam_zfar], no hit = cam_zfar).  Written per pixel:
+ *   frame KM_POINTS_CAMERA: (float)(D dx), (float)(D dy), (float)(-D)   (the camera's own axes: x right, y up, looking along -z)
+ *   frame KM_POINTS_WORLD : (float)(o + D d), evaluated in float64 and rounded once (o, x, y, z: kmanip_get_camera_poses)
+ *   depth_dev, unless NULL: (float)D, the image kmanip_render_depth writes, from the same launch
+ * A pixel without a hit is the point on the far plane: mask with depth >= cam_zfar.
+ * xyz_dev DEVICE float[num_envs, height, width, 3]; depth_dev DEVICE float[num_envs, height, width] or NULL.  Snapshots, both
+ * visual-parameter modes and kmanip_enable_timing are honoured as by kmanip_render_depth.  A NULL handle or xyz_dev, a camera the
+ * model does not have, height / width < 1 or an unknown frame return nonzero with kmanip_last_error set and launch nothing. */
+enum { KM_POINTS_CAMERA = 0, KM_POINTS_WORLD = 1 };
+KMANIP_API int kmanip_render_points(KHandle h, int cam, int height, int width, int frame,
+                                    float* xyz_dev, float* depth_dev, void* stream);
+
 /* Rendering BEHIND the steps (a data-generation loop whose policy does not look at the images: the reference's scripted heuristic,
  * examples/2_synthetic_data.py:28-41, logs them and acts on the state).  A render reads nothing of the state but qpos (and, in
  * visual ranges mode, the episode counters the colour / light / camera draw uses: kmanip_set_visual_param_ranges):
