@@ -43,8 +43,9 @@ extern "C" {
 /* Contact slots the solver keeps per step: 4 cube corners on the table, KM_SPHERE_SLOTS sphere-cube contacts and
  * KM_SPHERE_TABLE_SLOTS sphere-table contacts -- the first penetrating spheres in sphere-index order (fingers come first); a
  * further penetrating sphere is dropped for that sub-step (its mask bit stays clear), like the 5th+ cube corner.  Two per arm
- * and kind, except three per arm on the table for the two-arm models, whose hands rest on it (measured under random actions:
- * the single arm never has more than two spheres on the table, the Torso up to six). */
+ * and kind, except three per arm on the table for the two-arm models, whose hands rest on it.  tests/tools/regime_states.py
+ * builds the states that fill them: cell P2 all four sphere-cube slots of a two-arm model, cell T1 both table slots of the single
+ * arm and up to four of the six of a two-arm model (tests/test_regimes_gpu.py steps them against the oracle). */
 #define KM_SPHERE_SLOTS(nlink) (2 * ((nlink) / 10))
 #define KM_SPHERE_TABLE_SLOTS(nlink) ((nlink) >= 20 ? 6 : 2)
 #define KM_MAX_CAMS    4    /* cameras: 0 = grip_r, 1 = grip_l, 2 = top, 3 = head (__init__.py:157-161) */
