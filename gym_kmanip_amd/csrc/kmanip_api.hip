@@ -14,7 +14,7 @@
 
 #include "kmanip_device.hpp"
 
-#define KM_VERSION "kmanip-hip 0.33 (gfx950, f64)"
+#define KM_VERSION "kmanip-hip 0.34 (gfx950, f64)"
 
 static thread_local std::string g_create_error;
 
@@ -66,6 +66,11 @@ struct KHandle_ {
   KLinkCapsule* links_buf = nullptr;   // [KM_MAX_LINK_CAPSULES], allocated by the first call that sets a list
   // kmanip_set_depth_links: while on AND the list is not empty the depth renders launch k_render_depth_links
   bool depth_links = false;
+  // the state on the device (kmanip_get_state_dev / kmanip_set_state_dev / kmanip_copy_envs)
+  unsigned long long* index_errors = nullptr;   // index entries outside 0 .. num_envs-1 those calls skipped (kmanip_state_index_errors)
+  double* stage_buf = nullptr;                  // staging copy of a same-handle kmanip_copy_envs: [nq + nv + nu + nv + KM_EP_N][stage_cap]
+  int32_t* stage_cnt = nullptr;                 //   doubles, then step_idx and episode [2][stage_cap]; allocated by the first such call
+  int stage_cap = 0;
   std::vector<void*> allocs;
 };
 
@@ -378,6 +383,7 @@ int kmanip_create(const KModelDesc* desc, int num_envs, int device, uint64_t see
   if (const char* e = getenv("KMANIP_WAVE_CLOCKS")) if (e[0] == '1') CR(dalloc((void**)&h->st.wave_clk, sizeof(unsigned long long) * N));
   CR(dalloc((void**)&h->slot_env, sizeof(int32_t) * N));
   CR(dalloc((void**)&h->st.work, sizeof(int32_t) * N));
+  CR(dalloc((void**)&h->index_errors, sizeof(unsigned long long)));
   // the initialisation above ran on the null stream; the caller's (non-blocking) streams must not start before it
   CR(hipDeviceSynchronize());
 #undef CR
@@ -1113,6 +1119,120 @@ int kmanip_ik_eval(KHandle h, int arm, int n, const double* qpos, const double* 
   HIPCHK(h, hipDeviceSynchronize());
   HIPCHK(h, hipMemcpy(res, dres.p, sizeof(double) * n * mrow, hipMemcpyDeviceToHost));
   HIPCHK(h, hipMemcpy(jac, djac.p, sizeof(double) * n * mrow * nik, hipMemcpyDeviceToHost));
+  return 0;
+}
+
+// ---- the state on the device (include/kmanip.h KStateDev; kmanip_state.hip)
+// the handle's live state as one side of a transfer (episode / sim_time: NULL where the call does not write them)
+static KStateSide state_side(KHandle h, const int32_t* index) {
+  KStateSide s{};
+  s.f[0] = h->st.qpos; s.f[1] = h->st.qvel; s.f[2] = h->st.ctrl; s.f[3] = h->st.warm; s.f[4] = h->st.envp;
+  s.step = h->st.step_idx; s.episode = h->st.episode;
+  s.index = index;
+  s.sim_time = h->st.sim_time; s.control_dt = h->st.control_dt;
+  s.stride = s.range = h->num_envs;
+  return s;
+}
+static int state_dev_args(KHandle h, const char* what, const int32_t* index, int n, const KStateDev* io) {
+  if (!io) { h->err = std::string(what) + ": the KStateDev pointer is NULL"; return -1; }
+  if (n < 0) { h->err = std::string(what) + ": n must be >= 0"; return -1; }
+  if (!index && n > h->num_envs) { h->err = std::string(what) + ": n > num_envs with a NULL index"; return -1; }
+  return 0;
+}
+static KStateSide tensor_side(const KStateDev* io, const int32_t* index) {
+  KStateSide t{};
+  t.f[0] = io->qpos; t.f[1] = io->qvel; t.f[2] = io->ctrl; t.f[3] = io->qacc_warm;
+  t.step = io->step_idx; t.episode = io->episode;
+  t.index = index;
+  return t;
+}
+
+int kmanip_get_state_dev(KHandle h, const int32_t* env_index_dev, int n, const KStateDev* out, void* stream) {
+  if (!h) { g_create_error = "kmanip_get_state_dev: null handle"; return -1; }
+  if (state_dev_args(h, "kmanip_get_state_dev", env_index_dev, n, out)) return -1;
+  if (n == 0) return 0;
+  KM_ENTER(h);
+  kmanip_launch_state_io(h->desc, state_side(h, nullptr), tensor_side(out, env_index_dev), n, false, h->index_errors, (hipStream_t)stream);
+  HIPCHK(h, hipGetLastError());
+  return 0;
+}
+
+int kmanip_set_state_dev(KHandle h, const int32_t* env_index_dev, int n, const KStateDev* in, void* stream) {
+  if (!h) { g_create_error = "kmanip_set_state_dev: null handle"; return -1; }
+  if (state_dev_args(h, "kmanip_set_state_dev", env_index_dev, n, in)) return -1;
+  if (n == 0) return 0;
+  KM_ENTER(h);
+  kmanip_launch_state_io(h->desc, state_side(h, nullptr), tensor_side(in, env_index_dev), n, true, h->index_errors, (hipStream_t)stream);
+  HIPCHK(h, hipGetLastError());
+  return 0;
+}
+
+int kmanip_copy_envs(KHandle dst, const int32_t* dst_index_dev, KHandle src, const int32_t* src_index_dev, int n, unsigned flags, void* stream) {
+  if (!dst) { g_create_error = "kmanip_copy_envs: null destination handle"; return -1; }
+  if (!src) { dst->err = "kmanip_copy_envs: null source handle"; return -1; }
+  if (n < 0) { dst->err = "kmanip_copy_envs: n must be >= 0"; return -1; }
+  if (flags & ~(unsigned)(KM_COPY_EPISODE | KM_COPY_ENV_PARAMS)) { dst->err = "kmanip_copy_envs: unknown flag"; return -1; }
+  if ((!dst_index_dev && n > dst->num_envs) || (!src_index_dev && n > src->num_envs)) { dst->err = "kmanip_copy_envs: n > num_envs with a NULL index"; return -1; }
+  if (dst->device != src->device) { dst->err = "kmanip_copy_envs: the two handles are on different devices"; return -1; }
+  if (memcmp(&dst->desc, &src->desc, sizeof(KModelDesc)) != 0) { dst->err = "kmanip_copy_envs: the two handles were created from different KModelDesc"; return -1; }
+  bool params = false;
+  if (flags & KM_COPY_ENV_PARAMS) {
+    if (src->st.envp && !dst->st.envp) { dst->err = "kmanip_copy_envs: destination has no per-env parameters: call kmanip_set_env_params first"; return -2; }
+    params = dst->st.envp != nullptr;           // (neither has them: the flag does nothing)
+  }
+  if (n == 0) return 0;
+  KM_ENTER(dst);
+  hipStream_t s = (hipStream_t)stream;
+  const KModelDesc& d = dst->desc;
+  const KEnvParamDefaults model{{d.cube_mass, d.con_cube_friction[0], d.cube_frictionloss, 1.0}};
+  KStateSide to = state_side(dst, dst_index_dev), from = state_side(src, src_index_dev);
+  if (!(flags & KM_COPY_EPISODE)) to.episode = nullptr;
+  if (dst != src) {
+    kmanip_launch_state_gather(d, to, from, n, params, model, dst->index_errors, s);
+    HIPCHK(dst, hipGetLastError());
+    return 0;
+  }
+  // Same handle: every source row is read before any is written -- rows 0 .. n-1 go into the staging copy (first launch, nothing
+  // counted), and from there into their destination envs (second launch: both indices checked, bad entries counted once).
+  if (dst->stage_cap < n) {
+    // (the first such call, or one with more entries than any before: the only path here that allocates, and so synchronises)
+    const int cap = n > dst->num_envs ? n : dst->num_envs;
+    const int comps = 4 * d.nlink + 19 + KM_EP_N;
+    HIPCHK(dst, hipDeviceSynchronize());
+    void* pd = nullptr; void* pi = nullptr;
+    HIPCHK(dst, hipMalloc(&pd, sizeof(double) * (size_t)comps * cap));
+    dst->allocs.push_back(pd);
+    HIPCHK(dst, hipMalloc(&pi, sizeof(int32_t) * 2 * (size_t)cap));
+    dst->allocs.push_back(pi);
+    dst->stage_buf = (double*)pd; dst->stage_cnt = (int32_t*)pi; dst->stage_cap = cap;     // (a smaller one stays in allocs until kmanip_destroy)
+  }
+  KStateSide stage{};
+  {
+    const size_t cap = (size_t)dst->stage_cap;
+    const int K[KS_NFIELD] = {d.nlink + 7, d.nlink + 6, d.nlink, d.nlink + 6, KM_EP_N};
+    double* p = dst->stage_buf;
+    for (int f = 0; f < KS_NFIELD; f++) { stage.f[f] = p; p += (size_t)K[f] * cap; }
+    stage.step = dst->stage_cnt; stage.episode = dst->stage_cnt + cap;
+    stage.stride = stage.range = dst->stage_cap;
+    stage.staged = 1;
+  }
+  kmanip_launch_state_gather(d, stage, from, n, params, model, nullptr, s);
+  stage.index = src_index_dev; stage.range = src->num_envs;          // (checked again, so that a bad source entry is skipped and counted here)
+  kmanip_launch_state_gather(d, to, stage, n, params, model, dst->index_errors, s);
+  HIPCHK(dst, hipGetLastError());
+  return 0;
+}
+
+int kmanip_state_index_errors(KHandle h, int64_t* count) {
+  if (!h) { g_create_error = "kmanip_state_index_errors: null handle"; return -1; }
+  if (!count) { h->err = "kmanip_state_index_errors: count is NULL"; return -1; }
+  KM_ENTER(h);
+  unsigned long long c = 0;
+  HIPCHK(h, hipDeviceSynchronize());
+  HIPCHK(h, hipMemcpy(&c, h->index_errors, sizeof c, hipMemcpyDeviceToHost));
+  HIPCHK(h, hipMemset(h->index_errors, 0, sizeof c));
+  HIPCHK(h, hipDeviceSynchronize());
+  *count = (int64_t)c;
   return 0;
 }
 

@@ -620,3 +620,28 @@ struct KCostWeights { int ik, work, coupled, armtab, cubetab, binw; };
 void kmanip_launch_sort_envs(const KDeviceState& st, int32_t* slot_env, const KCostWeights& w, hipStream_t stream);
 void kmanip_launch_scripted_action(const KDeviceModel* dm, const KDeviceState& st, float* act, hipStream_t stream);
 void kmanip_launch_sample_action(const KDeviceModel* dm, const KDeviceState& st, float* act, int ahead, hipStream_t stream);
+
+// The env state in and out of a handle on the device (kmanip_state.hip; include/kmanip.h kmanip_get_state_dev / kmanip_set_state_dev /
+// kmanip_copy_envs).  Arguments of their own: no field of KDeviceState / KDeviceModel moves.
+// One side of a transfer.  A component-major side (a handle's state, or the staging copy of a same-handle kmanip_copy_envs) has
+// element (k, env) of field f at f[k * stride + env]; the tensor side of kmanip_launch_state_io is env-major, f[row * K + k], and
+// any of its pointers may be NULL (that field is skipped).  index[row] (NULL: row itself) is the env of a row and must lie in
+// 0 .. range-1, else the row is skipped and counted; a `staged` side holds row j AT j and has its index checked only.
+#define KS_NFIELD 5
+struct KStateSide {
+  double* f[KS_NFIELD];     // qpos, qvel, ctrl, qacc_warm, per-env parameters [KM_EP_N] (gather only; NULL source = the model's values)
+  int32_t* step;
+  int32_t* episode;
+  const int32_t* index;
+  double* sim_time;         // destination state only: the bound sim-time buffer (NULL: none), written as step * control_dt
+  double control_dt;
+  int stride, range, staged;
+};
+struct KStateShape { int K[KS_NFIELD]; };
+struct KEnvParamDefaults { double v[KM_EP_N]; };
+// state -> tensors (import = false) or tensors -> state, rows 0 .. n-1 of the tensors, ONE launch
+void kmanip_launch_state_io(const KModelDesc& hd, const KStateSide& state, const KStateSide& tensors, int n, bool import, unsigned long long* errors,
+                            hipStream_t stream);
+// dst row j <- src row j for every field (env_params: the KM_EP_* values too), ONE launch; errors may be NULL (not counted)
+void kmanip_launch_state_gather(const KModelDesc& hd, const KStateSide& dst, const KStateSide& src, int n, bool env_params,
+                                const KEnvParamDefaults& model, unsigned long long* errors, hipStream_t stream);

@@ -45,6 +45,7 @@ class KManipEnvHip:
         self.num_envs = int(num_envs)
         self.device = torch.device("cuda", device)
         self.device_index = device
+        self.seed, self.env_id_offset = int(seed), int(env_id_offset)
         h = C.c_void_p()
         rc = self.L.kmanip_create(C.byref(cm.desc), self.num_envs, device, C.c_uint64(seed),
                                   C.c_int64(env_id_offset), C.byref(h))
@@ -492,6 +493,7 @@ class KManipEnvHip:
     def set_seed(self, seed: int, restart_episodes: bool = True):
         """Re-key the cube-spawn stream (KManipEnv.reset(seed=...)); with restart_episodes the next k_reset is episode 0."""
         self._check(self.L.kmanip_set_seed(self.h, C.c_uint64(int(seed)), int(restart_episodes)), "kmanip_set_seed")
+        self.seed = int(seed)
 
     def get_episode(self):
         """Per-env episode counter (keys the cube-spawn stream together with seed and global env id)."""
@@ -543,6 +545,94 @@ class KManipEnvHip:
                 self._set_visual_raw(_torch().as_tensor(np.ascontiguousarray(vp[0], dtype=np.float64)).to(self.device))
             else:
                 self._set_visual_ranges_raw(vp[1], vp[2])
+
+    # ------------------------------------------------------------------ the state on the device
+    _STATE_FIELDS = (("qpos", "qpos", "nq"), ("qvel", "qvel", "nv"), ("ctrl", "ctrl", "nu"), ("warm", "qacc_warm", "nv"),
+                     ("step", "step_idx", None), ("episode", "episode", None))
+
+    def _env_index(self, envs, what="envs"):
+        """(int32 device tensor or None, its C pointer, n) of an env index: None = envs 0 .. num_envs-1."""
+        torch = _torch()
+        if envs is None:
+            return None, None, None
+        if not (isinstance(envs, torch.Tensor) and envs.is_cuda and envs.dtype == torch.int32):
+            envs = torch.as_tensor(envs).to(device=self.device, dtype=torch.int32)
+        envs = envs.contiguous()
+        self._check_buf(envs, (envs.numel(),), torch.int32, what)
+        return envs, C.c_void_p(envs.data_ptr()), int(envs.numel())
+
+    def _state_dev(self, tensors, n):
+        """KStateDev of a {name: tensor or None} dict, every tensor checked against n rows."""
+        torch = _torch()
+        sd = _libmod.KStateDev()
+        for name, cname, width in self._STATE_FIELDS:
+            t = tensors.get(name)
+            if t is None:
+                continue
+            if width is None:
+                self._check_buf(t, (n,), torch.int32, name)
+            else:
+                self._check_buf(t, (n, getattr(self.cm, width)), torch.float64, name)
+            setattr(sd, cname, t.data_ptr())
+        return sd
+
+    def state_tensors(self, envs=None, out=None):
+        """The state of `envs` as device tensors (kmanip_get_state_dev: one launch on the current stream, no synchronisation):
+        {"qpos" [n, nq], "qvel" [n, nv], "ctrl" [n, nu], "warm" [n, nv] float64, "step" [n], "episode" [n] int32}; row j is env
+        envs[j].  `envs`: an int32 device tensor or anything torch.as_tensor takes (repeats allowed); None = every env.  `out`: a
+        dict of such tensors to fill -- only the fields it names are read (the others are skipped) -- returned as given."""
+        torch = _torch()
+        idx, ip, n = self._env_index(envs)
+        n = self.num_envs if idx is None else n
+        if out is None:
+            out = {}
+            for name, _, width in self._STATE_FIELDS:
+                out[name] = (torch.empty((n,), dtype=torch.int32, device=self.device) if width is None else
+                             torch.empty((n, getattr(self.cm, width)), dtype=torch.float64, device=self.device))
+        unknown = set(out) - {f[0] for f in self._STATE_FIELDS}
+        if unknown:
+            raise ValueError("unknown state field(s) %s" % sorted(unknown))
+        sd = self._state_dev(out, n)
+        self._check(self.L.kmanip_get_state_dev(self.h, ip, n, C.byref(sd), self._stream()), "kmanip_get_state_dev")
+        return out
+
+    def set_state_tensors(self, envs=None, qpos=None, qvel=None, ctrl=None, warm=None, step=None, episode=None):
+        """Write the given fields of `envs` from device tensors shaped as state_tensors returns them (kmanip_set_state_dev: one
+        launch on the current stream).  Fields left None and envs not named keep every bit.  With `step` the bound sim_time of
+        those envs follows; observations, rewards, done bytes and contact masks do not: call observe() for them."""
+        idx, ip, n = self._env_index(envs)
+        n = self.num_envs if idx is None else n
+        sd = self._state_dev(dict(qpos=qpos, qvel=qvel, ctrl=ctrl, warm=warm, step=step, episode=episode), n)
+        self._check(self.L.kmanip_set_state_dev(self.h, ip, n, C.byref(sd), self._stream()), "kmanip_set_state_dev")
+
+    def copy_envs_from(self, src, src_envs=None, dst_envs=None, episode=False, env_params=True):
+        """Env dst_envs[j] of this handle becomes env src_envs[j] of `src` (kmanip_copy_envs, on the current stream): qpos, qvel,
+        ctrl, warm start and step counter, the episode counter with episode=True, the per-env physics parameters with
+        env_params=True.  An index left None is 0 .. n-1; with both None, n = this handle's num_envs.  `src` may be this handle
+        (any permutation: every source is read before any destination is written).  With env_params=True, a `src` that has
+        per-env parameters and a destination that has none, this handle first gets explicit parameters at the model's values
+        (set_env_params: synchronous) -- only after the library has accepted every other argument: a refused copy leaves this handle as it
+        was.  The clone's random streams stay its own: it follows its source only until a reset."""
+        sidx, sp, sn = self._env_index(src_envs, "src_envs")
+        didx, dp, dn = self._env_index(dst_envs, "dst_envs")
+        if sn is not None and dn is not None and sn != dn:
+            raise _libmod.KManipError("copy_envs_from: src_envs and dst_envs must have the same length (%d, %d)" % (sn, dn))
+        n = dn if dn is not None else sn if sn is not None else self.num_envs
+        flags = (_libmod.KM_COPY_EPISODE if episode else 0) | (_libmod.KM_COPY_ENV_PARAMS if env_params else 0)
+        rc = self.L.kmanip_copy_envs(self.h, dp, src.h, sp, n, flags, self._stream())
+        if rc != 0 and env_params and src._ep_active and not self._ep_active and \
+                b"destination has no per-env parameters" in self.L.kmanip_last_error(self.h):
+            # the library checks this last: every other argument was accepted, so only now does the destination change
+            self.set_env_params()
+            rc = self.L.kmanip_copy_envs(self.h, dp, src.h, sp, n, flags, self._stream())
+        self._check(rc, "kmanip_copy_envs")
+
+    def state_index_errors(self) -> int:
+        """How many index entries outside 0 .. num_envs-1 state_tensors / set_state_tensors / copy_envs_from (as the destination)
+        skipped since the last call; reads and clears the device counter (synchronous)."""
+        c = C.c_int64(0)
+        self._check(self.L.kmanip_state_index_errors(self.h, C.byref(c)), "kmanip_state_index_errors")
+        return int(c.value)
 
     # ------------------------------------------------------------------ per-env physics parameters (domain randomisation)
     def set_env_params(self, **fields):

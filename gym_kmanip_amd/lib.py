@@ -20,7 +20,8 @@ _lib = None
 EXPORTS = [
     "kmanip_model_desc_size", "kmanip_create", "kmanip_reset", "kmanip_step", "kmanip_step_chunk", "kmanip_get_state",
     "kmanip_set_state", "kmanip_get_episode", "kmanip_set_episode", "kmanip_get_counters", "kmanip_bind_sim_time", "kmanip_bind_reward_done_record", "kmanip_select_reward_done_record", "kmanip_observe", "kmanip_set_seed", "kmanip_get_diag", "kmanip_timing_summary", "kmanip_enable_timing", "kmanip_ik", "kmanip_ik_eval",
-    "kmanip_render_depth", "kmanip_render_rgb", "kmanip_render_rgb_multi", "kmanip_render_labels_multi", "kmanip_render_seg", "kmanip_set_render_links", "kmanip_get_render_links", "kmanip_set_depth_links", "kmanip_get_depth_links", "kmanip_get_camera_poses", "kmanip_render_points", "kmanip_snapshot_render_state", "kmanip_set_render_source", "kmanip_bind_step_depth", "kmanip_scripted_action", "kmanip_sample_action", "kmanip_set_env_params", "kmanip_get_env_params", "kmanip_set_env_param_ranges", "kmanip_set_visual_params", "kmanip_get_visual_params", "kmanip_set_visual_param_ranges", "kmanip_num_envs", "kmanip_last_error", "kmanip_version", "kmanip_destroy",
+    "kmanip_render_depth", "kmanip_render_rgb", "kmanip_render_rgb_multi", "kmanip_render_labels_multi", "kmanip_render_seg", "kmanip_set_render_links", "kmanip_get_render_links", "kmanip_set_depth_links", "kmanip_get_depth_links", "kmanip_get_camera_poses", "kmanip_render_points", "kmanip_snapshot_render_state", "kmanip_set_render_source", "kmanip_bind_step_depth", "kmanip_scripted_action", "kmanip_sample_action", "kmanip_set_env_params", "kmanip_get_env_params", "kmanip_set_env_param_ranges", "kmanip_set_visual_params", "kmanip_get_visual_params", "kmanip_set_visual_param_ranges",
+    "kmanip_get_state_dev", "kmanip_set_state_dev", "kmanip_copy_envs", "kmanip_state_index_errors", "kmanip_num_envs", "kmanip_last_error", "kmanip_version", "kmanip_destroy",
 ]
 
 
@@ -38,7 +39,14 @@ class KLinkCapsule(C.Structure):
                 ("p0", C.c_double * 3), ("seg", C.c_double * 3), ("radius", C.c_double)]
 
 
+class KStateDev(C.Structure):
+    """include/kmanip.h KStateDev: DEVICE pointers of kmanip_get_state_dev / kmanip_set_state_dev, NULL = that field is skipped."""
+    _fields_ = [("qpos", C.c_void_p), ("qvel", C.c_void_p), ("ctrl", C.c_void_p), ("qacc_warm", C.c_void_p),
+                ("step_idx", C.c_void_p), ("episode", C.c_void_p)]
+
+
 KM_MAX_LINK_CAPSULES = 24
+KM_COPY_EPISODE, KM_COPY_ENV_PARAMS = 1, 2       # include/kmanip.h: flags of kmanip_copy_envs
 KM_POINTS_FRAMES = {"camera": 0, "world": 1}     # include/kmanip.h KM_POINTS_CAMERA / KM_POINTS_WORLD
 
 
@@ -110,6 +118,10 @@ def load():
     lib.kmanip_set_visual_params.argtypes = [vp, vp, vp]
     lib.kmanip_get_visual_params.argtypes = [vp, vp, vp]
     lib.kmanip_set_visual_param_ranges.argtypes = [vp, f64p, f64p]
+    lib.kmanip_get_state_dev.argtypes = [vp, vp, C.c_int, C.POINTER(KStateDev), vp]
+    lib.kmanip_set_state_dev.argtypes = [vp, vp, C.c_int, C.POINTER(KStateDev), vp]
+    lib.kmanip_copy_envs.argtypes = [vp, vp, vp, vp, C.c_int, C.c_uint, vp]
+    lib.kmanip_state_index_errors.argtypes = [vp, C.POINTER(C.c_int64)]
     lib.kmanip_num_envs.argtypes = [vp]
     lib.kmanip_last_error.argtypes = [vp]
     lib.kmanip_last_error.restype = C.c_char_p

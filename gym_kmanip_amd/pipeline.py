@@ -223,3 +223,85 @@ class RenderBehind:
 
     def synchronize(self):
         self.stream.synchronize()
+
+
+def branch_indices(n: int, k: int):
+    """The candidate layout of BranchRollouts: (src, dst) int32 arrays of n * k entries, candidate j of real env e is plan env
+    e * k + j, so dst = 0 .. n*k-1 and src[e * k + j] = e; a [n * k, ...] tensor of the plan handle viewed as [n, k, ...] is indexed
+    [real env, candidate]."""
+    import numpy as np
+    if n < 1 or k < 1:
+        raise ValueError("branch_indices: n and k must be positive")
+    return np.repeat(np.arange(n, dtype=np.int32), k), np.arange(n * k, dtype=np.int32)
+
+
+class BranchRollouts:
+    """Sampling-based planning (random shooting, CEM, MPPI) on the device: every real env is copied into k candidate envs of a
+    second handle, the candidates are rolled out H steps in one launch and scored, all without a host round trip.
+
+        plan = BranchRollouts(env, k=64)
+        for t in range(T):
+            plan.branch()                                   # candidate e*k+j <- real env e   (one kmanip_copy_envs launch)
+            acts = plan.sample_actions(H)                   # [H, n*k, act_dim] from the plan handle's own action stream
+            reward, done = plan.rollout(acts)               # one kmanip_step_chunk launch: [H, n, k] views
+            j, chosen = plan.best(reward.sum(0))            # [n] argmax, [H, n, act_dim] action sequences
+            env.step_flat(chosen[0].contiguous())
+
+    The plan handle has the real handle's compiled model, device and seed (the one in force when the planner is built) and `env.num_envs * k` envs whose global ids start at
+    `env_id_offset` (default: 2^40 above the real handle's, clear of every shard of a real batch), so the candidates' action
+    streams differ from each other and from the real envs'.  An env's bits depend neither on its wave-mates nor on the launch
+    shape, so a candidate stepped with some actions computes EXACTLY what the real env computes with them: a predicted return is
+    the realised one, bit for bit (tests/test_state_dev_gpu.py).
+    RESET CAVEAT: that holds only while no reset falls inside the horizon.  Random streams are keyed by an env's own global id, so a
+    candidate that reaches the TimeLimit (or diverges) inside the rollout auto-resets to ITS OWN cube spawn, not the real env's.
+    rollout() returns the done bytes: mask the steps after a candidate's first nonzero byte.
+    Everything runs on the caller's current stream; the plan handle's per-env parameters follow the real handle's at every
+    branch()."""
+
+    def __init__(self, env, k: int, env_id_offset: Optional[int] = None):
+        torch = _torch()
+        self.env, self.k, self.n = env, int(k), env.num_envs
+        src, _ = branch_indices(self.n, self.k)
+        off = env.env_id_offset + (1 << 40) if env_id_offset is None else int(env_id_offset)
+        self.plan = env_hip.KManipEnvHip(env.cm, num_envs=self.n * self.k, device=env.device_index, seed=env.seed, env_id_offset=off)
+        self.src_index = torch.from_numpy(src).to(env.device)
+        self.rows = torch.arange(self.n, device=env.device)
+        self.acts = self.obs = None                 # the last rollout's actions and observations
+        torch.cuda.synchronize(env.device)          # the handle and the index were made on the default stream
+
+    def branch(self):
+        """Candidates e*k .. e*k+k-1 become real env e: state, step and episode counters, per-env parameters."""
+        self.plan.copy_envs_from(self.env, src_envs=self.src_index, episode=True, env_params=True)
+
+    def sample_actions(self, horizon: int):
+        """[horizon, n*k, act_dim] float32: action_space.sample() of every candidate for its next `horizon` steps, from the plan
+        handle's own counter-based stream (sample_action(ahead=t)): call after branch(), which sets the counters it is keyed by.
+        The stream is keyed (seed; candidate's global id, episode, step + t), so a caller that replans one control step later gets,
+        for candidate j, the TAIL of that candidate's previous plan plus one new last step: fresh exploration per replan (what
+        random shooting or CEM usually expect) needs actions of the caller's own, e.g. torch.rand on the device, which rollout()
+        takes just as well."""
+        torch = _torch()
+        acts = torch.empty((int(horizon), self.n * self.k, self.env.cm.act_dim), dtype=torch.float32, device=self.env.device)
+        for t in range(int(horizon)):
+            self.plan.sample_action(acts[t], ahead=t)
+        return acts
+
+    def rollout(self, acts):
+        """One step_chunk of the plan handle over acts [H, n*k, act_dim]: (reward float64, done uint8), each an [H, n, k] view.
+        The observations of the H steps stay in self.obs [H, n*k, obs_dim]."""
+        H = int(acts.shape[0])
+        self.acts = acts
+        self.obs, reward, done = self.plan.step_chunk(acts)
+        return reward.view(H, self.n, self.k), done.view(H, self.n, self.k)
+
+    def best(self, returns):
+        """returns [n, k] -> (j [n] int64: the candidate with the largest return of every real env, its action sequence
+        [H, n, act_dim] out of the last rollout's actions)."""
+        if self.acts is None:
+            raise ValueError("BranchRollouts.best: call rollout(acts) first")
+        j = returns.argmax(dim=1)
+        H = int(self.acts.shape[0])
+        return j, self.acts.view(H, self.n, self.k, -1)[:, self.rows, j]
+
+    def close(self):
+        self.plan.k_close()

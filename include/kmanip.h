@@ -250,6 +250,67 @@ KMANIP_API int kmanip_set_state(KHandle h, const double* qpos, const double* qve
 KMANIP_API int kmanip_get_episode(KHandle h, int32_t* episode);
 KMANIP_API int kmanip_set_episode(KHandle h, const int32_t* episode);
 
+/* The state as DEVICE tensors, for any subset of the envs, without leaving the device: what branching
+ * rollouts (a planner copies each real env into K candidates), resets to stored states and a policy that reads qvel or ctrl need.
+ * All pointers are DEVICE pointers, env-major like kmanip_get_state; any may be NULL (that field is skipped). */
+typedef struct KStateDev {
+  double*  qpos;       /* [n, nq] */
+  double*  qvel;       /* [n, nv] */
+  double*  ctrl;       /* [n, nu] */
+  double*  qacc_warm;  /* [n, nv] */
+  int32_t* step_idx;   /* [n] */
+  int32_t* episode;    /* [n] */
+} KStateDev;
+/* Row j of every tensor is env env_index_dev[j] (DEVICE int32[n]); a NULL index means envs 0 .. n-1.  n >= 0, and n <= num_envs with
+ * a NULL index: anything else, or a NULL KStateDev, returns nonzero with kmanip_last_error set and launches nothing; n == 0 succeeds
+ * and does nothing.
+ * ORDERING: asynchronous on `stream` -- ONE kernel launch for all fields, no host synchronisation, no allocation, no host copy.
+ * Enqueued after a kmanip_step on the same stream the call sees that step's result, and a step enqueued after it sees what it
+ * wrote; ordering against other streams is the caller's, as everywhere in this header.
+ * WHAT IS WRITTEN: kmanip_get_state_dev writes the named rows of the non-NULL tensors.  kmanip_set_state_dev writes the non-NULL
+ * fields of the named envs and, if a sim-time buffer is bound (kmanip_bind_sim_time) and step_idx is given, step_idx x
+ * control_timestep of those envs; envs the index does not name are not touched, not a bit.  It does NOT touch observations,
+ * rewards, done bytes, contact masks or IK diagnostics: a caller that wants those of the new state calls kmanip_observe, as after
+ * kmanip_set_state.  The step's scheduling predictors (work counters, SPREAD flags) stay the env's own: they order waves and
+ * never change a result.
+ * DUPLICATES: an env named twice in a read is fine (that is the broadcast).  An env named twice as a DESTINATION ends with, in
+ * every component, the value of ONE of the rows that name it -- which one is unspecified and may differ between components.
+ * OUT-OF-RANGE INDICES: an entry outside 0 .. num_envs-1 is never used as an address; its row is skipped (not read, not
+ * written) and a counter the handle owns is incremented (kmanip_state_index_errors); every other entry is carried out.  The call
+ * still returns 0: the index lives on the device.
+ * ERRORS: a refused call leaves the handle exactly as it was. */
+KMANIP_API int kmanip_get_state_dev(KHandle h, const int32_t* env_index_dev, int n, const KStateDev* out, void* stream);
+KMANIP_API int kmanip_set_state_dev(KHandle h, const int32_t* env_index_dev, int n, const KStateDev* in, void* stream);
+
+/* Env to env on the device: env dst_index_dev[j] of `dst` receives qpos, qvel, ctrl, qacc_warm and step_idx of env
+ * src_index_dev[j] of `src` (DEVICE int32[n] each; NULL = 0 .. n-1, then n <= that handle's num_envs), and the bound sim time of
+ * `dst` is updated as by kmanip_set_state_dev.  Rows, ordering (on `stream`, for BOTH handles), untouched envs, duplicates and the
+ * things not copied (observations, rewards, done bytes, contact masks, IK diagnostics, scheduling predictors) are as above; a bad
+ * entry on either side skips that entry and counts on the DESTINATION handle.  ONE launch.
+ *   KM_COPY_EPISODE     the episode counter travels too (without it the destination's counters stay).
+ *   KM_COPY_ENV_PARAMS  the KM_EP_* values in force for the source env travel too (in ranges mode: those drawn for its current
+ *                       episode).  `src` has per-env parameters and `dst` has none: nonzero, "destination has no per-env
+ *                       parameters: call kmanip_set_env_params first", nothing launched.  `src` has none and `dst` has them: the
+ *                       destination envs get the compiled model's values.  Neither has them: the flag does nothing.  A
+ *                       destination in ranges mode keeps the copied values until its next reset redraws them (the rule of
+ *                       kmanip_set_env_param_ranges).
+ * RANDOM STREAMS STAY PER ENV: the spawn, action and parameter streams are keyed by the DESTINATION handle's seed and the
+ * destination env's own global env id (env_id_offset + index), neither of which is copied, so a clone stepped with its source's actions follows it bit for bit only until either of them is reset
+ * (the TimeLimit's auto-reset included): from there the two draw different cubes.
+ * COMPATIBILITY: the two handles must be on one device and their KModelDesc byte-equal; otherwise nonzero with kmanip_last_error
+ * set on `dst`, nothing launched.
+ * SAME HANDLE: dst == src is allowed for any index pair, permutations included, and gives what reading every source row first and
+ * writing afterwards gives: the rows pass through a staging copy the handle owns (two launches of the same kernel).  The staging
+ * copy is allocated by the FIRST same-handle call (and again only by one with n larger than num_envs and than every n before):
+ * that call alone waits for the whole device; every other one is asynchronous like the rest.  A handle has ONE staging copy:
+ * two same-handle calls on different streams must be ordered by the caller like any two writers of one buffer. */
+enum { KM_COPY_EPISODE = 1, KM_COPY_ENV_PARAMS = 2 };
+KMANIP_API int kmanip_copy_envs(KHandle dst, const int32_t* dst_index_dev, KHandle src, const int32_t* src_index_dev,
+                     int n, unsigned flags, void* stream);
+/* The number of index entries the three calls above skipped on this handle since the last call of this function, which also
+ * clears it.  The counter lives on the device (allocated by kmanip_create).  Synchronous: waits for the whole device. */
+KMANIP_API int kmanip_state_index_errors(KHandle h, int64_t* count);
+
 /* Asynchronous device-to-device copy of the per-env counters into caller-owned DEVICE buffers (int32[num_envs] each, either
  * may be NULL) on `stream`: lets the k_step seam return sim_time (= step_idx * control_timestep, env_sim.py:194,200) as a
  * device tensor without synchronising. */
