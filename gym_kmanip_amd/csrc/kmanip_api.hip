@@ -14,7 +14,7 @@
 
 #include "kmanip_device.hpp"
 
-#define KM_VERSION "kmanip-hip 0.34 (gfx950, f64)"
+#define KM_VERSION "kmanip-hip 0.35 (gfx950, f64)"
 
 static thread_local std::string g_create_error;
 
@@ -446,6 +446,20 @@ int kmanip_observe(KHandle h, double* obs_dev, double* reward_dev, void* stream)
   if (!h) { g_create_error = "kmanip_observe: null handle"; return -1; }
   KM_ENTER(h);
   kmanip_launch_observe(h->dmodel, h->desc, h->st, obs_dev, reward_dev, (hipStream_t)stream);
+  HIPCHK(h, hipGetLastError());
+  return 0;
+}
+
+// mj_forward with actuation at every env's current state: qacc, joint forces, contact forces (include/kmanip.h KForcesDev;
+// kmanip_forces.hip).  One launch; the handle is only read.
+int kmanip_forces(KHandle h, const KForcesDev* out, void* stream) {
+  if (!h) { g_create_error = "kmanip_forces: null handle"; return -1; }
+  if (!out) { h->err = "kmanip_forces: the KForcesDev pointer is NULL"; return -1; }
+  if (h->desc.solver != KM_SOLVER_NEWTON) { h->err = "kmanip_forces: contact forces need the Newton solver"; return -1; }
+  if (!out->qacc && !out->qfrc_constraint && !out->qfrc_actuator && !out->contact_force && !out->contact_bit && !out->contact_frame &&
+      !out->contact_pos && !out->contact_dist && !out->contact_mask && !out->status) return 0;
+  KM_ENTER(h);
+  kmanip_launch_forces(h->dmodel, h->desc, h->st, *out, (hipStream_t)stream);
   HIPCHK(h, hipGetLastError());
   return 0;
 }

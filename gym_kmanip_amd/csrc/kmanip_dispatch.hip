@@ -17,6 +17,12 @@ void kmanip_launch_prepare_10_16_1(KDeviceModel*, hipStream_t);
 void kmanip_launch_prepare_20_32_1(KDeviceModel*, hipStream_t);
 void kmanip_launch_observe_20_32_1(const KDeviceModel*, const KDeviceState&, double*, double*, hipStream_t);
 
+// kmanip_forces.hip: the Newton classes, default and per-env parameter builds
+void kmanip_launch_forces_10_16(const KDeviceModel*, const KDeviceState&, const KForcesDev&, hipStream_t);
+void kmanip_launch_forces_20_32(const KDeviceModel*, const KDeviceState&, const KForcesDev&, hipStream_t);
+void kmanip_launch_forces_ep_10_16(const KDeviceModel*, const KDeviceState&, const KForcesDev&, hipStream_t);
+void kmanip_launch_forces_ep_20_32(const KDeviceModel*, const KDeviceState&, const KForcesDev&, hipStream_t);
+
 void kmanip_launch_step(const KDeviceModel* dm, const KModelDesc& hd, const KDeviceState& st, const float* act, double* obs, double* reward,
                         uint8_t* done, int nchunk, int epb, hipStream_t stream) {
   const bool newton = hd.solver == KM_SOLVER_NEWTON;
@@ -43,6 +49,10 @@ void kmanip_launch_observe(const KDeviceModel* dm, const KModelDesc& hd, const K
                            hipStream_t stream) {
   if (hd.nlink <= 10) kmanip_launch_observe_10_16_1(dm, st, obs, reward, stream);
   else kmanip_launch_observe_20_32_1(dm, st, obs, reward, stream);
+}
+void kmanip_launch_forces(const KDeviceModel* dm, const KModelDesc& hd, const KDeviceState& st, const KForcesDev& out, hipStream_t stream) {
+  if (st.envp) { if (hd.nlink <= 10) kmanip_launch_forces_ep_10_16(dm, st, out, stream); else kmanip_launch_forces_ep_20_32(dm, st, out, stream); }
+  else { if (hd.nlink <= 10) kmanip_launch_forces_10_16(dm, st, out, stream); else kmanip_launch_forces_20_32(dm, st, out, stream); }
 }
 void kmanip_launch_prepare_model(KDeviceModel* dm, const KModelDesc& hd, hipStream_t stream) {
   if (hd.nlink <= 10) kmanip_launch_prepare_10_16_1(dm, stream);

@@ -178,6 +178,52 @@ class KManipEnvHip:
                     "kmanip_observe")
         return obs, reward
 
+    # KForcesDev field -> (trailing shape in terms of nv / nu / nc = contact slots, dtype name)
+    _FORCE_FIELDS = {"qacc": (("nv",), "float64"), "qfrc_constraint": (("nv",), "float64"), "qfrc_actuator": (("nu",), "float64"),
+                     "contact_force": (("nc", 4), "float64"), "contact_bit": (("nc",), "int32"), "contact_frame": (("nc", 9), "float64"),
+                     "contact_pos": (("nc", 3), "float64"), "contact_dist": (("nc",), "float64"), "contact_mask": ((), "int32"),
+                     "status": ((), "uint8")}
+
+    def forces(self, out=None, fields=None):
+        """kmanip_forces: qacc, joint forces and contact forces of every env's CURRENT state (mj_forward with actuation; one launch
+        on the current stream, no synchronisation; the handle is only read).  Returns a dict of device tensors:
+          qacc, qfrc_constraint [n, nv]; qfrc_actuator [n, nu]; contact_force [n, NC, 4] (normal, tangent 1, tangent 2, torsion in
+          the contact frame); contact_bit [n, NC] int32 (KM_CON_* bit index of the pair in the slot, -1 = empty); contact_frame
+          [n, NC, 9]; contact_pos [n, NC, 3]; contact_dist [n, NC]; contact_mask [n] int32 (the uint32 mask's bits); status [n] uint8
+        NC = model.contact_slots(nlink).  `fields`: the names wanted (default: all); `out`: a dict of such tensors to fill -- only
+        the fields it names are computed -- returned as given.  Newton handles only."""
+        torch = _torch()
+        from .model import contact_slots
+        dims = {"nv": self.cm.nv, "nu": self.cm.nu, "nc": contact_slots(self.cm.nlink)}
+        shapes = {name: ((self.num_envs,) + tuple(dims.get(d, d) for d in shp), getattr(torch, dt))
+                  for name, (shp, dt) in self._FORCE_FIELDS.items()}
+        names = list(out) if out is not None else list(shapes) if fields is None else list(fields)
+        unknown = set(names) - set(shapes)
+        if unknown:
+            raise ValueError("unknown force field(s) %s" % sorted(unknown))
+        if out is None:
+            out = {name: torch.empty(shapes[name][0], dtype=shapes[name][1], device=self.device) for name in names}
+        fd = _libmod.KForcesDev()
+        for name, t in out.items():
+            self._check_buf(t, shapes[name][0], shapes[name][1], name)
+            setattr(fd, name, t.data_ptr())
+        self._check(self.L.kmanip_forces(self.h, C.byref(fd), self._stream()), "kmanip_forces")
+        return out
+
+    def normal_by_bit(self, f):
+        """[n, 32] float64: the normal force of the contact at each KM_CON_* mask bit of a forces() result (it needs contact_force
+        and contact_bit), 0 where the bit is clear.  Device-side indexing only: no further C call."""
+        torch = _torch()
+        bit = f["contact_bit"].to(torch.int64)
+        normal = torch.where(bit >= 0, f["contact_force"][:, :, 0], torch.zeros((), dtype=torch.float64, device=self.device))
+        out = torch.zeros((self.num_envs, 32), dtype=torch.float64, device=self.device)
+        return out.scatter_add_(1, bit.clamp(min=0), normal)
+
+    def finger_force(self, f):
+        """[n, 2 * narm] float64: normal force of each finger sphere on the cube (the bits of KM_CON_FINGERS_CUBE) of a forces()
+        result."""
+        return self.normal_by_bit(f)[:, 8:8 + 2 * (self.cm.nlink // 10)]
+
     def step_chunk(self, acts, obs=None, reward=None, done=None):
         """K control steps in one launch (kmanip_step_chunk): acts float32 [K, num_envs, act_dim] on the device ->
         (obs [K, N, obs_dim] f64, reward [K, N] f64, done [K, N] u8).  Same results as K step_flat calls; self.obs /

@@ -150,7 +150,7 @@ class KManipEnv(_EnvBase):
                  squeeze: bool = False, env_id_offset: int = 0, device_outputs: bool = False,
                  log_h5py: bool = False, log_prefix: str = "test", log_env_ids=None, log_backend=None,
                  log_reference_layout: bool = False, log_h5py_module=None, domain_randomization=None, visual_randomization=None,
-                 segmentation: bool = False, render_links: bool = False, **overrides):
+                 segmentation: bool = False, render_links: bool = False, contact_forces: bool = False, **overrides):
         spec: EnvSpec = ENV_SPECS[env_id]
         self.env_id = env_id
         self.seed = seed
@@ -194,6 +194,11 @@ class KManipEnv(_EnvBase):
         self.render_links = bool(render_links)
         if self.render_links:
             self.env.set_render_links(True)
+        # contact_forces=True (not in the reference): after every reset and step, info["finger_force"] ([num_envs, 2 * arms]: normal
+        # force of each finger sphere on the cube) and info["qfrc_actuator"] ([num_envs, q_len]) of the new state, as DEVICE tensors
+        # (env_hip.forces: one more launch per step; live buffers, like the device observations)
+        self.contact_forces = bool(contact_forces)
+        self._forces = None                              # the three tensors the launch fills: allocated by the first call, then reused
         # domain_randomization={name: (lo, hi)} (env_hip.ENV_PARAMS names): every reset redraws those physics parameters per env
         if domain_randomization:
             self.env.set_env_param_ranges(**domain_randomization)
@@ -257,6 +262,11 @@ class KManipEnv(_EnvBase):
             out[k] = a[0] if self.squeeze else a
         return out
 
+    def _force_info(self):
+        if self.contact_forces:
+            f = self._forces = self.env.forces(out=self._forces, fields=("contact_force", "contact_bit", "qfrc_actuator"))
+            self.info.update(finger_force=self.env.finger_force(f), qfrc_actuator=f["qfrc_actuator"])
+
     # ------------------------------------------------------------------ gym API
     def reset(self, seed=None, options=None):
         """env_base.py:219-239.  reset(seed=s) re-keys the cube-spawn stream and restarts its episode counter, so two resets
@@ -273,6 +283,7 @@ class KManipEnv(_EnvBase):
         self.episode_idx += 1
         self.info.update(step=self.step_idx, episode=self.episode_idx, sim_time=sim_time, cpu_time=time.time(),
                          reward=reward, is_success=False, terminated=False)
+        self._force_info()
         return self._observation(observation), self.info
 
     def step(self, action):
@@ -283,6 +294,7 @@ class KManipEnv(_EnvBase):
         self.step_idx += 1
         trunc_now = self.step_idx >= MAX_EPISODE_STEPS                              # TimeLimit wrapper
         obs_out = self._observation(observation)
+        self._force_info()
         if self.logger is not None:
             self._log_step(action, self._obs_dev)
         if self.device_outputs:

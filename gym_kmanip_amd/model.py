@@ -614,6 +614,11 @@ def draw_visual_params(seed: int, genv: int, episode: int, lo, hi) -> np.ndarray
     return out
 
 
+def contact_slots(nlink: int) -> int:
+    """include/kmanip.h KM_CONTACT_SLOTS: 4 cube corners + KM_SPHERE_SLOTS sphere-cube + KM_SPHERE_TABLE_SLOTS sphere-table (8 / 14)."""
+    return 4 + 2 * (nlink // 10) + (6 if nlink >= 20 else 2)
+
+
 # ---- segmentation labels of the camera renders (include/kmanip.h KM_SEG_*, DESIGN.md section 13)
 KM_SEG_BACKGROUND, KM_SEG_TABLE, KM_SEG_CUBE, KM_SEG_ROBOT_R, KM_SEG_ROBOT_L, KM_SEG_N = 0, 1, 2, 3, 4, 5
 SEG_CLASSES = ("background", "table", "cube", "robot_r", "robot_l")

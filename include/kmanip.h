@@ -341,6 +341,42 @@ KMANIP_API int kmanip_select_reward_done_record(KHandle h, int index);
  * reference's own Python (tests/golden/ref_obs_*.npz) and by callers that restore a checkpoint with kmanip_set_state. */
 KMANIP_API int kmanip_observe(KHandle h, double* obs_dev, double* reward_dev, void* stream);
 
+/* Contact forces, qacc and joint forces of every env's CURRENT state: mj_forward with actuation at the env's
+ * (qpos, qvel, ctrl) -- what dm_control's physics.forward() followed by data.qacc, data.qfrc_constraint, data.qfrc_actuator and
+ * mj_contactForce of every contact gives.  nv = nlink + 6, nu = nlink, NC = KM_CONTACT_SLOTS(nlink).
+ * All pointers are DEVICE pointers, env-major; any may be NULL (that field is skipped). */
+#define KM_CONTACT_SLOTS(nlink) (4 + KM_SPHERE_SLOTS(nlink) + KM_SPHERE_TABLE_SLOTS(nlink))   /* 8 / 14 */
+typedef struct KForcesDev {
+  double*   qacc;             /* [n, nv] */
+  double*   qfrc_constraint;  /* [n, nv]  = M (qacc - qacc_smooth): the joint-space sum of every constraint force (contacts, limits, friction loss) */
+  double*   qfrc_actuator;    /* [n, nu]  clamped servo force, per-env kp scale honoured */
+  double*   contact_force;    /* [n, NC, 4] normal, tangent 1, tangent 2, torsion, in the contact frame; condim-3 pair: torsion 0 */
+  int32_t*  contact_bit;      /* [n, NC]  the KM_CON_* bit index (0..31) of the pair in this slot, -1 = empty slot (its other fields 0) */
+  double*   contact_frame;    /* [n, NC, 9] rows normal, t1, t2 (world) */
+  double*   contact_pos;      /* [n, NC, 3] */
+  double*   contact_dist;     /* [n, NC] */
+  uint32_t* contact_mask;     /* [n] */
+  uint8_t*  status;           /* [n] 0 ok; 1 = non-finite state or failed factorisation / bad qacc: every other output of the env is 0
+                               *     and every slot empty (contact_bit -1) */
+} KForcesDev;
+/* ONE kernel launch, asynchronous on `stream`: no allocation, no synchronisation, no host copy.  Enqueued after a kmanip_step on the
+ * same stream it sees that step's result.
+ * SIGN: the frame normal points from the first body of the pair to the second -- table -> cube, link -> cube, table -> link.  The force
+ * acts on the second body along +frame and on the first with the opposite sign: the net contact force on the cube in the world frame
+ * is the sum of F0 n + F1 t1 + F2 t2 over the slots whose bit is a cube pair (KM_CON_ANY_CUBE_TABLE | KM_CON_ANY_SPHERE_CUBE).
+ * A slot's four numbers are the sums of its pyramid-edge forces along its basis rows (mj_contactForce): F0 >= 0, |F1|, |F2| <= mu F0,
+ * |F3| <= mu_torsion F0.
+ * SLOT ORDER: only the kinds are fixed -- 4 cube-corner slots, then KM_SPHERE_SLOTS sphere-cube, then KM_SPHERE_TABLE_SLOTS
+ * sphere-table; contact_bit says who sits where, and callers index by bit.  The occupied slots are exactly the bits of contact_mask.
+ * INPUTS: ctrl is used exactly as stored (the float32 rounding that starts kmanip_step's before_step is not applied); the stored
+ * qacc_warm is the solver's starting point.  After an auto-reset the forces are those of the new episode's first state.  Per-env
+ * parameters (KM_EP_*) are honoured, explicit and ranges mode alike.
+ * THE HANDLE IS READ ONLY: state, warm start, counters, the contact masks kmanip_get_diag returns, scheduling predictors, sim time and
+ * random streams stay bit for bit as they were; a step after the call is the step without it.
+ * ERRORS: a NULL handle, a NULL `out` or a handle whose solver is KM_SOLVER_PGS ("contact forces need the Newton solver") return
+ * nonzero with kmanip_last_error set and launch nothing.  Every field NULL: the call succeeds and does nothing. */
+KMANIP_API int kmanip_forces(KHandle h, const KForcesDev* out, void* stream);
+
 /* KManipEnv.reset(seed=...) (env_base.py:219-220): re-key the cube-spawn stream.  restart_episodes != 0 also rewinds every
  * env's episode counter so that the next kmanip_reset draws episode 0 of the new seed (reset(seed=s) is then reproducible). */
 KMANIP_API int kmanip_set_seed(KHandle h, uint64_t seed, int restart_episodes);
