@@ -14,7 +14,7 @@
 
 #include "kmanip_device.hpp"
 
-#define KM_VERSION "kmanip-hip 0.35 (gfx950, f64)"
+#define KM_VERSION "kmanip-hip 0.36 (gfx950, f64)"
 
 static thread_local std::string g_create_error;
 
@@ -460,6 +460,19 @@ int kmanip_forces(KHandle h, const KForcesDev* out, void* stream) {
       !out->contact_pos && !out->contact_dist && !out->contact_mask && !out->status) return 0;
   KM_ENTER(h);
   kmanip_launch_forces(h->dmodel, h->desc, h->st, *out, (hipStream_t)stream);
+  HIPCHK(h, hipGetLastError());
+  return 0;
+}
+
+// link and site poses, site Jacobians, M and bias forces of every env's current state (include/kmanip.h KKinDev;
+// kmanip_kinematics.hip).  One launch; the handle is only read; either solver.
+int kmanip_kinematics(KHandle h, const KKinDev* out, void* stream) {
+  if (!h) { g_create_error = "kmanip_kinematics: null handle"; return -1; }
+  if (!out) { h->err = "kmanip_kinematics: the KKinDev pointer is NULL"; return -1; }
+  if (!out->link_xpos && !out->link_xmat && !out->site_xpos && !out->site_xmat && !out->site_jacp && !out->site_jacr && !out->site_vel &&
+      !out->qM && !out->qfrc_bias && !out->status) return 0;
+  KM_ENTER(h);
+  kmanip_launch_kinematics(h->dmodel, h->desc, h->st, *out, (hipStream_t)stream);
   HIPCHK(h, hipGetLastError());
   return 0;
 }

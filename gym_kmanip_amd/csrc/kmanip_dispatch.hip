@@ -23,6 +23,12 @@ void kmanip_launch_forces_20_32(const KDeviceModel*, const KDeviceState&, const 
 void kmanip_launch_forces_ep_10_16(const KDeviceModel*, const KDeviceState&, const KForcesDev&, hipStream_t);
 void kmanip_launch_forces_ep_20_32(const KDeviceModel*, const KDeviceState&, const KForcesDev&, hipStream_t);
 
+// kmanip_kinematics.hip: one object per class serves both solvers, default and per-env parameter builds
+void kmanip_launch_kinematics_10_16(const KDeviceModel*, const KDeviceState&, const KKinDev&, hipStream_t);
+void kmanip_launch_kinematics_20_32(const KDeviceModel*, const KDeviceState&, const KKinDev&, hipStream_t);
+void kmanip_launch_kinematics_ep_10_16(const KDeviceModel*, const KDeviceState&, const KKinDev&, hipStream_t);
+void kmanip_launch_kinematics_ep_20_32(const KDeviceModel*, const KDeviceState&, const KKinDev&, hipStream_t);
+
 void kmanip_launch_step(const KDeviceModel* dm, const KModelDesc& hd, const KDeviceState& st, const float* act, double* obs, double* reward,
                         uint8_t* done, int nchunk, int epb, hipStream_t stream) {
   const bool newton = hd.solver == KM_SOLVER_NEWTON;
@@ -53,6 +59,10 @@ void kmanip_launch_observe(const KDeviceModel* dm, const KModelDesc& hd, const K
 void kmanip_launch_forces(const KDeviceModel* dm, const KModelDesc& hd, const KDeviceState& st, const KForcesDev& out, hipStream_t stream) {
   if (st.envp) { if (hd.nlink <= 10) kmanip_launch_forces_ep_10_16(dm, st, out, stream); else kmanip_launch_forces_ep_20_32(dm, st, out, stream); }
   else { if (hd.nlink <= 10) kmanip_launch_forces_10_16(dm, st, out, stream); else kmanip_launch_forces_20_32(dm, st, out, stream); }
+}
+void kmanip_launch_kinematics(const KDeviceModel* dm, const KModelDesc& hd, const KDeviceState& st, const KKinDev& out, hipStream_t stream) {
+  if (st.envp) { if (hd.nlink <= 10) kmanip_launch_kinematics_ep_10_16(dm, st, out, stream); else kmanip_launch_kinematics_ep_20_32(dm, st, out, stream); }
+  else { if (hd.nlink <= 10) kmanip_launch_kinematics_10_16(dm, st, out, stream); else kmanip_launch_kinematics_20_32(dm, st, out, stream); }
 }
 void kmanip_launch_prepare_model(KDeviceModel* dm, const KModelDesc& hd, hipStream_t stream) {
   if (hd.nlink <= 10) kmanip_launch_prepare_10_16_1(dm, stream);

@@ -224,6 +224,44 @@ class KManipEnvHip:
         result."""
         return self.normal_by_bit(f)[:, 8:8 + 2 * (self.cm.nlink // 10)]
 
+    # KKinDev field -> (trailing shape in terms of nl = links, nv, na = KM_MAX_ARMS, dtype name)
+    _KIN_FIELDS = {"link_xpos": (("nl", 3), "float64"), "link_xmat": (("nl", 9), "float64"), "site_xpos": (("na", 3), "float64"),
+                   "site_xmat": (("na", 9), "float64"), "site_jacp": (("na", 3, "nv"), "float64"), "site_jacr": (("na", 3, "nv"), "float64"),
+                   "site_vel": (("na", 6), "float64"), "qM": (("nv", "nv"), "float64"), "qfrc_bias": (("nv",), "float64"),
+                   "status": ((), "uint8")}
+
+    def kinematics(self, out=None, fields=None):
+        """kmanip_kinematics: link and site poses, site Jacobians, joint-space inertia and bias forces of every env's CURRENT state
+        (one launch on the current stream, no synchronisation; the handle is only read; either solver).  Returns a dict of device
+        tensors:
+          link_xpos [n, nlink, 3], link_xmat [n, nlink, 9] (MuJoCo's data.xpos / data.xmat of the link bodies); site_xpos [n, 2, 3],
+          site_xmat [n, 2, 9] (arm 0 = right; an absent arm: zeros); site_jacp, site_jacr [n, 2, 3, nv] (mj_jacSite, all nv columns);
+          site_vel [n, 2, 6] (jacp qvel, jacr qvel); qM [n, nv, nv] (mj_fullM, cube block diag(m, m, m, I)); qfrc_bias [n, nv];
+          status [n] uint8 (1: non-finite state, everything else of the env 0)
+        `fields`: the names wanted (default: all); `out`: a dict of such tensors to fill -- only the fields it names are computed --
+        returned as given."""
+        torch = _torch()
+        dims = {"nl": self.cm.nlink, "nv": self.cm.nv, "na": 2}
+        shapes = {name: ((self.num_envs,) + tuple(dims.get(d, d) for d in shp), getattr(torch, dt))
+                  for name, (shp, dt) in self._KIN_FIELDS.items()}
+        names = list(out) if out is not None else list(shapes) if fields is None else list(fields)
+        unknown = set(names) - set(shapes)
+        if unknown:
+            raise ValueError("unknown kinematics field(s) %s" % sorted(unknown))
+        if out is None:
+            out = {name: torch.empty(shapes[name][0], dtype=shapes[name][1], device=self.device) for name in names}
+        kd = _libmod.KKinDev()
+        for name, t in out.items():
+            self._check_buf(t, shapes[name][0], shapes[name][1], name)
+            setattr(kd, name, t.data_ptr())
+        self._check(self.L.kmanip_kinematics(self.h, C.byref(kd), self._stream()), "kmanip_kinematics")
+        return out
+
+    def site_jacobian(self, k, arm):
+        """[n, 6, nv] float64: the 6 x nv site Jacobian of `arm` (0 = right) from a kinematics() result (it needs site_jacp and
+        site_jacr), jacp over jacr: one cat, no further C call."""
+        return _torch().cat((k["site_jacp"][:, arm], k["site_jacr"][:, arm]), dim=1)
+
     def step_chunk(self, acts, obs=None, reward=None, done=None):
         """K control steps in one launch (kmanip_step_chunk): acts float32 [K, num_envs, act_dim] on the device ->
         (obs [K, N, obs_dim] f64, reward [K, N] f64, done [K, N] u8).  Same results as K step_flat calls; self.obs /

@@ -150,7 +150,8 @@ class KManipEnv(_EnvBase):
                  squeeze: bool = False, env_id_offset: int = 0, device_outputs: bool = False,
                  log_h5py: bool = False, log_prefix: str = "test", log_env_ids=None, log_backend=None,
                  log_reference_layout: bool = False, log_h5py_module=None, domain_randomization=None, visual_randomization=None,
-                 segmentation: bool = False, render_links: bool = False, contact_forces: bool = False, **overrides):
+                 segmentation: bool = False, render_links: bool = False, contact_forces: bool = False, ee_pose: bool = False,
+                 **overrides):
         spec: EnvSpec = ENV_SPECS[env_id]
         self.env_id = env_id
         self.seed = seed
@@ -199,6 +200,11 @@ class KManipEnv(_EnvBase):
         # (env_hip.forces: one more launch per step; live buffers, like the device observations)
         self.contact_forces = bool(contact_forces)
         self._forces = None                              # the three tensors the launch fills: allocated by the first call, then reused
+        # ee_pose=True (not in the reference): after every reset and step, info["site_xpos"] ([num_envs, 2, 3]) and info["site_xmat"]
+        # ([num_envs, 2, 9]) of the new state -- the eer / eel site poses, arm 0 = right -- as float64 DEVICE tensors
+        # (env_hip.kinematics: one more launch per step; live buffers, like the device observations)
+        self.ee_pose = bool(ee_pose)
+        self._kin = None                                 # the two tensors the launch fills: allocated by the first call, then reused
         # domain_randomization={name: (lo, hi)} (env_hip.ENV_PARAMS names): every reset redraws those physics parameters per env
         if domain_randomization:
             self.env.set_env_param_ranges(**domain_randomization)
@@ -266,6 +272,9 @@ class KManipEnv(_EnvBase):
         if self.contact_forces:
             f = self._forces = self.env.forces(out=self._forces, fields=("contact_force", "contact_bit", "qfrc_actuator"))
             self.info.update(finger_force=self.env.finger_force(f), qfrc_actuator=f["qfrc_actuator"])
+        if self.ee_pose:
+            k = self._kin = self.env.kinematics(out=self._kin, fields=("site_xpos", "site_xmat"))
+            self.info.update(site_xpos=k["site_xpos"], site_xmat=k["site_xmat"])
 
     # ------------------------------------------------------------------ gym API
     def reset(self, seed=None, options=None):

@@ -377,6 +377,46 @@ typedef struct KForcesDev {
  * nonzero with kmanip_last_error set and launch nothing.  Every field NULL: the call succeeds and does nothing. */
 KMANIP_API int kmanip_forces(KHandle h, const KForcesDev* out, void* stream);
 
+/* Link and site poses, site Jacobians, joint-space inertia and bias forces of every env's CURRENT state: what a
+ * dm_control user reads off physics.data after physics.forward() -- data.xpos / data.xmat of the link bodies, site("eer_site_pos").xpos
+ * / .xmat (examples/2_synthetic_data.py:34, env_sim.py:63-90), mj_jacSite (ik_mujoco.py:74), mj_fullM and data.qfrc_bias.
+ * nlink = KModelDesc::nlink, nv = nlink + 6 (the cube's six dofs last).  All pointers are DEVICE pointers, env-major; any may be NULL
+ * (that field is skipped). */
+typedef struct KKinDev {
+  double*  link_xpos;   /* [n, nlink, 3]  MuJoCo data.xpos of the link bodies                        */
+  double*  link_xmat;   /* [n, nlink, 9]  data.xmat, row-major                                       */
+  double*  site_xpos;   /* [n, KM_MAX_ARMS, 3]  eer / eel site (arm 0 = right); absent arm: zeros    */
+  double*  site_xmat;   /* [n, KM_MAX_ARMS, 9]                                                       */
+  double*  site_jacp;   /* [n, KM_MAX_ARMS, 3, nv]  mj_jacSite, world frame, all nv columns          */
+  double*  site_jacr;   /* [n, KM_MAX_ARMS, 3, nv]                                                   */
+  double*  site_vel;    /* [n, KM_MAX_ARMS, 6]  jacp qvel, then jacr qvel (world frame)              */
+  double*  qM;          /* [n, nv, nv]  dense joint-space inertia (mj_fullM), cube block included    */
+  double*  qfrc_bias;   /* [n, nv]      Coriolis + centrifugal + gravity, cube rows included         */
+  uint8_t* status;      /* [n] 0 ok; 1 = non-finite qpos/qvel: every other output of the env is 0    */
+} KKinDev;
+/* LAUNCH: ONE kernel launch, asynchronous on `stream`: no allocation, no synchronisation, no host copy.  Enqueued after a kmanip_step
+ * on the same stream it sees that step's result.
+ * INPUTS: the stored qpos and qvel as they are.  ctrl and the warm start have no influence on any output.
+ * PER-ENV PARAMETERS (KM_EP_*) are honoured, explicit and ranges mode alike: the cube's mass and inertia enter qM's cube block and the
+ * cube rows of qfrc_bias (nothing else here depends on a parameter).
+ * BOTH SOLVERS: nothing here depends on the solver; a KM_SOLVER_PGS handle is served (unlike kmanip_forces) and returns the bits a
+ * Newton handle returns.
+ * JACOBIANS: column j is non-zero only for the dofs of links that are ancestor-or-self of arm_site_link[a] -- all of them, not only
+ * arm_q_id[a] (the Torso's sites sit on the hand joints 10 / 19, which the IK does not move).  Hinge j: axis_j x (site - xpos_j) in jacp and axis_j in jacr; slide j:
+ * axis_j in jacp and 0 in jacr (axis_j the joint's axis in the world frame).  Every other column, the six cube columns included, is
+ * exactly 0.0; so is everything of an absent arm.  site_vel = [jacp qvel, jacr qvel].
+ * qM: bitwise symmetric, exact zeros between the two arms' trees and between robot and cube; cube block = diag(m, m, m, I0, I1, I2)
+ * (the cube's angular velocity is expressed in its body frame, MuJoCo's free-joint convention).  The operational-space inertia is
+ * not computed: callers form (J M^-1 J^T)^-1 from these tensors.
+ * qfrc_bias: what MuJoCo's mj_rne gives without acceleration; M qacc + qfrc_bias = qfrc_actuator (padded with six zeros) +
+ * qfrc_constraint with the tensors of kmanip_forces.
+ * THE HANDLE IS READ ONLY: nothing of the handle's state is written (state, warm start, counters, contact masks, scheduling
+ * predictors, sim time, random streams); a step after the call is the step without it.
+ * ERRORS: a NULL handle or a NULL `out` return nonzero with kmanip_last_error set and launch nothing.  Every field NULL: the call
+ * succeeds and does nothing.
+ * OUT OF SCOPE: env subsets, render snapshots, centre-of-mass Jacobians. */
+KMANIP_API int kmanip_kinematics(KHandle h, const KKinDev* out, void* stream);
+
 /* KManipEnv.reset(seed=...) (env_base.py:219-220): re-key the cube-spawn stream.  restart_episodes != 0 also rewinds every
  * env's episode counter so that the next kmanip_reset draws episode 0 of the new seed (reset(seed=s) is then reproducible). */
 KMANIP_API int kmanip_set_seed(KHandle h, uint64_t seed, int restart_episodes);
