@@ -14,7 +14,7 @@
 
 #include "kmanip_device.hpp"
 
-#define KM_VERSION "kmanip-hip 0.36 (gfx950, f64)"
+#define KM_VERSION "kmanip-hip 0.37 (gfx950, f64)"
 
 static thread_local std::string g_create_error;
 
@@ -875,6 +875,12 @@ int kmanip_set_episode(KHandle h, const int32_t* episode) {
 int kmanip_bind_sim_time(KHandle h, double* sim_time_dev) {
   if (!h) return -1;
   h->st.sim_time = sim_time_dev;
+  return 0;
+}
+
+int kmanip_bind_applied_force(KHandle h, const double* qfrc_dev) {
+  if (!h) return -1;
+  h->st.qfrc_applied = qfrc_dev;
   return 0;
 }
 

@@ -553,6 +553,10 @@ struct KDeviceState {
   int num_envs;
   int64_t env_id_offset;
   uint64_t seed;
+  // kmanip_bind_applied_force: caller-owned double[N][nv], ENV-major (MuJoCo's data.qfrc_applied), NULL = none (the default kernels).
+  // Read only by the KM_VAR_FRC kernels (k_step_frc, k_step_ep_frc, k_frc_forces, k_frc_forces_ep), once per launch; the last field, so that no other field's
+  // offset in the kernel argument moves.
+  const double* qfrc_applied;
 };
 
 // fills dm->staged (device memory) for the model's link-count class; kmanip_create, once

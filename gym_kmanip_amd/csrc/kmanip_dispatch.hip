@@ -12,6 +12,12 @@ KM_DECL(10, 16, 0) KM_DECL(10, 16, 1) KM_DECL(20, 32, 0) KM_DECL(20, 32, 1)
   void kmanip_launch_reset_ep_##NL##_##G##_##S(const KDeviceModel*, const KDeviceState&, const uint8_t*, double*, int, hipStream_t);
 KM_DECL(10, 16, 0) KM_DECL(10, 16, 1) KM_DECL(20, 32, 0) KM_DECL(20, 32, 1)
 #undef KM_DECL
+// the applied-force builds (kmanip_dyn.hip KM_VAR_FRC, with and without KM_VAR_PAR): launched while KDeviceState::qfrc_applied is set
+#define KM_DECL(NL, G, S)                                                                                          \
+  void kmanip_launch_step_frc_##NL##_##G##_##S(const KDeviceModel*, const KDeviceState&, const float*, double*, double*, uint8_t*, int, int, hipStream_t); \
+  void kmanip_launch_step_ep_frc_##NL##_##G##_##S(const KDeviceModel*, const KDeviceState&, const float*, double*, double*, uint8_t*, int, int, hipStream_t);
+KM_DECL(10, 16, 0) KM_DECL(10, 16, 1) KM_DECL(20, 32, 0) KM_DECL(20, 32, 1)
+#undef KM_DECL
 void kmanip_launch_observe_10_16_1(const KDeviceModel*, const KDeviceState&, double*, double*, hipStream_t);
 void kmanip_launch_prepare_10_16_1(KDeviceModel*, hipStream_t);
 void kmanip_launch_prepare_20_32_1(KDeviceModel*, hipStream_t);
@@ -22,6 +28,10 @@ void kmanip_launch_forces_10_16(const KDeviceModel*, const KDeviceState&, const 
 void kmanip_launch_forces_20_32(const KDeviceModel*, const KDeviceState&, const KForcesDev&, hipStream_t);
 void kmanip_launch_forces_ep_10_16(const KDeviceModel*, const KDeviceState&, const KForcesDev&, hipStream_t);
 void kmanip_launch_forces_ep_20_32(const KDeviceModel*, const KDeviceState&, const KForcesDev&, hipStream_t);
+void kmanip_launch_forces_frc_10_16(const KDeviceModel*, const KDeviceState&, const KForcesDev&, hipStream_t);
+void kmanip_launch_forces_frc_20_32(const KDeviceModel*, const KDeviceState&, const KForcesDev&, hipStream_t);
+void kmanip_launch_forces_ep_frc_10_16(const KDeviceModel*, const KDeviceState&, const KForcesDev&, hipStream_t);
+void kmanip_launch_forces_ep_frc_20_32(const KDeviceModel*, const KDeviceState&, const KForcesDev&, hipStream_t);
 
 // kmanip_kinematics.hip: one object per class serves both solvers, default and per-env parameter builds
 void kmanip_launch_kinematics_10_16(const KDeviceModel*, const KDeviceState&, const KKinDev&, hipStream_t);
@@ -32,6 +42,16 @@ void kmanip_launch_kinematics_ep_20_32(const KDeviceModel*, const KDeviceState&,
 void kmanip_launch_step(const KDeviceModel* dm, const KModelDesc& hd, const KDeviceState& st, const float* act, double* obs, double* reward,
                         uint8_t* done, int nchunk, int epb, hipStream_t stream) {
   const bool newton = hd.solver == KM_SOLVER_NEWTON;
+  if (st.qfrc_applied && st.envp) {
+    if (hd.nlink <= 10) { if (newton) kmanip_launch_step_ep_frc_10_16_1(dm, st, act, obs, reward, done, nchunk, epb, stream); else kmanip_launch_step_ep_frc_10_16_0(dm, st, act, obs, reward, done, nchunk, epb, stream); }
+    else { if (newton) kmanip_launch_step_ep_frc_20_32_1(dm, st, act, obs, reward, done, nchunk, epb, stream); else kmanip_launch_step_ep_frc_20_32_0(dm, st, act, obs, reward, done, nchunk, epb, stream); }
+    return;
+  }
+  if (st.qfrc_applied) {
+    if (hd.nlink <= 10) { if (newton) kmanip_launch_step_frc_10_16_1(dm, st, act, obs, reward, done, nchunk, epb, stream); else kmanip_launch_step_frc_10_16_0(dm, st, act, obs, reward, done, nchunk, epb, stream); }
+    else { if (newton) kmanip_launch_step_frc_20_32_1(dm, st, act, obs, reward, done, nchunk, epb, stream); else kmanip_launch_step_frc_20_32_0(dm, st, act, obs, reward, done, nchunk, epb, stream); }
+    return;
+  }
   if (st.envp) {
     if (hd.nlink <= 10) { if (newton) kmanip_launch_step_ep_10_16_1(dm, st, act, obs, reward, done, nchunk, epb, stream); else kmanip_launch_step_ep_10_16_0(dm, st, act, obs, reward, done, nchunk, epb, stream); }
     else { if (newton) kmanip_launch_step_ep_20_32_1(dm, st, act, obs, reward, done, nchunk, epb, stream); else kmanip_launch_step_ep_20_32_0(dm, st, act, obs, reward, done, nchunk, epb, stream); }
@@ -57,7 +77,9 @@ void kmanip_launch_observe(const KDeviceModel* dm, const KModelDesc& hd, const K
   else kmanip_launch_observe_20_32_1(dm, st, obs, reward, stream);
 }
 void kmanip_launch_forces(const KDeviceModel* dm, const KModelDesc& hd, const KDeviceState& st, const KForcesDev& out, hipStream_t stream) {
-  if (st.envp) { if (hd.nlink <= 10) kmanip_launch_forces_ep_10_16(dm, st, out, stream); else kmanip_launch_forces_ep_20_32(dm, st, out, stream); }
+  if (st.qfrc_applied && st.envp) { if (hd.nlink <= 10) kmanip_launch_forces_ep_frc_10_16(dm, st, out, stream); else kmanip_launch_forces_ep_frc_20_32(dm, st, out, stream); }
+  else if (st.qfrc_applied) { if (hd.nlink <= 10) kmanip_launch_forces_frc_10_16(dm, st, out, stream); else kmanip_launch_forces_frc_20_32(dm, st, out, stream); }
+  else if (st.envp) { if (hd.nlink <= 10) kmanip_launch_forces_ep_10_16(dm, st, out, stream); else kmanip_launch_forces_ep_20_32(dm, st, out, stream); }
   else { if (hd.nlink <= 10) kmanip_launch_forces_10_16(dm, st, out, stream); else kmanip_launch_forces_20_32(dm, st, out, stream); }
 }
 void kmanip_launch_kinematics(const KDeviceModel* dm, const KModelDesc& hd, const KDeviceState& st, const KKinDev& out, hipStream_t stream) {

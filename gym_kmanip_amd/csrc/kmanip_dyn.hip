@@ -38,7 +38,21 @@
 #ifndef KM_VAR_PAR
 #define KM_VAR_PAR 0
 #endif
-#if KM_VAR_PAR
+// KM_VAR_FRC=1: the applied-force build (kmanip_bind_applied_force), orthogonal to KM_VAR_PAR and built by the
+// same rule: a third and a fourth compilation per variant, kernels k_step_frc / k_step_ep_frc in namespaces of their own, launched
+// only while a handle has a force buffer bound.  Step kernels only: a reset never reads the buffer.
+#ifndef KM_VAR_FRC
+#define KM_VAR_FRC 0
+#endif
+#if KM_VAR_PAR && KM_VAR_FRC
+namespace km_envp_frc {
+#define KM_K_STEP k_step_ep_frc
+#define KM_K_RESET k_reset_ep_frc     // (never instantiated)
+#elif KM_VAR_FRC
+namespace km_frc {
+#define KM_K_STEP k_step_frc
+#define KM_K_RESET k_reset_frc        // (never instantiated)
+#elif KM_VAR_PAR
 namespace km_envp {
 #define KM_K_STEP k_step_ep           // (kernel names of their own: profiles and tools/kernel_resources.py tell the builds apart)
 #define KM_K_RESET k_reset_ep
@@ -121,6 +135,9 @@ __global__ __launch_bounds__(64) void KM_K_STEP(const KDeviceModel* __restrict__
   ep_load<NL>(w, dm, st, env, sub, invm);       // (after the diagnostic poisoning above: Ws::ep is part of the workspace)
 #endif
   load_state<NL, G>(w, st, env, sub);
+#if KM_VAR_FRC
+  const int frc_bad = load_applied<NL, G>(w, st, env, sub);      // (a chunk holds the row for all its steps)
+#endif
   int step_idx = st.step_idx[env], episode = st.episode[env];
   const size_t NE = (size_t)st.num_envs;
   GSYNC();
@@ -154,9 +171,16 @@ __global__ __launch_bounds__(64) void KM_K_STEP(const KDeviceModel* __restrict__
   }
   GSYNC();
   pf.ph(30);
+#if KM_VAR_FRC
+  // a non-finite applied force: the env counts as diverged for this step before a sub-step starts
+  int bad = frc_bad;
+  spread_next = 0;
+  const int nsub = frc_bad ? 0 : m->n_sub_steps;
+#else
   int bad = 0;
   spread_next = 0;
   const int nsub = m->n_sub_steps;
+#endif
   for (int s = 0; s < nsub; s++) {
     // the lane's dof index, opaque to the optimiser once per sub-step: everything derived from it (LDS addresses, per-link
     // constants, masks) is recomputed inside the sub-step instead of being hoisted out of this loop and kept alive -- or
@@ -340,7 +364,15 @@ static void launch_observe_t(const KDeviceModel* dm, const KDeviceState& st, dou
   constexpr int EPB = 64 / G;
   hipLaunchKernelGGL((k_observe<NL, G, EPB>), dim3((st.num_envs + EPB - 1) / EPB), dim3(64), 0, stream, dm, st, obs, reward);
 }
-#if KM_VAR_PAR
+#if KM_VAR_PAR && KM_VAR_FRC
+}  // namespace km_envp_frc
+using namespace km_envp_frc;
+#define KM_LAUNCH_STEP kmanip_launch_step_ep_frc_
+#elif KM_VAR_FRC
+}  // namespace km_frc
+using namespace km_frc;
+#define KM_LAUNCH_STEP kmanip_launch_step_frc_
+#elif KM_VAR_PAR
 }  // namespace km_envp
 using namespace km_envp;
 #define KM_LAUNCH_STEP kmanip_launch_step_ep_
@@ -349,7 +381,7 @@ using namespace km_envp;
 #define KM_LAUNCH_STEP kmanip_launch_step_
 #define KM_LAUNCH_RESET kmanip_launch_reset_
 #endif
-// ---- one (NL, G, SOLVER[, PAR]) variant per translation unit (the Makefile compiles this file eight times, in parallel)
+// ---- one (NL, G, SOLVER[, PAR][, FRC]) variant per translation unit (the Makefile compiles this file sixteen times, in parallel)
 #ifndef KM_VAR_NL
 #error "compile with -DKM_VAR_NL=<10|20> -DKM_VAR_G=<16|32> -DKM_VAR_SOLVER=<0|1>"
 #endif
@@ -360,11 +392,13 @@ void KM_CAT4(KM_LAUNCH_STEP, KM_VAR_NL, KM_VAR_G, KM_VAR_SOLVER)(const KDeviceMo
                                                                     hipStream_t stream) {
   launch_step_t<KM_VAR_NL, KM_VAR_G, KM_VAR_SOLVER>(dm, st, act, obs, reward, done, nchunk, epb, stream);
 }
+#if !KM_VAR_FRC      // (a reset ignores the applied force: the force builds have no reset kernel)
 void KM_CAT4(KM_LAUNCH_RESET, KM_VAR_NL, KM_VAR_G, KM_VAR_SOLVER)(const KDeviceModel* dm, const KDeviceState& st,
                                                                      const uint8_t* mask, double* obs, int epb, hipStream_t stream) {
   launch_reset_t<KM_VAR_NL, KM_VAR_G, KM_VAR_SOLVER>(dm, st, mask, obs, epb, stream);
 }
-#if KM_VAR_SOLVER == 1 && !KM_VAR_PAR      // (solver-independent: one copy per link-count class)
+#endif
+#if KM_VAR_SOLVER == 1 && !KM_VAR_PAR && !KM_VAR_FRC      // (solver-independent: one copy per link-count class)
 void KM_CAT4(kmanip_launch_prepare_, KM_VAR_NL, KM_VAR_G, KM_VAR_SOLVER)(KDeviceModel* dm, hipStream_t stream) {
   hipLaunchKernelGGL((k_prepare_model<KM_VAR_NL>), dim3(1), dim3(64), 0, stream, dm);
 }
@@ -375,7 +409,7 @@ void KM_CAT4(kmanip_launch_observe_, KM_VAR_NL, KM_VAR_G, KM_VAR_SOLVER)(const K
 #endif
 // ---- KM_PROFILE builds: host accessors of the phase accumulators (g_prof, kmanip_device.hpp)
 #ifdef KM_PROFILE
-#if KM_VAR_NL == 10 && KM_VAR_SOLVER == 1 && !KM_VAR_PAR
+#if KM_VAR_NL == 10 && KM_VAR_SOLVER == 1 && !KM_VAR_PAR && !KM_VAR_FRC
 extern "C" int kmanip_dbg_prof(unsigned long long* out, int reset) {
   if (out && hipMemcpyFromSymbol(out, HIP_SYMBOL(g_prof), sizeof(unsigned long long) * KM_NPH) != hipSuccess) return -1;
   if (reset) { unsigned long long z[KM_NPH] = {0}; if (hipMemcpyToSymbol(HIP_SYMBOL(g_prof), z, sizeof z) != hipSuccess) return -1; }
@@ -386,7 +420,7 @@ extern "C" int kmanip_dbg_prof_blocks(unsigned long long* out, int nblocks) {
   return hipMemcpyFromSymbol(out, HIP_SYMBOL(g_prof_blk), sizeof(unsigned long long) * KM_NPH * 4 * nblocks) == hipSuccess ? 0 : -1;
 }
 #endif
-#if KM_VAR_NL == 20 && KM_VAR_SOLVER == 1 && !KM_VAR_PAR
+#if KM_VAR_NL == 20 && KM_VAR_SOLVER == 1 && !KM_VAR_PAR && !KM_VAR_FRC
 extern "C" int kmanip_dbg_prof20(unsigned long long* out, int reset) {          // the DualArm / Torso Newton object's accumulators
   if (out && hipMemcpyFromSymbol(out, HIP_SYMBOL(g_prof), sizeof(unsigned long long) * KM_NPH) != hipSuccess) return -1;
   if (reset) { unsigned long long z[KM_NPH] = {0}; if (hipMemcpyToSymbol(HIP_SYMBOL(g_prof), z, sizeof z) != hipSuccess) return -1; }

@@ -385,6 +385,17 @@ __device__ __forceinline__ real pgs_row(real Ja, real aref, real R, real den, re
   return dlt;
 }
 
+#if KM_VAR_FRC
+// rhs + qfrc_applied of one dof (the KM_VAR_FRC builds).  The sum is an addition of its own, never contracted into the servo force's
+// arithmetic; a zero component leaves rhs as it is, to the sign of a zero (-0 + 0 would be +0), so that a buffer of zeros gives the
+// default kernels' bits.
+__device__ __forceinline__ real add_applied(real rhs, real f) {
+#pragma clang fp contract(off)
+  const real s = rhs + f;
+  return f == 0.0 ? rhs : s;
+}
+#endif
+
 // mj_step2 up to (not including) integration: actuation, qacc_smooth, warm start, PGS.  Returns this
 // lane's component of qacc (lane `sub` owns dof `sub`).
 template <int NL, int G>
@@ -400,6 +411,9 @@ __device__ __forceinline__ real solve_accel(Ws<NL>& w, const LModel<NL>& lm, con
       if (lm.forcelimited[sub]) force = fmin(fmax(force, lm.forcerange[sub][0]), lm.forcerange[sub][1]);
       rhs += force;
     }
+#if KM_VAR_FRC
+    if (actuation) rhs = add_applied(rhs, w.frc[sub]);      // qfrc_applied: every dof, outside the servo's clamps
+#endif
     w.tmp[sub] = rhs;
   }
   GSYNC();

@@ -251,6 +251,20 @@ __device__ __forceinline__ void load_state(Ws<NL>& w, const KDeviceState& st, in
   for (int k = 0; k < KL; k++) { const int i = sub + G * k; if (i < NL) w.ctrl[i] = (real)(float)c[k]; }
   if (sub == 0) { w.bad = 0; w.work = 0; }
 }
+#if KM_VAR_FRC
+// the env's row of KDeviceState::qfrc_applied -> Ws::frc, lane `sub` its own dof's component, once per launch.  Returns nonzero on
+// every lane of the group if a component is not finite: the row is then stored as zeros and the caller treats the env as diverged
+// before any solver runs (no loop ever iterates on a NaN input).  The caller synchronises the group before Ws::frc is read.
+template <int NL, int G>
+__device__ __forceinline__ int load_applied(Ws<NL>& w, const KDeviceState& st, int env, int sub) {
+  constexpr int NV = Dim<NL>::NV;
+  static_assert(NV <= G, "one dof per lane");
+  const real f = st.qfrc_applied[(size_t)env * NV + (sub < NV ? sub : NV - 1)];
+  const int bad = gor<G>(!isfinite(f));
+  if (sub < NV) w.frc[sub] = bad ? 0.0 : f;
+  return bad;
+}
+#endif
 template <int NL> struct LdsIO {
   Ws<NL>& w; const KDeviceState& st; int env;
   __device__ __forceinline__ real qpos(int i) const { return w.qpos[i]; }

@@ -928,6 +928,10 @@ __device__ __forceinline__ real solve_newton(Ws<NL>& w, const LModel<NL>& lm, co
   real mrow[NL];
 #pragma unroll
   for (int j = 0; j < NL; j++) mrow[j] = w.Minv[si][j];
+#if KM_VAR_FRC
+  real fap = w.frc[sv];          // qfrc_applied of this lane's dof, in the same batch
+  km_pin(fap);
+#endif
   km_pin(bia, ctl, cr0, cr1, kpv, qps); km_pin(fr0, fr1); km_pin_i(flim);
   real rhs = -bia;
   if (sub < NV) {
@@ -937,6 +941,9 @@ __device__ __forceinline__ real solve_newton(Ws<NL>& w, const LModel<NL>& lm, co
       if (flim) force = fmin(fmax(force, fr0), fr1);
       rhs += force;
     }
+#if KM_VAR_FRC
+    if (actuation) rhs = add_applied(rhs, fap);      // every dof, outside the servo's clamps
+#endif
     w.tmp[sub] = rhs;
   }
   GSYNC();

@@ -1,5 +1,9 @@
 // kmanip_dyn_ws.hpp -- part of kmanip_dyn.hip, included only by it (inside its variant namespace): per-env workspace (Dim, EnvP, LModel, ConRec, Ws, SlotC, CReg) and the lane-group reductions.
 #pragma once
+// KM_VAR_FRC=1: the applied-force build of a variant (kmanip_bind_applied_force), orthogonal to KM_VAR_PAR
+#ifndef KM_VAR_FRC
+#define KM_VAR_FRC 0
+#endif
 template <int NL> struct Dim {
   static constexpr int NV = NL + 6;
   static constexpr int NQ = NL + 7;
@@ -69,7 +73,9 @@ struct ConRec {
   real f[6];       // edge forces
 };
 
-#define KM_WS_PAD(NL) ((NL) <= 10 ? (KM_VAR_PAR ? 24 : 9) : 1)      // doubles of padding at the end of Ws (see the note on row strides in it)
+// doubles of padding at the end of Ws (see the note on row strides in it); the KM_VAR_FRC builds' Ws::frc is 16 doubles = 128 bytes for
+// the 10-link model, so their padding moves by 16 doubles to keep consecutive envs 128 bytes apart modulo the bank row
+#define KM_WS_PAD(NL) ((NL) <= 10 ? (KM_VAR_PAR ? (KM_VAR_FRC ? 8 : 24) : (KM_VAR_FRC ? 25 : 9)) : 1)
 template <int NL>
 struct Ws {
   static constexpr int NV = Dim<NL>::NV, NQ = Dim<NL>::NQ, NS = Dim<NL>::NS, NC = Dim<NL>::NC;
@@ -119,6 +125,9 @@ struct Ws {
   uint32_t slot_anc[NC];   // ... and the ancestor mask of that sphere's link (round 6: the constraint assembly read it through two more dependent loads)
 #if KM_VAR_PAR
   EnvP<NL> ep;             // this env's physics parameters (per env, never per wave slot)
+#endif
+#if KM_VAR_FRC
+  real frc[NV];            // this env's row of KDeviceState::qfrc_applied (load_applied: once per launch; zeros if a component is not finite)
 #endif
   real pad_[KM_WS_PAD(NL)];
 };

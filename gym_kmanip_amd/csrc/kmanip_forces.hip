@@ -17,7 +17,17 @@
 #ifndef KM_VAR_PAR
 #define KM_VAR_PAR 0
 #endif
-#if KM_VAR_PAR
+// KM_VAR_FRC=1: the applied-force builds (kmanip_bind_applied_force), as in kmanip_dyn.hip
+#ifndef KM_VAR_FRC
+#define KM_VAR_FRC 0
+#endif
+#if KM_VAR_PAR && KM_VAR_FRC
+namespace km_envp_frc {
+#define KM_K_FORCES k_frc_forces_ep
+#elif KM_VAR_FRC
+namespace km_frc {
+#define KM_K_FORCES k_frc_forces      // ("frc" first: tools that list the k_forces kernels by name keep seeing the default four)
+#elif KM_VAR_PAR
 namespace km_envp {
 #define KM_K_FORCES k_forces_ep
 #else
@@ -98,10 +108,16 @@ __global__ __launch_bounds__(64) void KM_K_FORCES(const KDeviceModel* __restrict
   load_state<NL, G>(w, st, env, sub);
   // ctrl exactly as stored: load_state's float32 rounding is the start of before_step, which does not run here
   for (int i = sub; i < NL; i += G) w.ctrl[i] = st.ctrl[(size_t)i * st.num_envs + env];
+#if KM_VAR_FRC
+  const int frc_bad = load_applied<NL, G>(w, st, env, sub);
+#endif
   GSYNC();
   const real F0[4] = {0, 0, 0, 0}, fr0[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, cp0[3] = {0, 0, 0};
-  // a non-finite state (k_observe's test): status 1, nothing else computed
+  // a non-finite state (k_observe's test) or, in the force builds, a non-finite applied force: status 1, nothing else computed
   int lb = 0;
+#if KM_VAR_FRC
+  lb = frc_bad;
+#endif
   for (int i = sub; i < NQ; i += G) lb |= !isfinite(w.qpos[i]);
   for (int i = sub; i < NV; i += G) lb |= !isfinite(w.qvel[i]);
   if (gor<G>(lb)) { write_forces<NL, G>(out, env, sub, false, 0, 0, 0, F0, -1, fr0, cp0, 0, 0u); return; }
@@ -165,14 +181,22 @@ static void launch_forces_t(const KDeviceModel* dm, const KDeviceState& st, cons
   constexpr int EPB = 64 / G;
   hipLaunchKernelGGL((KM_K_FORCES<NL, G, EPB>), dim3((st.num_envs + EPB - 1) / EPB), dim3(64), 0, stream, dm, st, out);
 }
-#if KM_VAR_PAR
+#if KM_VAR_PAR && KM_VAR_FRC
+}  // namespace km_envp_frc
+using namespace km_envp_frc;
+#define KM_LAUNCH_FORCES kmanip_launch_forces_ep_frc_
+#elif KM_VAR_FRC
+}  // namespace km_frc
+using namespace km_frc;
+#define KM_LAUNCH_FORCES kmanip_launch_forces_frc_
+#elif KM_VAR_PAR
 }  // namespace km_envp
 using namespace km_envp;
 #define KM_LAUNCH_FORCES kmanip_launch_forces_ep_
 #else
 #define KM_LAUNCH_FORCES kmanip_launch_forces_
 #endif
-// ---- one (NL, G[, PAR]) variant per translation unit (the Makefile compiles this file four times)
+// ---- one (NL, G[, PAR][, FRC]) variant per translation unit (the Makefile compiles this file eight times)
 #ifndef KM_VAR_NL
 #error "compile with -DKM_VAR_NL=<10|20> -DKM_VAR_G=<16|32> -DKM_VAR_SOLVER=1"
 #endif

@@ -67,6 +67,7 @@ class KManipEnvHip:
         self._ep_ranges = None           # (lo, hi) float64[KM_EP_N] of ranges mode, or None
         self._vp_active = False          # per-env visual parameters in force (set_visual_params / set_visual_param_ranges)
         self._vp_ranges = None           # (lo, hi) float64[KM_VP_N] of visual ranges mode, or None
+        self.applied_force = None        # the bound qfrc_applied tensor (bind_applied_force), or None
 
     # ------------------------------------------------------------------ helpers
     def _check(self, rc, what):
@@ -160,6 +161,26 @@ class KManipEnvHip:
         self._rd_rec = (rec0, rec1)                          # (keeps the tensors alive while bound)
         p = [C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0) for t in (rec0, rec1)]
         self._check(self.L.kmanip_bind_reward_done_record(self.h, p[0], p[1]), "kmanip_bind_reward_done_record")
+
+    def bind_applied_force(self, t=None):
+        """kmanip_bind_applied_force: MuJoCo's data.qfrc_applied.  `t`: a float64, contiguous [num_envs, nv] tensor on this handle's
+        device, row e = env e in the dof order of kinematics()' qM / qfrc_bias: joint torques / forces, then the force on the cube
+        (world frame), then the torque on it (cube frame); gym_kmanip_amd.applied has helpers that fill such rows.  While bound,
+        every sub-step of step_flat / k_step / step_chunk adds the row to the smooth forces, and forces() reports the forced
+        state; the library only ever reads the tensor, once per launch on the step's stream, so writing into it between steps
+        is how the force changes.  It is not state (state_tensors, copy_envs_from, checkpoint do not carry it) and resets ignore it.
+        Anything but such a tensor raises before the library is called and leaves the binding as it was.  The handle keeps a
+        reference; None unbinds (the default kernels again).  Returns `t`."""
+        if t is not None:
+            self._check_buf(t, (self.num_envs, self.cm.nv), _torch().float64, "applied force")
+        self._check(self.L.kmanip_bind_applied_force(self.h, C.c_void_p(t.data_ptr()) if t is not None else None),
+                    "kmanip_bind_applied_force")
+        self.applied_force = t
+        return t
+
+    def new_applied_force(self):
+        """Allocate a zero [num_envs, nv] float64 tensor, bind it (bind_applied_force) and return it."""
+        return self.bind_applied_force(_torch().zeros((self.num_envs, self.cm.nv), dtype=_torch().float64, device=self.device))
 
     def select_reward_done_record(self, index: int):
         """kmanip_select_reward_done_record: the bound buffer (0 / 1) the following steps fill.  The caller must have made the

@@ -151,7 +151,7 @@ class KManipEnv(_EnvBase):
                  log_h5py: bool = False, log_prefix: str = "test", log_env_ids=None, log_backend=None,
                  log_reference_layout: bool = False, log_h5py_module=None, domain_randomization=None, visual_randomization=None,
                  segmentation: bool = False, render_links: bool = False, contact_forces: bool = False, ee_pose: bool = False,
-                 **overrides):
+                 applied_force: bool = False, **overrides):
         spec: EnvSpec = ENV_SPECS[env_id]
         self.env_id = env_id
         self.seed = seed
@@ -205,6 +205,10 @@ class KManipEnv(_EnvBase):
         # (env_hip.kinematics: one more launch per step; live buffers, like the device observations)
         self.ee_pose = bool(ee_pose)
         self._kin = None                                 # the two tensors the launch fills: allocated by the first call, then reused
+        # applied_force=True (not in the reference): a zero float64 DEVICE tensor [num_envs, nv] is bound as MuJoCo's qfrc_applied
+        # (env_hip.bind_applied_force) and exposed as self.applied_force and info["applied_force"]: what the caller writes into it
+        # acts in every following step; the shell never changes its contents (resets included)
+        self.applied_force = self.env.new_applied_force() if applied_force else None
         # domain_randomization={name: (lo, hi)} (env_hip.ENV_PARAMS names): every reset redraws those physics parameters per env
         if domain_randomization:
             self.env.set_env_param_ranges(**domain_randomization)
@@ -216,6 +220,8 @@ class KManipEnv(_EnvBase):
             "a_len": self.action_len, "obs_list": self.obs_list, "act_list": self.act_list,
             "cameras": self.cameras, "sim": self.sim,
         }
+        if self.applied_force is not None:
+            self.info["applied_force"] = self.applied_force
         # optional episode logging, env_base.py:82-101 (rerun is a viewer, not on the path: not offered)
         self.log_h5py = log_h5py
         self.logger = None

@@ -321,6 +321,28 @@ KMANIP_API int kmanip_get_counters(KHandle h, int32_t* step_idx_dev, int32_t* ep
  * steps since the env's last reset x control_timestep.  NULL unbinds.  The buffer must outlive the binding. */
 KMANIP_API int kmanip_bind_sim_time(KHandle h, double* sim_time_dev);
 
+/* MuJoCo's data.qfrc_applied.  qfrc_dev: DEVICE double[num_envs, nv], env-major, nv = nlink + 6, caller-owned;
+ * NULL unbinds.
+ * ROW LAYOUT (the dof order of qM / qfrc_bias in kmanip_kinematics): columns 0 .. nlink-1 joint torque (hinge) or force (slide);
+ * nlink .. nlink+2 force on the cube at its centre of mass, world frame; nlink+3 .. nlink+5 torque on the cube in the cube's BODY
+ * frame (free-joint convention).
+ * THE STEP: while a buffer is bound, every sub-step of kmanip_step and kmanip_step_chunk adds row `env` to the smooth right-hand side
+ * (rhs = -bias + servo force + applied), with both solvers, the first sub-step (which uses the pre-IK products) included.  The force is
+ * not clamped by forcerange or ctrlrange: those limit actuators.  The buffer is read once per launch, at the env's load; a chunk holds
+ * it for all its steps.  Ordering is the stream's: a write enqueued before the step on the step's stream is seen.  The bind itself is a
+ * host-side switch, like kmanip_bind_sim_time; the buffer must outlive the binding.  A buffer of zeros gives the bits of no buffer.
+ * WHAT THE LIBRARY DOES NOT DO WITH IT: it never writes the buffer and never clears it.  It is not state: kmanip_get/set_state*,
+ * kmanip_copy_envs, checkpoints and snapshots do not carry it.  Resets ignore it: kmanip_reset and the auto-reset's forward pass
+ * (actuation disabled) compute what they compute without a buffer, bit for bit (MuJoCo's mj_resetData zeroes qfrc_applied; here the
+ * caller zeroes the rows of done envs if it wants that).
+ * kmanip_forces honours the buffer; kmanip_kinematics and kmanip_observe do not depend on it.
+ * NON-FINITE COMPONENTS are data, not an error: the check runs at the env's load, before any solver.  Such an env is treated as
+ * diverged for that step -- KM_DONE_DIVERGED, zero observation and reward, empty contact mask, the usual reset of a diverged env -- and
+ * gets status 1 with zero outputs from kmanip_forces; every other env is untouched, bit for bit.
+ * ERRORS: a NULL handle returns nonzero.  The pointer cannot be validated on the host.  Scheduling predictors keep working on what
+ * they already measure. */
+KMANIP_API int kmanip_bind_applied_force(KHandle h, const double* qfrc_dev);
+
 /* The multi-GPU learner's per-step exchange is one packed record per env, (reward, done as a double), all-gathered across the
  * ranks (gym_kmanip_amd/dist.py).  Bound here, every kmanip_step writes that record itself into ONE of two
  * caller-owned double[num_envs, 2] buffers -- the one chosen by kmanip_select_reward_done_record (rec0 after the bind) -- so that
@@ -357,7 +379,7 @@ typedef struct KForcesDev {
   double*   contact_dist;     /* [n, NC] */
   uint32_t* contact_mask;     /* [n] */
   uint8_t*  status;           /* [n] 0 ok; 1 = non-finite state or failed factorisation / bad qacc: every other output of the env is 0
-                               *     and every slot empty (contact_bit -1) */
+                               *     and every slot empty (contact_bit -1); also a non-finite component in the env's bound applied force */
 } KForcesDev;
 /* ONE kernel launch, asynchronous on `stream`: no allocation, no synchronisation, no host copy.  Enqueued after a kmanip_step on the
  * same stream it sees that step's result.
@@ -369,7 +391,9 @@ typedef struct KForcesDev {
  * SLOT ORDER: only the kinds are fixed -- 4 cube-corner slots, then KM_SPHERE_SLOTS sphere-cube, then KM_SPHERE_TABLE_SLOTS
  * sphere-table; contact_bit says who sits where, and callers index by bit.  The occupied slots are exactly the bits of contact_mask.
  * INPUTS: ctrl is used exactly as stored (the float32 rounding that starts kmanip_step's before_step is not applied); the stored
- * qacc_warm is the solver's starting point.  After an auto-reset the forces are those of the new episode's first state.  Per-env
+ * qacc_warm is the solver's starting point.  A bound applied force (kmanip_bind_applied_force) is honoured: qacc and qfrc_constraint =
+ * M (qacc - qacc_smooth) are those of the forced state, and M qacc + qfrc_bias = qfrc_actuator (padded with six zeros) + qfrc_applied +
+ * qfrc_constraint with kmanip_kinematics' qM and qfrc_bias; an env whose row has a non-finite component gets status 1.  After an auto-reset the forces are those of the new episode's first state.  Per-env
  * parameters (KM_EP_*) are honoured, explicit and ranges mode alike.
  * THE HANDLE IS READ ONLY: state, warm start, counters, the contact masks kmanip_get_diag returns, scheduling predictors, sim time and
  * random streams stay bit for bit as they were; a step after the call is the step without it.
@@ -443,7 +467,8 @@ KMANIP_API int kmanip_timing_summary(KHandle h, double* ik_ms_sum, double* dyn_m
  * policies such as ACT, scripted / replayed action streams): exactly the result of nsteps consecutive kmanip_step calls,
  * with act_dev float[nsteps, num_envs, act_dim], obs_dev double[nsteps, num_envs, obs_dim], reward_dev double[nsteps,
  * num_envs], done_dev uint8[nsteps, num_envs].  Without a launch boundary per step the waves do not wait for the
- * batch's slowest env at every step, so throughput follows the mean wave rather than the slowest one. */
+ * batch's slowest env at every step, so throughput follows the mean wave rather than the slowest one.  A bound applied force
+ * (kmanip_bind_applied_force) is read once, at the launch: the same row acts in every step of the chunk. */
 KMANIP_API int kmanip_step_chunk(KHandle h, int nsteps, const float* act_dev, double* obs_dev, double* reward_dev,
                       uint8_t* done_dev, void* stream);
 
