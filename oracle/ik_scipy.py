@@ -177,8 +177,10 @@ def ik_jac(q_pos, physics=None, goal_orn=None, q_mask=None, ee_site=None, rad=0.
     return np.vstack((jac_pos, jac_quat, jac_reg, jac_reg))
 
 
-def ik(physics, goal_pos=None, goal_orn=None, q_mask=None, q_pos_home=None, q_pos_prev=None, ee_site=None):
-    """Returns (q_pos, result or None).  physics.qpos is left mutated like the reference."""
+def ik(physics, goal_pos=None, goal_orn=None, q_mask=None, q_pos_home=None, q_pos_prev=None, ee_site=None,
+       max_nfev=None):
+    """Returns (q_pos, result or None).  physics.qpos is left mutated like the reference.  max_nfev (the reference
+    never sets it) stops least_squares after that many evaluations: result.x is then an intermediate iterate."""
     q_mask = np.asarray(q_mask)
     q_pos = physics.qpos[q_mask].copy()
     ik_func = partial(ik_res, physics=physics, goal_pos=goal_pos, goal_orn=goal_orn,
@@ -187,7 +189,8 @@ def ik(physics, goal_pos=None, goal_orn=None, q_mask=None, q_pos_home=None, q_po
     result = None
     try:
         result = least_squares(ik_func, q_pos, jac=ik_jac_func,
-                               bounds=(physics.jnt_range[q_mask, 0], physics.jnt_range[q_mask, 1]), verbose=0)
+                               bounds=(physics.jnt_range[q_mask, 0], physics.jnt_range[q_mask, 1]), verbose=0,
+                               max_nfev=max_nfev)
         q_pos = result.x
     except ValueError:
         pass

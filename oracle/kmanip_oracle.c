@@ -316,9 +316,15 @@ static void svd_jacobi(double* A, int R, int n, const double* f, double* s, doub
   for (int sweep = 0; sweep < 60; sweep++) {
     int rotated = 0;
     for (int p = 0; p < n - 1; p++) for (int q = p + 1; q < n; q++) {
-      double al = 0, be = 0, ga = 0;
-      for (int r = 0; r < R; r++) { double ap = A[r * n + p], aq = A[r * n + q]; al += ap * ap; be += aq * aq; ga += ap * aq; }
-      if (fabs(ga) <= 1e-15 * sqrt(al * be) || ga == 0) continue;
+      double al = 0, be = 0, ga = 0, gabs = 0;
+      for (int r = 0; r < R; r++) { double ap = A[r * n + p], aq = A[r * n + q]; al += ap * ap; be += aq * aq; ga += ap * aq; gabs += fabs(ap * aq); }
+      /* Converged when the coupling is below 1e-15 of the column norms AND is rounding residue (below 1e-12 of the magnitude of
+       * its own terms).  A coordinate pressed onto a bound scales its column of J_h by d = sqrt(x - lb), down to 1e-50: its
+       * coupling to the other columns is then tiny but exact, and it carries the first-order term of that coordinate's step,
+       * p = -(x - lb) (1 + delta), delta ~ 1e-5.  Dropped, p hits the bound to the last bit, select_step's stride is 1 - ulp, and
+       * once theta is within 1e-8 of 1 its constrained and reflected candidates tie, which selects the anti-gradient step
+       * (tests/test_ik_edges_cpu.py). */
+      if (ga == 0 || (fabs(ga) <= 1e-15 * sqrt(al * be) && fabs(ga) <= 1e-12 * gabs)) continue;
       rotated = 1;
       double zeta = (be - al) / (2 * ga);
       double t = (zeta >= 0 ? 1.0 : -1.0) / (fabs(zeta) + sqrt(1 + zeta * zeta));
