@@ -78,6 +78,29 @@ def test_exported_text_is_primitive_only_and_complete(name):
     assert {s.get("name") for s in root.iter("site")} == set(spec["sites"])
 
 
+@pytest.mark.parametrize("name", NAMES)
+def test_export_of_an_anisotropic_asset_carries_the_three_values_in_order(name, tmp_path):
+    """tests/tools/aniso_model.py: every link and the cube with three different principal inertias.  The exported text states each
+    triple in the asset's order, and the extractor reads the same triples back."""
+    sys.path.insert(0, os.path.join(ROOT, "tests", "tools"))
+    import aniso_model as AM
+    import regime_states as R
+    cm = AM.aniso(R.model(name))
+    spec = cm.asset
+    text = E.export(spec)
+    bodies = {b.get("name"): b for b in ET.fromstring(text).iter("body")}
+    triple = lambda b: [float(x) for x in bodies[b].find("inertial").get("diaginertia").split()]
+    for i, l in enumerate(spec["links"]):
+        want = [cm.desc.inertia[i][k] for k in range(3)]
+        assert len(set(want)) == 3 and l["inertial"]["diaginertia"] == want
+        assert triple(l["name"]) == want, l["name"]
+    assert triple("cube") == list(cm.desc.cube_inertia) == list(AM.CUBE_INERTIA)
+    (tmp_path / (name + ".xml")).write_text(text)
+    back = X.build(name + ".xml", name, assets_dir=str(tmp_path))
+    assert [list(l["inertial"]["diaginertia"]) for l in back["links"]] == [l["inertial"]["diaginertia"] for l in spec["links"]]
+    assert list(back["cube"]["diaginertia"]) == spec["cube"]["diaginertia"]
+
+
 def test_contact_bits_give_the_surrogate_pair_set():
     """MuJoCo collides two geoms iff (contype1 & conaffinity2) | (contype2 & conaffinity1)."""
     hit = lambda a, b: bool((E.BITS[a][0] & E.BITS[b][1]) | (E.BITS[b][0] & E.BITS[a][1]))
