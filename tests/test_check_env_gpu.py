@@ -11,6 +11,9 @@ import pytest
 from gym_kmanip_amd.model import ENV_SPECS
 
 pytestmark = pytest.mark.gpu
+
+RGB_LEVELS = 1            # an RGB pixel is off when a channel differs from the oracle's by more than this many grey levels ...
+RGB_BAD_SHARE = 1e-3      # ... and fewer than this share of an image's pixels may be off (rays grazing a silhouette)
 ALL_IDS = sorted(ENV_SPECS)
 
 
@@ -117,7 +120,7 @@ def test_rgb_render_parity_vs_oracle(env_id):
         for e in range(n):
             ref = orc.render_rgb(qpos[e], ci, h, w)
             diff = np.abs(img[e].astype(int) - ref.astype(int)).max(axis=-1)
-            assert (diff > 1).mean() < 1e-3, (name, e, (diff > 1).sum())
+            assert (diff > RGB_LEVELS).mean() < RGB_BAD_SHARE, (name, e, (diff > RGB_LEVELS).sum())
     dev.k_close()
 
 
@@ -233,7 +236,7 @@ def test_rgb_render_reference_resolution_vs_oracle():
         for e in range(n):
             ref = orc.render_rgb(qpos[e], KM_CAM_INDEX[name], h, w)
             diff = np.abs(img[e].astype(int) - ref.astype(int)).max(axis=-1)
-            assert (diff > 1).mean() < 1e-3, (name, e, int((diff > 1).sum()))
+            assert (diff > RGB_LEVELS).mean() < RGB_BAD_SHARE, (name, e, int((diff > RGB_LEVELS).sum()))
             if name == "head":
                 red = (ref[..., 0] > 100) & (ref[..., 1] == 0)
                 assert red.any() and (ref[..., 0] == ref[..., 1]).mean() > 0.5      # cube pixels and table / background pixels

@@ -432,6 +432,10 @@ def test_full_size_configs_3_and_4_shard(env_id):
         e.k_close()
 
 
+DEPTH_TOL = 1e-6            # metres: a depth pixel is off when it differs from the oracle's by more than this ...
+DEPTH_BAD_SHARE = 5e-4      # ... and fewer than this share of an image's pixels may be off (rays grazing a silhouette)
+
+
 @pytest.mark.parametrize("env,cams", [("KManipSoloArm", [0]), ("KManipTorso", [0, 1])])
 def test_render_depth_parity(env, cams):
     """Gripper-cam depth (BASELINE config 5) vs the oracle's ray caster on stepped states.  float64 maths on both
@@ -449,8 +453,8 @@ def test_render_depth_parity(env, cams):
         assert img.shape == (6, 64, 64) and img.dtype == np.float32
         for e in range(6):
             ref = orc.render_depth(qpos[e], cam, 64, 64)
-            bad = np.abs(img[e] - ref) > 1e-6
-            assert bad.mean() < 5e-4, (cam, e, bad.sum())
+            bad = np.abs(img[e] - ref) > DEPTH_TOL
+            assert bad.mean() < DEPTH_BAD_SHARE, (cam, e, bad.sum())
         assert (img >= cm.desc.cam_znear - 1e-6).all() and (img <= cm.desc.cam_zfar + 1e-6).all()
         assert np.unique(np.round(img, 3)).size > 10          # a real image, not a constant
     dev.k_close()
