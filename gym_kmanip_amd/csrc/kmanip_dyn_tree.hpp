@@ -5,8 +5,50 @@
 // jumping compose it with the transform of the 2^k-th ancestor (staged in the link's own xmat/xpos slots).
 // kin (optional, 15 doubles): the world frame of THIS lane's link as it was written to LDS -- rotation R[9], origin p[3], centre of
 // mass c[3] (zeros on lanes without a link) -- so that the passes that follow need not read their own link back (round 6)
+// One-row groups (G == 16, NL <= 10; lane = link): the staged transforms never leave the registers.  A round fetches the ancestor
+// lane's R[9] and p[3] with a lane gather inside the group's 16 lanes (ds_bpermute: the LDS crossbar, no LDS memory) -- 24 dwords
+// issued back to back behind ONE wait -- where it used to write 12 doubles to LDS, synchronise, read the ancestor's 12 and wait
+// again; xmat / xpos reach LDS once, after the last round, with cpos / axis.  The gather sits OUTSIDE the `a >= 0` branch at a
+// clamped source lane (a gather's source lane must be active; lanes of a group enter and leave this function together), the
+// products and their order are the ones below, the jump tables stay run-time model data.
+// lane (addr >> 2)'s copy of v
+__device__ __forceinline__ real lane_gather(int addr, real v) {
+  const int lo = __builtin_amdgcn_ds_bpermute(addr, __double2loint(v)), hi = __builtin_amdgcn_ds_bpermute(addr, __double2hiint(v));
+  return __hiloint2double(hi, lo);
+}
+// PINNED CONTRACTIONS.  Which product of a * b + c * d is rounded on its own and which is fused into the add is the compiler's
+// choice -- it follows the operand order the optimiser leaves, and that order moves when the code around an expression moves (with
+// the frames in registers, the three products of R * com came out the other way round: tools/ir_fma_order.py shows such a swap
+// in the optimised IR).  The one-row paths that this file moved off LDS therefore spell their sums out, with contraction off, in
+// the pairing the compiler gives dot3 / cross3 / mat_vec3 as written -- the bits the library has always produced:
+//   a0 b0 + a1 b1 + a2 b2 = fma(a2, b2, fma(a0, b0, rnd(a1 b1)))        a b - c d = fma(a, b, -rnd(c d))
+__device__ __forceinline__ real dot3_pinned(real a0, real b0, real a1, real b1, real a2, real b2) {
+#pragma clang fp contract(off)
+  const real m = a1 * b1;
+  return __builtin_fma(a2, b2, __builtin_fma(a0, b0, m));
+}
+__device__ __forceinline__ real dot3_pinned(const real* a, const real* b) { return dot3_pinned(a[0], b[0], a[1], b[1], a[2], b[2]); }
+__device__ __forceinline__ real diff2_pinned(real a, real b, real c, real d) {
+#pragma clang fp contract(off)
+  const real m = c * d;
+  return __builtin_fma(a, b, -m);
+}
+__device__ __forceinline__ real sum2_pinned(real a, real b, real c, real d) {
+#pragma clang fp contract(off)
+  const real m = c * d;
+  return __builtin_fma(a, b, m);
+}
+__device__ __forceinline__ void cross3_pinned(real* r, const real* a, const real* b) {
+  const real x = diff2_pinned(a[1], b[2], a[2], b[1]), y = diff2_pinned(a[2], b[0], a[0], b[2]), z = diff2_pinned(a[0], b[1], a[1], b[0]);
+  r[0] = x; r[1] = y; r[2] = z;
+}
+__device__ __forceinline__ void mat_vec3_pinned(real* r, const real* m, const real* v) {
+  const real x = dot3_pinned(m[0], v[0], m[1], v[1], m[2], v[2]), y = dot3_pinned(m[3], v[0], m[4], v[1], m[5], v[2]), z = dot3_pinned(m[6], v[0], m[7], v[1], m[8], v[2]);
+  r[0] = x; r[1] = y; r[2] = z;
+}
 template <int NL, int G>
 __device__ __forceinline__ void fk_parallel(Ws<NL>& w, const LModel<NL>& lm, int sub, real* kin = nullptr) {
+  constexpr bool ROW = G == 16 && NL <= 10;
   real R[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, p[3] = {0, 0, 0};
   const bool on = sub < NL;
   // (round 6) everything the pass reads about this lane's link -- its coordinate, its constant frame in the parent, its joint
@@ -29,14 +71,21 @@ __device__ __forceinline__ void fk_parallel(Ws<NL>& w, const LModel<NL>& lm, int
 #pragma unroll
       for (int a = 0; a < 3; a++) {
         const real c0 = lR[3 * a], c1 = lR[3 * a + 1];
-        R[3 * a] = cs * c0 + sn * c1;
-        R[3 * a + 1] = cs * c1 - sn * c0;
+        if constexpr (ROW) {
+          R[3 * a] = sum2_pinned(cs, c0, sn, c1);
+          R[3 * a + 1] = diff2_pinned(cs, c1, sn, c0);
+        } else {
+          R[3 * a] = cs * c0 + sn * c1;
+          R[3 * a + 1] = cs * c1 - sn * c0;
+        }
         R[3 * a + 2] = lR[3 * a + 2];
       }
     }
+    if constexpr (!ROW) {
 #pragma unroll
-    for (int c = 0; c < 9; c++) w.k.xmat[sub][c] = R[c];
-    w.k.xpos[sub][0] = p[0]; w.k.xpos[sub][1] = p[1]; w.k.xpos[sub][2] = p[2];
+      for (int c = 0; c < 9; c++) w.k.xmat[sub][c] = R[c];
+      w.k.xpos[sub][0] = p[0]; w.k.xpos[sub][1] = p[1]; w.k.xpos[sub][2] = p[2];
+    }
   } else if (sub == NL) {
     real cq[4] = {w.qpos[NL + 3], w.qpos[NL + 4], w.qpos[NL + 5], w.qpos[NL + 6]}, cm[9];
     normalize4_fast(cq);
@@ -44,6 +93,32 @@ __device__ __forceinline__ void fk_parallel(Ws<NL>& w, const LModel<NL>& lm, int
 #pragma unroll
     for (int c = 0; c < 9; c++) w.k.cube_mat[c] = cm[c];
   }
+  if constexpr (ROW) {
+    const int nrounds = __builtin_amdgcn_readfirstlane(rounds);      // (one model, one value: a scalar loop)
+    const int row4 = (threadIdx.x & 48) << 2;                        // byte address of the group's lane 0 in the gather's lane space
+    for (int k = 0; k < nrounds; k++) {
+      const int jk = k == 0 ? jmp0 : (k == 1 ? jmp1 : (k == 2 ? jmp2 : jmp3));
+      const int a = on ? jk : -1;
+      const int src = row4 + (((a >= 0 ? a : 0) & 15) << 2);
+      real A[9], pa[3];
+#pragma unroll
+      for (int c = 0; c < 9; c++) A[c] = lane_gather(src, R[c]);
+#pragma unroll
+      for (int c = 0; c < 3; c++) pa[c] = lane_gather(src, p[c]);
+      km_pin(pa, A);
+      if (a >= 0) {
+        real Rn[9], t[3];
+        mat_vec3_pinned(t, A, p);
+        p[0] = t[0] + pa[0]; p[1] = t[1] + pa[1]; p[2] = t[2] + pa[2];
+#pragma unroll
+        for (int i = 0; i < 3; i++)
+#pragma unroll
+          for (int j = 0; j < 3; j++) Rn[3 * i + j] = dot3_pinned(A[3 * i], R[j], A[3 * i + 1], R[3 + j], A[3 * i + 2], R[6 + j]);
+#pragma unroll
+        for (int c = 0; c < 9; c++) R[c] = Rn[c];
+      }
+    }
+  } else {
   GSYNC();
   for (int k = 0; k < rounds; k++) {
     const int jk = k == 0 ? jmp0 : (k == 1 ? jmp1 : (k == 2 ? jmp2 : jmp3));
@@ -70,10 +145,17 @@ __device__ __forceinline__ void fk_parallel(Ws<NL>& w, const LModel<NL>& lm, int
     }
     GSYNC();
   }
+  }
   real cpo[3] = {0, 0, 0};
   if (on) {
     real cw[3];
-    mat_vec3(cw, R, cl);
+    if constexpr (ROW) {
+#pragma unroll
+      for (int c = 0; c < 9; c++) w.k.xmat[sub][c] = R[c];
+      w.k.xpos[sub][0] = p[0]; w.k.xpos[sub][1] = p[1]; w.k.xpos[sub][2] = p[2];
+    }
+    if constexpr (ROW) mat_vec3_pinned(cw, R, cl);
+    else mat_vec3(cw, R, cl);
     cpo[0] = p[0] + cw[0]; cpo[1] = p[1] + cw[1]; cpo[2] = p[2] + cw[2];
     w.k.cpos[sub][0] = cpo[0]; w.k.cpos[sub][1] = cpo[1]; w.k.cpos[sub][2] = cpo[2];
     w.k.axis[sub][0] = R[2]; w.k.axis[sub][1] = R[5]; w.k.axis[sub][2] = R[8];
@@ -292,6 +374,22 @@ __device__ __forceinline__ void composite_mass_bias_rows(Ws<NL>& w, const LModel
     // row's entry is stored unconditionally -- rows this lane does not own go to a scratch slot of its own (w.tmp[j], not live before
     // the solve) -- so nothing is conditional, and the scheduler issues the rows' loads together.  Same operations, same bits.
     real mcol[W];
+    if constexpr (W == NL && NL <= 10) {
+      // One-row groups (lane = link, base = 0): row i's joint axis, origin and type are lane i's OWN registers (ax, oj, jtb), so they
+      // arrive by row broadcast.  Read from LDS -- whatever the scheduling hint below asked for -- the rows came out as a chain of
+      // load -> wait -> compute steps: about a dozen exposed LDS round trips per call with one wave per SIMD.  Same values (the
+      // LDS copies are these registers, stored by fk_parallel), same operations on them.  Lane i < NL is inside this branch: active.
+      static_for<0, W>([&](auto cc) {
+        constexpr int i = decltype(cc)::value;
+        const real ai[3] = {gbcast<16, i>(ax[0]), gbcast<16, i>(ax[1]), gbcast<16, i>(ax[2])};
+        const real oi[3] = {gbcast<16, i>(oj[0]), gbcast<16, i>(oj[1]), gbcast<16, i>(oj[2])};
+        const int jti = dpp_i32<0x150 + i>(jtb);
+        cross3_pinned(t, oi, F);
+        const real mo[3] = {N[0] - t[0], N[1] - t[1], N[2] - t[2]};
+        const real val = jti == KM_JNT_SLIDE ? dot3_pinned(ai, F) : dot3_pinned(ai, mo);
+        mcol[i] = ((am >> i) & 1u) ? val : 0.0;
+      });
+    } else {
 #pragma unroll
     for (int c = 0; c < W; c++) {
       const int i = base + c < NL ? base + c : NL - 1;      // rows of the block only: M has no entries between blocks (clamped: never stored)
@@ -305,6 +403,7 @@ __device__ __forceinline__ void composite_mass_bias_rows(Ws<NL>& w, const LModel
     // (scheduling hint for the block above: all the rows' LDS reads first, then the arithmetic)
     __builtin_amdgcn_sched_group_barrier(0x100, 8 * W, 0);
     __builtin_amdgcn_sched_group_barrier(0x002, 64 * W, 0);
+    }
 #pragma unroll
     for (int c = 0; c < W; c++) {
       const int i = base + c;
