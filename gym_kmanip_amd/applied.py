@@ -5,12 +5,18 @@ the library.  A row has nv = nlink + 6 columns in the dof order of kinematics()'
   0 .. nlink-1          joint torque (hinge) or force (slide)
   nlink .. nlink+2      force on the cube at its centre of mass, world frame
   nlink+3 .. nlink+5    torque on the cube in the cube's BODY frame (free-joint convention)
-Both helpers ACCUMULATE into `out` ([n, nv], allocated as zeros when None) and return it, so several wrenches add up in one row:
+cube_wrench and site_wrench ACCUMULATE into `out` ([n, nv], allocated as zeros when None) and return it, so several wrenches add up
+in one row:
 
     tau = env.new_applied_force()                              # zeros, bound
     tau.zero_()
     applied.cube_wrench(cm, env.state_tensors()["qpos"], force=push, out=tau)
     applied.site_wrench(cm, env.kinematics(), 0, force=f_hand, out=tau)
+
+from_inverse and fwdinv_residual work on the results of KManipEnvHip.inverse (MuJoCo's mj_inverse) and forces:
+
+    inv = env.inverse(qacc_wanted)                             # the total force behind qacc_wanted
+    tau.copy_(applied.from_inverse(inv, env.forces()))         # ... minus what the servos already give: forces()["qacc"] == qacc_wanted
 """
 from __future__ import annotations
 
@@ -35,6 +41,30 @@ def _vec3(v, like, n, what):
     if v.shape not in ((3,), (n, 3)):
         raise ValueError("%s must have shape (3,) or (%d, 3), got %s" % (what, n, tuple(v.shape)))
     return v.expand(n, 3)
+
+
+def _pad_actuator(inv, f):
+    """qfrc_actuator [n, nu] of a forces() result as [n, nv] rows (the cube's six columns zero)."""
+    torch = _torch()
+    qi, fa = inv["qfrc_inverse"], f["qfrc_actuator"]
+    return torch.cat((fa, torch.zeros((fa.shape[0], qi.shape[1] - fa.shape[1]), dtype=fa.dtype, device=fa.device)), dim=1)
+
+
+def from_inverse(inv, f):
+    """Rows for bind_applied_force from an inverse() result `inv` (it needs qfrc_inverse) and a forces() result `f` of the same state
+    (it needs qfrc_actuator): qfrc_inverse - pad(qfrc_actuator), the force that ON TOP OF THE SERVOS produces the acceleration
+    `inv` was evaluated at.  A new [n, nv] tensor."""
+    return inv["qfrc_inverse"] - _pad_actuator(inv, f)
+
+
+def fwdinv_residual(f, inv, applied=None):
+    """[n]: per-env max |qfrc_inverse - pad(qfrc_actuator) - applied|, where `inv` is inverse() evaluated at f["qacc"] and `applied`
+    the applied-force rows that were bound when `f` was computed (None: none).  At the exact forward solution it is zero: the figure
+    measures how far the solver stopped from it (the comparison of MuJoCo's mj_compareFwdInv)."""
+    r = from_inverse(inv, f)
+    if applied is not None:
+        r = r - applied
+    return r.abs().amax(dim=1)
 
 
 def quat_to_mat(q):

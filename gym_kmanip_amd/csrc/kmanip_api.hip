@@ -14,7 +14,7 @@
 
 #include "kmanip_device.hpp"
 
-#define KM_VERSION "kmanip-hip 0.38 (gfx950, f64)"
+#define KM_VERSION "kmanip-hip 0.39 (gfx950, f64)"
 
 static thread_local std::string g_create_error;
 
@@ -473,6 +473,20 @@ int kmanip_kinematics(KHandle h, const KKinDev* out, void* stream) {
       !out->qM && !out->qfrc_bias && !out->status) return 0;
   KM_ENTER(h);
   kmanip_launch_kinematics(h->dmodel, h->desc, h->st, *out, (hipStream_t)stream);
+  HIPCHK(h, hipGetLastError());
+  return 0;
+}
+
+// mj_inverse at a given acceleration: qfrc_inverse, J^T f and the contact forces at that acceleration (include/kmanip.h KInverseIn /
+// KInverseDev; kmanip_inverse.hip).  One launch; the handle is only read; either solver.
+int kmanip_inverse(KHandle h, const KInverseIn* in, const KInverseDev* out, void* stream) {
+  if (!h) { g_create_error = "kmanip_inverse: null handle"; return -1; }
+  if (!in) { h->err = "kmanip_inverse: the KInverseIn pointer is NULL"; return -1; }
+  if (!out) { h->err = "kmanip_inverse: the KInverseDev pointer is NULL"; return -1; }
+  if (!in->qacc) { h->err = "kmanip_inverse: KInverseIn::qacc is NULL"; return -1; }
+  if (!out->qfrc_inverse && !out->qfrc_constraint && !out->contact_force && !out->contact_bit && !out->contact_mask && !out->status) return 0;
+  KM_ENTER(h);
+  kmanip_launch_inverse(h->dmodel, h->desc, h->st, *in, *out, (hipStream_t)stream);
   HIPCHK(h, hipGetLastError());
   return 0;
 }

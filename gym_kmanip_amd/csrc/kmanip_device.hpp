@@ -579,6 +579,9 @@ void kmanip_launch_observe(const KDeviceModel* dm, const KModelDesc& hd, const K
 void kmanip_launch_forces(const KDeviceModel* dm, const KModelDesc& hd, const KDeviceState& st, const KForcesDev& out, hipStream_t stream);
 // kmanip_kinematics (either solver); the per-env parameter build while KDeviceState::envp is set
 void kmanip_launch_kinematics(const KDeviceModel* dm, const KModelDesc& hd, const KDeviceState& st, const KKinDev& out, hipStream_t stream);
+// kmanip_inverse (either solver); the per-env parameter build while KDeviceState::envp is set
+void kmanip_launch_inverse(const KDeviceModel* dm, const KModelDesc& hd, const KDeviceState& st, const KInverseIn& in, const KInverseDev& out,
+                           hipStream_t stream);
 // The render launchers' visual inputs (kmanip_set_visual_params / _ranges), a kernel argument of the VIS
 // kernels only -- never a KDeviceState field: the step kernels' argument stays as it is.  All NULL: the default kernels.
 //   vp       explicit values double[KM_VP_N][N], read at the render's launch

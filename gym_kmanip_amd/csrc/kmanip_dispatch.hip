@@ -38,6 +38,11 @@ void kmanip_launch_kinematics_10_16(const KDeviceModel*, const KDeviceState&, co
 void kmanip_launch_kinematics_20_32(const KDeviceModel*, const KDeviceState&, const KKinDev&, hipStream_t);
 void kmanip_launch_kinematics_ep_10_16(const KDeviceModel*, const KDeviceState&, const KKinDev&, hipStream_t);
 void kmanip_launch_kinematics_ep_20_32(const KDeviceModel*, const KDeviceState&, const KKinDev&, hipStream_t);
+// kmanip_inverse.hip: one object per class serves both solvers, default and per-env parameter builds
+void kmanip_launch_inverse_10_16(const KDeviceModel*, const KDeviceState&, const KInverseIn&, const KInverseDev&, hipStream_t);
+void kmanip_launch_inverse_20_32(const KDeviceModel*, const KDeviceState&, const KInverseIn&, const KInverseDev&, hipStream_t);
+void kmanip_launch_inverse_ep_10_16(const KDeviceModel*, const KDeviceState&, const KInverseIn&, const KInverseDev&, hipStream_t);
+void kmanip_launch_inverse_ep_20_32(const KDeviceModel*, const KDeviceState&, const KInverseIn&, const KInverseDev&, hipStream_t);
 
 void kmanip_launch_step(const KDeviceModel* dm, const KModelDesc& hd, const KDeviceState& st, const float* act, double* obs, double* reward,
                         uint8_t* done, int nchunk, int epb, hipStream_t stream) {
@@ -85,6 +90,11 @@ void kmanip_launch_forces(const KDeviceModel* dm, const KModelDesc& hd, const KD
 void kmanip_launch_kinematics(const KDeviceModel* dm, const KModelDesc& hd, const KDeviceState& st, const KKinDev& out, hipStream_t stream) {
   if (st.envp) { if (hd.nlink <= 10) kmanip_launch_kinematics_ep_10_16(dm, st, out, stream); else kmanip_launch_kinematics_ep_20_32(dm, st, out, stream); }
   else { if (hd.nlink <= 10) kmanip_launch_kinematics_10_16(dm, st, out, stream); else kmanip_launch_kinematics_20_32(dm, st, out, stream); }
+}
+void kmanip_launch_inverse(const KDeviceModel* dm, const KModelDesc& hd, const KDeviceState& st, const KInverseIn& in, const KInverseDev& out,
+                           hipStream_t stream) {
+  if (st.envp) { if (hd.nlink <= 10) kmanip_launch_inverse_ep_10_16(dm, st, in, out, stream); else kmanip_launch_inverse_ep_20_32(dm, st, in, out, stream); }
+  else { if (hd.nlink <= 10) kmanip_launch_inverse_10_16(dm, st, in, out, stream); else kmanip_launch_inverse_20_32(dm, st, in, out, stream); }
 }
 void kmanip_launch_prepare_model(KDeviceModel* dm, const KModelDesc& hd, hipStream_t stream) {
   if (hd.nlink <= 10) kmanip_launch_prepare_10_16_1(dm, stream);

@@ -231,6 +231,46 @@ class KManipEnvHip:
         self._check(self.L.kmanip_forces(self.h, C.byref(fd), self._stream()), "kmanip_forces")
         return out
 
+    # KInverseDev field -> (trailing shape in terms of nv / nc = contact slots, dtype name)
+    _INVERSE_FIELDS = {"qfrc_inverse": (("nv",), "float64"), "qfrc_constraint": (("nv",), "float64"), "contact_force": (("nc", 4), "float64"),
+                       "contact_bit": (("nc",), "int32"), "contact_mask": ((), "int32"), "status": ((), "uint8")}
+
+    def inverse(self, qacc, qpos=None, qvel=None, out=None, fields=None):
+        """kmanip_inverse: MuJoCo's mj_inverse -- the generalised force that produces the GIVEN acceleration (one launch on the current
+        stream, no synchronisation, nothing solved; the handle is only read; either solver).  qacc: float64 [n, nv] in the dof order
+        of kinematics()' qM / qfrc_bias; qpos [n, nq] / qvel [n, nv]: the state to evaluate at, None = the handle's (a given one is
+        used exactly as set_state_tensors followed by the call would use it, and the handle keeps its own).  Returns a dict of
+        device tensors:
+          qfrc_inverse [n, nv] = M qacc + qfrc_bias - qfrc_constraint: the total force (servos + applied) behind qacc;
+          qfrc_constraint [n, nv] = J^T f(qacc): friction loss, limits and contacts at that acceleration; contact_force [n, NC, 4],
+          contact_bit [n, NC] int32, contact_mask [n] int32: as forces(), at that acceleration (normal_by_bit / finger_force work on
+          the result); status [n] uint8 (1: non-finite state or qacc, everything else of the env 0, contact_bit -1)
+        `fields`: the names wanted (default: all); `out`: a dict of such tensors to fill -- only the fields it names are computed --
+        returned as given.  ctrl, the warm start and a bound applied force do not enter; gym_kmanip_amd.applied.from_inverse turns
+        the result into rows for bind_applied_force."""
+        torch = _torch()
+        from .model import contact_slots
+        dims = {"nv": self.cm.nv, "nc": contact_slots(self.cm.nlink)}
+        shapes = {name: ((self.num_envs,) + tuple(dims.get(d, d) for d in shp), getattr(torch, dt))
+                  for name, (shp, dt) in self._INVERSE_FIELDS.items()}
+        names = list(out) if out is not None else list(shapes) if fields is None else list(fields)
+        unknown = set(names) - set(shapes)
+        if unknown:
+            raise ValueError("unknown inverse field(s) %s" % sorted(unknown))
+        iv = _libmod.KInverseIn()
+        for name, t, width in (("qacc", qacc, self.cm.nv), ("qpos", qpos, self.cm.nq), ("qvel", qvel, self.cm.nv)):
+            if t is not None or name == "qacc":
+                self._check_buf(t, (self.num_envs, width), torch.float64, name)
+                setattr(iv, name, t.data_ptr())
+        if out is None:
+            out = {name: torch.empty(shapes[name][0], dtype=shapes[name][1], device=self.device) for name in names}
+        od = _libmod.KInverseDev()
+        for name, t in out.items():
+            self._check_buf(t, shapes[name][0], shapes[name][1], name)
+            setattr(od, name, t.data_ptr())
+        self._check(self.L.kmanip_inverse(self.h, C.byref(iv), C.byref(od), self._stream()), "kmanip_inverse")
+        return out
+
     def normal_by_bit(self, f):
         """[n, 32] float64: the normal force of the contact at each KM_CON_* mask bit of a forces() result (it needs contact_force
         and contact_bit), 0 where the bit is clear.  Device-side indexing only: no further C call."""

@@ -441,6 +441,45 @@ typedef struct KKinDev {
  * OUT OF SCOPE: env subsets, render snapshots, centre-of-mass Jacobians. */
 KMANIP_API int kmanip_kinematics(KHandle h, const KKinDev* out, void* stream);
 
+/* Inverse dynamics of a GIVEN acceleration: MuJoCo's mj_inverse / data.qfrc_inverse.  Per env, at the state
+ * (qpos, qvel) and for qacc in the dof order of qM / qfrc_bias:
+ *     f(qacc)         = the constraint rows' forces at x = J qacc - aref: friction-loss rows saturating at +-floss, limit rows and
+ *                       pyramid edges one-sided (-x / R for x < 0, else 0)
+ *     qfrc_constraint = J^T f(qacc)
+ *     qfrc_inverse    = M qacc + qfrc_bias - qfrc_constraint
+ * The soft constraints make f a closed-form function of qacc: nothing is solved.  There is no passive force in this model (friction
+ * loss is a constraint row), so qfrc_inverse is the TOTAL generalised force that produces qacc: at the forward solution it equals
+ * qfrc_actuator (padded with six zeros) + qfrc_applied of kmanip_forces, and bound as the applied force on top of the servos
+ * (minus their qfrc_actuator) it makes kmanip_forces return qacc, the forward problem being strictly convex.
+ * nv = nlink + 6, nq = nlink + 7, NC = KM_CONTACT_SLOTS(nlink).  All pointers are DEVICE pointers, env-major, row e = env e. */
+typedef struct KInverseIn {
+  const double* qacc;   /* [n, nv] row-major, required */
+  const double* qpos;   /* [n, nq] or NULL: the handle's state */
+  const double* qvel;   /* [n, nv] or NULL */
+} KInverseIn;
+typedef struct KInverseDev {
+  double*   qfrc_inverse;     /* [n, nv] */
+  double*   qfrc_constraint;  /* [n, nv] */
+  double*   contact_force;    /* [n, NC, 4] normal, t1, t2, torsion: the decode and sign convention of KForcesDev::contact_force */
+  int32_t*  contact_bit;      /* [n, NC], -1 = empty */
+  uint32_t* contact_mask;     /* [n] */
+  uint8_t*  status;           /* [n] 0 ok; 1 = non-finite state or qacc, or a failed factorisation of M: every other output of the env
+                               *     is 0 and every slot empty (contact_bit -1) */
+} KInverseDev;
+/* ONE kernel launch, asynchronous on `stream`: no allocation, no synchronisation, no host copy.  Any output may be NULL (that field is
+ * skipped); every field NULL: the call succeeds and does nothing.
+ * INPUTS: a given qpos / qvel replaces the handle's for this call only, used exactly as kmanip_set_state_dev followed by the call would
+ * use it (the quaternion as stored: the kinematics normalise it as they do in a step).  ctrl, the warm start and a bound applied
+ * force do not enter.  Per-env parameters (KM_EP_*) are honoured, explicit and ranges mode alike.
+ * SLOTS: order, contact_bit, contact_mask and the sign of contact_force are those of kmanip_forces, which also keeps the contact
+ * geometry (frame, point, distance): it does not depend on qacc.
+ * BOTH SOLVERS: nothing is solved, and the rows are always those of the Newton path's assembly (the primal rows of the oracle); a
+ * KM_SOLVER_PGS handle is served and returns the bits a Newton handle returns.
+ * THE HANDLE IS READ ONLY: state, warm start, counters, contact masks, scheduling predictors, sim time and random streams stay bit for
+ * bit as they were; a step after the call is the step without it.
+ * ERRORS: a NULL handle, a NULL `in`, a NULL `out` or a NULL in->qacc return nonzero with kmanip_last_error set and launch nothing. */
+KMANIP_API int kmanip_inverse(KHandle h, const KInverseIn* in, const KInverseDev* out, void* stream);
+
 /* KManipEnv.reset(seed=...) (env_base.py:219-220): re-key the cube-spawn stream.  restart_episodes != 0 also rewinds every
  * env's episode counter so that the next kmanip_reset draws episode 0 of the new seed (reset(seed=s) is then reproducible). */
 KMANIP_API int kmanip_set_seed(KHandle h, uint64_t seed, int restart_episodes);
