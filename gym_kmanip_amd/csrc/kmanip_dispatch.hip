@@ -1,102 +1,84 @@
-// kmanip_dispatch.hip -- host-side choice of the k_step / k_reset variant (link-count class x solver).
+// kmanip_dispatch.hip -- host-side choice of the per-variant object: build x link-count class x solver.
 #include "kmanip_device.hpp"
 
-#define KM_DECL(NL, G, S)                                                                                          \
-  void kmanip_launch_step_##NL##_##G##_##S(const KDeviceModel*, const KDeviceState&, const float*, double*, double*, uint8_t*, int, int, hipStream_t); \
-  void kmanip_launch_reset_##NL##_##G##_##S(const KDeviceModel*, const KDeviceState&, const uint8_t*, double*, int, hipStream_t);
-KM_DECL(10, 16, 0) KM_DECL(10, 16, 1) KM_DECL(20, 32, 0) KM_DECL(20, 32, 1)
-#undef KM_DECL
-// the per-env physics parameter builds (kmanip_dyn.hip KM_VAR_PAR): launched while KDeviceState::envp is set
-#define KM_DECL(NL, G, S)                                                                                          \
-  void kmanip_launch_step_ep_##NL##_##G##_##S(const KDeviceModel*, const KDeviceState&, const float*, double*, double*, uint8_t*, int, int, hipStream_t); \
-  void kmanip_launch_reset_ep_##NL##_##G##_##S(const KDeviceModel*, const KDeviceState&, const uint8_t*, double*, int, hipStream_t);
-KM_DECL(10, 16, 0) KM_DECL(10, 16, 1) KM_DECL(20, 32, 0) KM_DECL(20, 32, 1)
-#undef KM_DECL
-// the applied-force builds (kmanip_dyn.hip KM_VAR_FRC, with and without KM_VAR_PAR): launched while KDeviceState::qfrc_applied is set
-#define KM_DECL(NL, G, S)                                                                                          \
-  void kmanip_launch_step_frc_##NL##_##G##_##S(const KDeviceModel*, const KDeviceState&, const float*, double*, double*, uint8_t*, int, int, hipStream_t); \
-  void kmanip_launch_step_ep_frc_##NL##_##G##_##S(const KDeviceModel*, const KDeviceState&, const float*, double*, double*, uint8_t*, int, int, hipStream_t);
-KM_DECL(10, 16, 0) KM_DECL(10, 16, 1) KM_DECL(20, 32, 0) KM_DECL(20, 32, 1)
-#undef KM_DECL
-void kmanip_launch_observe_10_16_1(const KDeviceModel*, const KDeviceState&, double*, double*, hipStream_t);
-void kmanip_launch_prepare_10_16_1(KDeviceModel*, hipStream_t);
-void kmanip_launch_prepare_20_32_1(KDeviceModel*, hipStream_t);
-void kmanip_launch_observe_20_32_1(const KDeviceModel*, const KDeviceState&, double*, double*, hipStream_t);
+// the link classes (links, lanes per env), in table order: nlink <= 10 selects the first
+#define KM_CLASSES(X, B) X(B, 10, 16) X(B, 20, 32)
+// the builds of a per-variant translation unit, by the tag in its launchers' names, in table order (index = PAR + 2 * FRC): default,
+// per-env physics parameters (KM_VAR_PAR: launched while KDeviceState::envp is set), applied force (KM_VAR_FRC: while
+// KDeviceState::qfrc_applied is set), both.  A reset ignores the force, and so do kmanip_kinematics and kmanip_inverse: no force builds.
+#define KM_BUILDS_PAR(X) X() X(ep_)
+#define KM_BUILDS(X) KM_BUILDS_PAR(X) X(frc_) X(ep_frc_)
+#define KM_NAME(kind, B, NL, G, S) kmanip_launch_##kind##_##B##NL##_##G##S
 
-// kmanip_forces.hip: the Newton classes, default and per-env parameter builds
-void kmanip_launch_forces_10_16(const KDeviceModel*, const KDeviceState&, const KForcesDev&, hipStream_t);
-void kmanip_launch_forces_20_32(const KDeviceModel*, const KDeviceState&, const KForcesDev&, hipStream_t);
-void kmanip_launch_forces_ep_10_16(const KDeviceModel*, const KDeviceState&, const KForcesDev&, hipStream_t);
-void kmanip_launch_forces_ep_20_32(const KDeviceModel*, const KDeviceState&, const KForcesDev&, hipStream_t);
-void kmanip_launch_forces_frc_10_16(const KDeviceModel*, const KDeviceState&, const KForcesDev&, hipStream_t);
-void kmanip_launch_forces_frc_20_32(const KDeviceModel*, const KDeviceState&, const KForcesDev&, hipStream_t);
-void kmanip_launch_forces_ep_frc_10_16(const KDeviceModel*, const KDeviceState&, const KForcesDev&, hipStream_t);
-void kmanip_launch_forces_ep_frc_20_32(const KDeviceModel*, const KDeviceState&, const KForcesDev&, hipStream_t);
+typedef void StepFn(const KDeviceModel*, const KDeviceState&, const float*, double*, double*, uint8_t*, int, int, hipStream_t);
+typedef void ResetFn(const KDeviceModel*, const KDeviceState&, const uint8_t*, double*, int, hipStream_t);
+typedef void ObserveFn(const KDeviceModel*, const KDeviceState&, double*, double*, hipStream_t);
+typedef void PrepareFn(KDeviceModel*, hipStream_t);
+typedef void ForcesFn(const KDeviceModel*, const KDeviceState&, const KForcesDev&, hipStream_t);
+typedef void KinFn(const KDeviceModel*, const KDeviceState&, const KKinDev&, hipStream_t);
+typedef void InverseFn(const KDeviceModel*, const KDeviceState&, const KInverseIn&, const KInverseDev&, hipStream_t);
 
-// kmanip_kinematics.hip: one object per class serves both solvers, default and per-env parameter builds
-void kmanip_launch_kinematics_10_16(const KDeviceModel*, const KDeviceState&, const KKinDev&, hipStream_t);
-void kmanip_launch_kinematics_20_32(const KDeviceModel*, const KDeviceState&, const KKinDev&, hipStream_t);
-void kmanip_launch_kinematics_ep_10_16(const KDeviceModel*, const KDeviceState&, const KKinDev&, hipStream_t);
-void kmanip_launch_kinematics_ep_20_32(const KDeviceModel*, const KDeviceState&, const KKinDev&, hipStream_t);
-// kmanip_inverse.hip: one object per class serves both solvers, default and per-env parameter builds
-void kmanip_launch_inverse_10_16(const KDeviceModel*, const KDeviceState&, const KInverseIn&, const KInverseDev&, hipStream_t);
-void kmanip_launch_inverse_20_32(const KDeviceModel*, const KDeviceState&, const KInverseIn&, const KInverseDev&, hipStream_t);
-void kmanip_launch_inverse_ep_10_16(const KDeviceModel*, const KDeviceState&, const KInverseIn&, const KInverseDev&, hipStream_t);
-void kmanip_launch_inverse_ep_20_32(const KDeviceModel*, const KDeviceState&, const KInverseIn&, const KInverseDev&, hipStream_t);
+// kmanip_dyn.hip: step per solver in every build, reset per solver in the parameter builds; observe and prepare are
+// solver-independent, one copy per class (in the default Newton object)
+#define KM_STEP_ROW(B, NL, G) {KM_NAME(step, B, NL, G, _0), KM_NAME(step, B, NL, G, _1)},
+#define KM_RESET_ROW(B, NL, G) {KM_NAME(reset, B, NL, G, _0), KM_NAME(reset, B, NL, G, _1)},
+#define KM_OBSERVE_ROW(B, NL, G) KM_NAME(observe, B, NL, G, _1),
+#define KM_PREPARE_ROW(B, NL, G) KM_NAME(prepare, B, NL, G, _1),
+// kmanip_forces.hip (the Newton classes, every build), kmanip_kinematics.hip and kmanip_inverse.hip (one object per class serves both
+// solvers, the parameter builds)
+#define KM_FORCES_ROW(B, NL, G) KM_NAME(forces, B, NL, G, ),
+#define KM_KIN_ROW(B, NL, G) KM_NAME(kinematics, B, NL, G, ),
+#define KM_INVERSE_ROW(B, NL, G) KM_NAME(inverse, B, NL, G, ),
+
+#define KM_DECL_SOLVERS(Fn, kind, B, NL, G) Fn KM_NAME(kind, B, NL, G, _0), KM_NAME(kind, B, NL, G, _1);
+#define KM_DECL_FRC(B, NL, G) KM_DECL_SOLVERS(StepFn, step, B, NL, G) ForcesFn KM_NAME(forces, B, NL, G, );
+#define KM_DECL_PAR(B, NL, G) KM_DECL_SOLVERS(ResetFn, reset, B, NL, G) KinFn KM_NAME(kinematics, B, NL, G, ); InverseFn KM_NAME(inverse, B, NL, G, );
+#define KM_DECL_ONCE(B, NL, G) ObserveFn KM_NAME(observe, B, NL, G, _1); PrepareFn KM_NAME(prepare, B, NL, G, _1);
+#define KM_DECL_BUILD_FRC(B) KM_CLASSES(KM_DECL_FRC, B)
+#define KM_DECL_BUILD_PAR(B) KM_CLASSES(KM_DECL_PAR, B)
+KM_BUILDS(KM_DECL_BUILD_FRC) KM_BUILDS_PAR(KM_DECL_BUILD_PAR) KM_CLASSES(KM_DECL_ONCE, )
+
+// the tables: [build][class][solver], [build][class] or [class]
+#define KM_STEP_BUILD(B) {KM_CLASSES(KM_STEP_ROW, B)},
+#define KM_RESET_BUILD(B) {KM_CLASSES(KM_RESET_ROW, B)},
+#define KM_FORCES_BUILD(B) {KM_CLASSES(KM_FORCES_ROW, B)},
+#define KM_KIN_BUILD(B) {KM_CLASSES(KM_KIN_ROW, B)},
+#define KM_INVERSE_BUILD(B) {KM_CLASSES(KM_INVERSE_ROW, B)},
+static constexpr StepFn* step_tab[4][2][2] = {KM_BUILDS(KM_STEP_BUILD)};
+static constexpr ResetFn* reset_tab[2][2][2] = {KM_BUILDS_PAR(KM_RESET_BUILD)};
+static constexpr ObserveFn* observe_tab[2] = {KM_CLASSES(KM_OBSERVE_ROW, )};
+static constexpr PrepareFn* prepare_tab[2] = {KM_CLASSES(KM_PREPARE_ROW, )};
+static constexpr ForcesFn* forces_tab[4][2] = {KM_BUILDS(KM_FORCES_BUILD)};
+static constexpr KinFn* kin_tab[2][2] = {KM_BUILDS_PAR(KM_KIN_BUILD)};
+static constexpr InverseFn* inverse_tab[2][2] = {KM_BUILDS_PAR(KM_INVERSE_BUILD)};
+
+static int cls(const KModelDesc& hd) { return hd.nlink <= 10 ? 0 : 1; }
+static int newton(const KModelDesc& hd) { return hd.solver == KM_SOLVER_NEWTON ? 1 : 0; }
+static int par(const KDeviceState& st) { return st.envp ? 1 : 0; }
+static int frc(const KDeviceState& st) { return st.qfrc_applied ? 2 : 0; }
 
 void kmanip_launch_step(const KDeviceModel* dm, const KModelDesc& hd, const KDeviceState& st, const float* act, double* obs, double* reward,
                         uint8_t* done, int nchunk, int epb, hipStream_t stream) {
-  const bool newton = hd.solver == KM_SOLVER_NEWTON;
-  if (st.qfrc_applied && st.envp) {
-    if (hd.nlink <= 10) { if (newton) kmanip_launch_step_ep_frc_10_16_1(dm, st, act, obs, reward, done, nchunk, epb, stream); else kmanip_launch_step_ep_frc_10_16_0(dm, st, act, obs, reward, done, nchunk, epb, stream); }
-    else { if (newton) kmanip_launch_step_ep_frc_20_32_1(dm, st, act, obs, reward, done, nchunk, epb, stream); else kmanip_launch_step_ep_frc_20_32_0(dm, st, act, obs, reward, done, nchunk, epb, stream); }
-    return;
-  }
-  if (st.qfrc_applied) {
-    if (hd.nlink <= 10) { if (newton) kmanip_launch_step_frc_10_16_1(dm, st, act, obs, reward, done, nchunk, epb, stream); else kmanip_launch_step_frc_10_16_0(dm, st, act, obs, reward, done, nchunk, epb, stream); }
-    else { if (newton) kmanip_launch_step_frc_20_32_1(dm, st, act, obs, reward, done, nchunk, epb, stream); else kmanip_launch_step_frc_20_32_0(dm, st, act, obs, reward, done, nchunk, epb, stream); }
-    return;
-  }
-  if (st.envp) {
-    if (hd.nlink <= 10) { if (newton) kmanip_launch_step_ep_10_16_1(dm, st, act, obs, reward, done, nchunk, epb, stream); else kmanip_launch_step_ep_10_16_0(dm, st, act, obs, reward, done, nchunk, epb, stream); }
-    else { if (newton) kmanip_launch_step_ep_20_32_1(dm, st, act, obs, reward, done, nchunk, epb, stream); else kmanip_launch_step_ep_20_32_0(dm, st, act, obs, reward, done, nchunk, epb, stream); }
-    return;
-  }
-  if (hd.nlink <= 10) { if (newton) kmanip_launch_step_10_16_1(dm, st, act, obs, reward, done, nchunk, epb, stream); else kmanip_launch_step_10_16_0(dm, st, act, obs, reward, done, nchunk, epb, stream); }
-  else { if (newton) kmanip_launch_step_20_32_1(dm, st, act, obs, reward, done, nchunk, epb, stream); else kmanip_launch_step_20_32_0(dm, st, act, obs, reward, done, nchunk, epb, stream); }
+  step_tab[par(st) + frc(st)][cls(hd)][newton(hd)](dm, st, act, obs, reward, done, nchunk, epb, stream);
 }
 void kmanip_launch_reset(const KDeviceModel* dm, const KModelDesc& hd, const KDeviceState& st, const uint8_t* mask, double* obs,
                          int epb, hipStream_t stream) {
-  const bool newton = hd.solver == KM_SOLVER_NEWTON;
-  if (st.envp) {
-    if (hd.nlink <= 10) { if (newton) kmanip_launch_reset_ep_10_16_1(dm, st, mask, obs, epb, stream); else kmanip_launch_reset_ep_10_16_0(dm, st, mask, obs, epb, stream); }
-    else { if (newton) kmanip_launch_reset_ep_20_32_1(dm, st, mask, obs, epb, stream); else kmanip_launch_reset_ep_20_32_0(dm, st, mask, obs, epb, stream); }
-    return;
-  }
-  if (hd.nlink <= 10) { if (newton) kmanip_launch_reset_10_16_1(dm, st, mask, obs, epb, stream); else kmanip_launch_reset_10_16_0(dm, st, mask, obs, epb, stream); }
-  else { if (newton) kmanip_launch_reset_20_32_1(dm, st, mask, obs, epb, stream); else kmanip_launch_reset_20_32_0(dm, st, mask, obs, epb, stream); }
+  reset_tab[par(st)][cls(hd)][newton(hd)](dm, st, mask, obs, epb, stream);
 }
 void kmanip_launch_observe(const KDeviceModel* dm, const KModelDesc& hd, const KDeviceState& st, double* obs, double* reward,
                            hipStream_t stream) {
-  if (hd.nlink <= 10) kmanip_launch_observe_10_16_1(dm, st, obs, reward, stream);
-  else kmanip_launch_observe_20_32_1(dm, st, obs, reward, stream);
+  observe_tab[cls(hd)](dm, st, obs, reward, stream);
 }
 void kmanip_launch_forces(const KDeviceModel* dm, const KModelDesc& hd, const KDeviceState& st, const KForcesDev& out, hipStream_t stream) {
-  if (st.qfrc_applied && st.envp) { if (hd.nlink <= 10) kmanip_launch_forces_ep_frc_10_16(dm, st, out, stream); else kmanip_launch_forces_ep_frc_20_32(dm, st, out, stream); }
-  else if (st.qfrc_applied) { if (hd.nlink <= 10) kmanip_launch_forces_frc_10_16(dm, st, out, stream); else kmanip_launch_forces_frc_20_32(dm, st, out, stream); }
-  else if (st.envp) { if (hd.nlink <= 10) kmanip_launch_forces_ep_10_16(dm, st, out, stream); else kmanip_launch_forces_ep_20_32(dm, st, out, stream); }
-  else { if (hd.nlink <= 10) kmanip_launch_forces_10_16(dm, st, out, stream); else kmanip_launch_forces_20_32(dm, st, out, stream); }
+  forces_tab[par(st) + frc(st)][cls(hd)](dm, st, out, stream);
 }
 void kmanip_launch_kinematics(const KDeviceModel* dm, const KModelDesc& hd, const KDeviceState& st, const KKinDev& out, hipStream_t stream) {
-  if (st.envp) { if (hd.nlink <= 10) kmanip_launch_kinematics_ep_10_16(dm, st, out, stream); else kmanip_launch_kinematics_ep_20_32(dm, st, out, stream); }
-  else { if (hd.nlink <= 10) kmanip_launch_kinematics_10_16(dm, st, out, stream); else kmanip_launch_kinematics_20_32(dm, st, out, stream); }
+  kin_tab[par(st)][cls(hd)](dm, st, out, stream);
 }
 void kmanip_launch_inverse(const KDeviceModel* dm, const KModelDesc& hd, const KDeviceState& st, const KInverseIn& in, const KInverseDev& out,
                            hipStream_t stream) {
-  if (st.envp) { if (hd.nlink <= 10) kmanip_launch_inverse_ep_10_16(dm, st, in, out, stream); else kmanip_launch_inverse_ep_20_32(dm, st, in, out, stream); }
-  else { if (hd.nlink <= 10) kmanip_launch_inverse_10_16(dm, st, in, out, stream); else kmanip_launch_inverse_20_32(dm, st, in, out, stream); }
+  inverse_tab[par(st)][cls(hd)](dm, st, in, out, stream);
 }
 void kmanip_launch_prepare_model(KDeviceModel* dm, const KModelDesc& hd, hipStream_t stream) {
-  if (hd.nlink <= 10) kmanip_launch_prepare_10_16_1(dm, stream);
-  else kmanip_launch_prepare_20_32_1(dm, stream);
+  prepare_tab[cls(hd)](dm, stream);
 }

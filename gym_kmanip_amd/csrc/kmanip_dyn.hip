@@ -31,63 +31,13 @@
 //   PGS              : per-contact block form on the 4x4 Gram matrix (algebraically the same row order)
 #include "kmanip_ik_coop.hpp"
 #include <stdlib.h>
-// KM_VAR_PAR=1: the per-env physics parameter build of a variant (kmanip_set_env_params).  The Makefile
-// compiles this file a second time per variant with it; those kernels live in their own namespace and are launched only while a
-// handle has parameters; the default objects take none of the parameter code paths (same instruction counts, registers,
-// scratch and LDS as before).
-#ifndef KM_VAR_PAR
-#define KM_VAR_PAR 0
-#endif
-// KM_VAR_FRC=1: the applied-force build (kmanip_bind_applied_force), orthogonal to KM_VAR_PAR and built by the
-// same rule: a third and a fourth compilation per variant, kernels k_step_frc / k_step_ep_frc in namespaces of their own, launched
-// only while a handle has a force buffer bound.  Step kernels only: a reset never reads the buffer.
-#ifndef KM_VAR_FRC
-#define KM_VAR_FRC 0
-#endif
-#if KM_VAR_PAR && KM_VAR_FRC
-namespace km_envp_frc {
-#define KM_K_STEP k_step_ep_frc
-#define KM_K_RESET k_reset_ep_frc     // (never instantiated)
-#elif KM_VAR_FRC
-namespace km_frc {
-#define KM_K_STEP k_step_frc
-#define KM_K_RESET k_reset_frc        // (never instantiated)
-#elif KM_VAR_PAR
-namespace km_envp {
-#define KM_K_STEP k_step_ep           // (kernel names of their own: profiles and tools/kernel_resources.py tell the builds apart)
-#define KM_K_RESET k_reset_ep
-#else
-#define KM_K_STEP k_step
-#define KM_K_RESET k_reset
-#endif
-// tree loops over link candidates (static addresses + a mask bit each): fully unrolled for the 10-link model, where all the
-// loads can be in flight together; the 20-link models sit at the 512-register limit and keep them rolled
-#define KM_TREE_UNROLL(NL) NL <= 10 ? NL : 1
-
-// Work units one Newton iteration of each kind adds to Ws::work (roughly kilo-clocks on the two-arm kernels; only their ORDER
-// matters: k_sort_envs ranks the envs by them).  Two-arm kernels only: the single-arm headline launch is one residency round.
-// (measured on the single-arm kernel, tests/tools/wave_times.py with -DKM_WORK_COUNTERS_ALL: wave cycles = 375 k + 308 x the
-// slowest env's work units + 13.8 k x the largest IK evaluation count, R^2 0.66; the counters cost it 1.5 %, so it ships without)
-#ifdef KM_WORK_COUNTERS_ALL
-#define KM_WORK_COUNTERS(NL) true
-#else
-#define KM_WORK_COUNTERS(NL) ((NL) > 10)
-#endif
-#define KM_WORK_ALL 40
-#define KM_WORK_ARM 14
-#define KM_WORK_PLAIN 3
-#define KM_WORK_CUBE 5
-// the device code of one step, by phase (textual order matters: each part uses the ones before it)
-#include "kmanip_dyn_ws.hpp"
-#include "kmanip_dyn_tree.hpp"
-#include "kmanip_dyn_constraints.hpp"
-#include "kmanip_dyn_newton.hpp"
-#include "kmanip_dyn_env.hpp"
+// the build macros (KM_VAR_*, the per-build kernel and launcher names), the variant namespace and the device code of one step, by phase
+#include "kmanip_dyn_variant.hpp"
 // ---------------------------------------------------------------------------------------------
 // EPB = envs per single-wave workgroup (<= 64 / G).  Fewer envs per wave = more waves per SIMD: the kernel is
 // bound by LDS/dependent-issue latency, so waves of different envs hide each other's waits.
 template <int NL, int G, int SOLVER, int EPB, bool CHUNK>
-__global__ __launch_bounds__(64) void KM_K_STEP(const KDeviceModel* __restrict__ dm, KDeviceState st, const float* __restrict__ act,
+__global__ __launch_bounds__(64) void KM_KERNEL(k_step)(const KDeviceModel* __restrict__ dm, KDeviceState st, const float* __restrict__ act,
                                              double* __restrict__ obs, double* __restrict__ reward, uint8_t* __restrict__ done,
                                              int nchunk) {
   constexpr int NV = Dim<NL>::NV, NQ = Dim<NL>::NQ;
@@ -121,7 +71,7 @@ __global__ __launch_bounds__(64) void KM_K_STEP(const KDeviceModel* __restrict__
   Ws<NL>& w = ws[grp];
   real invm = 0;                       // diagonal of M^-1 for the cube dof owned by this lane (KM_VAR_PAR: set by ep_load below)
 #if !KM_VAR_PAR
-  if (sub >= NL && sub < NV) invm = sub < NL + 3 ? 1.0 / m->cube_mass : 1.0 / m->cube_inertia[sub - NL - 3];
+  invm = cube_invm<NL>(m, sub);
 #endif
   Prof pf;
   pf.start();
@@ -259,11 +209,8 @@ __global__ __launch_bounds__(64) void KM_K_STEP(const KDeviceModel* __restrict__
 
 // KManipEnvSim.k_reset for the envs selected by mask (NULL = all)
 template <int NL, int G, int SOLVER, int EPB>
-__global__ __launch_bounds__(64) void KM_K_RESET(const KDeviceModel* __restrict__ dm, KDeviceState st,
+__global__ __launch_bounds__(64) void KM_KERNEL(k_reset)(const KDeviceModel* __restrict__ dm, KDeviceState st,
                                               const uint8_t* __restrict__ mask, double* __restrict__ obs) {
-#if !KM_VAR_PAR
-  constexpr int NV = Dim<NL>::NV;
-#endif
   __shared__ Ws<NL> ws[EPB];
   __shared__ LModel<NL> lm;
   stage_model<NL>(lm, dm);
@@ -275,11 +222,7 @@ __global__ __launch_bounds__(64) void KM_K_RESET(const KDeviceModel* __restrict_
   Ws<NL>& w = ws[grp];
   CReg<NL> cr;
   real invm = 0;
-#if KM_VAR_PAR
-  ep_load<NL>(w, dm, st, env, sub, invm);
-#else
-  if (sub >= NL && sub < NV) invm = sub < NL + 3 ? 1.0 / m->cube_mass : 1.0 / m->cube_inertia[sub - NL - 3];
-#endif
+  env_invm<NL>(w, dm, st, env, sub, invm);
   int episode = st.episode[env] + 1;
   Prof pf;
   pf.start();
@@ -297,21 +240,17 @@ __global__ __launch_bounds__(64) void k_observe(const KDeviceModel* __restrict__
                                                 double* __restrict__ reward) {
   __shared__ Ws<NL> ws[EPB];
   __shared__ LModel<NL> lm;
-  stage_model<NL>(lm, dm);
   const KModelDesc* m = &dm->d;
   const int lane = threadIdx.x, grp = lane / G, sub = lane % G;
-  const int env = xcd_block(blockIdx.x, gridDim.x) * EPB + grp;
-  if (grp >= EPB || env >= st.num_envs) return;
+  int env;
+  if (!query_env<NL, EPB>(lm, dm, st, grp, env)) return;
   Ws<NL>& w = ws[grp];
-  init_ws<NL>(w, sub);
-  load_state<NL, G>(w, st, env, sub);
+  real invm = 0;
+  query_load<NL, G>(w, dm, st, env, sub, invm);
   GSYNC();
   // a state restored from a diverged checkpoint: what k_step reports for such an env -- zero observation and reward, no contacts
   // (the kinematics of a non-finite state would put garbage into the mask the diagnostics and the next cost sort read)
-  int lb = 0;
-  for (int i = sub; i < Dim<NL>::NQ; i += G) lb |= !isfinite(w.qpos[i]);
-  for (int i = sub; i < Dim<NL>::NV; i += G) lb |= !isfinite(w.qvel[i]);
-  if (gor<G>(lb)) {
+  if (state_nonfinite<NL, G>(w, sub)) {
     if (obs) for (int i = sub; i < m->obs_dim; i += G) obs[(size_t)env * m->obs_dim + i] = 0;
     if (sub == 0) { st.contact_mask[env] = 0; if (reward) reward[env] = 0; }
     return;
@@ -326,14 +265,14 @@ __global__ __launch_bounds__(64) void k_observe(const KDeviceModel* __restrict__
 template <int NL, int G, int SOLVER, int EPB>
 static void launch_step_e(const KDeviceModel* dm, const KDeviceState& st, const float* act, double* obs, double* reward, uint8_t* done, int nchunk, hipStream_t stream) {
   if (nchunk > 1) {
-    if constexpr (EPB == 64 / G) hipLaunchKernelGGL((KM_K_STEP<NL, G, SOLVER, EPB, true>), dim3((st.num_envs + EPB - 1) / EPB), dim3(64), 0, stream, dm, st, act, obs, reward, done, nchunk);
+    if constexpr (EPB == 64 / G) hipLaunchKernelGGL((KM_KERNEL(k_step)<NL, G, SOLVER, EPB, true>), dim3((st.num_envs + EPB - 1) / EPB), dim3(64), 0, stream, dm, st, act, obs, reward, done, nchunk);
   } else {
-    hipLaunchKernelGGL((KM_K_STEP<NL, G, SOLVER, EPB, false>), dim3((st.num_envs + EPB - 1) / EPB), dim3(64), 0, stream, dm, st, act, obs, reward, done, 1);
+    hipLaunchKernelGGL((KM_KERNEL(k_step)<NL, G, SOLVER, EPB, false>), dim3((st.num_envs + EPB - 1) / EPB), dim3(64), 0, stream, dm, st, act, obs, reward, done, 1);
   }
 }
 template <int NL, int G, int SOLVER, int EPB>
 static void launch_reset_e(const KDeviceModel* dm, const KDeviceState& st, const uint8_t* mask, double* obs, hipStream_t stream) {
-  hipLaunchKernelGGL((KM_K_RESET<NL, G, SOLVER, EPB>), dim3((st.num_envs + EPB - 1) / EPB), dim3(64), 0, stream, dm, st, mask, obs);
+  hipLaunchKernelGGL((KM_KERNEL(k_reset)<NL, G, SOLVER, EPB>), dim3((st.num_envs + EPB - 1) / EPB), dim3(64), 0, stream, dm, st, mask, obs);
 }
 template <int NL, int G, int SOLVER>
 static void launch_step_t(const KDeviceModel* dm, const KDeviceState& st, const float* act, double* obs, double* reward, uint8_t* done, int nchunk,
@@ -364,45 +303,24 @@ static void launch_observe_t(const KDeviceModel* dm, const KDeviceState& st, dou
   constexpr int EPB = 64 / G;
   hipLaunchKernelGGL((k_observe<NL, G, EPB>), dim3((st.num_envs + EPB - 1) / EPB), dim3(64), 0, stream, dm, st, obs, reward);
 }
-#if KM_VAR_PAR && KM_VAR_FRC
-}  // namespace km_envp_frc
-using namespace km_envp_frc;
-#define KM_LAUNCH_STEP kmanip_launch_step_ep_frc_
-#elif KM_VAR_FRC
-}  // namespace km_frc
-using namespace km_frc;
-#define KM_LAUNCH_STEP kmanip_launch_step_frc_
-#elif KM_VAR_PAR
-}  // namespace km_envp
-using namespace km_envp;
-#define KM_LAUNCH_STEP kmanip_launch_step_ep_
-#define KM_LAUNCH_RESET kmanip_launch_reset_ep_
-#else
-#define KM_LAUNCH_STEP kmanip_launch_step_
-#define KM_LAUNCH_RESET kmanip_launch_reset_
-#endif
+KM_VARIANT_END
 // ---- one (NL, G, SOLVER[, PAR][, FRC]) variant per translation unit (the Makefile compiles this file sixteen times, in parallel)
-#ifndef KM_VAR_NL
-#error "compile with -DKM_VAR_NL=<10|20> -DKM_VAR_G=<16|32> -DKM_VAR_SOLVER=<0|1>"
-#endif
-#define KM_CAT4_(a, b, c, d) a##b##_##c##_##d
-#define KM_CAT4(a, b, c, d) KM_CAT4_(a, b, c, d)
-void KM_CAT4(KM_LAUNCH_STEP, KM_VAR_NL, KM_VAR_G, KM_VAR_SOLVER)(const KDeviceModel* dm, const KDeviceState& st, const float* act,
+void KM_LAUNCHER3(step)(const KDeviceModel* dm, const KDeviceState& st, const float* act,
                                                                     double* obs, double* reward, uint8_t* done, int nchunk, int epb,
                                                                     hipStream_t stream) {
   launch_step_t<KM_VAR_NL, KM_VAR_G, KM_VAR_SOLVER>(dm, st, act, obs, reward, done, nchunk, epb, stream);
 }
 #if !KM_VAR_FRC      // (a reset ignores the applied force: the force builds have no reset kernel)
-void KM_CAT4(KM_LAUNCH_RESET, KM_VAR_NL, KM_VAR_G, KM_VAR_SOLVER)(const KDeviceModel* dm, const KDeviceState& st,
+void KM_LAUNCHER3(reset)(const KDeviceModel* dm, const KDeviceState& st,
                                                                      const uint8_t* mask, double* obs, int epb, hipStream_t stream) {
   launch_reset_t<KM_VAR_NL, KM_VAR_G, KM_VAR_SOLVER>(dm, st, mask, obs, epb, stream);
 }
 #endif
 #if KM_VAR_SOLVER == 1 && !KM_VAR_PAR && !KM_VAR_FRC      // (solver-independent: one copy per link-count class)
-void KM_CAT4(kmanip_launch_prepare_, KM_VAR_NL, KM_VAR_G, KM_VAR_SOLVER)(KDeviceModel* dm, hipStream_t stream) {
+void KM_LAUNCHER3(prepare)(KDeviceModel* dm, hipStream_t stream) {
   hipLaunchKernelGGL((k_prepare_model<KM_VAR_NL>), dim3(1), dim3(64), 0, stream, dm);
 }
-void KM_CAT4(kmanip_launch_observe_, KM_VAR_NL, KM_VAR_G, KM_VAR_SOLVER)(const KDeviceModel* dm, const KDeviceState& st, double* obs,
+void KM_LAUNCHER3(observe)(const KDeviceModel* dm, const KDeviceState& st, double* obs,
                                                                        double* reward, hipStream_t stream) {
   launch_observe_t<KM_VAR_NL, KM_VAR_G>(dm, st, obs, reward, stream);
 }

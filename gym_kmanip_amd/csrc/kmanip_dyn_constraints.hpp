@@ -1,4 +1,4 @@
-// kmanip_dyn_constraints.hpp -- part of kmanip_dyn.hip, included only by it (inside its variant namespace): frames, collision, impedance, constraint rows and the PGS solver.
+// kmanip_dyn_constraints.hpp -- one of the phase headers kmanip_dyn_variant.hpp includes (inside the variant namespace) into each per-variant translation unit: frames, collision, impedance, constraint rows and the PGS solver.
 #pragma once
 // mju_makeFrame
 __device__ __forceinline__ void make_frame(real* fr) {

@@ -1,4 +1,4 @@
-// kmanip_dyn_env.hpp -- part of kmanip_dyn.hip, included only by it (inside its variant namespace): step phases, obs / reward, per-env parameters, reset, state load / store, model staging.
+// kmanip_dyn_env.hpp -- one of the phase headers kmanip_dyn_variant.hpp includes (inside the variant namespace) into each per-variant translation unit: step phases, obs / reward, per-env parameters, reset, state load / store, model staging, the entry and the slot rows of the state queries.
 #pragma once
 // everything mj_step1 computes that mj_step2 needs, at the state held in w.qpos / w.qvel
 template <int NL, int G, int SOLVER>
@@ -361,4 +361,88 @@ __device__ __forceinline__ real env_reward(Ws<NL>& w, const KModelDesc* m, int s
     if (!w.touch_ct) rew += m->reward_lift_cube;
   }
   return rew;
+}
+
+// ---- the state queries (k_observe, kmanip_forces.hip, kmanip_kinematics.hip, kmanip_inverse.hip) and what k_step / k_reset share with them
+// this lane's diagonal of M^-1 for the cube dof it owns (0 on every other lane), from the model's values ...
+template <int NL>
+__device__ __forceinline__ real cube_invm(const KModelDesc* m, int sub) {
+  real invm = 0;
+  if (sub >= NL && sub < Dim<NL>::NV) invm = sub < NL + 3 ? 1.0 / m->cube_mass : 1.0 / m->cube_inertia[sub - NL - 3];
+  return invm;
+}
+// ... or, KM_VAR_PAR builds, from the env's own, staged into Ws::ep with it
+template <int NL>
+__device__ __forceinline__ void env_invm(Ws<NL>& w, const KDeviceModel* dm, const KDeviceState& st, int env, int sub, real& invm) {
+#if KM_VAR_PAR
+  ep_load<NL>(w, dm, st, env, sub, invm);
+#else
+  invm = cube_invm<NL>(&dm->d, sub);
+#endif
+}
+// A non-finite loaded state, or a further reason `lb` of this lane's: the same flag on every lane of the group.  k_step reports such
+// an env as diverged; a query gives status 1 and computes nothing (the kinematics of a non-finite state are garbage).
+template <int NL, int G>
+__device__ __forceinline__ int state_nonfinite(const Ws<NL>& w, int sub, int lb = 0) {
+  for (int i = sub; i < Dim<NL>::NQ; i += G) lb |= !isfinite(w.qpos[i]);
+  for (int i = sub; i < Dim<NL>::NV; i += G) lb |= !isfinite(w.qvel[i]);
+  return gor<G>(lb);
+}
+// The entry of a query kernel, 64 / G envs per single-wave workgroup, in two parts around the exit of a group without an env (the
+// kernel's own return: the whole group exits together).  query_env: the model staged (every lane: it ends in a workgroup barrier),
+// lane group -> env behind the XCD-aware block mapping; false = no env.
+template <int NL, int EPB>
+__device__ __forceinline__ bool query_env(LModel<NL>& lm, const KDeviceModel* dm, const KDeviceState& st, int grp, int& env) {
+  stage_model<NL>(lm, dm);
+  env = xcd_block(blockIdx.x, gridDim.x) * EPB + grp;
+  return grp < EPB && env < st.num_envs;
+}
+// query_load: the workspace initialised, the env's parameters (invm) and its state loaded (load_state: with float32(ctrl)).  The
+// caller synchronises the group (GSYNC) before it reads the state.  (k_inverse spells the three calls out: it requests the
+// caller's row between them.)
+template <int NL, int G>
+__device__ __forceinline__ void query_load(Ws<NL>& w, const KDeviceModel* dm, const KDeviceState& st, int env, int sub, real& invm) {
+  init_ws<NL>(w, sub);
+  env_invm<NL>(w, dm, st, env, sub, invm);
+  load_state<NL, G>(w, st, env, sub);
+}
+// which KM_CON_* bit sits in contact slot c (< NC), -1 = none: corner slots hold the penetrating corners in corner order (the mask's
+// low byte has exactly the kept ones), sphere slots name their sphere (sph = Ws::slot_sph of the slot)
+template <int NL>
+__device__ __forceinline__ int slot_contact_bit(int c, uint32_t act, uint32_t mask, int sph) {
+  int bit = -1;
+  if ((act >> c) & 1u) {
+    if (c < 4) {
+      uint32_t mm = mask & KM_CON_ANY_CUBE_TABLE;
+      for (int k = 0; k < c; k++) mm &= mm - 1u;
+      bit = __ffs((int)mm) - 1;
+    } else bit = (c < 4 + Dim<NL>::NSS ? 8 : 20) + sph;
+  }
+  return bit;
+}
+// one env's slot rows of a query's outputs, lane = slot: the force and the bit and, for KForcesDev, the contact geometry.
+// !ok or an empty slot (bit < 0): zeros, bit -1.
+template <int NL, class Out>
+__device__ __forceinline__ void write_slot_rows(const Out& out, size_t e, int sub, bool ok, const real (&F)[4], int bit,
+                                                const real* fr = nullptr, const real* cp = nullptr, real dist = 0) {
+  constexpr int NC = Dim<NL>::NC;
+  if (sub >= NC) return;
+  const size_t s = e * NC + sub;
+  const bool on = ok && bit >= 0;
+  if (out.contact_force) {
+#pragma unroll
+    for (int k = 0; k < 4; k++) out.contact_force[s * 4 + k] = on ? F[k] : 0.0;
+  }
+  if (out.contact_bit) out.contact_bit[s] = on ? bit : -1;
+  if constexpr (std::is_same<Out, KForcesDev>::value) {
+    if (out.contact_frame) {
+#pragma unroll
+      for (int k = 0; k < 9; k++) out.contact_frame[s * 9 + k] = on ? fr[k] : 0.0;
+    }
+    if (out.contact_pos) {
+#pragma unroll
+      for (int k = 0; k < 3; k++) out.contact_pos[s * 3 + k] = on ? cp[k] : 0.0;
+    }
+    if (out.contact_dist) out.contact_dist[s] = on ? dist : 0.0;
+  }
 }

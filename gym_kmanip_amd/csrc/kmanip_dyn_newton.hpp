@@ -1,4 +1,4 @@
-// kmanip_dyn_newton.hpp -- part of kmanip_dyn.hip, included only by it (inside its variant namespace): Cholesky row kernels and the Newton solver.
+// kmanip_dyn_newton.hpp -- one of the phase headers kmanip_dyn_variant.hpp includes (inside the variant namespace) into each per-variant translation unit: Cholesky row kernels and the Newton solver.
 #pragma once
 // =============================================================================================
 // Newton solver (MuJoCo's default solver, i.e. what the reference actually runs: no <option> element in

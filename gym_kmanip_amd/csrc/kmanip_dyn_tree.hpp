@@ -1,4 +1,4 @@
-// kmanip_dyn_tree.hpp -- part of kmanip_dyn.hip, included only by it (inside its variant namespace): kinematic tree: FK, composite inertias, mass matrix, bias forces, M^-1.
+// kmanip_dyn_tree.hpp -- one of the phase headers kmanip_dyn_variant.hpp includes (inside the variant namespace) into each per-variant translation unit: kinematic tree: FK, composite inertias, mass matrix, bias forces, M^-1.
 #pragma once
 // mj_kinematics, all links at once: lane i builds link i's transform in its parent (constant rotation times the
 // planar joint rotation; one sincos per lane instead of NL in a row), then ceil(log2(depth)) rounds of pointer

@@ -1,9 +1,5 @@
-// kmanip_dyn_ws.hpp -- part of kmanip_dyn.hip, included only by it (inside its variant namespace): per-env workspace (Dim, EnvP, LModel, ConRec, Ws, SlotC, CReg) and the lane-group reductions.
+// kmanip_dyn_ws.hpp -- one of the phase headers kmanip_dyn_variant.hpp includes (inside the variant namespace) into each per-variant translation unit: per-env workspace (Dim, EnvP, LModel, ConRec, Ws, SlotC, CReg) and the lane-group reductions.
 #pragma once
-// KM_VAR_FRC=1: the applied-force build of a variant (kmanip_bind_applied_force), orthogonal to KM_VAR_PAR
-#ifndef KM_VAR_FRC
-#define KM_VAR_FRC 0
-#endif
 template <int NL> struct Dim {
   static constexpr int NV = NL + 6;
   static constexpr int NQ = NL + 7;

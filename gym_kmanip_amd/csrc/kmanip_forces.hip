@@ -13,41 +13,7 @@
 // parameter builds, 64 / G envs per wave like k_observe.  The handle is read only: nothing of KDeviceState is written.
 #include "kmanip_ik_coop.hpp"
 #include <stdlib.h>
-// ---- the build macros of kmanip_dyn.hip (the headers below read them); KM_VAR_SOLVER is always 1 here
-#ifndef KM_VAR_PAR
-#define KM_VAR_PAR 0
-#endif
-// KM_VAR_FRC=1: the applied-force builds (kmanip_bind_applied_force), as in kmanip_dyn.hip
-#ifndef KM_VAR_FRC
-#define KM_VAR_FRC 0
-#endif
-#if KM_VAR_PAR && KM_VAR_FRC
-namespace km_envp_frc {
-#define KM_K_FORCES k_frc_forces_ep
-#elif KM_VAR_FRC
-namespace km_frc {
-#define KM_K_FORCES k_frc_forces      // ("frc" first: tools that list the k_forces kernels by name keep seeing the default four)
-#elif KM_VAR_PAR
-namespace km_envp {
-#define KM_K_FORCES k_forces_ep
-#else
-#define KM_K_FORCES k_forces
-#endif
-#define KM_TREE_UNROLL(NL) NL <= 10 ? NL : 1
-#ifdef KM_WORK_COUNTERS_ALL
-#define KM_WORK_COUNTERS(NL) true
-#else
-#define KM_WORK_COUNTERS(NL) ((NL) > 10)
-#endif
-#define KM_WORK_ALL 40
-#define KM_WORK_ARM 14
-#define KM_WORK_PLAIN 3
-#define KM_WORK_CUBE 5
-#include "kmanip_dyn_ws.hpp"
-#include "kmanip_dyn_tree.hpp"
-#include "kmanip_dyn_constraints.hpp"
-#include "kmanip_dyn_newton.hpp"
-#include "kmanip_dyn_env.hpp"
+#include "kmanip_dyn_variant.hpp"      // (the build macros; KM_VAR_SOLVER is always 1 here)
 static_assert(KM_VAR_SOLVER == 1, "k_forces reads the Newton path's registers");
 
 // one env's rows of every requested output: lane = dof for the nv- and nu-wide rows, lane = slot for the slot rows.
@@ -55,31 +21,14 @@ static_assert(KM_VAR_SOLVER == 1, "k_forces reads the Newton path's registers");
 template <int NL, int G>
 __device__ __forceinline__ void write_forces(const KForcesDev& out, int env, int sub, bool ok, real a, real fc, real fa, const real (&F)[4],
                                              int bit, const real (&fr)[9], const real (&cp)[3], real dist, uint32_t mask) {
-  constexpr int NV = Dim<NL>::NV, NC = Dim<NL>::NC;
+  constexpr int NV = Dim<NL>::NV;
   const size_t e = (size_t)env;
   if (sub < NV) {
     if (out.qacc) out.qacc[e * NV + sub] = ok ? a : 0.0;
     if (out.qfrc_constraint) out.qfrc_constraint[e * NV + sub] = ok ? fc : 0.0;
   }
   if (sub < NL && out.qfrc_actuator) out.qfrc_actuator[e * NL + sub] = ok ? fa : 0.0;
-  if (sub < NC) {
-    const size_t s = e * NC + sub;
-    const bool on = ok && bit >= 0;
-    if (out.contact_force) {
-#pragma unroll
-      for (int k = 0; k < 4; k++) out.contact_force[s * 4 + k] = on ? F[k] : 0.0;
-    }
-    if (out.contact_bit) out.contact_bit[s] = on ? bit : -1;
-    if (out.contact_frame) {
-#pragma unroll
-      for (int k = 0; k < 9; k++) out.contact_frame[s * 9 + k] = on ? fr[k] : 0.0;
-    }
-    if (out.contact_pos) {
-#pragma unroll
-      for (int k = 0; k < 3; k++) out.contact_pos[s * 3 + k] = on ? cp[k] : 0.0;
-    }
-    if (out.contact_dist) out.contact_dist[s] = on ? dist : 0.0;
-  }
+  write_slot_rows<NL>(out, e, sub, ok, F, bit, fr, cp, dist);
   if (sub == 0) {
     if (out.contact_mask) out.contact_mask[e] = ok ? mask : 0u;
     if (out.status) out.status[e] = ok ? 0 : 1;
@@ -87,40 +36,29 @@ __device__ __forceinline__ void write_forces(const KForcesDev& out, int env, int
 }
 
 template <int NL, int G, int EPB>
-__global__ __launch_bounds__(64) void KM_K_FORCES(const KDeviceModel* __restrict__ dm, KDeviceState st, KForcesDev out) {
-  constexpr int NV = Dim<NL>::NV, NQ = Dim<NL>::NQ, NC = Dim<NL>::NC, NSS = Dim<NL>::NSS;
+__global__ __launch_bounds__(64) void KM_KERNEL_FRC_FIRST(forces)(const KDeviceModel* __restrict__ dm, KDeviceState st, KForcesDev out) {
+  constexpr int NV = Dim<NL>::NV, NC = Dim<NL>::NC;
   static_assert(NC <= 16, "the slot lanes sit in the group's first DPP row");
   __shared__ Ws<NL> ws[EPB];
   __shared__ LModel<NL> lm;
-  stage_model<NL>(lm, dm);
   const KModelDesc* m = &dm->d;
   const int lane = threadIdx.x, grp = lane / G, sub = lane % G;
-  const int env = xcd_block(blockIdx.x, gridDim.x) * EPB + grp;
-  if (grp >= EPB || env >= st.num_envs) return;      // whole group exits together
+  int env;
+  if (!query_env<NL, EPB>(lm, dm, st, grp, env)) return;      // whole group exits together
   Ws<NL>& w = ws[grp];
   real invm = 0;                       // diagonal of M^-1 for the cube dof owned by this lane
-  init_ws<NL>(w, sub);
-#if KM_VAR_PAR
-  ep_load<NL>(w, dm, st, env, sub, invm);
-#else
-  if (sub >= NL && sub < NV) invm = sub < NL + 3 ? 1.0 / m->cube_mass : 1.0 / m->cube_inertia[sub - NL - 3];
-#endif
-  load_state<NL, G>(w, st, env, sub);
+  query_load<NL, G>(w, dm, st, env, sub, invm);
   // ctrl exactly as stored: load_state's float32 rounding is the start of before_step, which does not run here
   for (int i = sub; i < NL; i += G) w.ctrl[i] = st.ctrl[(size_t)i * st.num_envs + env];
 #if KM_VAR_FRC
   const int frc_bad = load_applied<NL, G>(w, st, env, sub);
+#else
+  const int frc_bad = 0;
 #endif
   GSYNC();
   const real F0[4] = {0, 0, 0, 0}, fr0[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, cp0[3] = {0, 0, 0};
   // a non-finite state (k_observe's test) or, in the force builds, a non-finite applied force: status 1, nothing else computed
-  int lb = 0;
-#if KM_VAR_FRC
-  lb = frc_bad;
-#endif
-  for (int i = sub; i < NQ; i += G) lb |= !isfinite(w.qpos[i]);
-  for (int i = sub; i < NV; i += G) lb |= !isfinite(w.qvel[i]);
-  if (gor<G>(lb)) { write_forces<NL, G>(out, env, sub, false, 0, 0, 0, F0, -1, fr0, cp0, 0, 0u); return; }
+  if (state_nonfinite<NL, G>(w, sub, frc_bad)) { write_forces<NL, G>(out, env, sub, false, 0, 0, 0, F0, -1, fr0, cp0, 0, 0u); return; }
   Prof pf;
   pf.start();
   CReg<NL> cr;
@@ -163,45 +101,18 @@ __global__ __launch_bounds__(64) void KM_K_FORCES(const KDeviceModel* __restrict
 #pragma unroll
   for (int k = 0; k < 4; k++) u[k] -= cr.sc.A[k];
   slot_eval<false>(cr.sc, u, F, Wd);
-  // which KM_CON_* bit sits in this lane's slot: corner slots hold the penetrating corners in corner order (the mask's low byte has
-  // exactly the kept ones), sphere slots name their sphere
-  int bit = -1;
-  if (sub < NC && ((act >> sub) & 1u)) {
-    if (sub < 4) {
-      uint32_t mm = mask & KM_CON_ANY_CUBE_TABLE;
-      for (int k = 0; k < sub; k++) mm &= mm - 1u;
-      bit = __ffs((int)mm) - 1;
-    } else bit = (sub < 4 + NSS ? 8 : 20) + sph;
-  }
+  int bit = -1;      // (the slot lanes: which pair sits in the lane's slot)
+  if (sub < NC) bit = slot_contact_bit<NL>(sub, act, mask, sph);
   write_forces<NL, G>(out, env, sub, true, a, fc, fa, F, bit, fr, cp, dist, mask);
 }
 
 template <int NL, int G>
 static void launch_forces_t(const KDeviceModel* dm, const KDeviceState& st, const KForcesDev& out, hipStream_t stream) {
   constexpr int EPB = 64 / G;
-  hipLaunchKernelGGL((KM_K_FORCES<NL, G, EPB>), dim3((st.num_envs + EPB - 1) / EPB), dim3(64), 0, stream, dm, st, out);
+  hipLaunchKernelGGL((KM_KERNEL_FRC_FIRST(forces)<NL, G, EPB>), dim3((st.num_envs + EPB - 1) / EPB), dim3(64), 0, stream, dm, st, out);
 }
-#if KM_VAR_PAR && KM_VAR_FRC
-}  // namespace km_envp_frc
-using namespace km_envp_frc;
-#define KM_LAUNCH_FORCES kmanip_launch_forces_ep_frc_
-#elif KM_VAR_FRC
-}  // namespace km_frc
-using namespace km_frc;
-#define KM_LAUNCH_FORCES kmanip_launch_forces_frc_
-#elif KM_VAR_PAR
-}  // namespace km_envp
-using namespace km_envp;
-#define KM_LAUNCH_FORCES kmanip_launch_forces_ep_
-#else
-#define KM_LAUNCH_FORCES kmanip_launch_forces_
-#endif
+KM_VARIANT_END
 // ---- one (NL, G[, PAR][, FRC]) variant per translation unit (the Makefile compiles this file eight times)
-#ifndef KM_VAR_NL
-#error "compile with -DKM_VAR_NL=<10|20> -DKM_VAR_G=<16|32> -DKM_VAR_SOLVER=1"
-#endif
-#define KM_CAT3_(a, b, c) a##b##_##c
-#define KM_CAT3(a, b, c) KM_CAT3_(a, b, c)
-void KM_CAT3(KM_LAUNCH_FORCES, KM_VAR_NL, KM_VAR_G)(const KDeviceModel* dm, const KDeviceState& st, const KForcesDev& out, hipStream_t stream) {
+void KM_LAUNCHER2(forces)(const KDeviceModel* dm, const KDeviceState& st, const KForcesDev& out, hipStream_t stream) {
   launch_forces_t<KM_VAR_NL, KM_VAR_G>(dm, st, out, stream);
 }

@@ -12,32 +12,8 @@
 // wave like k_forces.  The handle is read only: nothing of KDeviceState is written.
 #include "kmanip_ik_coop.hpp"
 #include <stdlib.h>
-// ---- the build macros of kmanip_dyn.hip (the headers below read them); KM_VAR_SOLVER is always 1 here, KM_VAR_FRC always 0
-#ifndef KM_VAR_PAR
-#define KM_VAR_PAR 0
-#endif
-#define KM_VAR_FRC 0
-#if KM_VAR_PAR
-namespace km_envp {
-#define KM_K_INVERSE k_inverse_ep
-#else
-#define KM_K_INVERSE k_inverse
-#endif
-#define KM_TREE_UNROLL(NL) NL <= 10 ? NL : 1
-#ifdef KM_WORK_COUNTERS_ALL
-#define KM_WORK_COUNTERS(NL) true
-#else
-#define KM_WORK_COUNTERS(NL) ((NL) > 10)
-#endif
-#define KM_WORK_ALL 40
-#define KM_WORK_ARM 14
-#define KM_WORK_PLAIN 3
-#define KM_WORK_CUBE 5
-#include "kmanip_dyn_ws.hpp"
-#include "kmanip_dyn_tree.hpp"
-#include "kmanip_dyn_constraints.hpp"
-#include "kmanip_dyn_newton.hpp"
-#include "kmanip_dyn_env.hpp"
+#define KM_VAR_FRC 0      // (no applied-force builds: a bound force does not enter)
+#include "kmanip_dyn_variant.hpp"      // (the build macros; KM_VAR_SOLVER is always 1 here)
 static_assert(KM_VAR_SOLVER == 1, "k_inverse runs the Newton path's constraint assembly");
 
 // one env's rows of every requested output: lane = dof for the nv-wide rows, lane = slot for the slot rows.
@@ -45,21 +21,13 @@ static_assert(KM_VAR_SOLVER == 1, "k_inverse runs the Newton path's constraint a
 template <int NL, int G>
 __device__ __forceinline__ void write_inverse(const KInverseDev& out, int env, int sub, bool ok, real fi, real fc, const real (&F)[4],
                                               int bit, uint32_t mask) {
-  constexpr int NV = Dim<NL>::NV, NC = Dim<NL>::NC;
+  constexpr int NV = Dim<NL>::NV;
   const size_t e = (size_t)env;
   if (sub < NV) {
     if (out.qfrc_inverse) out.qfrc_inverse[e * NV + sub] = ok ? fi : 0.0;
     if (out.qfrc_constraint) out.qfrc_constraint[e * NV + sub] = ok ? fc : 0.0;
   }
-  if (sub < NC) {
-    const size_t s = e * NC + sub;
-    const bool on = ok && bit >= 0;
-    if (out.contact_force) {
-#pragma unroll
-      for (int k = 0; k < 4; k++) out.contact_force[s * 4 + k] = on ? F[k] : 0.0;
-    }
-    if (out.contact_bit) out.contact_bit[s] = on ? bit : -1;
-  }
+  write_slot_rows<NL>(out, e, sub, ok, F, bit);
   if (sub == 0) {
     if (out.contact_mask) out.contact_mask[e] = ok ? mask : 0u;
     if (out.status) out.status[e] = ok ? 0 : 1;
@@ -67,27 +35,22 @@ __device__ __forceinline__ void write_inverse(const KInverseDev& out, int env, i
 }
 
 template <int NL, int G, int EPB>
-__global__ __launch_bounds__(64) void KM_K_INVERSE(const KDeviceModel* __restrict__ dm, KDeviceState st, KInverseIn in, KInverseDev out) {
-  constexpr int NV = Dim<NL>::NV, NQ = Dim<NL>::NQ, NC = Dim<NL>::NC, NSS = Dim<NL>::NSS;
+__global__ __launch_bounds__(64) void KM_KERNEL(k_inverse)(const KDeviceModel* __restrict__ dm, KDeviceState st, KInverseIn in, KInverseDev out) {
+  constexpr int NV = Dim<NL>::NV, NQ = Dim<NL>::NQ, NC = Dim<NL>::NC;
   static_assert(NV <= G, "lane = dof");
   static_assert(NC <= 16, "the slot lanes sit in the group's first DPP row");
   __shared__ Ws<NL> ws[EPB];
   __shared__ LModel<NL> lm;
-  stage_model<NL>(lm, dm);
   const KModelDesc* m = &dm->d;
   const int lane = threadIdx.x, grp = lane / G, sub = lane % G;
-  const int env = xcd_block(blockIdx.x, gridDim.x) * EPB + grp;
-  if (grp >= EPB || env >= st.num_envs) return;      // whole group exits together
+  int env;
+  if (!query_env<NL, EPB>(lm, dm, st, grp, env)) return;      // whole group exits together
   Ws<NL>& w = ws[grp];
   real invm = 0;                       // diagonal of M^-1 for the cube dof owned by this lane
-  init_ws<NL>(w, sub);
-#if KM_VAR_PAR
-  ep_load<NL>(w, dm, st, env, sub, invm);
-#else
-  if (sub >= NL && sub < NV) invm = sub < NL + 3 ? 1.0 / m->cube_mass : 1.0 / m->cube_inertia[sub - NL - 3];
-#endif
-  // the caller's rows, requested before the handle's columns are waited for: this lane's qacc, and the state override
   const size_t e = (size_t)env;
+  init_ws<NL>(w, sub);            // (query_load's calls, spelt out around the load below)
+  env_invm<NL>(w, dm, st, env, sub, invm);
+  // the caller's rows, requested before the handle's columns are waited for: this lane's qacc, and the state override
   const real a = sub < NV ? in.qacc[e * NV + sub] : 0.0;
   load_state<NL, G>(w, st, env, sub);
   if (in.qpos) for (int i = sub; i < NQ; i += G) w.qpos[i] = in.qpos[e * NQ + i];      // as stored: what kmanip_set_state_dev would have written
@@ -95,10 +58,7 @@ __global__ __launch_bounds__(64) void KM_K_INVERSE(const KDeviceModel* __restric
   GSYNC();
   const real F0[4] = {0, 0, 0, 0};
   // a non-finite state (k_observe's test) or acceleration: status 1, nothing else computed
-  int lb = !isfinite(a);
-  for (int i = sub; i < NQ; i += G) lb |= !isfinite(w.qpos[i]);
-  for (int i = sub; i < NV; i += G) lb |= !isfinite(w.qvel[i]);
-  if (gor<G>(lb)) { write_inverse<NL, G>(out, env, sub, false, 0, 0, F0, -1, 0u); return; }
+  if (state_nonfinite<NL, G>(w, sub, !isfinite(a))) { write_inverse<NL, G>(out, env, sub, false, 0, 0, F0, -1, 0u); return; }
   Prof pf;
   pf.start();
   CReg<NL> cr;
@@ -128,38 +88,19 @@ __global__ __launch_bounds__(64) void KM_K_INVERSE(const KDeviceModel* __restric
   slot_grad<NL, G, KM_SUB_ALL>(cr, act, F, g);          // g = -J^T F over the active slots
   fc -= g;
   const real fi = sub < NV ? (Ma + bia) - fc : 0.0;
-  // which KM_CON_* bit sits in this lane's slot (k_forces' decode): corner slots hold the penetrating corners in corner order (the
-  // mask's low byte has exactly the kept ones), sphere slots name their sphere
-  int bit = -1;
-  if (sub < NC && ((act >> sub) & 1u)) {
-    if (sub < 4) {
-      uint32_t mm = mask & KM_CON_ANY_CUBE_TABLE;
-      for (int k = 0; k < sub; k++) mm &= mm - 1u;
-      bit = __ffs((int)mm) - 1;
-    } else bit = (sub < 4 + NSS ? 8 : 20) + sph;
-  }
+  int bit = -1;      // (the slot lanes: which pair sits in the lane's slot)
+  if (sub < NC) bit = slot_contact_bit<NL>(sub, act, mask, sph);
   write_inverse<NL, G>(out, env, sub, true, fi, fc, F, bit, mask);
 }
 
 template <int NL, int G>
 static void launch_inverse_t(const KDeviceModel* dm, const KDeviceState& st, const KInverseIn& in, const KInverseDev& out, hipStream_t stream) {
   constexpr int EPB = 64 / G;
-  hipLaunchKernelGGL((KM_K_INVERSE<NL, G, EPB>), dim3((st.num_envs + EPB - 1) / EPB), dim3(64), 0, stream, dm, st, in, out);
+  hipLaunchKernelGGL((KM_KERNEL(k_inverse)<NL, G, EPB>), dim3((st.num_envs + EPB - 1) / EPB), dim3(64), 0, stream, dm, st, in, out);
 }
-#if KM_VAR_PAR
-}  // namespace km_envp
-using namespace km_envp;
-#define KM_LAUNCH_INVERSE kmanip_launch_inverse_ep_
-#else
-#define KM_LAUNCH_INVERSE kmanip_launch_inverse_
-#endif
+KM_VARIANT_END
 // ---- one (NL, G[, PAR]) variant per translation unit (the Makefile compiles this file four times)
-#ifndef KM_VAR_NL
-#error "compile with -DKM_VAR_NL=<10|20> -DKM_VAR_G=<16|32> -DKM_VAR_SOLVER=1"
-#endif
-#define KM_CAT3_(a, b, c) a##b##_##c
-#define KM_CAT3(a, b, c) KM_CAT3_(a, b, c)
-void KM_CAT3(KM_LAUNCH_INVERSE, KM_VAR_NL, KM_VAR_G)(const KDeviceModel* dm, const KDeviceState& st, const KInverseIn& in, const KInverseDev& out,
+void KM_LAUNCHER2(inverse)(const KDeviceModel* dm, const KDeviceState& st, const KInverseIn& in, const KInverseDev& out,
                                                      hipStream_t stream) {
   launch_inverse_t<KM_VAR_NL, KM_VAR_G>(dm, st, in, out, stream);
 }

@@ -13,31 +13,7 @@
 // too.  Both parameter builds, 64 / G envs per wave like k_observe.  The handle is read only: nothing of KDeviceState is written.
 #include "kmanip_ik_coop.hpp"
 #include <stdlib.h>
-// ---- the build macros of kmanip_dyn.hip (the headers below read them); KM_VAR_SOLVER is always 1 here
-#ifndef KM_VAR_PAR
-#define KM_VAR_PAR 0
-#endif
-#if KM_VAR_PAR
-namespace km_envp {
-#define KM_K_KIN k_kinematics_ep
-#else
-#define KM_K_KIN k_kinematics
-#endif
-#define KM_TREE_UNROLL(NL) NL <= 10 ? NL : 1
-#ifdef KM_WORK_COUNTERS_ALL
-#define KM_WORK_COUNTERS(NL) true
-#else
-#define KM_WORK_COUNTERS(NL) ((NL) > 10)
-#endif
-#define KM_WORK_ALL 40
-#define KM_WORK_ARM 14
-#define KM_WORK_PLAIN 3
-#define KM_WORK_CUBE 5
-#include "kmanip_dyn_ws.hpp"
-#include "kmanip_dyn_tree.hpp"
-#include "kmanip_dyn_constraints.hpp"
-#include "kmanip_dyn_newton.hpp"
-#include "kmanip_dyn_env.hpp"
+#include "kmanip_dyn_variant.hpp"      // (the build macros; KM_VAR_SOLVER is always 1 here, KM_VAR_FRC left to its default)
 static_assert(KM_VAR_SOLVER == 1, "k_kinematics is built with the Newton workspace layout");
 
 // `count` zeros into env e's row of a field (consecutive lanes, consecutive addresses)
@@ -103,30 +79,21 @@ __device__ __forceinline__ void kin_tree(Ws<NL>& w, const LModel<NL>& lm, const 
 }
 
 template <int NL, int G, int EPB>
-__global__ __launch_bounds__(64) void KM_K_KIN(const KDeviceModel* __restrict__ dm, KDeviceState st, KKinDev out) {
-  constexpr int NV = Dim<NL>::NV, NQ = Dim<NL>::NQ;
+__global__ __launch_bounds__(64) void KM_KERNEL(k_kinematics)(const KDeviceModel* __restrict__ dm, KDeviceState st, KKinDev out) {
+  constexpr int NV = Dim<NL>::NV;
   static_assert(NV <= G, "lane = dof");
   __shared__ Ws<NL> ws[EPB];
   __shared__ LModel<NL> lm;
-  stage_model<NL>(lm, dm);
   const KModelDesc* m = &dm->d;
   const int lane = threadIdx.x, grp = lane / G, sub = lane % G;
-  const int env = xcd_block(blockIdx.x, gridDim.x) * EPB + grp;
-  if (grp >= EPB || env >= st.num_envs) return;      // whole group exits together
+  int env;
+  if (!query_env<NL, EPB>(lm, dm, st, grp, env)) return;      // whole group exits together
   Ws<NL>& w = ws[grp];
-  real invm = 0;
-  init_ws<NL>(w, sub);
-#if KM_VAR_PAR
-  ep_load<NL>(w, dm, st, env, sub, invm);
-#endif
-  (void)invm;
-  load_state<NL, G>(w, st, env, sub);
+  real invm = 0;      // (not needed: nothing is inverted)
+  query_load<NL, G>(w, dm, st, env, sub, invm);
   GSYNC();
   // a non-finite state (k_observe's test): status 1, nothing else computed
-  int lb = 0;
-  for (int i = sub; i < NQ; i += G) lb |= !isfinite(w.qpos[i]);
-  for (int i = sub; i < NV; i += G) lb |= !isfinite(w.qvel[i]);
-  if (gor<G>(lb)) { write_kin_bad<NL, G>(out, env, sub); return; }
+  if (state_nonfinite<NL, G>(w, sub)) { write_kin_bad<NL, G>(out, env, sub); return; }
   kin_tree<NL, G>(w, lm, m, sub);
   const size_t e = (size_t)env;
   // ---- link frames: the workspace's arrays as they lie
@@ -212,21 +179,10 @@ __global__ __launch_bounds__(64) void KM_K_KIN(const KDeviceModel* __restrict__ 
 template <int NL, int G>
 static void launch_kinematics_t(const KDeviceModel* dm, const KDeviceState& st, const KKinDev& out, hipStream_t stream) {
   constexpr int EPB = 64 / G;
-  hipLaunchKernelGGL((KM_K_KIN<NL, G, EPB>), dim3((st.num_envs + EPB - 1) / EPB), dim3(64), 0, stream, dm, st, out);
+  hipLaunchKernelGGL((KM_KERNEL(k_kinematics)<NL, G, EPB>), dim3((st.num_envs + EPB - 1) / EPB), dim3(64), 0, stream, dm, st, out);
 }
-#if KM_VAR_PAR
-}  // namespace km_envp
-using namespace km_envp;
-#define KM_LAUNCH_KIN kmanip_launch_kinematics_ep_
-#else
-#define KM_LAUNCH_KIN kmanip_launch_kinematics_
-#endif
+KM_VARIANT_END
 // ---- one (NL, G[, PAR]) variant per translation unit (the Makefile compiles this file four times)
-#ifndef KM_VAR_NL
-#error "compile with -DKM_VAR_NL=<10|20> -DKM_VAR_G=<16|32> -DKM_VAR_SOLVER=1"
-#endif
-#define KM_CAT3_(a, b, c) a##b##_##c
-#define KM_CAT3(a, b, c) KM_CAT3_(a, b, c)
-void KM_CAT3(KM_LAUNCH_KIN, KM_VAR_NL, KM_VAR_G)(const KDeviceModel* dm, const KDeviceState& st, const KKinDev& out, hipStream_t stream) {
+void KM_LAUNCHER2(kinematics)(const KDeviceModel* dm, const KDeviceState& st, const KKinDev& out, hipStream_t stream) {
   launch_kinematics_t<KM_VAR_NL, KM_VAR_G>(dm, st, out, stream);
 }

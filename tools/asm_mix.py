@@ -74,7 +74,7 @@ def func_ranges(src):
     prev = ""
     for i, t in enumerate(open(src, errors="replace").read().split("\n"), 1):
         if not t.startswith((" ", "\t", "#", "/")):
-            m = re.search(r"\b(?:void|real|int|bool|double|float|uint32_t|BSrc<G>)\s+([A-Za-z_0-9]+)\s*\(", t)
+            m = re.search(r"\b(?:void|real|int|bool|double|float|uint32_t|BSrc<G>)\s+(?:KM_KERNEL\()?([A-Za-z_0-9]+)\)?\s*\(", t)      # (KM_KERNEL(k_step): the name without the build's suffix)
             if m and ("__device__" in t or "__global__" in t or "__device__" in prev or "__global__" in prev):
                 starts.append((i, m.group(1)))
         prev = t
@@ -86,7 +86,7 @@ cols = ["f64", "mov", "dppmov", "sel", "agpr", "lane", "perm", "cmp64", "cmp", "
 tot = collections.Counter()
 agg = collections.defaultdict(collections.Counter)
 FILES = ("kmanip_dyn.hip", "kmanip_dyn_ws.hpp", "kmanip_dyn_tree.hpp", "kmanip_dyn_constraints.hpp", "kmanip_dyn_newton.hpp",
-         "kmanip_dyn_env.hpp", "kmanip_ik_coop.hpp", "kmanip_device.hpp")
+         "kmanip_dyn_env.hpp", "kmanip_dyn_variant.hpp", "kmanip_ik_coop.hpp", "kmanip_device.hpp")
 for fname in FILES:
     st = func_ranges(os.path.join(here, fname))
     for (f, l), c in counts.items():

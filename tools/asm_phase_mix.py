@@ -149,7 +149,7 @@ class Source:
         for i, ln in enumerate(self.lines, 1):
             if not re.match(r"^(?:__device__|__global__|static)\b", ln) or ln.startswith("static_assert") or ln.rstrip().endswith(";"):
                 continue
-            names = [n for n in re.findall(r"\b([A-Za-z_0-9]+)\s*\(", ln) if n not in ("__launch_bounds__", "__attribute__")]
+            names = [n for n in re.findall(r"\b([A-Za-z_0-9]+)\s*\(", re.sub(r"KM_KERNEL\((\w+)\)", r"\1", ln)) if n not in ("__launch_bounds__", "__attribute__")]
             if names:
                 self.starts.append((i, names[0]))
 
