@@ -14,7 +14,7 @@
 
 #include "kmanip_device.hpp"
 
-#define KM_VERSION "kmanip-hip 0.39 (gfx950, f64)"
+#define KM_VERSION "kmanip-hip 0.40 (gfx950, f64)"
 
 static thread_local std::string g_create_error;
 
@@ -487,6 +487,24 @@ int kmanip_inverse(KHandle h, const KInverseIn* in, const KInverseDev* out, void
   if (!out->qfrc_inverse && !out->qfrc_constraint && !out->contact_force && !out->contact_bit && !out->contact_mask && !out->status) return 0;
   KM_ENTER(h);
   kmanip_launch_inverse(h->dmodel, h->desc, h->st, *in, *out, (hipStream_t)stream);
+  HIPCHK(h, hipGetLastError());
+  return 0;
+}
+
+// mj_forward at rows the caller passes: kmanip_forces' outputs for n hypothetical states, each naming the env whose model parameters
+// and unnamed fields it takes (include/kmanip.h KForwardIn; kmanip_forward.hip).  One launch; the handle is only read.
+int kmanip_forward(KHandle h, const KForwardIn* in, int n, const KForcesDev* out, void* stream) {
+  if (!h) { g_create_error = "kmanip_forward: null handle"; return -1; }
+  if (!in) { h->err = "kmanip_forward: the KForwardIn pointer is NULL"; return -1; }
+  if (!out) { h->err = "kmanip_forward: the KForcesDev pointer is NULL"; return -1; }
+  if (h->desc.solver != KM_SOLVER_NEWTON) { h->err = "kmanip_forward: contact forces need the Newton solver"; return -1; }
+  if (n < 0) { h->err = "kmanip_forward: n is negative"; return -1; }
+  if (!in->env_index && n > h->st.num_envs) { h->err = "kmanip_forward: more rows than envs need KForwardIn::env_index"; return -1; }
+  if (n == 0) return 0;
+  if (!out->qacc && !out->qfrc_constraint && !out->qfrc_actuator && !out->contact_force && !out->contact_bit && !out->contact_frame &&
+      !out->contact_pos && !out->contact_dist && !out->contact_mask && !out->status) return 0;
+  KM_ENTER(h);
+  kmanip_launch_forward(h->dmodel, h->desc, h->st, *in, n, *out, (hipStream_t)stream);
   HIPCHK(h, hipGetLastError());
   return 0;
 }

@@ -582,6 +582,10 @@ void kmanip_launch_kinematics(const KDeviceModel* dm, const KModelDesc& hd, cons
 // kmanip_inverse (either solver); the per-env parameter build while KDeviceState::envp is set
 void kmanip_launch_inverse(const KDeviceModel* dm, const KModelDesc& hd, const KDeviceState& st, const KInverseIn& in, const KInverseDev& out,
                            hipStream_t stream);
+// kmanip_forward (Newton handles only: the caller checks), n > 0 rows; the per-env parameter build while KDeviceState::envp is set, the
+// applied-force build while in.qfrc_applied or KDeviceState::qfrc_applied is set
+void kmanip_launch_forward(const KDeviceModel* dm, const KModelDesc& hd, const KDeviceState& st, const KForwardIn& in, int n,
+                           const KForcesDev& out, hipStream_t stream);
 // The render launchers' visual inputs (kmanip_set_visual_params / _ranges), a kernel argument of the VIS
 // kernels only -- never a KDeviceState field: the step kernels' argument stays as it is.  All NULL: the default kernels.
 //   vp       explicit values double[KM_VP_N][N], read at the render's launch

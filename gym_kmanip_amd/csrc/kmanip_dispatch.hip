@@ -17,6 +17,7 @@ typedef void PrepareFn(KDeviceModel*, hipStream_t);
 typedef void ForcesFn(const KDeviceModel*, const KDeviceState&, const KForcesDev&, hipStream_t);
 typedef void KinFn(const KDeviceModel*, const KDeviceState&, const KKinDev&, hipStream_t);
 typedef void InverseFn(const KDeviceModel*, const KDeviceState&, const KInverseIn&, const KInverseDev&, hipStream_t);
+typedef void ForwardFn(const KDeviceModel*, const KDeviceState&, const KForwardIn&, int, const KForcesDev&, hipStream_t);
 
 // kmanip_dyn.hip: step per solver in every build, reset per solver in the parameter builds; observe and prepare are
 // solver-independent, one copy per class (in the default Newton object)
@@ -24,14 +25,15 @@ typedef void InverseFn(const KDeviceModel*, const KDeviceState&, const KInverseI
 #define KM_RESET_ROW(B, NL, G) {KM_NAME(reset, B, NL, G, _0), KM_NAME(reset, B, NL, G, _1)},
 #define KM_OBSERVE_ROW(B, NL, G) KM_NAME(observe, B, NL, G, _1),
 #define KM_PREPARE_ROW(B, NL, G) KM_NAME(prepare, B, NL, G, _1),
-// kmanip_forces.hip (the Newton classes, every build), kmanip_kinematics.hip and kmanip_inverse.hip (one object per class serves both
+// kmanip_forces.hip and kmanip_forward.hip (the Newton classes, every build), kmanip_kinematics.hip and kmanip_inverse.hip (one object per class serves both
 // solvers, the parameter builds)
 #define KM_FORCES_ROW(B, NL, G) KM_NAME(forces, B, NL, G, ),
 #define KM_KIN_ROW(B, NL, G) KM_NAME(kinematics, B, NL, G, ),
 #define KM_INVERSE_ROW(B, NL, G) KM_NAME(inverse, B, NL, G, ),
+#define KM_FORWARD_ROW(B, NL, G) KM_NAME(forward, B, NL, G, ),
 
 #define KM_DECL_SOLVERS(Fn, kind, B, NL, G) Fn KM_NAME(kind, B, NL, G, _0), KM_NAME(kind, B, NL, G, _1);
-#define KM_DECL_FRC(B, NL, G) KM_DECL_SOLVERS(StepFn, step, B, NL, G) ForcesFn KM_NAME(forces, B, NL, G, );
+#define KM_DECL_FRC(B, NL, G) KM_DECL_SOLVERS(StepFn, step, B, NL, G) ForcesFn KM_NAME(forces, B, NL, G, ); ForwardFn KM_NAME(forward, B, NL, G, );
 #define KM_DECL_PAR(B, NL, G) KM_DECL_SOLVERS(ResetFn, reset, B, NL, G) KinFn KM_NAME(kinematics, B, NL, G, ); InverseFn KM_NAME(inverse, B, NL, G, );
 #define KM_DECL_ONCE(B, NL, G) ObserveFn KM_NAME(observe, B, NL, G, _1); PrepareFn KM_NAME(prepare, B, NL, G, _1);
 #define KM_DECL_BUILD_FRC(B) KM_CLASSES(KM_DECL_FRC, B)
@@ -44,6 +46,7 @@ KM_BUILDS(KM_DECL_BUILD_FRC) KM_BUILDS_PAR(KM_DECL_BUILD_PAR) KM_CLASSES(KM_DECL
 #define KM_FORCES_BUILD(B) {KM_CLASSES(KM_FORCES_ROW, B)},
 #define KM_KIN_BUILD(B) {KM_CLASSES(KM_KIN_ROW, B)},
 #define KM_INVERSE_BUILD(B) {KM_CLASSES(KM_INVERSE_ROW, B)},
+#define KM_FORWARD_BUILD(B) {KM_CLASSES(KM_FORWARD_ROW, B)},
 static constexpr StepFn* step_tab[4][2][2] = {KM_BUILDS(KM_STEP_BUILD)};
 static constexpr ResetFn* reset_tab[2][2][2] = {KM_BUILDS_PAR(KM_RESET_BUILD)};
 static constexpr ObserveFn* observe_tab[2] = {KM_CLASSES(KM_OBSERVE_ROW, )};
@@ -51,6 +54,7 @@ static constexpr PrepareFn* prepare_tab[2] = {KM_CLASSES(KM_PREPARE_ROW, )};
 static constexpr ForcesFn* forces_tab[4][2] = {KM_BUILDS(KM_FORCES_BUILD)};
 static constexpr KinFn* kin_tab[2][2] = {KM_BUILDS_PAR(KM_KIN_BUILD)};
 static constexpr InverseFn* inverse_tab[2][2] = {KM_BUILDS_PAR(KM_INVERSE_BUILD)};
+static constexpr ForwardFn* forward_tab[4][2] = {KM_BUILDS(KM_FORWARD_BUILD)};
 
 static int cls(const KModelDesc& hd) { return hd.nlink <= 10 ? 0 : 1; }
 static int newton(const KModelDesc& hd) { return hd.solver == KM_SOLVER_NEWTON ? 1 : 0; }
@@ -78,6 +82,11 @@ void kmanip_launch_kinematics(const KDeviceModel* dm, const KModelDesc& hd, cons
 void kmanip_launch_inverse(const KDeviceModel* dm, const KModelDesc& hd, const KDeviceState& st, const KInverseIn& in, const KInverseDev& out,
                            hipStream_t stream) {
   inverse_tab[par(st)][cls(hd)](dm, st, in, out, stream);
+}
+void kmanip_launch_forward(const KDeviceModel* dm, const KModelDesc& hd, const KDeviceState& st, const KForwardIn& in, int n,
+                           const KForcesDev& out, hipStream_t stream) {
+  // the force build iff a row can have a force: the caller's rows or the handle's bound buffer
+  forward_tab[par(st) + ((in.qfrc_applied || st.qfrc_applied) ? 2 : 0)][cls(hd)](dm, st, in, n, out, stream);
 }
 void kmanip_launch_prepare_model(KDeviceModel* dm, const KModelDesc& hd, hipStream_t stream) {
   prepare_tab[cls(hd)](dm, stream);

@@ -1,0 +1,117 @@
+"""Finite-difference derivatives of the forward dynamics, assembled from two KManipEnvHip.forward launches:
+MuJoCo's mjd_transitionFD / mjd_inverseFD idea on top of kmanip_forward.
+
+Positions are perturbed in the TANGENT space, whose columns are qvel's: nv = nlink + 6 columns for nq = nlink + 7 coordinates.
+Joint and cube-position columns add eps; cube-rotation column k multiplies the cube's quaternion on the right by
+exp(eps e_k / 2) -- the body-frame convention of qvel's angular part, MuJoCo's mj_integratePos.
+
+Everything here is torch arithmetic on whatever device the caller's tensors live on, one operation per kernel, so a CPU stand-in
+with a .forward of the same shape (tests/tools/forward_oracle.py OracleForward) is driven through the same code and is handed
+bit-equal rows."""
+import math
+
+WRT = ("qpos", "qvel", "ctrl", "qfrc_applied")
+_BLOCK = {"qpos": "dqpos", "qvel": "dqvel", "ctrl": "dctrl", "qfrc_applied": "dfrc"}
+
+
+def tangent_perturb(cm, qpos, col, eps):
+    """A copy of qpos [n, nq] moved by eps along tangent column `col` (0 .. nv-1).  Columns below nlink + 3 (joints, cube position):
+    that coordinate += eps.  Column nlink + 3 + k: quat <- quat (x) [cos(eps / 2), sin(eps / 2) e_k], the rotation by eps about the
+    cube's own axis k.  The product is not re-normalised (its norm is the input's up to rounding; the kinematics normalise the
+    quaternion as they do in a step)."""
+    nl = cm.nlink
+    if not 0 <= col < nl + 6:
+        raise ValueError("tangent column %d outside 0 .. %d" % (col, nl + 5))
+    out = qpos.clone()
+    if col < nl + 3:
+        out[:, col] += eps
+        return out
+    v1 = [0.0, 0.0, 0.0]
+    v1[col - nl - 3] = math.sin(0.5 * eps)
+    w1, (x1, y1, z1) = math.cos(0.5 * eps), v1
+    w0, x0, y0, z0 = (qpos[:, nl + 3 + k] for k in range(4))
+    out[:, nl + 3] = w0 * w1 - x0 * x1 - y0 * y1 - z0 * z1
+    out[:, nl + 4] = w0 * x1 + x0 * w1 + y0 * z1 - z0 * y1
+    out[:, nl + 5] = w0 * y1 - x0 * z1 + y0 * w1 + z0 * x1
+    out[:, nl + 6] = w0 * z1 + x0 * y1 - y0 * x1 + z0 * w1
+    return out
+
+
+def forward_fd(env, envs=None, qpos=None, qvel=None, ctrl=None, qfrc_applied=None, eps=1e-6,
+               wrt=("qpos", "qvel", "ctrl", "qfrc_applied"), warm_offset=1.0):
+    """Centred finite differences of env.forward's qacc and qfrc_constraint with respect to the inputs named in `wrt`, at the rows
+    (envs, qpos, qvel, ctrl, qfrc_applied) as forward() takes them.  Two launches: the nominal rows, then all 2 ncol n perturbed
+    rows at once, each with the nominal qacc + warm_offset (on every dof) as its warm start.
+    WHY NOT THE NOMINAL qacc ITSELF: the Newton solver returns its starting point untouched when the gradient there, scaled by
+    1 / (meaninertia nv), is below the model's solver_tolerance (MuJoCo's rule), and it stops iterating by the same test.  A row
+    moved by eps starts that close to its own solution whenever the input's effect on the forces is small -- measured on an
+    MI355X with warm_offset = 0: the dqvel blocks were off by 8.5e-9 x normaliser / eps (0.18 in an entry), the solver's tolerance
+    divided by eps, while dqpos / dctrl / dfrc met the bar.  Started one unit of acceleration away, the solver iterates, and its
+    last full Newton step lands on the row's solution to rounding (what the parity tests measure from a zero start; a zero start
+    would fail the same way at an equilibrium, where qacc = 0 is the solution).  warm_offset = 0 gives the plain warm start.
+    Returns a dict of tensors on the inputs' device:
+      qacc, qfrc_constraint [n, nv], status [n] uint8     the nominal rows
+      dqacc_dqpos [n, nv, nv] (tangent columns: tangent_perturb), dqacc_dqvel [n, nv, nv], dqacc_dctrl [n, nv, nu],
+      dqacc_dfrc [n, nv, nv]; dqfrc_constraint_dqpos / _dqvel / _dctrl / _dfrc likewise      the blocks of `wrt` only
+      status_fd [n] uint8          the largest status over the row's perturbed copies (nonzero: the row's blocks are not derivatives)
+      contact_mask_fd [ncol, 2, n] int32      the contact mask of every perturbed row, + then -, columns in `wrt` order
+    An input that is differentiated must be given as rows (state_tensors(envs) returns the stored ones); qfrc_applied=None in `wrt`
+    means rows of zeros, given explicitly to both launches (a bound force is then not read: pass its rows to differentiate about
+    it).  Inputs not in `wrt` may stay None: every row then uses what its env stores.
+    THE DYNAMICS ARE PIECEWISE SMOOTH.  Across a change of the active set -- a contact opening or closing, a friction-loss row
+    saturating, a servo reaching its force or control clamp -- qacc has a kink, and where +eps and -eps fall on different sides
+    of one the quotient is a SECANT across it, not a derivative; contact_mask_fd shows the contact part of that.  No smoothing is
+    applied."""
+    import torch
+    cm = env.cm
+    nv, nu = cm.nv, cm.nu
+    wrt = tuple(wrt)
+    unknown = set(wrt) - set(WRT)
+    if unknown:
+        raise ValueError("unknown wrt name(s) %s" % sorted(unknown))
+    given = {"qpos": qpos, "qvel": qvel, "ctrl": ctrl, "qfrc_applied": qfrc_applied}
+    for name in wrt:
+        if given[name] is None and name != "qfrc_applied":
+            raise ValueError("forward_fd: %s is differentiated and must be given as rows" % name)
+    nominal = None
+    if "qfrc_applied" in wrt and qfrc_applied is None:
+        ref = next((t for t in (qpos, qvel, ctrl) if t is not None), None)
+        if ref is None:          # nothing given at all: the row count and the device come from a first nominal launch
+            nominal = env.forward(envs=envs, fields=("qacc",))
+            ref = nominal["qacc"]
+        given["qfrc_applied"] = torch.zeros((ref.shape[0], nv), dtype=torch.float64, device=ref.device)
+    fields = ("qacc", "qfrc_constraint", "contact_mask", "status")
+    nominal = env.forward(envs=envs, qpos=given["qpos"], qvel=given["qvel"], ctrl=given["ctrl"], qfrc_applied=given["qfrc_applied"],
+                          fields=fields)
+    a0 = nominal["qacc"]
+    n, dev = int(a0.shape[0]), a0.device
+    out = {"qacc": a0, "qfrc_constraint": nominal["qfrc_constraint"], "status": nominal["status"]}
+    width = {"qpos": nv, "qvel": nv, "ctrl": nu, "qfrc_applied": nv}
+    ncol = sum(width[name] for name in wrt)
+    if ncol == 0 or n == 0:
+        return out
+    reps = 2 * ncol
+    idx = torch.arange(n, dtype=torch.int32, device=dev) if envs is None else torch.as_tensor(envs).to(device=dev, dtype=torch.int32)
+    big = {name: (None if t is None else t.repeat(reps, 1)) for name, t in given.items()}
+    c = 0
+    for name in wrt:
+        for j in range(width[name]):
+            for s, sign in enumerate((1.0, -1.0)):
+                lo = (2 * c + s) * n
+                if name == "qpos":
+                    big[name][lo:lo + n] = tangent_perturb(cm, given[name], j, sign * eps)
+                else:
+                    big[name][lo:lo + n, j] += sign * eps
+            c += 1
+    pert = env.forward(envs=idx.repeat(reps), qpos=big["qpos"], qvel=big["qvel"], ctrl=big["ctrl"], warm=(a0 + warm_offset).repeat(reps, 1),
+                       qfrc_applied=big["qfrc_applied"], fields=fields)
+    out["status_fd"] = pert["status"].reshape(reps, n).max(dim=0).values
+    out["contact_mask_fd"] = pert["contact_mask"].reshape(ncol, 2, n)
+    for key in ("qacc", "qfrc_constraint"):
+        v = pert[key].reshape(ncol, 2, n, nv)
+        d = ((v[:, 0] - v[:, 1]) / (2.0 * eps)).permute(1, 2, 0)          # [n, nv, ncol]
+        c = 0
+        for name in wrt:
+            out["d%s_%s" % (key, _BLOCK[name])] = d[:, :, c:c + width[name]].contiguous()
+            c += width[name]
+    return out

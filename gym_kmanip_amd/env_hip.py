@@ -271,18 +271,64 @@ class KManipEnvHip:
         self._check(self.L.kmanip_inverse(self.h, C.byref(iv), C.byref(od), self._stream()), "kmanip_inverse")
         return out
 
+    def forward(self, envs=None, qpos=None, qvel=None, ctrl=None, warm=None, qfrc_applied=None, out=None, fields=None):
+        """kmanip_forward: MuJoCo's mj_forward on a scratch mjData -- qacc, joint forces and contact forces at rows the CALLER
+        passes, as many as it likes (one launch on the current stream, no synchronisation; the handle is only read, to the bit).
+        Row r takes the model parameters (per-env parameters included) of env envs[r] -- an int32 device tensor or anything
+        torch.as_tensor takes, repeats allowed, more rows than envs allowed; None = row r is env r, and then at most num_envs
+        rows -- and, per field, the caller's row or, for None, what that env stores: qpos [n, nq], qvel [n, nv], ctrl [n, nu]
+        (used exactly as given, no float32 rounding), warm [n, nv] (the solver's starting point), qfrc_applied [n, nv] (None:
+        the env's row of a bound applied force, none if nothing is bound).  n = len(envs), else the rows of the first given
+        tensor, else num_envs.  With everything None it computes what forces() computes.  Returns the dict forces() returns,
+        n rows (normal_by_bit / finger_force work on it); status [n] uint8: 0 ok; 1 a non-finite value in an input the row uses,
+        given or stored, a failed factorisation or a bad qacc; 2 an env index outside 0 .. num_envs-1 (never used as an
+        address; state_index_errors does not count it) -- every other output of such a row is 0 and contact_bit -1.
+        `fields`: the names wanted (default: all); `out`: a dict of such tensors to fill -- only the fields it names are
+        computed -- returned as given.  Newton handles only."""
+        torch = _torch()
+        from .model import contact_slots
+        idx, ip, n = self._env_index(envs)
+        given = (("qpos", qpos, self.cm.nq), ("qvel", qvel, self.cm.nv), ("ctrl", ctrl, self.cm.nu), ("qacc_warm", warm, self.cm.nv),
+                 ("qfrc_applied", qfrc_applied, self.cm.nv))
+        if n is None:
+            first = next((t for _, t, _ in given if t is not None), None)
+            n = self.num_envs if first is None else (int(first.shape[0]) if isinstance(first, torch.Tensor) and first.dim() else -1)
+        dims = {"nv": self.cm.nv, "nu": self.cm.nu, "nc": contact_slots(self.cm.nlink)}
+        shapes = {name: ((n,) + tuple(dims.get(d, d) for d in shp), getattr(torch, dt))
+                  for name, (shp, dt) in self._FORCE_FIELDS.items()}
+        names = list(out) if out is not None else list(shapes) if fields is None else list(fields)
+        unknown = set(names) - set(shapes)
+        if unknown:
+            raise ValueError("unknown force field(s) %s" % sorted(unknown))
+        fi = _libmod.KForwardIn()
+        if idx is not None:
+            fi.env_index = idx.data_ptr()
+        for name, t, width in given:
+            if t is not None:
+                self._check_buf(t, (n, width), torch.float64, "warm" if name == "qacc_warm" else name)
+                setattr(fi, name, t.data_ptr())
+        if out is None:
+            out = {name: torch.empty(shapes[name][0], dtype=shapes[name][1], device=self.device) for name in names}
+        fd = _libmod.KForcesDev()
+        for name, t in out.items():
+            self._check_buf(t, shapes[name][0], shapes[name][1], name)
+            setattr(fd, name, t.data_ptr())
+        self._check(self.L.kmanip_forward(self.h, C.byref(fi), n, C.byref(fd), self._stream()), "kmanip_forward")
+        return out
+
     def normal_by_bit(self, f):
-        """[n, 32] float64: the normal force of the contact at each KM_CON_* mask bit of a forces() result (it needs contact_force
-        and contact_bit), 0 where the bit is clear.  Device-side indexing only: no further C call."""
+        """[n, 32] float64: the normal force of the contact at each KM_CON_* mask bit of a forces() / forward() / inverse() result
+        (it needs contact_force and contact_bit; n = the result's rows), 0 where the bit is clear.  Device-side indexing only: no
+        further C call."""
         torch = _torch()
         bit = f["contact_bit"].to(torch.int64)
-        normal = torch.where(bit >= 0, f["contact_force"][:, :, 0], torch.zeros((), dtype=torch.float64, device=self.device))
-        out = torch.zeros((self.num_envs, 32), dtype=torch.float64, device=self.device)
+        normal = torch.where(bit >= 0, f["contact_force"][:, :, 0], torch.zeros((), dtype=torch.float64, device=bit.device))
+        out = torch.zeros((bit.shape[0], 32), dtype=torch.float64, device=bit.device)
         return out.scatter_add_(1, bit.clamp(min=0), normal)
 
     def finger_force(self, f):
-        """[n, 2 * narm] float64: normal force of each finger sphere on the cube (the bits of KM_CON_FINGERS_CUBE) of a forces()
-        result."""
+        """[n, 2 * narm] float64: normal force of each finger sphere on the cube (the bits of KM_CON_FINGERS_CUBE) of a forces() /
+        forward() result."""
         return self.normal_by_bit(f)[:, 8:8 + 2 * (self.cm.nlink // 10)]
 
     # KKinDev field -> (trailing shape in terms of nl = links, nv, na = KM_MAX_ARMS, dtype name)

@@ -480,6 +480,41 @@ typedef struct KInverseDev {
  * ERRORS: a NULL handle, a NULL `in`, a NULL `out` or a NULL in->qacc return nonzero with kmanip_last_error set and launch nothing. */
 KMANIP_API int kmanip_inverse(KHandle h, const KInverseIn* in, const KInverseDev* out, void* stream);
 
+/* Forward dynamics at rows the CALLER passes, as many as it likes: MuJoCo's mj_forward on a scratch mjData.
+ * What kmanip_forces computes for the state a handle holds, one row per env, this computes for n rows of hypothetical states: row r
+ * names an env and gives, per field, its own values or none.  nq = nlink + 7, nv = nlink + 6, nu = nlink.  All pointers are DEVICE
+ * pointers, row-major. */
+typedef struct KForwardIn {
+  const int32_t* env_index;    /* [n] DEVICE: row r takes model parameters (KM_EP_*) and every NULL field below from env env_index[r];
+                                  NULL = rows 0 .. n-1 are envs 0 .. n-1, and then n <= num_envs */
+  const double*  qpos;         /* [n, nq] or NULL: the named env's stored qpos */
+  const double*  qvel;         /* [n, nv] or NULL */
+  const double*  ctrl;         /* [n, nu] or NULL; used exactly as given / stored, no float32 rounding (kmanip_forces' rule) */
+  const double*  qacc_warm;    /* [n, nv] or NULL: the named env's stored warm start */
+  const double*  qfrc_applied; /* [n, nv] or NULL: the named env's row of a bound applied force, none if nothing is bound */
+} KForwardIn;
+/* OUTPUTS: KForcesDev with n rows in place of num_envs, written at the ROW; every field keeps its meaning, sign convention and slot
+ * order (kmanip_forces above); any field may be NULL, every field NULL: the call succeeds and does nothing.
+ * status: 0 ok; 1 = a non-finite value in any input the row uses (given or stored), a failed factorisation or a bad qacc, tested as
+ * kmanip_forces tests it; 2 = env_index[r] lies outside 0 .. num_envs-1: the entry is never used as an address, and the call still
+ * returns 0.  With status 1 or 2 every other output of the row is 0 and every slot empty (contact_bit -1).  The counter of
+ * kmanip_state_index_errors keeps its meaning and is not touched.
+ * ONE kernel launch, asynchronous on `stream`: no allocation, no synchronisation, no host copy.  Enqueued after a kmanip_step on the
+ * same stream it sees that step's result.
+ * n >= 0; n == 0 succeeds and does nothing.  n may exceed num_envs when an index is given, and the same env may be named in any
+ * number of rows.  A given row replaces the env's for this call only and is used exactly as kmanip_set_state_dev followed by
+ * kmanip_forces would use it (the quaternion as stored: the kinematics normalise it as they do in a step).
+ * THE INVARIANT: with every input field NULL and n == num_envs, a row computes what kmanip_forces computes for that env, the bound
+ * applied force and per-env parameters (explicit and ranges mode alike) included.
+ * THE HANDLE IS READ ONLY: state, warm start, counters, the contact masks kmanip_get_diag returns, scheduling predictors, sim time and
+ * random streams stay bit for bit as they were; a step after the call is the step without it.
+ * ERRORS: a NULL handle, a NULL `in`, a NULL `out`, n < 0, n > num_envs with a NULL env_index, or a handle whose solver is
+ * KM_SOLVER_PGS ("contact forces need the Newton solver": the rows are solved by the Newton path) return nonzero with
+ * kmanip_last_error set and launch nothing.
+ * OUT OF SCOPE: kinematics at rows, discrete-time transition matrices, analytic derivatives (gym_kmanip_amd/derivatives.py builds
+ * finite differences from two calls). */
+KMANIP_API int kmanip_forward(KHandle h, const KForwardIn* in, int n, const KForcesDev* out, void* stream);
+
 /* KManipEnv.reset(seed=...) (env_base.py:219-220): re-key the cube-spawn stream.  restart_episodes != 0 also rewinds every
  * env's episode counter so that the next kmanip_reset draws episode 0 of the new seed (reset(seed=s) is then reproducible). */
 KMANIP_API int kmanip_set_seed(KHandle h, uint64_t seed, int restart_episodes);
