@@ -509,6 +509,27 @@ int kmanip_forward(KHandle h, const KForwardIn* in, int n, const KForcesDev* out
   return 0;
 }
 
+// MuJoCo's rollout at rows the caller passes: nstep steps of nsub sub-steps from each row's state under the caller's ctrl (and force),
+// held or per step, the state after every step recorded at the row (include/kmanip.h KRolloutIn / KRolloutDev; kmanip_rollout.hip;
+// DESIGN.md section 27).  One launch; the handle is only read; the handle's solver.
+int kmanip_rollout(KHandle h, const KRolloutIn* in, int n, int nstep, int nsub, const KRolloutDev* out, void* stream) {
+  if (!h) { g_create_error = "kmanip_rollout: null handle"; return -1; }
+  if (!in) { h->err = "kmanip_rollout: the KRolloutIn pointer is NULL"; return -1; }
+  if (!out) { h->err = "kmanip_rollout: the KRolloutDev pointer is NULL"; return -1; }
+  if (n < 0) { h->err = "kmanip_rollout: n is negative"; return -1; }
+  if (nstep < 0) { h->err = "kmanip_rollout: nstep is negative"; return -1; }
+  if (nsub < 0) { h->err = "kmanip_rollout: nsub is negative"; return -1; }
+  if (!in->env_index && n > h->st.num_envs) { h->err = "kmanip_rollout: more rows than envs need KRolloutIn::env_index"; return -1; }
+  if (in->ctrl_per_step && !in->ctrl) { h->err = "kmanip_rollout: ctrl_per_step is set and KRolloutIn::ctrl is NULL"; return -1; }
+  if (in->frc_per_step && !in->qfrc_applied) { h->err = "kmanip_rollout: frc_per_step is set and KRolloutIn::qfrc_applied is NULL"; return -1; }
+  if (n == 0 || nstep == 0) return 0;
+  if (!out->qpos && !out->qvel && !out->qacc_warm && !out->contact_mask && !out->reward && !out->status && !out->steps_done) return 0;
+  KM_ENTER(h);
+  kmanip_launch_rollout(h->dmodel, h->desc, h->st, *in, n, nstep, nsub ? nsub : h->desc.n_sub_steps, *out, (hipStream_t)stream);
+  HIPCHK(h, hipGetLastError());
+  return 0;
+}
+
 // the render launchers' visual inputs for a render of source `src` (-1 live state, 0 / 1 a snapshot): in ranges mode the draw
 // uses the episode counters of that source (a snapshot taken before ranges mode was on has none: the live ones)
 static KVisArgs vis_args(KHandle h, int src) {

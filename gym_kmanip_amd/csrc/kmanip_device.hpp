@@ -586,6 +586,10 @@ void kmanip_launch_inverse(const KDeviceModel* dm, const KModelDesc& hd, const K
 // applied-force build while in.qfrc_applied or KDeviceState::qfrc_applied is set
 void kmanip_launch_forward(const KDeviceModel* dm, const KModelDesc& hd, const KDeviceState& st, const KForwardIn& in, int n,
                            const KForcesDev& out, hipStream_t stream);
+// kmanip_rollout (either solver: the handle's), n > 0 rows, nstep > 0 steps of nsub > 0 sub-steps; the builds are picked as
+// kmanip_launch_forward picks them
+void kmanip_launch_rollout(const KDeviceModel* dm, const KModelDesc& hd, const KDeviceState& st, const KRolloutIn& in, int n, int nstep,
+                           int nsub, const KRolloutDev& out, hipStream_t stream);
 // The render launchers' visual inputs (kmanip_set_visual_params / _ranges), a kernel argument of the VIS
 // kernels only -- never a KDeviceState field: the step kernels' argument stays as it is.  All NULL: the default kernels.
 //   vp       explicit values double[KM_VP_N][N], read at the render's launch

@@ -316,6 +316,72 @@ class KManipEnvHip:
         self._check(self.L.kmanip_forward(self.h, C.byref(fi), n, C.byref(fd), self._stream()), "kmanip_forward")
         return out
 
+    # KRolloutDev field -> (trailing shape in terms of nq / nv, or None for the per-row fields, dtype name)
+    _ROLLOUT_FIELDS = {"qpos": (("nq",), "float64"), "qvel": (("nv",), "float64"), "qacc_warm": (("nv",), "float64"),
+                       "contact_mask": ((), "int32"), "reward": ((), "float64"), "status": (None, "uint8"), "steps_done": (None, "int32")}
+
+    def rollout(self, envs=None, qpos=None, qvel=None, ctrl=None, warm=None, qfrc_applied=None, nstep=None, nsub=None, out=None,
+                fields=None):
+        """kmanip_rollout: MuJoCo's `rollout` -- open-loop integration in ctrl space from rows the CALLER passes, as many as it likes
+        (one launch on the current stream, no synchronisation; the handle is only read, to the bit; the handle's solver).  Rows
+        and their None fields as in forward(): row r takes the model parameters of env envs[r] and, per field, the caller's row
+        or what that env stores -- qpos [n, nq], qvel [n, nv], warm [n, nv] (the first sub-step's starting point).  ctrl [n, nu]
+        is held for all steps, ctrl [n, nstep, nu] gives row (r, t) to step t; it is used exactly as given: no action decode, no
+        IK, no CTRL_ALPHA filter, no float32 rounding (the servos' own clamps act).  qfrc_applied [n, nv] / [n, nstep, nv]
+        likewise (None: the env's row of a bound applied force, held, none if nothing is bound).  nstep: given by a rank-3
+        tensor, else the argument, else 1.  One step is nsub sub-steps (None: the model's n_sub_steps, a control step; 1:
+        MuJoCo's mj_step).  Returns a dict of device tensors:
+          qpos [n, nstep, nq], qvel, qacc_warm [n, nstep, nv]: the state after each step; contact_mask [n, nstep] int32 (the uint32
+          mask's bits) and reward [n, nstep]: of that state, as the step reports them; status [n] uint8: 0 ran all steps; 1 a
+          non-finite input the row uses, a failed factorisation, a bad qacc or a non-finite qpos; 2 an env index outside
+          0 .. num_envs-1 (never used as an address; state_index_errors does not count it); steps_done [n] int32: the steps
+          recorded before the row stopped -- its records from there on are zeros.  A row never resets.
+        `fields`: the names wanted (default: all; without contact_mask and reward the kernel skips the kinematics + collision
+        pass that feeds them); `out`: a dict of such tensors to fill -- only the fields it names are computed -- returned as
+        given."""
+        torch = _torch()
+        idx, ip, n = self._env_index(envs)
+        held = (("qpos", qpos, self.cm.nq), ("qvel", qvel, self.cm.nv), ("qacc_warm", warm, self.cm.nv))
+        stepped = (("ctrl", ctrl, self.cm.nu), ("qfrc_applied", qfrc_applied, self.cm.nv))
+        if n is None:
+            first = next((t for _, t, _ in held + stepped if t is not None), None)
+            n = self.num_envs if first is None else (int(first.shape[0]) if isinstance(first, torch.Tensor) and first.dim() else -1)
+        per_step = {name: isinstance(t, torch.Tensor) and t.dim() == 3 for name, t, _ in stepped}
+        lengths = {int(t.shape[1]) for name, t, _ in stepped if per_step[name]}
+        if nstep is not None:
+            lengths.add(int(nstep))
+        if len(lengths) > 1:
+            raise _libmod.KManipError("rollout: nstep and the per-step tensors disagree: %s" % sorted(lengths))
+        nstep = lengths.pop() if lengths else 1
+        nsub = 0 if nsub is None else int(nsub)          # (0: the model's n_sub_steps; a negative one is refused by the library)
+        dims ={"nq": self.cm.nq, "nv": self.cm.nv}
+        shapes = {name: (((n,) if shp is None else (n, nstep) + tuple(dims[d] for d in shp)), getattr(torch, dt))
+                  for name, (shp, dt) in self._ROLLOUT_FIELDS.items()}
+        names = list(out) if out is not None else list(shapes) if fields is None else list(fields)
+        unknown = set(names) - set(shapes)
+        if unknown:
+            raise ValueError("unknown rollout field(s) %s" % sorted(unknown))
+        ri = _libmod.KRolloutIn()
+        if idx is not None:
+            ri.env_index = idx.data_ptr()
+        for name, t, width in held:
+            if t is not None:
+                self._check_buf(t, (n, width), torch.float64, "warm" if name == "qacc_warm" else name)
+                setattr(ri, name, t.data_ptr())
+        for name, t, width in stepped:
+            if t is not None:
+                self._check_buf(t, (n, nstep, width) if per_step[name] else (n, width), torch.float64, name)
+                setattr(ri, name, t.data_ptr())
+        ri.ctrl_per_step, ri.frc_per_step = int(per_step["ctrl"]), int(per_step["qfrc_applied"])
+        if out is None:
+            out = {name: torch.empty(shapes[name][0], dtype=shapes[name][1], device=self.device) for name in names}
+        rd = _libmod.KRolloutDev()
+        for name, t in out.items():
+            self._check_buf(t, shapes[name][0], shapes[name][1], name)
+            setattr(rd, name, t.data_ptr())
+        self._check(self.L.kmanip_rollout(self.h, C.byref(ri), n, nstep, nsub, C.byref(rd), self._stream()), "kmanip_rollout")
+        return out
+
     def normal_by_bit(self, f):
         """[n, 32] float64: the normal force of the contact at each KM_CON_* mask bit of a forces() / forward() / inverse() result
         (it needs contact_force and contact_bit; n = the result's rows), 0 where the bit is clear.  Device-side indexing only: no

@@ -256,7 +256,8 @@ class BranchRollouts:
     candidate that reaches the TimeLimit (or diverges) inside the rollout auto-resets to ITS OWN cube spawn, not the real env's.
     rollout() returns the done bytes: mask the steps after a candidate's first nonzero byte.
     Everything runs on the caller's current stream; the plan handle's per-env parameters follow the real handle's at every
-    branch()."""
+    branch().  A planner that works in ctrl space (torque-level or servo-target MPPI / CEM, iLQR) needs no second handle:
+    KManipEnvHip.rollout() integrates K rows per env from the caller's own ctrl, per step, and never resets."""
 
     def __init__(self, env, k: int, env_id_offset: Optional[int] = None):
         torch = _torch()
