@@ -235,6 +235,17 @@ static void build_sphere_arm(const KModelDesc* d, uint8_t* out) {
   }
 }
 
+// the row arguments of kmanip_forward / kmanip_rollout (`what`; `in_t` / `out_t`: the names of its structs)
+template <class In, class Out>
+static int row_args(KHandle h, const char* what, const char* in_t, const char* out_t, const In* in, const Out* out, int n) {
+  const std::string w = std::string(what) + ": ";
+  if (!in) { h->err = w + "the " + in_t + " pointer is NULL"; return -1; }
+  if (!out) { h->err = w + "the " + out_t + " pointer is NULL"; return -1; }
+  if (n < 0) { h->err = w + "n is negative"; return -1; }
+  if (!in->env_index && n > h->st.num_envs) { h->err = w + "more rows than envs need " + in_t + "::env_index"; return -1; }
+  return 0;
+}
+
 extern "C" {
 
 int kmanip_model_desc_size(void) { return (int)sizeof(KModelDesc); }
@@ -450,14 +461,19 @@ int kmanip_observe(KHandle h, double* obs_dev, double* reward_dev, void* stream)
   return 0;
 }
 
+// nothing requested of kmanip_forces / kmanip_forward: the call succeeds and launches nothing
+static bool forces_out_empty(const KForcesDev& o) {
+  return !o.qacc && !o.qfrc_constraint && !o.qfrc_actuator && !o.contact_force && !o.contact_bit && !o.contact_frame && !o.contact_pos &&
+         !o.contact_dist && !o.contact_mask && !o.status;
+}
+
 // mj_forward with actuation at every env's current state: qacc, joint forces, contact forces (include/kmanip.h KForcesDev;
 // kmanip_forces.hip).  One launch; the handle is only read.
 int kmanip_forces(KHandle h, const KForcesDev* out, void* stream) {
   if (!h) { g_create_error = "kmanip_forces: null handle"; return -1; }
   if (!out) { h->err = "kmanip_forces: the KForcesDev pointer is NULL"; return -1; }
   if (h->desc.solver != KM_SOLVER_NEWTON) { h->err = "kmanip_forces: contact forces need the Newton solver"; return -1; }
-  if (!out->qacc && !out->qfrc_constraint && !out->qfrc_actuator && !out->contact_force && !out->contact_bit && !out->contact_frame &&
-      !out->contact_pos && !out->contact_dist && !out->contact_mask && !out->status) return 0;
+  if (forces_out_empty(*out)) return 0;
   KM_ENTER(h);
   kmanip_launch_forces(h->dmodel, h->desc, h->st, *out, (hipStream_t)stream);
   HIPCHK(h, hipGetLastError());
@@ -495,14 +511,10 @@ int kmanip_inverse(KHandle h, const KInverseIn* in, const KInverseDev* out, void
 // and unnamed fields it takes (include/kmanip.h KForwardIn; kmanip_forward.hip).  One launch; the handle is only read.
 int kmanip_forward(KHandle h, const KForwardIn* in, int n, const KForcesDev* out, void* stream) {
   if (!h) { g_create_error = "kmanip_forward: null handle"; return -1; }
-  if (!in) { h->err = "kmanip_forward: the KForwardIn pointer is NULL"; return -1; }
-  if (!out) { h->err = "kmanip_forward: the KForcesDev pointer is NULL"; return -1; }
+  if (row_args(h, "kmanip_forward", "KForwardIn", "KForcesDev", in, out, n)) return -1;
   if (h->desc.solver != KM_SOLVER_NEWTON) { h->err = "kmanip_forward: contact forces need the Newton solver"; return -1; }
-  if (n < 0) { h->err = "kmanip_forward: n is negative"; return -1; }
-  if (!in->env_index && n > h->st.num_envs) { h->err = "kmanip_forward: more rows than envs need KForwardIn::env_index"; return -1; }
   if (n == 0) return 0;
-  if (!out->qacc && !out->qfrc_constraint && !out->qfrc_actuator && !out->contact_force && !out->contact_bit && !out->contact_frame &&
-      !out->contact_pos && !out->contact_dist && !out->contact_mask && !out->status) return 0;
+  if (forces_out_empty(*out)) return 0;
   KM_ENTER(h);
   kmanip_launch_forward(h->dmodel, h->desc, h->st, *in, n, *out, (hipStream_t)stream);
   HIPCHK(h, hipGetLastError());
@@ -514,12 +526,9 @@ int kmanip_forward(KHandle h, const KForwardIn* in, int n, const KForcesDev* out
 // DESIGN.md section 27).  One launch; the handle is only read; the handle's solver.
 int kmanip_rollout(KHandle h, const KRolloutIn* in, int n, int nstep, int nsub, const KRolloutDev* out, void* stream) {
   if (!h) { g_create_error = "kmanip_rollout: null handle"; return -1; }
-  if (!in) { h->err = "kmanip_rollout: the KRolloutIn pointer is NULL"; return -1; }
-  if (!out) { h->err = "kmanip_rollout: the KRolloutDev pointer is NULL"; return -1; }
-  if (n < 0) { h->err = "kmanip_rollout: n is negative"; return -1; }
+  if (row_args(h, "kmanip_rollout", "KRolloutIn", "KRolloutDev", in, out, n)) return -1;
   if (nstep < 0) { h->err = "kmanip_rollout: nstep is negative"; return -1; }
   if (nsub < 0) { h->err = "kmanip_rollout: nsub is negative"; return -1; }
-  if (!in->env_index && n > h->st.num_envs) { h->err = "kmanip_rollout: more rows than envs need KRolloutIn::env_index"; return -1; }
   if (in->ctrl_per_step && !in->ctrl) { h->err = "kmanip_rollout: ctrl_per_step is set and KRolloutIn::ctrl is NULL"; return -1; }
   if (in->frc_per_step && !in->qfrc_applied) { h->err = "kmanip_rollout: frc_per_step is set and KRolloutIn::qfrc_applied is NULL"; return -1; }
   if (n == 0 || nstep == 0) return 0;

@@ -10,12 +10,14 @@
 // warm start carried by integrate -- with qpos_ik == qpos: no teleport, every sub-step a plain mj_step.  Both solvers: the rollout
 // runs the handle's (only solve's return value is read, no register of the Newton path).  The optional trailing pass per step is
 // k_step's too: fk_parallel + collide_parallel + env_reward on the state after the step.  The entry is k_forward's
-// (kmanip_forward.hip), restated here rather than shared: a helper moved into the common headers reorders the code of the other
-// kernels.  A translation unit of its own, so that every other object is the one it was, to the register.
+// (row_env, row_load), written once for both in kmanip_dyn_rows.hpp, a header only those units and kmanip_forces.hip include: a helper
+// moved into the common headers reorders the code of the other kernels.  A translation unit of its own, so
+// that the step's and the state queries' objects are the ones they were, to the register.
 // One wave per workgroup, 64 / G ROWS per wave; the state stays in LDS for all nstep x nsub sub-steps.
 #include "kmanip_ik_coop.hpp"
 #include <stdlib.h>
 #include "kmanip_dyn_variant.hpp"
+#include "kmanip_dyn_rows.hpp"         // (row_env, row_load: shared with k_forward)
 
 // zero records of steps t0 .. nstep-1 of one row (a row that stopped, or never started), then its status and step count
 template <int NL, int G>
@@ -42,71 +44,26 @@ __device__ __forceinline__ void rollout_finish(const KRolloutDev& out, size_t ro
 template <int NL, int G, int SOLVER, int EPB>
 __global__ __launch_bounds__(64) void KM_KERNEL(k_rollout)(const KDeviceModel* __restrict__ dm, KDeviceState st, KRolloutIn in, int n, int nstep,
                                                            int nsub, KRolloutDev out) {
-  constexpr int NV = Dim<NL>::NV, NQ = Dim<NL>::NQ;
-  static_assert(NV <= G, "lane = dof");
+  constexpr int NV = Dim<NL>::NV, NQ = Dim<NL>::NQ, KL = (NL + G - 1) / G;
   __shared__ Ws<NL> ws[EPB];
   __shared__ LModel<NL> lm;
   const KModelDesc* m = &dm->d;
   const int lane = threadIdx.x, grp = lane / G, sub = lane % G;
-  // k_forward's entry: the model staged by every lane, then a group without a row exits whole
-  stage_model<NL>(lm, dm);
-  const int row = xcd_block(blockIdx.x, gridDim.x) * EPB + grp;
-  if (grp >= EPB || row >= n) return;
+  int row, env;
+  if (!row_env<NL, EPB>(lm, dm, in, n, grp, row, env)) return;      // whole group exits together
   const size_t r = (size_t)row;
-  const int env = in.env_index ? in.env_index[row] : row;
   // an index outside the handle (group-uniform): never used as an address
   if (env < 0 || env >= st.num_envs) { rollout_finish<NL, G>(out, r, sub, nstep, 0, 2); return; }
   Ws<NL>& w = ws[grp];
   real invm = 0;                       // diagonal of M^-1 for the cube dof owned by this lane
-  const int NE = st.num_envs;
-  init_ws<NL>(w, sub);
+  init_ws<NL>(w, sub);            // (query_load's calls, row_load in load_state's place)
   env_invm<NL>(w, dm, st, env, sub, invm);
-  // the caller's rows of the state and of step 0's (or the held) ctrl and force, requested before the handle's columns are waited
-  // for; row (r, t) of a per-step tensor is row r * nstep + t
-  constexpr int KQ = (NQ + G - 1) / G, KV = (NV + G - 1) / G, KL = (NL + G - 1) / G;
+  // the caller's rows of ctrl and the force, held or step 0's: row (r, t) of a per-step tensor is row r * nstep + t
   // (a per-step flag counts only with the caller's own tensor: kmanip_rollout refuses it on a NULL one)
-  const bool cstep = in.ctrl_per_step && in.ctrl;
+  const bool cstep = in.ctrl_per_step && in.ctrl, fstep = in.frc_per_step && in.qfrc_applied;
   const double* crow = in.ctrl ? in.ctrl + r * (cstep ? (size_t)nstep : (size_t)1) * NL : nullptr;
-  real gq[KQ], gv[KV], gw[KV], gc[KL];
-#pragma unroll
-  for (int k = 0; k < KQ; k++) { const int i = sub + G * k, ic = i < NQ ? i : NQ - 1; gq[k] = in.qpos ? in.qpos[r * NQ + ic] : 0.0; }
-#pragma unroll
-  for (int k = 0; k < KV; k++) {
-    const int i = sub + G * k, ic = i < NV ? i : NV - 1;
-    gv[k] = in.qvel ? in.qvel[r * NV + ic] : 0.0;
-    gw[k] = in.qacc_warm ? in.qacc_warm[r * NV + ic] : 0.0;
-  }
-#pragma unroll
-  for (int k = 0; k < KL; k++) { const int i = sub + G * k, ic = i < NL ? i : NL - 1; gc[k] = crow ? crow[ic] : st.ctrl[(size_t)ic * NE + env]; }
-#if KM_VAR_FRC
-  // the caller's rows or the env's row of the bound buffer (the launcher picks this build only if one of the two exists)
-  const int fv = sub < NV ? sub : NV - 1;
-  const bool fstep = in.frc_per_step && in.qfrc_applied;
-  const double* frow = in.qfrc_applied ? in.qfrc_applied + r * (fstep ? (size_t)nstep : (size_t)1) * NV
-                                       : (st.qfrc_applied ? st.qfrc_applied + (size_t)env * NV : nullptr);
-  const real fap = frow ? frow[fv] : 0.0;
-#endif
-  load_state<NL, G>(w, st, env, sub);
-  // the overrides: each lane rewrites the entries it wrote in load_state (the same lane -> index map); ctrl as given / stored
-#pragma unroll
-  for (int k = 0; k < KQ; k++) { const int i = sub + G * k; if (in.qpos && i < NQ) w.qpos[i] = gq[k]; }
-#pragma unroll
-  for (int k = 0; k < KV; k++) { const int i = sub + G * k; if (i < NV) { if (in.qvel) w.qvel[i] = gv[k]; if (in.qacc_warm) w.warm[i] = gw[k]; } }
-#pragma unroll
-  for (int k = 0; k < KL; k++) { const int i = sub + G * k; if (i < NL) w.ctrl[i] = gc[k]; }
-  int lb = 0;                          // this lane's reasons for status 1
-#pragma unroll
-  for (int k = 0; k < KV; k++) { const int i = sub + G * k; if (i < NV) lb |= !isfinite(in.qacc_warm ? gw[k] : w.warm[i]); }
-#pragma unroll
-  for (int k = 0; k < KL; k++) lb |= !isfinite(gc[k]);      // (lanes past the last actuator hold a copy of it)
-#if KM_VAR_FRC
-  {                                    // load_applied's test: a row with a non-finite component is stored as zeros and computes nothing
-    const int frc_bad = gor<G>(!isfinite(fap));
-    if (sub < NV) w.frc[sub] = frc_bad ? 0.0 : fap;
-    lb |= frc_bad;
-  }
-#endif
-  GSYNC();
+  const double* frow = in.qfrc_applied ? in.qfrc_applied + r * (fstep ? (size_t)nstep : (size_t)1) * NV : nullptr;
+  const int lb = row_load<NL, G>(w, st, in, r, env, sub, crow, frow);
   // a non-finite input of step 0, given or stored: status 1, no step
   if (state_nonfinite<NL, G>(w, sub, lb)) { rollout_finish<NL, G>(out, r, sub, nstep, 0, 1); return; }
   Prof pf;
@@ -120,7 +77,7 @@ __global__ __launch_bounds__(64) void KM_KERNEL(k_rollout)(const KDeviceModel* _
 #pragma unroll
     for (int k = 0; k < KL; k++) { const int i = sub + G * k, ic = i < NL ? i : NL - 1; nc[k] = (cstep && more) ? crow[(size_t)(t + 1) * NL + ic] : 0.0; }
 #if KM_VAR_FRC
-    const real nf = (fstep && more) ? frow[(size_t)(t + 1) * NV + fv] : 0.0;
+    const real nf = (fstep && more) ? frow[(size_t)(t + 1) * NV + (sub < NV ? sub : NV - 1)] : 0.0;
 #endif
     int bad = 0;
     for (int s = 0; s < nsub; s++) {
@@ -130,6 +87,7 @@ __global__ __launch_bounds__(64) void KM_KERNEL(k_rollout)(const KDeviceModel* _
       CReg<NL> cr;                     // (one per sub-step: nothing of it can be carried round the loops)
       step1_products<NL, G, SOLVER>(w, lm, m, subv, cr, invm, pf);
       real a = solve<NL, G, SOLVER>(w, lm, m, subv, 1, cr, invm, pf);
+      // bad_qacc (kmanip_dyn_rows.hpp), spelt out: through the helper the two-arm kernels' loop is scheduled differently
       int la = (sub < NV) && (!isfinite(a) || fabs(a) > 1e10);   // mjWARN_BADQACC
       bad = gor<G>(la) | w.bad;
       if (bad) break;

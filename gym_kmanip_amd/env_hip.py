@@ -97,6 +97,43 @@ class KManipEnvHip:
                 what, dtype, tuple(shape), self.device, t.dtype, tuple(t.shape), t.device,
                 "" if t.is_contiguous() else " (non-contiguous)"))
 
+    def _query_out(self, table, lead, dims, out, fields, dev, noun):
+        """The outputs of a query: `table` maps a field to (trailing shape in terms of `dims`, dtype name); a field is `lead` + that
+        shape, or lead[:1] where the table has None (one value per row).  The fields are those of `out`, else `fields`, else all;
+        without `out` they are allocated.  Every tensor is checked and its pointer set in `dev`, the entry's ctypes struct.
+        Returns `out`."""
+        torch = _torch()
+        shapes = {name: (lead[:1] if shp is None else lead + tuple(dims.get(d, d) for d in shp), getattr(torch, dt))
+                  for name, (shp, dt) in table.items()}
+        names = list(out) if out is not None else list(shapes) if fields is None else list(fields)
+        unknown = set(names) - set(shapes)
+        if unknown:
+            raise ValueError("unknown %s field(s) %s" % (noun, sorted(unknown)))
+        if out is None:
+            out = {name: torch.empty(shapes[name][0], dtype=shapes[name][1], device=self.device) for name in names}
+        for name, t in out.items():
+            self._check_buf(t, shapes[name][0], shapes[name][1], name)
+            setattr(dev, name, t.data_ptr())
+        return out
+
+    def _query_rows(self, envs, given, ins):
+        """The rows of forward() / rollout(): n = len(envs), else the rows of the first given tensor, else num_envs.  `given`:
+        (field of `ins`, tensor or None, shape of one row) triples; every tensor is checked as float64 [n, *shape] (n = -1, which
+        no tensor passes, for one without a leading dimension) and its pointer set in `ins`, the entry's ctypes input struct.
+        Returns (n, the env index tensor or None: the caller holds it until the launch)."""
+        torch = _torch()
+        idx, _, n = self._env_index(envs)
+        if idx is not None:
+            ins.env_index = idx.data_ptr()
+        if n is None:
+            first = next((t for _, t, _ in given if t is not None), None)
+            n = self.num_envs if first is None else (int(first.shape[0]) if isinstance(first, torch.Tensor) and first.dim() else -1)
+        for name, t, shape in given:
+            if t is not None:
+                self._check_buf(t, (n,) + shape, torch.float64, "warm" if name == "qacc_warm" else name)
+                setattr(ins, name, t.data_ptr())
+        return n, idx
+
     def pack_action(self, action) -> "object":
         """dict of arrays keyed like the reference action space (env_base.py:151-188) -> flat [N, act_dim].  A dict of
         DEVICE tensors is packed on the device (one strided copy per key into the handle's action buffer: no host
@@ -213,21 +250,10 @@ class KManipEnvHip:
           [n, NC, 9]; contact_pos [n, NC, 3]; contact_dist [n, NC]; contact_mask [n] int32 (the uint32 mask's bits); status [n] uint8
         NC = model.contact_slots(nlink).  `fields`: the names wanted (default: all); `out`: a dict of such tensors to fill -- only
         the fields it names are computed -- returned as given.  Newton handles only."""
-        torch = _torch()
         from .model import contact_slots
         dims = {"nv": self.cm.nv, "nu": self.cm.nu, "nc": contact_slots(self.cm.nlink)}
-        shapes = {name: ((self.num_envs,) + tuple(dims.get(d, d) for d in shp), getattr(torch, dt))
-                  for name, (shp, dt) in self._FORCE_FIELDS.items()}
-        names = list(out) if out is not None else list(shapes) if fields is None else list(fields)
-        unknown = set(names) - set(shapes)
-        if unknown:
-            raise ValueError("unknown force field(s) %s" % sorted(unknown))
-        if out is None:
-            out = {name: torch.empty(shapes[name][0], dtype=shapes[name][1], device=self.device) for name in names}
         fd = _libmod.KForcesDev()
-        for name, t in out.items():
-            self._check_buf(t, shapes[name][0], shapes[name][1], name)
-            setattr(fd, name, t.data_ptr())
+        out = self._query_out(self._FORCE_FIELDS, (self.num_envs,), dims, out, fields, fd, "force")
         self._check(self.L.kmanip_forces(self.h, C.byref(fd), self._stream()), "kmanip_forces")
         return out
 
@@ -251,23 +277,13 @@ class KManipEnvHip:
         torch = _torch()
         from .model import contact_slots
         dims = {"nv": self.cm.nv, "nc": contact_slots(self.cm.nlink)}
-        shapes = {name: ((self.num_envs,) + tuple(dims.get(d, d) for d in shp), getattr(torch, dt))
-                  for name, (shp, dt) in self._INVERSE_FIELDS.items()}
-        names = list(out) if out is not None else list(shapes) if fields is None else list(fields)
-        unknown = set(names) - set(shapes)
-        if unknown:
-            raise ValueError("unknown inverse field(s) %s" % sorted(unknown))
         iv = _libmod.KInverseIn()
         for name, t, width in (("qacc", qacc, self.cm.nv), ("qpos", qpos, self.cm.nq), ("qvel", qvel, self.cm.nv)):
             if t is not None or name == "qacc":
                 self._check_buf(t, (self.num_envs, width), torch.float64, name)
                 setattr(iv, name, t.data_ptr())
-        if out is None:
-            out = {name: torch.empty(shapes[name][0], dtype=shapes[name][1], device=self.device) for name in names}
         od = _libmod.KInverseDev()
-        for name, t in out.items():
-            self._check_buf(t, shapes[name][0], shapes[name][1], name)
-            setattr(od, name, t.data_ptr())
+        out = self._query_out(self._INVERSE_FIELDS, (self.num_envs,), dims, out, fields, od, "inverse")
         self._check(self.L.kmanip_inverse(self.h, C.byref(iv), C.byref(od), self._stream()), "kmanip_inverse")
         return out
 
@@ -285,34 +301,13 @@ class KManipEnvHip:
         address; state_index_errors does not count it) -- every other output of such a row is 0 and contact_bit -1.
         `fields`: the names wanted (default: all); `out`: a dict of such tensors to fill -- only the fields it names are
         computed -- returned as given.  Newton handles only."""
-        torch = _torch()
         from .model import contact_slots
-        idx, ip, n = self._env_index(envs)
-        given = (("qpos", qpos, self.cm.nq), ("qvel", qvel, self.cm.nv), ("ctrl", ctrl, self.cm.nu), ("qacc_warm", warm, self.cm.nv),
-                 ("qfrc_applied", qfrc_applied, self.cm.nv))
-        if n is None:
-            first = next((t for _, t, _ in given if t is not None), None)
-            n = self.num_envs if first is None else (int(first.shape[0]) if isinstance(first, torch.Tensor) and first.dim() else -1)
-        dims = {"nv": self.cm.nv, "nu": self.cm.nu, "nc": contact_slots(self.cm.nlink)}
-        shapes = {name: ((n,) + tuple(dims.get(d, d) for d in shp), getattr(torch, dt))
-                  for name, (shp, dt) in self._FORCE_FIELDS.items()}
-        names = list(out) if out is not None else list(shapes) if fields is None else list(fields)
-        unknown = set(names) - set(shapes)
-        if unknown:
-            raise ValueError("unknown force field(s) %s" % sorted(unknown))
         fi = _libmod.KForwardIn()
-        if idx is not None:
-            fi.env_index = idx.data_ptr()
-        for name, t, width in given:
-            if t is not None:
-                self._check_buf(t, (n, width), torch.float64, "warm" if name == "qacc_warm" else name)
-                setattr(fi, name, t.data_ptr())
-        if out is None:
-            out = {name: torch.empty(shapes[name][0], dtype=shapes[name][1], device=self.device) for name in names}
+        n, idx = self._query_rows(envs, (("qpos", qpos, (self.cm.nq,)), ("qvel", qvel, (self.cm.nv,)), ("ctrl", ctrl, (self.cm.nu,)),
+                                         ("qacc_warm", warm, (self.cm.nv,)), ("qfrc_applied", qfrc_applied, (self.cm.nv,))), fi)
+        dims = {"nv": self.cm.nv, "nu": self.cm.nu, "nc": contact_slots(self.cm.nlink)}
         fd = _libmod.KForcesDev()
-        for name, t in out.items():
-            self._check_buf(t, shapes[name][0], shapes[name][1], name)
-            setattr(fd, name, t.data_ptr())
+        out = self._query_out(self._FORCE_FIELDS, (n,), dims, out, fields, fd, "force")
         self._check(self.L.kmanip_forward(self.h, C.byref(fi), n, C.byref(fd), self._stream()), "kmanip_forward")
         return out
 
@@ -340,12 +335,7 @@ class KManipEnvHip:
         pass that feeds them); `out`: a dict of such tensors to fill -- only the fields it names are computed -- returned as
         given."""
         torch = _torch()
-        idx, ip, n = self._env_index(envs)
-        held = (("qpos", qpos, self.cm.nq), ("qvel", qvel, self.cm.nv), ("qacc_warm", warm, self.cm.nv))
         stepped = (("ctrl", ctrl, self.cm.nu), ("qfrc_applied", qfrc_applied, self.cm.nv))
-        if n is None:
-            first = next((t for _, t, _ in held + stepped if t is not None), None)
-            n = self.num_envs if first is None else (int(first.shape[0]) if isinstance(first, torch.Tensor) and first.dim() else -1)
         per_step = {name: isinstance(t, torch.Tensor) and t.dim() == 3 for name, t, _ in stepped}
         lengths = {int(t.shape[1]) for name, t, _ in stepped if per_step[name]}
         if nstep is not None:
@@ -354,31 +344,13 @@ class KManipEnvHip:
             raise _libmod.KManipError("rollout: nstep and the per-step tensors disagree: %s" % sorted(lengths))
         nstep = lengths.pop() if lengths else 1
         nsub = 0 if nsub is None else int(nsub)          # (0: the model's n_sub_steps; a negative one is refused by the library)
-        dims ={"nq": self.cm.nq, "nv": self.cm.nv}
-        shapes = {name: (((n,) if shp is None else (n, nstep) + tuple(dims[d] for d in shp)), getattr(torch, dt))
-                  for name, (shp, dt) in self._ROLLOUT_FIELDS.items()}
-        names = list(out) if out is not None else list(shapes) if fields is None else list(fields)
-        unknown = set(names) - set(shapes)
-        if unknown:
-            raise ValueError("unknown rollout field(s) %s" % sorted(unknown))
         ri = _libmod.KRolloutIn()
-        if idx is not None:
-            ri.env_index = idx.data_ptr()
-        for name, t, width in held:
-            if t is not None:
-                self._check_buf(t, (n, width), torch.float64, "warm" if name == "qacc_warm" else name)
-                setattr(ri, name, t.data_ptr())
-        for name, t, width in stepped:
-            if t is not None:
-                self._check_buf(t, (n, nstep, width) if per_step[name] else (n, width), torch.float64, name)
-                setattr(ri, name, t.data_ptr())
+        given = (("qpos", qpos, (self.cm.nq,)), ("qvel", qvel, (self.cm.nv,)), ("qacc_warm", warm, (self.cm.nv,)))
+        given += tuple((name, t, (nstep, width) if per_step[name] else (width,)) for name, t, width in stepped)
+        n, idx = self._query_rows(envs, given, ri)
         ri.ctrl_per_step, ri.frc_per_step = int(per_step["ctrl"]), int(per_step["qfrc_applied"])
-        if out is None:
-            out = {name: torch.empty(shapes[name][0], dtype=shapes[name][1], device=self.device) for name in names}
         rd = _libmod.KRolloutDev()
-        for name, t in out.items():
-            self._check_buf(t, shapes[name][0], shapes[name][1], name)
-            setattr(rd, name, t.data_ptr())
+        out = self._query_out(self._ROLLOUT_FIELDS, (n, nstep), {"nq": self.cm.nq, "nv": self.cm.nv}, out, fields, rd, "rollout")
         self._check(self.L.kmanip_rollout(self.h, C.byref(ri), n, nstep, nsub, C.byref(rd), self._stream()), "kmanip_rollout")
         return out
 
@@ -413,20 +385,9 @@ class KManipEnvHip:
           status [n] uint8 (1: non-finite state, everything else of the env 0)
         `fields`: the names wanted (default: all); `out`: a dict of such tensors to fill -- only the fields it names are computed --
         returned as given."""
-        torch = _torch()
         dims = {"nl": self.cm.nlink, "nv": self.cm.nv, "na": 2}
-        shapes = {name: ((self.num_envs,) + tuple(dims.get(d, d) for d in shp), getattr(torch, dt))
-                  for name, (shp, dt) in self._KIN_FIELDS.items()}
-        names = list(out) if out is not None else list(shapes) if fields is None else list(fields)
-        unknown = set(names) - set(shapes)
-        if unknown:
-            raise ValueError("unknown kinematics field(s) %s" % sorted(unknown))
-        if out is None:
-            out = {name: torch.empty(shapes[name][0], dtype=shapes[name][1], device=self.device) for name in names}
         kd = _libmod.KKinDev()
-        for name, t in out.items():
-            self._check_buf(t, shapes[name][0], shapes[name][1], name)
-            setattr(kd, name, t.data_ptr())
+        out = self._query_out(self._KIN_FIELDS, (self.num_envs,), dims, out, fields, kd, "kinematics")
         self._check(self.L.kmanip_kinematics(self.h, C.byref(kd), self._stream()), "kmanip_kinematics")
         return out
 
