@@ -235,7 +235,7 @@ static void build_sphere_arm(const KModelDesc* d, uint8_t* out) {
   }
 }
 
-// the row arguments of kmanip_forward / kmanip_rollout (`what`; `in_t` / `out_t`: the names of its structs)
+// the row arguments of kmanip_forward / kmanip_rollout / kmanip_feedback (`what`; `in_t` / `out_t`: the names of its structs)
 template <class In, class Out>
 static int row_args(KHandle h, const char* what, const char* in_t, const char* out_t, const In* in, const Out* out, int n) {
   const std::string w = std::string(what) + ": ";
@@ -535,6 +535,28 @@ int kmanip_rollout(KHandle h, const KRolloutIn* in, int n, int nstep, int nsub, 
   if (!out->qpos && !out->qvel && !out->qacc_warm && !out->contact_mask && !out->reward && !out->status && !out->steps_done) return 0;
   KM_ENTER(h);
   kmanip_launch_rollout(h->dmodel, h->desc, h->st, *in, n, nstep, nsub ? nsub : h->desc.n_sub_steps, *out, (hipStream_t)stream);
+  HIPCHK(h, hipGetLastError());
+  return 0;
+}
+
+// kmanip_rollout with the policy u = ctrl + gain (state - reference) evaluated at every step boundary on the device (include/kmanip.h
+// KFeedbackIn / KFeedbackDev; kmanip_feedback.hip).  One launch; the handle is only read; the handle's solver.
+int kmanip_feedback(KHandle h, const KFeedbackIn* in, int n, int nstep, int nsub, const KFeedbackDev* out, void* stream) {
+  if (!h) { g_create_error = "kmanip_feedback: null handle"; return -1; }
+  if (row_args(h, "kmanip_feedback", "KFeedbackIn", "KFeedbackDev", in, out, n)) return -1;
+  if (nstep < 0) { h->err = "kmanip_feedback: nstep is negative"; return -1; }
+  if (nsub < 0) { h->err = "kmanip_feedback: nsub is negative"; return -1; }
+  if (in->ctrl_per_step && !in->ctrl) { h->err = "kmanip_feedback: ctrl_per_step is set and KFeedbackIn::ctrl is NULL"; return -1; }
+  if (in->frc_per_step && !in->qfrc_applied) { h->err = "kmanip_feedback: frc_per_step is set and KFeedbackIn::qfrc_applied is NULL"; return -1; }
+  if (!in->qpos_ref) { h->err = "kmanip_feedback: KFeedbackIn::qpos_ref is NULL"; return -1; }
+  if (!in->qvel_ref) { h->err = "kmanip_feedback: KFeedbackIn::qvel_ref is NULL"; return -1; }
+  if (!in->gain_t) { h->err = "kmanip_feedback: KFeedbackIn::gain_t is NULL"; return -1; }
+  if (in->ng <= 0) { h->err = "kmanip_feedback: ng is not positive"; return -1; }
+  if (!in->gain_index && in->ng < n) { h->err = "kmanip_feedback: more rows than gain trajectories need KFeedbackIn::gain_index"; return -1; }
+  if (n == 0 || nstep == 0) return 0;
+  if (!out->qpos && !out->qvel && !out->qacc_warm && !out->contact_mask && !out->reward && !out->status && !out->steps_done && !out->ctrl) return 0;
+  KM_ENTER(h);
+  kmanip_launch_feedback(h->dmodel, h->desc, h->st, *in, n, nstep, nsub ? nsub : h->desc.n_sub_steps, *out, (hipStream_t)stream);
   HIPCHK(h, hipGetLastError());
   return 0;
 }

@@ -590,6 +590,9 @@ void kmanip_launch_forward(const KDeviceModel* dm, const KModelDesc& hd, const K
 // kmanip_launch_forward picks them
 void kmanip_launch_rollout(const KDeviceModel* dm, const KModelDesc& hd, const KDeviceState& st, const KRolloutIn& in, int n, int nstep,
                            int nsub, const KRolloutDev& out, hipStream_t stream);
+// kmanip_feedback: kmanip_launch_rollout's arguments and choice of build
+void kmanip_launch_feedback(const KDeviceModel* dm, const KModelDesc& hd, const KDeviceState& st, const KFeedbackIn& in, int n, int nstep,
+                            int nsub, const KFeedbackDev& out, hipStream_t stream);
 // The render launchers' visual inputs (kmanip_set_visual_params / _ranges), a kernel argument of the VIS
 // kernels only -- never a KDeviceState field: the step kernels' argument stays as it is.  All NULL: the default kernels.
 //   vp       explicit values double[KM_VP_N][N], read at the render's launch

@@ -19,6 +19,7 @@ typedef void KinFn(const KDeviceModel*, const KDeviceState&, const KKinDev&, hip
 typedef void InverseFn(const KDeviceModel*, const KDeviceState&, const KInverseIn&, const KInverseDev&, hipStream_t);
 typedef void ForwardFn(const KDeviceModel*, const KDeviceState&, const KForwardIn&, int, const KForcesDev&, hipStream_t);
 typedef void RolloutFn(const KDeviceModel*, const KDeviceState&, const KRolloutIn&, int, int, int, const KRolloutDev&, hipStream_t);
+typedef void FeedbackFn(const KDeviceModel*, const KDeviceState&, const KFeedbackIn&, int, int, int, const KFeedbackDev&, hipStream_t);
 
 // kmanip_dyn.hip: step per solver in every build, reset per solver in the parameter builds; observe and prepare are
 // solver-independent, one copy per class (in the default Newton object)
@@ -26,6 +27,8 @@ typedef void RolloutFn(const KDeviceModel*, const KDeviceState&, const KRolloutI
 #define KM_RESET_ROW(B, NL, G) {KM_NAME(reset, B, NL, G, _0), KM_NAME(reset, B, NL, G, _1)},
 // kmanip_rollout.hip: per solver in every build, like the step
 #define KM_ROLLOUT_ROW(B, NL, G) {KM_NAME(rollout, B, NL, G, _0), KM_NAME(rollout, B, NL, G, _1)},
+// kmanip_feedback.hip: likewise
+#define KM_FEEDBACK_ROW(B, NL, G) {KM_NAME(feedback, B, NL, G, _0), KM_NAME(feedback, B, NL, G, _1)},
 #define KM_OBSERVE_ROW(B, NL, G) KM_NAME(observe, B, NL, G, _1),
 #define KM_PREPARE_ROW(B, NL, G) KM_NAME(prepare, B, NL, G, _1),
 // kmanip_forces.hip and kmanip_forward.hip (the Newton classes, every build), kmanip_kinematics.hip and kmanip_inverse.hip (one object per class serves both
@@ -36,7 +39,7 @@ typedef void RolloutFn(const KDeviceModel*, const KDeviceState&, const KRolloutI
 #define KM_FORWARD_ROW(B, NL, G) KM_NAME(forward, B, NL, G, ),
 
 #define KM_DECL_SOLVERS(Fn, kind, B, NL, G) Fn KM_NAME(kind, B, NL, G, _0), KM_NAME(kind, B, NL, G, _1);
-#define KM_DECL_FRC(B, NL, G) KM_DECL_SOLVERS(StepFn, step, B, NL, G) KM_DECL_SOLVERS(RolloutFn, rollout, B, NL, G) ForcesFn KM_NAME(forces, B, NL, G, ); ForwardFn KM_NAME(forward, B, NL, G, );
+#define KM_DECL_FRC(B, NL, G) KM_DECL_SOLVERS(StepFn, step, B, NL, G) KM_DECL_SOLVERS(RolloutFn, rollout, B, NL, G) KM_DECL_SOLVERS(FeedbackFn, feedback, B, NL, G) ForcesFn KM_NAME(forces, B, NL, G, ); ForwardFn KM_NAME(forward, B, NL, G, );
 #define KM_DECL_PAR(B, NL, G) KM_DECL_SOLVERS(ResetFn, reset, B, NL, G) KinFn KM_NAME(kinematics, B, NL, G, ); InverseFn KM_NAME(inverse, B, NL, G, );
 #define KM_DECL_ONCE(B, NL, G) ObserveFn KM_NAME(observe, B, NL, G, _1); PrepareFn KM_NAME(prepare, B, NL, G, _1);
 #define KM_DECL_BUILD_FRC(B) KM_CLASSES(KM_DECL_FRC, B)
@@ -51,6 +54,7 @@ KM_BUILDS(KM_DECL_BUILD_FRC) KM_BUILDS_PAR(KM_DECL_BUILD_PAR) KM_CLASSES(KM_DECL
 #define KM_INVERSE_BUILD(B) {KM_CLASSES(KM_INVERSE_ROW, B)},
 #define KM_FORWARD_BUILD(B) {KM_CLASSES(KM_FORWARD_ROW, B)},
 #define KM_ROLLOUT_BUILD(B) {KM_CLASSES(KM_ROLLOUT_ROW, B)},
+#define KM_FEEDBACK_BUILD(B) {KM_CLASSES(KM_FEEDBACK_ROW, B)},
 static constexpr StepFn* step_tab[4][2][2] = {KM_BUILDS(KM_STEP_BUILD)};
 static constexpr ResetFn* reset_tab[2][2][2] = {KM_BUILDS_PAR(KM_RESET_BUILD)};
 static constexpr ObserveFn* observe_tab[2] = {KM_CLASSES(KM_OBSERVE_ROW, )};
@@ -60,6 +64,7 @@ static constexpr KinFn* kin_tab[2][2] = {KM_BUILDS_PAR(KM_KIN_BUILD)};
 static constexpr InverseFn* inverse_tab[2][2] = {KM_BUILDS_PAR(KM_INVERSE_BUILD)};
 static constexpr ForwardFn* forward_tab[4][2] = {KM_BUILDS(KM_FORWARD_BUILD)};
 static constexpr RolloutFn* rollout_tab[4][2][2] = {KM_BUILDS(KM_ROLLOUT_BUILD)};
+static constexpr FeedbackFn* feedback_tab[4][2][2] = {KM_BUILDS(KM_FEEDBACK_BUILD)};
 
 static int cls(const KModelDesc& hd) { return hd.nlink <= 10 ? 0 : 1; }
 static int newton(const KModelDesc& hd) { return hd.solver == KM_SOLVER_NEWTON ? 1 : 0; }
@@ -97,6 +102,11 @@ void kmanip_launch_rollout(const KDeviceModel* dm, const KModelDesc& hd, const K
                            int nsub, const KRolloutDev& out, hipStream_t stream) {
   // the force build iff a row can have a force: the caller's rows or the handle's bound buffer
   rollout_tab[par(st) + ((in.qfrc_applied || st.qfrc_applied) ? 2 : 0)][cls(hd)][newton(hd)](dm, st, in, n, nstep, nsub, out, stream);
+}
+void kmanip_launch_feedback(const KDeviceModel* dm, const KModelDesc& hd, const KDeviceState& st, const KFeedbackIn& in, int n, int nstep,
+                            int nsub, const KFeedbackDev& out, hipStream_t stream) {
+  // (the builds as kmanip_launch_rollout picks them)
+  feedback_tab[par(st) + ((in.qfrc_applied || st.qfrc_applied) ? 2 : 0)][cls(hd)][newton(hd)](dm, st, in, n, nstep, nsub, out, stream);
 }
 void kmanip_launch_prepare_model(KDeviceModel* dm, const KModelDesc& hd, hipStream_t stream) {
   prepare_tab[cls(hd)](dm, stream);

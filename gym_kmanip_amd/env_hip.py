@@ -311,6 +311,26 @@ class KManipEnvHip:
         self._check(self.L.kmanip_forward(self.h, C.byref(fi), n, C.byref(fd), self._stream()), "kmanip_forward")
         return out
 
+    def _stepped_rows(self, what, envs, qpos, qvel, ctrl, warm, qfrc_applied, nstep, nsub, ins, per_step_lengths=()):
+        """The rows of rollout() / rollout_feedback(): nstep from the rank-3 tensors (and `per_step_lengths`, further per-step
+        lengths of the caller's), else the argument, else 1; every given tensor checked and set in `ins` (_query_rows), the two
+        per-step flags with them.  Returns (n, nstep, nsub for the library, the env index tensor or None)."""
+        torch = _torch()
+        stepped = (("ctrl", ctrl, self.cm.nu), ("qfrc_applied", qfrc_applied, self.cm.nv))
+        per_step = {name: isinstance(t, torch.Tensor) and t.dim() == 3 for name, t, _ in stepped}
+        lengths = {int(t.shape[1]) for name, t, _ in stepped if per_step[name]} | {int(x) for x in per_step_lengths}
+        if nstep is not None:
+            lengths.add(int(nstep))
+        if len(lengths) > 1:
+            raise _libmod.KManipError("%s: nstep and the per-step tensors disagree: %s" % (what, sorted(lengths)))
+        nstep = lengths.pop() if lengths else 1
+        nsub = 0 if nsub is None else int(nsub)          # (0: the model's n_sub_steps; a negative one is refused by the library)
+        given = (("qpos", qpos, (self.cm.nq,)), ("qvel", qvel, (self.cm.nv,)), ("qacc_warm", warm, (self.cm.nv,)))
+        given += tuple((name, t, (nstep, width) if per_step[name] else (width,)) for name, t, width in stepped)
+        n, idx = self._query_rows(envs, given, ins)
+        ins.ctrl_per_step, ins.frc_per_step = int(per_step["ctrl"]), int(per_step["qfrc_applied"])
+        return n, nstep, nsub, idx
+
     # KRolloutDev field -> (trailing shape in terms of nq / nv, or None for the per-row fields, dtype name)
     _ROLLOUT_FIELDS = {"qpos": (("nq",), "float64"), "qvel": (("nv",), "float64"), "qacc_warm": (("nv",), "float64"),
                        "contact_mask": ((), "int32"), "reward": ((), "float64"), "status": (None, "uint8"), "steps_done": (None, "int32")}
@@ -334,24 +354,61 @@ class KManipEnvHip:
         `fields`: the names wanted (default: all; without contact_mask and reward the kernel skips the kinematics + collision
         pass that feeds them); `out`: a dict of such tensors to fill -- only the fields it names are computed -- returned as
         given."""
-        torch = _torch()
-        stepped = (("ctrl", ctrl, self.cm.nu), ("qfrc_applied", qfrc_applied, self.cm.nv))
-        per_step = {name: isinstance(t, torch.Tensor) and t.dim() == 3 for name, t, _ in stepped}
-        lengths = {int(t.shape[1]) for name, t, _ in stepped if per_step[name]}
-        if nstep is not None:
-            lengths.add(int(nstep))
-        if len(lengths) > 1:
-            raise _libmod.KManipError("rollout: nstep and the per-step tensors disagree: %s" % sorted(lengths))
-        nstep = lengths.pop() if lengths else 1
-        nsub = 0 if nsub is None else int(nsub)          # (0: the model's n_sub_steps; a negative one is refused by the library)
         ri = _libmod.KRolloutIn()
-        given = (("qpos", qpos, (self.cm.nq,)), ("qvel", qvel, (self.cm.nv,)), ("qacc_warm", warm, (self.cm.nv,)))
-        given += tuple((name, t, (nstep, width) if per_step[name] else (width,)) for name, t, width in stepped)
-        n, idx = self._query_rows(envs, given, ri)
-        ri.ctrl_per_step, ri.frc_per_step = int(per_step["ctrl"]), int(per_step["qfrc_applied"])
+        n, nstep, nsub, idx = self._stepped_rows("rollout", envs, qpos, qvel, ctrl, warm, qfrc_applied, nstep, nsub, ri)
         rd = _libmod.KRolloutDev()
         out = self._query_out(self._ROLLOUT_FIELDS, (n, nstep), {"nq": self.cm.nq, "nv": self.cm.nv}, out, fields, rd, "rollout")
         self._check(self.L.kmanip_rollout(self.h, C.byref(ri), n, nstep, nsub, C.byref(rd), self._stream()), "kmanip_rollout")
+        return out
+
+    _FEEDBACK_FIELDS = dict(_ROLLOUT_FIELDS, ctrl=(("nu",), "float64"))
+
+    def rollout_feedback(self, envs=None, qpos=None, qvel=None, ctrl=None, warm=None, qfrc_applied=None, gains=None, qpos_ref=None,
+                         qvel_ref=None, gain_index=None, nstep=None, nsub=None, out=None, fields=None, gains_t=None):
+        """kmanip_feedback: rollout() with a per-step affine state feedback evaluated on the device, in the same ONE launch -- the
+        policy of an iLQR / DDP backward pass, a regulator, or the stabilising feedback under MPPI samples.  At the START of every
+        step t, with (q, v) the row's state there,
+          dx = [derivatives.tangent_diff(q, qpos_ref[g, t]) ; v - qvel_ref[g, t]],    u = ctrl[r, t] + gains[g, t] @ dx
+        and u acts during step t (unclamped: the servos' own clamps act in the sub-steps).  Rows, their None fields, ctrl /
+        qfrc_applied held or per step, nstep and nsub as in rollout(); ctrl is the open-loop term.
+          gains [ng, nstep, nu, 2 nv] per step, or [ng, nu, 2 nv] held for all steps (a regulator), in the textbook orientation: the
+            library is handed the transposed contiguous copy.  gains_t [ng, nstep, 2 nv, nu] / [ng, 2 nv, nu] in its place skips
+            that copy.
+          qpos_ref [ng, nstep, nq] / [ng, nq], qvel_ref [ng, nstep, nv] / [ng, nv]: the reference state BEFORE step t, per step or
+            held like the gains.  Record t of an earlier rollout is the state AFTER step t, i.e. the reference of step t + 1.
+          gain_index: int32 [n], row r follows trajectory gain_index[r] (repeats allowed); None = row r follows trajectory r.
+        Returns rollout()'s dict plus ctrl [n, nstep, nu], the u of every step; status 1 also for a non-finite u (steps_done = the
+        step it was computed for), status 2 also for a gain index outside 0 .. ng-1 (never used as an address).  With zero gains
+        the result is rollout()'s, bit for bit."""
+        torch = _torch()
+        if (gains is None) == (gains_t is None):
+            raise _libmod.KManipError("rollout_feedback: give gains or gains_t (one of them)")
+        if gains is not None:
+            if not isinstance(gains, torch.Tensor) or gains.dim() not in (3, 4):
+                raise _libmod.KManipError("rollout_feedback: gains must be a [ng, nstep, nu, 2 nv] or [ng, nu, 2 nv] tensor")
+            gains_t = gains.transpose(-1, -2).contiguous()
+        if not isinstance(gains_t, torch.Tensor) or gains_t.dim() not in (3, 4):
+            raise _libmod.KManipError("rollout_feedback: gains_t must be a [ng, nstep, 2 nv, nu] or [ng, 2 nv, nu] tensor")
+        per_step = gains_t.dim() == 4
+        ng = int(gains_t.shape[0])
+        fi = _libmod.KFeedbackIn()
+        n, nstep, nsub, idx = self._stepped_rows("rollout_feedback", envs, qpos, qvel, ctrl, warm, qfrc_applied, nstep, nsub, fi,
+                                                 per_step_lengths=(gains_t.shape[1],) if per_step else ())
+        lead = (ng, nstep) if per_step else (ng,)
+        for name, t, shape in (("gain_t", gains_t, (2 * self.cm.nv, self.cm.nu)), ("qpos_ref", qpos_ref, (self.cm.nq,)),
+                               ("qvel_ref", qvel_ref, (self.cm.nv,))):
+            self._check_buf(t, lead + shape, torch.float64, "gains" if name == "gain_t" else name)
+            setattr(fi, name, t.data_ptr())
+        gidx, _, gn = self._env_index(gain_index, "gain_index")
+        if gidx is not None:
+            if gn != n:
+                raise _libmod.KManipError("rollout_feedback: gain_index has %d entries for %d rows" % (gn, n))
+            fi.gain_index = gidx.data_ptr()
+        fi.ng, fi.gain_per_step = ng, int(per_step)
+        fd = _libmod.KFeedbackDev()
+        out = self._query_out(self._FEEDBACK_FIELDS, (n, nstep), {"nq": self.cm.nq, "nv": self.cm.nv, "nu": self.cm.nu}, out, fields, fd,
+                              "rollout_feedback")
+        self._check(self.L.kmanip_feedback(self.h, C.byref(fi), n, nstep, nsub, C.byref(fd), self._stream()), "kmanip_feedback")
         return out
 
     def normal_by_bit(self, f):

@@ -1,0 +1,174 @@
+"""iLQR in ctrl space over KManipEnvHip.rollout, derivatives.transition_fd and KManipEnvHip.rollout_feedback.
+
+One iteration is three device calls whatever the horizon T: the nominal trajectory (one rollout launch), its linearisation
+(transition_fd over all n T start-of-step states as rows: two launches), and the line search -- the backward pass's policy
+u_t = u_t + alpha k_t + K_t (x_t - x_t_nominal) rolled out CLOSED LOOP for every step size alpha at once, one rollout_feedback launch
+of n len(alphas) rows that share the n gain trajectories through gain_index.
+
+The state is (qpos in the tangent space, qvel), 2 nv wide, as transition_fd defines it; differences of states are
+derivatives.tangent_diff's.  Everything is torch arithmetic on the device of the caller's tensors and needs only env.rollout,
+env.rollout_feedback, env.cm and that device, so a CPU stand-in (tests/tools/feedback_oracle.py OracleFeedback) runs the same code."""
+from .derivatives import tangent_diff, transition_fd
+
+
+def _start_states(first, records):
+    """[n, T, w]: the state BEFORE each step -- the initial row, then records 0 .. T-2 (record t is the state after step t)."""
+    import torch
+    return torch.cat([first[:, None], records[:, :-1]], dim=1)
+
+
+def trajectory_fd(env, envs, qpos0, qvel0, warm0, ctrl, qfrc_applied=None, nsub=None, eps=1e-6):
+    """The nominal trajectory of ctrl [n, T, nu] from (qpos0, qvel0, warm0) and its linearisation at every step.  One rollout launch,
+    then ONE transition_fd call over the n T start-of-step states as rows (row e T + t names env envs[e]; its warm start is the
+    trajectory's qacc_warm before that step).  envs None: row e is env e.  qfrc_applied [n, nv], held, or None.  Returns a dict:
+      A [n, T, 2 nv, 2 nv], B [n, T, 2 nv, nu]       d x_{t+1} / d x_t, d x_{t+1} / d u_t
+      qpos [n, T + 1, nq], qvel [n, T + 1, nv]       x_0 .. x_T (x_t: the state before step t)
+      warm [n, T, nv]                                 the warm start of every step
+      status [n] uint8                                the nominal rollout's; status_fd [n]: the largest over the row's steps"""
+    import torch
+    cm = env.cm
+    n, T = int(ctrl.shape[0]), int(ctrl.shape[1])
+    dev = ctrl.device
+    idx = torch.arange(n, dtype=torch.int32, device=dev) if envs is None else torch.as_tensor(envs).to(device=dev, dtype=torch.int32)
+    roll = env.rollout(envs=idx, qpos=qpos0, qvel=qvel0, warm=warm0, ctrl=ctrl, qfrc_applied=qfrc_applied, nsub=nsub,
+                       fields=("qpos", "qvel", "qacc_warm", "status"))
+    qs, vs, ws = _start_states(qpos0, roll["qpos"]), _start_states(qvel0, roll["qvel"]), _start_states(warm0, roll["qacc_warm"])
+    flat = lambda t: t.reshape(n * T, t.shape[-1]).contiguous()
+    d = transition_fd(env, envs=idx.repeat_interleave(T), qpos=flat(qs), qvel=flat(vs), ctrl=flat(ctrl), warm=flat(ws),
+                      qfrc_applied=None if qfrc_applied is None else qfrc_applied.repeat_interleave(T, dim=0), nsub=nsub, eps=eps)
+    nx = 2 * cm.nv
+    return {"A": d["A"].reshape(n, T, nx, nx), "B": d["B"].reshape(n, T, nx, cm.nu),
+            "qpos": torch.cat([qpos0[:, None], roll["qpos"]], dim=1), "qvel": torch.cat([qvel0[:, None], roll["qvel"]], dim=1), "warm": ws,
+            "status": roll["status"], "status_fd": torch.maximum(d["status"], d["status_fd"]).reshape(n, T).max(dim=1).values}
+
+
+class QuadraticCost:
+    """sum_{t < T} 1/2 (dx_t' Q dx_t + u_t' R u_t) + 1/2 dx_T' Qf dx_T with dx = [tangent_diff(qpos, goal_qpos) ; qvel - goal_qvel]:
+    the distance to a goal state measured in the tangent space.  goal_qpos [n, nq] (or [nq]), goal_qvel [n, nv] (or [nv]); Q, Qf
+    [2 nv, 2 nv] or their diagonals [2 nv]; R [nu, nu] or [nu].  The derivatives treat dx as linear in the state's tangent (exact
+    for joints, cube position and velocities; for the cube's rotation the log map's Jacobian is taken as the identity, the
+    Gauss-Newton habit -- weigh the rotation columns with zeros for a joint-space goal and nothing is approximated)."""
+
+    def __init__(self, cm, goal_qpos, goal_qvel, Q, R, Qf):
+        import torch
+        self.cm = cm
+        mat = lambda m: torch.diag(m) if m.dim() == 1 else m
+        self.goal_qpos, self.goal_qvel = goal_qpos.reshape(-1, cm.nq), goal_qvel.reshape(-1, cm.nv)
+        self.Q, self.R, self.Qf = mat(Q), mat(R), mat(Qf)
+
+    def dx(self, qpos, qvel):
+        """[n, L, 2 nv] of states [n, L, nq] / [n, L, nv] (n rows against the goal's n, or its one row)."""
+        import torch
+        n, L = int(qpos.shape[0]), int(qpos.shape[1])
+        reps = n // int(self.goal_qpos.shape[0])
+        gq = self.goal_qpos.repeat(reps, 1)[:, None].expand(n, L, -1).reshape(n * L, -1)
+        dq = tangent_diff(self.cm, qpos.reshape(n * L, -1), gq).reshape(n, L, -1)
+        return torch.cat([dq, qvel - self.goal_qvel.repeat(reps, 1)[:, None]], dim=2)
+
+    def total(self, qpos, qvel, ctrl):
+        """[n]: the cost of trajectories qpos [n, T + 1, nq], qvel [n, T + 1, nv] (x_0 .. x_T) under ctrl [n, T, nu]."""
+        d = self.dx(qpos, qvel)
+        run = 0.5 * ((d[:, :-1] @ self.Q) * d[:, :-1]).sum(dim=(1, 2)) + 0.5 * ((ctrl @ self.R) * ctrl).sum(dim=(1, 2))
+        return run + 0.5 * ((d[:, -1] @ self.Qf) * d[:, -1]).sum(dim=1)
+
+    def derivatives(self, qpos, qvel, ctrl):
+        """(lx [n, T + 1, 2 nv], lu [n, T, nu], lxx [T + 1, 2 nv, 2 nv], luu [T, nu, nu]) along a trajectory; entry T of lx / lxx is
+        the final cost's."""
+        import torch
+        d = self.dx(qpos, qvel)
+        T = int(ctrl.shape[1])
+        lxx = torch.cat([self.Q[None].expand(T, -1, -1), self.Qf[None]], dim=0)
+        lx = torch.einsum("tij,ntj->nti", lxx, d)
+        return lx, ctrl @ self.R.transpose(0, 1), lxx, self.R[None].expand(T, -1, -1)
+
+
+def backward_pass(A, B, lx, lu, lxx, luu, reg=0.0):
+    """The batched Riccati recursion of iLQR.  A [n, T, nx, nx], B [n, T, nx, nu]; lx [n, T + 1, nx], lu [n, T, nu], lxx
+    [n or 1 .., T + 1, nx, nx] and luu [.., T, nu, nu] (a leading batch dimension is optional), entry T of lx / lxx the final cost's;
+    no cross term.  reg: Levenberg regularisation added to the diagonal of Quu, a number or [n].  Returns (k [n, T, nu],
+    K [n, T, nu, nx], dV [n, 2]): the policy du_t = alpha k_t + K_t dx_t and the expected reduction of the cost for a step alpha,
+    -(alpha dV[:, 0] + alpha^2 dV[:, 1])."""
+    import torch
+    n, T, nx, nu = B.shape
+    if lxx.dim() == 3:
+        lxx = lxx[None]
+    if luu.dim() == 3:
+        luu = luu[None]
+    reg = torch.as_tensor(reg, dtype=A.dtype, device=A.device).reshape(-1, 1, 1)
+    eye = torch.eye(nu, dtype=A.dtype, device=A.device)
+    Vx, Vxx = lx[:, T], lxx[:, T].expand(n, nx, nx)
+    k, K = torch.zeros_like(lu), torch.zeros((n, T, nu, nx), dtype=A.dtype, device=A.device)
+    dV = torch.zeros((n, 2), dtype=A.dtype, device=A.device)
+    for t in range(T - 1, -1, -1):
+        At, Bt = A[:, t], B[:, t]
+        AtT, BtT = At.transpose(1, 2), Bt.transpose(1, 2)
+        Qx = lx[:, t] + (AtT @ Vx[:, :, None])[:, :, 0]
+        Qu = lu[:, t] + (BtT @ Vx[:, :, None])[:, :, 0]
+        Qxx = lxx[:, t] + AtT @ Vxx @ At
+        Quu = luu[:, t] + BtT @ Vxx @ Bt
+        Qux = BtT @ Vxx @ At
+        sol = torch.linalg.solve(Quu + reg * eye, torch.cat([Qu[:, :, None], Qux], dim=2))
+        kt, Kt = -sol[:, :, 0], -sol[:, :, 1:]
+        KtT = Kt.transpose(1, 2)
+        Vx = Qx + (KtT @ (Quu @ kt[:, :, None] + Qu[:, :, None]) + Qux.transpose(1, 2) @ kt[:, :, None])[:, :, 0]
+        Vxx = Qxx + KtT @ Quu @ Kt + KtT @ Qux + Qux.transpose(1, 2) @ Kt
+        Vxx = 0.5 * (Vxx + Vxx.transpose(1, 2))
+        dV[:, 0] += (kt * Qu).sum(dim=1)
+        dV[:, 1] += 0.5 * (kt * (Quu @ kt[:, :, None])[:, :, 0]).sum(dim=1)
+        k[:, t], K[:, t] = kt, Kt
+    return k, K, dV
+
+
+def forward_pass(env, envs, qpos0, qvel0, warm0, ctrl, k, K, qpos_ref, qvel_ref, cost, alphas, qfrc_applied=None, nsub=None):
+    """The line search in ONE rollout_feedback launch of n len(alphas) rows: row a n + e starts at env e's initial state, carries the
+    open-loop term ctrl[e] + alphas[a] k[e] and follows gain trajectory e (gain_index), i.e. K[e] about the nominal states
+    qpos_ref / qvel_ref [n, T, ..] before each step.  Returns a dict: cost [len(alphas), n] (inf where the row stopped early),
+    best [n] the index of the cheapest alpha per env, best_cost [n], ctrl [n, T, nu] the controls the best row applied, rows: the
+    launch's result."""
+    import torch
+    n, T, nu = ctrl.shape
+    dev = ctrl.device
+    al = torch.as_tensor(alphas, dtype=ctrl.dtype, device=dev)
+    na = int(al.numel())
+    idx = torch.arange(n, dtype=torch.int32, device=dev) if envs is None else torch.as_tensor(envs).to(device=dev, dtype=torch.int32)
+    open_loop = (ctrl[None] + al[:, None, None, None] * k[None]).reshape(na * n, T, nu).contiguous()
+    rows = env.rollout_feedback(envs=idx.repeat(na), qpos=qpos0.repeat(na, 1), qvel=qvel0.repeat(na, 1), warm=warm0.repeat(na, 1),
+                                ctrl=open_loop, qfrc_applied=None if qfrc_applied is None else qfrc_applied.repeat(na, 1), gains=K,
+                                qpos_ref=qpos_ref.contiguous(), qvel_ref=qvel_ref.contiguous(),
+                                gain_index=torch.arange(n, dtype=torch.int32, device=dev).repeat(na), nsub=nsub,
+                                fields=("qpos", "qvel", "ctrl", "status"))
+    q = torch.cat([qpos0.repeat(na, 1)[:, None], rows["qpos"]], dim=1)
+    v = torch.cat([qvel0.repeat(na, 1)[:, None], rows["qvel"]], dim=1)
+    c = cost.total(q, v, rows["ctrl"])
+    c = torch.where(rows["status"] == 0, c, torch.full_like(c, float("inf"))).reshape(na, n)
+    best_cost, best = c.min(dim=0)
+    pick = best * n + torch.arange(n, device=dev)
+    return {"cost": c, "best": best, "best_cost": best_cost, "ctrl": rows["ctrl"][pick], "rows": rows}
+
+
+def ilqr(env, envs, qpos0, qvel0, warm0, ctrl, cost, iters=10, alphas=(1.0, 0.5, 0.25), reg=1e-6, reg_factor=10.0, qfrc_applied=None,
+         nsub=None, eps=1e-6):
+    """iLQR from the initial rows (qpos0, qvel0, warm0) [n, ..] and the control guess ctrl [n, T, nu]: per iteration trajectory_fd,
+    cost.derivatives, backward_pass and forward_pass.  An env accepts the cheapest of its line-search rows if it is cheaper than its
+    nominal trajectory, and divides its regularisation by reg_factor; otherwise it keeps its controls and multiplies it.  Returns a
+    dict: ctrl [n, T, nu]; cost [iters + 1, n], the accepted cost after every iteration (entry 0: the guess's), never increasing;
+    accepted [iters, n] bool; k, K of the last backward pass; reg [n]."""
+    import torch
+    n = int(ctrl.shape[0])
+    ctrl = ctrl.clone()
+    reg = torch.full((n,), float(reg), dtype=ctrl.dtype, device=ctrl.device)
+    history, accepted = [], []
+    k = K = None
+    for _ in range(iters):
+        fd = trajectory_fd(env, envs, qpos0, qvel0, warm0, ctrl, qfrc_applied=qfrc_applied, nsub=nsub, eps=eps)
+        if not history:
+            history.append(cost.total(fd["qpos"], fd["qvel"], ctrl))
+        k, K, _ = backward_pass(fd["A"], fd["B"], *cost.derivatives(fd["qpos"], fd["qvel"], ctrl), reg=reg)
+        fp = forward_pass(env, envs, qpos0, qvel0, warm0, ctrl, k, K, fd["qpos"][:, :-1], fd["qvel"][:, :-1], cost, alphas,
+                          qfrc_applied=qfrc_applied, nsub=nsub)
+        ok = fp["best_cost"] < history[-1]
+        ctrl = torch.where(ok[:, None, None], fp["ctrl"], ctrl)
+        reg = torch.where(ok, reg / reg_factor, reg * reg_factor)
+        history.append(torch.where(ok, fp["best_cost"], history[-1]))
+        accepted.append(ok)
+    return {"ctrl": ctrl, "cost": torch.stack(history), "accepted": torch.stack(accepted), "k": k, "K": K, "reg": reg}
