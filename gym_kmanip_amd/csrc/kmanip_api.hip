@@ -245,6 +245,18 @@ static int row_args(KHandle h, const char* what, const char* in_t, const char* o
   if (!in->env_index && n > h->st.num_envs) { h->err = w + "more rows than envs need " + in_t + "::env_index"; return -1; }
   return 0;
 }
+// ... and of the two that step (kmanip_rollout / kmanip_feedback): row_args, then the step counts and the per-step flags
+template <class In, class Out>
+static int stepped_args(KHandle h, const char* what, const char* in_t, const char* out_t, const In* in, const Out* out, int n, int nstep,
+                        int nsub) {
+  if (row_args(h, what, in_t, out_t, in, out, n)) return -1;
+  const std::string w = std::string(what) + ": ";
+  if (nstep < 0) { h->err = w + "nstep is negative"; return -1; }
+  if (nsub < 0) { h->err = w + "nsub is negative"; return -1; }
+  if (in->ctrl_per_step && !in->ctrl) { h->err = w + "ctrl_per_step is set and " + in_t + "::ctrl is NULL"; return -1; }
+  if (in->frc_per_step && !in->qfrc_applied) { h->err = w + "frc_per_step is set and " + in_t + "::qfrc_applied is NULL"; return -1; }
+  return 0;
+}
 
 extern "C" {
 
@@ -526,11 +538,7 @@ int kmanip_forward(KHandle h, const KForwardIn* in, int n, const KForcesDev* out
 // DESIGN.md section 27).  One launch; the handle is only read; the handle's solver.
 int kmanip_rollout(KHandle h, const KRolloutIn* in, int n, int nstep, int nsub, const KRolloutDev* out, void* stream) {
   if (!h) { g_create_error = "kmanip_rollout: null handle"; return -1; }
-  if (row_args(h, "kmanip_rollout", "KRolloutIn", "KRolloutDev", in, out, n)) return -1;
-  if (nstep < 0) { h->err = "kmanip_rollout: nstep is negative"; return -1; }
-  if (nsub < 0) { h->err = "kmanip_rollout: nsub is negative"; return -1; }
-  if (in->ctrl_per_step && !in->ctrl) { h->err = "kmanip_rollout: ctrl_per_step is set and KRolloutIn::ctrl is NULL"; return -1; }
-  if (in->frc_per_step && !in->qfrc_applied) { h->err = "kmanip_rollout: frc_per_step is set and KRolloutIn::qfrc_applied is NULL"; return -1; }
+  if (stepped_args(h, "kmanip_rollout", "KRolloutIn", "KRolloutDev", in, out, n, nstep, nsub)) return -1;
   if (n == 0 || nstep == 0) return 0;
   if (!out->qpos && !out->qvel && !out->qacc_warm && !out->contact_mask && !out->reward && !out->status && !out->steps_done) return 0;
   KM_ENTER(h);
@@ -540,14 +548,11 @@ int kmanip_rollout(KHandle h, const KRolloutIn* in, int n, int nstep, int nsub, 
 }
 
 // kmanip_rollout with the policy u = ctrl + gain (state - reference) evaluated at every step boundary on the device (include/kmanip.h
-// KFeedbackIn / KFeedbackDev; kmanip_feedback.hip).  One launch; the handle is only read; the handle's solver.
+// KFeedbackIn / KFeedbackDev; kmanip_rollout.hip built with KM_VAR_FB; DESIGN.md sections 29 and 30).  One launch; the handle is only
+// read; the handle's solver.
 int kmanip_feedback(KHandle h, const KFeedbackIn* in, int n, int nstep, int nsub, const KFeedbackDev* out, void* stream) {
   if (!h) { g_create_error = "kmanip_feedback: null handle"; return -1; }
-  if (row_args(h, "kmanip_feedback", "KFeedbackIn", "KFeedbackDev", in, out, n)) return -1;
-  if (nstep < 0) { h->err = "kmanip_feedback: nstep is negative"; return -1; }
-  if (nsub < 0) { h->err = "kmanip_feedback: nsub is negative"; return -1; }
-  if (in->ctrl_per_step && !in->ctrl) { h->err = "kmanip_feedback: ctrl_per_step is set and KFeedbackIn::ctrl is NULL"; return -1; }
-  if (in->frc_per_step && !in->qfrc_applied) { h->err = "kmanip_feedback: frc_per_step is set and KFeedbackIn::qfrc_applied is NULL"; return -1; }
+  if (stepped_args(h, "kmanip_feedback", "KFeedbackIn", "KFeedbackDev", in, out, n, nstep, nsub)) return -1;
   if (!in->qpos_ref) { h->err = "kmanip_feedback: KFeedbackIn::qpos_ref is NULL"; return -1; }
   if (!in->qvel_ref) { h->err = "kmanip_feedback: KFeedbackIn::qvel_ref is NULL"; return -1; }
   if (!in->gain_t) { h->err = "kmanip_feedback: KFeedbackIn::gain_t is NULL"; return -1; }

@@ -27,7 +27,7 @@ typedef void FeedbackFn(const KDeviceModel*, const KDeviceState&, const KFeedbac
 #define KM_RESET_ROW(B, NL, G) {KM_NAME(reset, B, NL, G, _0), KM_NAME(reset, B, NL, G, _1)},
 // kmanip_rollout.hip: per solver in every build, like the step
 #define KM_ROLLOUT_ROW(B, NL, G) {KM_NAME(rollout, B, NL, G, _0), KM_NAME(rollout, B, NL, G, _1)},
-// kmanip_feedback.hip: likewise
+// kmanip_rollout.hip built with KM_VAR_FB (the kmanip_feedback_* objects): likewise
 #define KM_FEEDBACK_ROW(B, NL, G) {KM_NAME(feedback, B, NL, G, _0), KM_NAME(feedback, B, NL, G, _1)},
 #define KM_OBSERVE_ROW(B, NL, G) KM_NAME(observe, B, NL, G, _1),
 #define KM_PREPARE_ROW(B, NL, G) KM_NAME(prepare, B, NL, G, _1),
@@ -70,6 +70,10 @@ static int cls(const KModelDesc& hd) { return hd.nlink <= 10 ? 0 : 1; }
 static int newton(const KModelDesc& hd) { return hd.solver == KM_SOLVER_NEWTON ? 1 : 0; }
 static int par(const KDeviceState& st) { return st.envp ? 1 : 0; }
 static int frc(const KDeviceState& st) { return st.qfrc_applied ? 2 : 0; }
+// a call over rows the caller passes (KForwardIn, KRolloutIn, KFeedbackIn): the force build iff a row can have a force -- the caller's
+// rows or the handle's bound buffer
+template <class In>
+static int row_build(const KDeviceState& st, const In& in) { return par(st) + ((in.qfrc_applied || st.qfrc_applied) ? 2 : 0); }
 
 void kmanip_launch_step(const KDeviceModel* dm, const KModelDesc& hd, const KDeviceState& st, const float* act, double* obs, double* reward,
                         uint8_t* done, int nchunk, int epb, hipStream_t stream) {
@@ -95,18 +99,15 @@ void kmanip_launch_inverse(const KDeviceModel* dm, const KModelDesc& hd, const K
 }
 void kmanip_launch_forward(const KDeviceModel* dm, const KModelDesc& hd, const KDeviceState& st, const KForwardIn& in, int n,
                            const KForcesDev& out, hipStream_t stream) {
-  // the force build iff a row can have a force: the caller's rows or the handle's bound buffer
-  forward_tab[par(st) + ((in.qfrc_applied || st.qfrc_applied) ? 2 : 0)][cls(hd)](dm, st, in, n, out, stream);
+  forward_tab[row_build(st, in)][cls(hd)](dm, st, in, n, out, stream);
 }
 void kmanip_launch_rollout(const KDeviceModel* dm, const KModelDesc& hd, const KDeviceState& st, const KRolloutIn& in, int n, int nstep,
                            int nsub, const KRolloutDev& out, hipStream_t stream) {
-  // the force build iff a row can have a force: the caller's rows or the handle's bound buffer
-  rollout_tab[par(st) + ((in.qfrc_applied || st.qfrc_applied) ? 2 : 0)][cls(hd)][newton(hd)](dm, st, in, n, nstep, nsub, out, stream);
+  rollout_tab[row_build(st, in)][cls(hd)][newton(hd)](dm, st, in, n, nstep, nsub, out, stream);
 }
 void kmanip_launch_feedback(const KDeviceModel* dm, const KModelDesc& hd, const KDeviceState& st, const KFeedbackIn& in, int n, int nstep,
                             int nsub, const KFeedbackDev& out, hipStream_t stream) {
-  // (the builds as kmanip_launch_rollout picks them)
-  feedback_tab[par(st) + ((in.qfrc_applied || st.qfrc_applied) ? 2 : 0)][cls(hd)][newton(hd)](dm, st, in, n, nstep, nsub, out, stream);
+  feedback_tab[row_build(st, in)][cls(hd)][newton(hd)](dm, st, in, n, nstep, nsub, out, stream);
 }
 void kmanip_launch_prepare_model(KDeviceModel* dm, const KModelDesc& hd, hipStream_t stream) {
   prepare_tab[cls(hd)](dm, stream);

@@ -1,8 +1,8 @@
 // kmanip_dyn_rows.hpp -- what the queries that solve share beyond the phase headers: the decode of the Newton path's registers into a
-// KForcesDev row, its writer and the bad-qacc test (k_forces, k_forward; k_rollout's sub-step spells the test out) and the entry of a
-// kernel over rows the caller passes (k_forward, k_rollout).  Included by kmanip_forces.hip, kmanip_forward.hip and kmanip_rollout.hip only,
-// right after kmanip_dyn_variant.hpp and so inside the build's namespace: the other per-variant objects never see it and stay the ones
-// they were (DESIGN.md sections 25 and 28).
+// KForcesDev row, its writer and the bad-qacc test (k_forces, k_forward; k_rollout's and k_feedback's sub-step spells the test out) and
+// the entry of a kernel over rows the caller passes (k_forward, k_rollout, k_feedback).  Included by kmanip_forces.hip,
+// kmanip_forward.hip and kmanip_rollout.hip (the source of k_rollout and k_feedback) only, right after kmanip_dyn_variant.hpp and so
+// inside the build's namespace: the other per-variant objects never see it and stay the ones they were (DESIGN.md sections 25 and 28).
 #pragma once
 
 // a failed factorisation or mjWARN_BADQACC, as k_step tests it: the same flag on every lane of the group
@@ -86,8 +86,8 @@ __device__ __forceinline__ void write_forces_row(const KForcesDev& out, int row,
 }
 
 // ---- the entry of a kernel over n rows the caller passes, 64 / G rows per single-wave workgroup, in two parts like query_env /
-// query_load, around the kernel's own returns (a group without a row; status 2).  In: KForwardIn or KRolloutIn, which name env_index,
-// qpos, qvel, qacc_warm, ctrl and qfrc_applied alike.
+// query_load, around the kernel's own returns (a group without a row; status 2).  In: KForwardIn, KRolloutIn or KFeedbackIn, which name
+// env_index, qpos, qvel, qacc_warm, ctrl and qfrc_applied alike.
 // row_env: the model staged (every lane: it ends in a workgroup barrier), lane group -> row behind the XCD-aware block mapping, row ->
 // env (env_index NULL: row r is env r); false = no row.  The env is the caller's word: the kernel tests it before row_load uses it.
 template <int NL, int EPB, class In>

@@ -1,6 +1,7 @@
 // kmanip_dyn_variant.hpp -- the build macros of one per-variant object and the device code of one step, by phase.  Included once,
 // after kmanip_ik_coop.hpp, by each translation unit the Makefile compiles per (links, lanes per env[, solver]) variant:
-// kmanip_dyn.hip, kmanip_forces.hip, kmanip_kinematics.hip and kmanip_inverse.hip.  It opens the build's namespace; KM_VARIANT_END,
+// kmanip_dyn.hip, kmanip_forces.hip, kmanip_kinematics.hip, kmanip_inverse.hip, kmanip_forward.hip and kmanip_rollout.hip (the
+// kmanip_feedback_* objects are kmanip_rollout.hip's, built with its own KM_VAR_FB).  It opens the build's namespace; KM_VARIANT_END,
 // after the unit's kernels and launch templates, closes it.
 #pragma once
 #ifndef KM_VAR_NL
@@ -15,7 +16,8 @@
 #endif
 // KM_VAR_FRC=1: the applied-force build (kmanip_bind_applied_force), orthogonal to KM_VAR_PAR and built by the
 // same rule: a third and a fourth compilation per variant, kernels in namespaces of their own, launched only while a handle has a
-// force buffer bound.  kmanip_dyn.hip (step kernels only: a reset never reads the buffer) and kmanip_forces.hip have these builds.
+// force buffer bound.  kmanip_dyn.hip (step kernels only: a reset never reads the buffer), kmanip_forces.hip, kmanip_forward.hip and
+// kmanip_rollout.hip have these builds (the last two also launch them for a force the caller passes).
 #ifndef KM_VAR_FRC
 #define KM_VAR_FRC 0
 #endif

@@ -1,5 +1,5 @@
-// kmanip_rollout.hip -- open-loop rollouts in ctrl space from rows the CALLER passes, as many as it likes, in ONE launch (gfx950,
-// wave64): kmanip_rollout.
+// kmanip_rollout.hip -- rollouts in ctrl space from rows the CALLER passes, as many as it likes, in ONE launch (gfx950, wave64): the
+// source of two kernels, open-loop kmanip_rollout (k_rollout) and, compiled with -DKM_VAR_FB=1, closed-loop kmanip_feedback (k_feedback).
 //
 // MuJoCo's `rollout`: row r names an env (KRolloutIn::env_index; NULL = row r is env r), takes that env's model parameters and, per
 // field, either the caller's row of qpos / qvel / qacc_warm / ctrl / qfrc_applied or what the env stores, and is integrated for nstep
@@ -14,14 +14,44 @@
 // moved into the common headers reorders the code of the other kernels.  A translation unit of its own, so
 // that the step's and the state queries' objects are the ones they were, to the register.
 // One wave per workgroup, 64 / G ROWS per wave; the state stays in LDS for all nstep x nsub sub-steps.
+//
+// KM_VAR_FB=1 adds a time-varying affine state feedback evaluated at every step boundary, t = 0 included:
+//   dx  = [ tangent_diff(qpos, qpos_ref[g, t]) ; qvel - qvel_ref[g, t] ]                       (2 nv)
+//   u_i = ctrl[r, t, i] + sum_j gain_t[g, t, j, i] dx_j              (j ascending, an FMA chain from 0, then one add)
+// g = gain_index[r] (NULL: r), the policy an iLQR backward pass returns, a regulator (the one gain held) or the stabilising
+// feedback under MPPI samples.  u replaces the step's ctrl in the workspace and is recorded, unclamped, with the step; everything
+// else -- the entry, the sub-step loop, the trailing pass, status and steps_done, the zero tail, the next step's open-loop force
+// requested under the current one -- is written once below for both kernels (DESIGN.md sections 27, 29 and 30): the feedback-only
+// statements stand in #if KM_VAR_FB regions, so that each object still sees, after preprocessing, the statements of its kernel alone.
+// The gain is stored TRANSPOSED, [2 nv, nu]: lane = actuator, so the lanes of a group read consecutive addresses for every j; each
+// lane requests its 2 nv entries before the tangent difference is computed, and they are dead before the first sub-step starts
+// (the 20-link Newton variant has no room for 52 doubles across the loop).  dx goes through a small LDS array of this unit's own
+// (Ws is every kernel's and stays as it is); the lanes of a group read the same dx_j: a broadcast.
 #include "kmanip_ik_coop.hpp"
 #include <stdlib.h>
 #include "kmanip_dyn_variant.hpp"
 #include "kmanip_dyn_rows.hpp"         // (row_env, row_load: shared with k_forward)
 
+// KM_VAR_FB=1: the closed-loop build of this unit (the Makefile's kmanip_feedback_* objects), next to KM_VAR_PAR and KM_VAR_FRC.  It
+// names the structs (KFeedbackIn / KFeedbackDev begin with KRolloutIn's / KRolloutDev's fields), the kernel and the launcher.
+#ifndef KM_VAR_FB
+#define KM_VAR_FB 0
+#endif
+#if KM_VAR_FB
+typedef KFeedbackIn RollIn;
+typedef KFeedbackDev RollDev;
+#define KM_ROLL_KERNEL k_feedback
+#define KM_ROLL_LAUNCHER KM_LAUNCHER3(feedback)
+#else
+typedef KRolloutIn RollIn;
+typedef KRolloutDev RollDev;
+#define KM_ROLL_KERNEL k_rollout
+#define KM_ROLL_LAUNCHER KM_LAUNCHER3(rollout)
+#endif
+
 // zero records of steps t0 .. nstep-1 of one row (a row that stopped, or never started), then its status and step count
 template <int NL, int G>
-__device__ __forceinline__ void rollout_finish(const KRolloutDev& out, size_t row, int sub, int nstep, int t0, int status) {
+__device__ __forceinline__ void rollout_finish(const RollDev& out, size_t row, int sub, int nstep, int t0, int status) {
   constexpr int NV = Dim<NL>::NV, NQ = Dim<NL>::NQ;
   for (int t = t0; t < nstep; t++) {
     const size_t e = row * (size_t)nstep + t;
@@ -30,6 +60,9 @@ __device__ __forceinline__ void rollout_finish(const KRolloutDev& out, size_t ro
       if (out.qvel) out.qvel[e * NV + sub] = 0.0;
       if (out.qacc_warm) out.qacc_warm[e * NV + sub] = 0.0;
     }
+#if KM_VAR_FB
+    if (sub < NL && out.ctrl) out.ctrl[e * NL + sub] = 0.0;
+#endif
     if (sub == 0) {
       if (out.contact_mask) out.contact_mask[e] = 0u;
       if (out.reward) out.reward[e] = 0.0;
@@ -41,43 +74,123 @@ __device__ __forceinline__ void rollout_finish(const KRolloutDev& out, size_t ro
   }
 }
 
+#if KM_VAR_FB
+// The rotation part of derivatives.tangent_diff (MuJoCo's mj_differentiatePos): the body-frame log of conj(a) (x) b, a = the
+// reference's quaternion, b = the state's, operation for operation as the Python spells it.  No contraction: the vector part is two
+// differences of separately rounded products, so that equal quaternions give exactly zero (with an FMA, wa xb - xa wb would be the
+// rounding error of a product).
+__device__ __forceinline__ void quat_log_diff(const real (&a)[4], const real (&b)[4], real (&r)[3]) {
+#pragma clang fp contract(off)
+  const real wa = a[0], xa = a[1], ya = a[2], za = a[3], wb = b[0], xb = b[1], yb = b[2], zb = b[3];
+  const real w = ((wa * wb + xa * xb) + ya * yb) + za * zb;
+  const real x = (wa * xb - xa * wb) + (za * yb - ya * zb);
+  const real y = (wa * yb - ya * wb) + (xa * zb - za * xb);
+  const real z = (wa * zb - za * wb) + (ya * xb - xa * yb);
+  const real s = sqrt((x * x + y * y) + z * z);
+  real ang = 2.0 * atan2(s, w);
+  if (ang > 3.141592653589793) ang = ang - 6.283185307179586;
+  // angle / sin(angle / 2) -> 2 / w as the vector part vanishes
+  const real k = s > 0 ? ang / s : 2.0 / (w != 0 ? w : 1.0);
+  r[0] = k * x; r[1] = k * y; r[2] = k * z;
+}
+#endif
+
 template <int NL, int G, int SOLVER, int EPB>
-__global__ __launch_bounds__(64) void KM_KERNEL(k_rollout)(const KDeviceModel* __restrict__ dm, KDeviceState st, KRolloutIn in, int n, int nstep,
-                                                           int nsub, KRolloutDev out) {
-  constexpr int NV = Dim<NL>::NV, NQ = Dim<NL>::NQ, KL = (NL + G - 1) / G;
+__global__ __launch_bounds__(64) void KM_KERNEL(KM_ROLL_KERNEL)(const KDeviceModel* __restrict__ dm, KDeviceState st, RollIn in, int n, int nstep,
+                                                                int nsub, RollDev out) {
+  constexpr int NV = Dim<NL>::NV, NQ = Dim<NL>::NQ;
   __shared__ Ws<NL> ws[EPB];
   __shared__ LModel<NL> lm;
   const KModelDesc* m = &dm->d;
   const int lane = threadIdx.x, grp = lane / G, sub = lane % G;
+#if KM_VAR_FB
+  constexpr int KQ = (NQ + G - 1) / G, NX = 2 * NV;
+  static_assert(NL <= G && NV <= G, "lane = actuator, lane = dof");
+  __shared__ real dxs[EPB][NX];        // the policy's state difference, per row
+  real* dx = dxs[grp];
+#endif
   int row, env;
   if (!row_env<NL, EPB>(lm, dm, in, n, grp, row, env)) return;      // whole group exits together
   const size_t r = (size_t)row;
   // an index outside the handle (group-uniform): never used as an address
+#if KM_VAR_FB
+  // (likewise the row's gain trajectory outside its range)
+  const int g = in.gain_index ? in.gain_index[row] : row;
+  if (env < 0 || env >= st.num_envs || g < 0 || g >= in.ng) { rollout_finish<NL, G>(out, r, sub, nstep, 0, 2); return; }
+#else
   if (env < 0 || env >= st.num_envs) { rollout_finish<NL, G>(out, r, sub, nstep, 0, 2); return; }
+#endif
   Ws<NL>& w = ws[grp];
   real invm = 0;                       // diagonal of M^-1 for the cube dof owned by this lane
   init_ws<NL>(w, sub);            // (query_load's calls, row_load in load_state's place)
   env_invm<NL>(w, dm, st, env, sub, invm);
   // the caller's rows of ctrl and the force, held or step 0's: row (r, t) of a per-step tensor is row r * nstep + t
-  // (a per-step flag counts only with the caller's own tensor: kmanip_rollout refuses it on a NULL one)
+  // (a per-step flag counts only with the caller's own tensor: the host entry refuses it on a NULL one)
   const bool cstep = in.ctrl_per_step && in.ctrl, fstep = in.frc_per_step && in.qfrc_applied;
   const double* crow = in.ctrl ? in.ctrl + r * (cstep ? (size_t)nstep : (size_t)1) * NL : nullptr;
   const double* frow = in.qfrc_applied ? in.qfrc_applied + r * (fstep ? (size_t)nstep : (size_t)1) * NV : nullptr;
   const int lb = row_load<NL, G>(w, st, in, r, env, sub, crow, frow);
   // a non-finite input of step 0, given or stored: status 1, no step
   if (state_nonfinite<NL, G>(w, sub, lb)) { rollout_finish<NL, G>(out, r, sub, nstep, 0, 1); return; }
+#if KM_VAR_FB
+  // this lane's actuator (lanes past the last hold a copy of it) and dof, and the open-loop term of step 0: what row_load stored
+  const int ia = sub < NL ? sub : NL - 1, iv = sub < NV ? sub : NV - 1;
+  real oc = w.ctrl[ia];
+  // entry (g, t) of the references and the gain: t = 0 throughout while one gain is held
+  const size_t gT = (size_t)g * (in.gain_per_step ? (size_t)nstep : (size_t)1);
+#endif
   Prof pf;
   pf.start();
   const bool trail = out.contact_mask || out.reward;       // (kernel arguments: uniform over the launch)
   int t = 0, status = 0;
   for (; t < nstep; t++) {
-    // the next step's ctrl / force entries, requested now: they arrive under this step's sub-steps
+    // the next step's open-loop ctrl / force entries, requested now: they arrive under this step's sub-steps
     const bool more = t + 1 < nstep;
+#if KM_VAR_FB
+    // (a held ctrl is simply asked for again: the policy overwrites the workspace's copy every step)
+    real nc = 0.0;
+    if (more) nc = crow ? crow[(cstep ? (size_t)(t + 1) * NL : (size_t)0) + ia] : st.ctrl[(size_t)ia * st.num_envs + env];
+#else
+    constexpr int KL = (NL + G - 1) / G;
     real nc[KL];
 #pragma unroll
     for (int k = 0; k < KL; k++) { const int i = sub + G * k, ic = i < NL ? i : NL - 1; nc[k] = (cstep && more) ? crow[(size_t)(t + 1) * NL + ic] : 0.0; }
+#endif
 #if KM_VAR_FRC
     const real nf = (fstep && more) ? frow[(size_t)(t + 1) * NV + (sub < NV ? sub : NV - 1)] : 0.0;
+#endif
+#if KM_VAR_FB
+    // ---- the policy at the start of step t
+    {
+      const size_t gt = gT + (in.gain_per_step ? (size_t)t : (size_t)0);
+      // this actuator's column of the transposed gain, all 2 nv entries requested together, ahead of the arithmetic below
+      const double* kcol = in.gain_t + gt * NX * NL + ia;
+      real kg[NX];
+#pragma unroll
+      for (int j = 0; j < NX; j++) kg[j] = kcol[(size_t)j * NL];
+      const double* qr = in.qpos_ref + gt * NQ;
+      real rq[KQ], ra[4], qb[4], rot[3];
+#pragma unroll
+      for (int k = 0; k < KQ; k++) { const int i = sub + G * k; rq[k] = qr[i < NQ ? i : NQ - 1]; }
+      const real rv = in.qvel_ref[gt * NV + iv];
+#pragma unroll
+      for (int k = 0; k < 4; k++) { ra[k] = qr[NL + 3 + k]; qb[k] = w.qpos[NL + 3 + k]; }
+      // joints and cube position: lane = coordinate; the rotation: every lane computes it, lanes 0 .. 2 store it; qvel: lane = dof
+#pragma unroll
+      for (int k = 0; k < KQ; k++) { const int i = sub + G * k; if (i < NL + 3) dx[i] = w.qpos[i] - rq[k]; }
+      quat_log_diff(ra, qb, rot);
+      if (sub < 3) dx[NL + 3 + sub] = rot[sub];
+      if (sub < NV) dx[NV + sub] = w.qvel[sub] - rv;
+      GSYNC();
+      real acc = 0.0;
+#pragma unroll
+      for (int j = 0; j < NX; j++) acc = fma(kg[j], dx[j], acc);
+      const real u = oc + acc;
+      // a non-finite u (a non-finite reference or gain entry the row uses, or an overflow): the row stops, t steps recorded
+      if (gor<G>(!isfinite(u))) { status = 1; break; }
+      if (sub < NL) w.ctrl[sub] = u;
+      GSYNC();
+    }
 #endif
     int bad = 0;
     for (int s = 0; s < nsub; s++) {
@@ -107,6 +220,9 @@ __global__ __launch_bounds__(64) void KM_KERNEL(k_rollout)(const KDeviceModel* _
       if (out.qvel) out.qvel[e * NV + subr] = w.qvel[subr];
       if (out.qacc_warm) out.qacc_warm[e * NV + subr] = w.warm[subr];
     }
+#if KM_VAR_FB
+    if (subr < NL && out.ctrl) out.ctrl[e * NL + subr] = w.ctrl[subr];      // (the ctrl that acted is the workspace's)
+#endif
     if (trail) {
       // k_step's trailing mj_step1: kinematics + collision feed the contact mask and the reward
       fk_parallel<NL, G>(w, lm, subr);
@@ -118,12 +234,18 @@ __global__ __launch_bounds__(64) void KM_KERNEL(k_rollout)(const KDeviceModel* _
       }
     }
     if (more) {
-      // step t + 1's inputs into the workspace; a non-finite entry ends the row here, t + 1 steps recorded
+      // step t + 1's open-loop inputs (into the workspace, or kept for the policy); a non-finite entry ends the row here, t + 1
+      // steps recorded
+#if KM_VAR_FB
+      oc = nc;
+      int ln = !isfinite(nc);
+#else
       int ln = 0;
       if (cstep) {
 #pragma unroll
         for (int k = 0; k < KL; k++) { const int i = sub + G * k; if (i < NL) w.ctrl[i] = nc[k]; ln |= !isfinite(nc[k]); }
       }
+#endif
 #if KM_VAR_FRC
       if (fstep) {
         const int frc_bad = gor<G>(!isfinite(nf));
@@ -141,14 +263,14 @@ __global__ __launch_bounds__(64) void KM_KERNEL(k_rollout)(const KDeviceModel* _
 }
 
 template <int NL, int G, int SOLVER>
-static void launch_rollout_t(const KDeviceModel* dm, const KDeviceState& st, const KRolloutIn& in, int n, int nstep, int nsub,
-                             const KRolloutDev& out, hipStream_t stream) {
+static void launch_rollout_t(const KDeviceModel* dm, const KDeviceState& st, const RollIn& in, int n, int nstep, int nsub, const RollDev& out,
+                             hipStream_t stream) {
   constexpr int EPB = 64 / G;
-  hipLaunchKernelGGL((KM_KERNEL(k_rollout)<NL, G, SOLVER, EPB>), dim3((n + EPB - 1) / EPB), dim3(64), 0, stream, dm, st, in, n, nstep, nsub, out);
+  hipLaunchKernelGGL((KM_KERNEL(KM_ROLL_KERNEL)<NL, G, SOLVER, EPB>), dim3((n + EPB - 1) / EPB), dim3(64), 0, stream, dm, st, in, n, nstep, nsub, out);
 }
 KM_VARIANT_END
-// ---- one (NL, G, SOLVER[, PAR][, FRC]) variant per translation unit (the Makefile compiles this file sixteen times)
-void KM_LAUNCHER3(rollout)(const KDeviceModel* dm, const KDeviceState& st, const KRolloutIn& in, int n, int nstep, int nsub,
-                           const KRolloutDev& out, hipStream_t stream) {
+// ---- one (NL, G, SOLVER[, PAR][, FRC][, FB]) variant per translation unit (the Makefile compiles this file thirty-two times)
+void KM_ROLL_LAUNCHER(const KDeviceModel* dm, const KDeviceState& st, const RollIn& in, int n, int nstep, int nsub, const RollDev& out,
+                      hipStream_t stream) {
   launch_rollout_t<KM_VAR_NL, KM_VAR_G, KM_VAR_SOLVER>(dm, st, in, n, nstep, nsub, out, stream);
 }

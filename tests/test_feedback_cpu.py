@@ -226,3 +226,26 @@ def test_the_guard_fails_for_a_feedback_variant_without_a_row(tmp_path):
     rows = [r for r in PARITY_ROWS if not (r[1] == "pgs" and "forced" in r[2])]
     miss = missing_rows(text, rows)
     assert (10, 16, 0, False, True) in miss and (20, 32, 0, True, True) in miss
+
+
+# ------------------------------------------------------------------------------------------------------- one source, two kernels
+def test_the_feedback_objects_are_the_rollout_source_with_one_more_macro():
+    """k_feedback is kmanip_rollout.hip compiled with -DKM_VAR_FB=1 and nothing else: make's dry run (nothing
+    is compiled) gives the feedback object and its rollout sibling the same command line but for that flag and the object's name."""
+    import subprocess
+    csrc = os.path.dirname(MAKEFILE)
+    objs = {"feedback": "kmanip_feedback_ep_frc_20_32_0.o", "rollout": "kmanip_rollout_ep_frc_20_32_0.o"}
+    lines = {}
+    for kind, obj in objs.items():
+        out = subprocess.run(["make", "-n", "-B", obj], cwd=csrc, check=True, capture_output=True, text=True).stdout
+        cmds = [ln.split() for ln in out.splitlines() if " -c " in ln and "-o %s" % obj in ln]
+        assert len(cmds) == 1, out
+        lines[kind] = cmds[0]
+    for kind, cmd in lines.items():
+        assert cmd[cmd.index("-c") + 1] == "kmanip_rollout.hip", cmd
+        assert cmd[cmd.index("-o") + 1] == objs[kind], cmd
+        assert cmd.count("-DKM_VAR_FB=1") == (1 if kind == "feedback" else 0), cmd
+        assert not [a for a in cmd if a.startswith("-DKM_VAR_FB") and a != "-DKM_VAR_FB=1"], cmd
+    bare = {kind: [a for a in cmd if a not in ("-DKM_VAR_FB=1", objs[kind])] for kind, cmd in lines.items()}
+    assert bare["feedback"] == bare["rollout"]
+    assert not os.path.exists(os.path.join(csrc, "kmanip_feedback.hip"))
