@@ -566,6 +566,44 @@ int kmanip_feedback(KHandle h, const KFeedbackIn* in, int n, int nstep, int nsub
   return 0;
 }
 
+// MuJoCo's mjd_transitionFD at rows the caller passes (include/kmanip.h KTransFdIn / KTransFdDev; kmanip_transfd.hip; DESIGN.md section
+// 31).  Two launches ordered by the stream: the nominal rows through kmanip_rollout's kernel, then the column pairs, which read the
+// nominal qacc_warm the first wrote.  The handle is only read; the handle's solver.
+int kmanip_transition_fd(KHandle h, const KTransFdIn* in, int n, int nsub, const KTransFdDev* out, void* stream) {
+  if (!h) { g_create_error = "kmanip_transition_fd: null handle"; return -1; }
+  if (row_args(h, "kmanip_transition_fd", "KTransFdIn", "KTransFdDev", in, out, n)) return -1;
+  if (nsub < 0) { h->err = "kmanip_transition_fd: nsub is negative"; return -1; }
+  const int wrt = in->wrt, nv = h->desc.nlink + 6, nu = h->desc.nlink;
+  if (wrt & ~(KM_WRT_QPOS | KM_WRT_QVEL | KM_WRT_CTRL | KM_WRT_FRC)) { h->err = "kmanip_transition_fd: wrt has bits outside KM_WRT_*"; return -1; }
+  if (!(in->eps - in->eps == 0.0) || !(in->eps > 0.0)) { h->err = "kmanip_transition_fd: eps is not a finite positive number"; return -1; }
+  if (!(in->warm_offset - in->warm_offset == 0.0)) { h->err = "kmanip_transition_fd: warm_offset is not finite"; return -1; }
+  if (n == 0) return 0;                // (tensors of no rows have no address: nothing below is asked of them)
+  if (wrt && !out->deriv_t) { h->err = "kmanip_transition_fd: wrt is set and KTransFdDev::deriv_t is NULL"; return -1; }
+  if (wrt && !in->qacc_warm && !out->qacc_warm) {
+    h->err = "kmanip_transition_fd: without KTransFdIn::qacc_warm the perturbed rows start from KTransFdDev::qacc_warm, which is NULL";
+    return -1;
+  }
+  const int ncol = ((wrt & KM_WRT_QPOS) ? nv : 0) + ((wrt & KM_WRT_QVEL) ? nv : 0) + ((wrt & KM_WRT_CTRL) ? nu : 0) + ((wrt & KM_WRT_FRC) ? nv : 0);
+  if (2LL * ncol * n > 2147483647LL) { h->err = "kmanip_transition_fd: 2 ncol n perturbed rows are more than an int counts"; return -1; }
+  const int ns = nsub ? nsub : h->desc.n_sub_steps;
+  const hipStream_t s = (hipStream_t)stream;
+  const bool nominal = out->qpos || out->qvel || out->qacc_warm || out->contact_mask || out->status;
+  if (!nominal && !wrt) return 0;
+  KM_ENTER(h);
+  if (nominal) {
+    const KRolloutIn ri = {in->env_index, in->qpos, in->qvel, in->qacc_warm, in->ctrl, in->qfrc_applied, 0, 0};
+    const KRolloutDev ro = {out->qpos, out->qvel, out->qacc_warm, out->contact_mask, nullptr, out->status, nullptr};
+    kmanip_launch_rollout(h->dmodel, h->desc, h->st, ri, n, 1, ns, ro, s);
+    HIPCHK(h, hipGetLastError());
+  }
+  if (wrt) {
+    // tangent_perturb's rotation columns: cos and sin of eps / 2, once, on the host
+    kmanip_launch_transfd(h->dmodel, h->desc, h->st, *in, n, ncol, ns, cos(0.5 * in->eps), sin(0.5 * in->eps), *out, s);
+    HIPCHK(h, hipGetLastError());
+  }
+  return 0;
+}
+
 // the render launchers' visual inputs for a render of source `src` (-1 live state, 0 / 1 a snapshot): in ranges mode the draw
 // uses the episode counters of that source (a snapshot taken before ranges mode was on has none: the live ones)
 static KVisArgs vis_args(KHandle h, int src) {

@@ -593,6 +593,10 @@ void kmanip_launch_rollout(const KDeviceModel* dm, const KModelDesc& hd, const K
 // kmanip_feedback: kmanip_launch_rollout's arguments and choice of build
 void kmanip_launch_feedback(const KDeviceModel* dm, const KModelDesc& hd, const KDeviceState& st, const KFeedbackIn& in, int n, int nstep,
                             int nsub, const KFeedbackDev& out, hipStream_t stream);
+// kmanip_transition_fd's second launch (either solver: the handle's): the n * ncol > 0 column pairs of n rows, nsub > 0 sub-steps, ch /
+// sh = cos / sin of eps / 2; the applied-force build also while in.wrt has KM_WRT_FRC
+void kmanip_launch_transfd(const KDeviceModel* dm, const KModelDesc& hd, const KDeviceState& st, const KTransFdIn& in, int n, int ncol,
+                           int nsub, double ch, double sh, const KTransFdDev& out, hipStream_t stream);
 // The render launchers' visual inputs (kmanip_set_visual_params / _ranges), a kernel argument of the VIS
 // kernels only -- never a KDeviceState field: the step kernels' argument stays as it is.  All NULL: the default kernels.
 //   vp       explicit values double[KM_VP_N][N], read at the render's launch

@@ -411,6 +411,98 @@ class KManipEnvHip:
         self._check(self.L.kmanip_feedback(self.h, C.byref(fi), n, nstep, nsub, C.byref(fd), self._stream()), "kmanip_feedback")
         return out
 
+    # KTransFdDev field -> (trailing shape in terms of nq / nv / ncol / nx = 2 nv, dtype name)
+    _TRANSFD_FIELDS = {"qpos": (("nq",), "float64"), "qvel": (("nv",), "float64"), "qacc_warm": (("nv",), "float64"),
+                       "contact_mask": ((), "int32"), "status": ((), "uint8"), "deriv_t": (("ncol", "nx"), "float64"),
+                       "status_cols": (("ncol",), "uint8"), "contact_mask_fd": (("ncol", 2), "int32")}
+
+    def transition_fd(self, envs=None, qpos=None, qvel=None, ctrl=None, qfrc_applied=None, warm=None, nsub=None, eps=1e-6,
+                      wrt=("qpos", "qvel", "ctrl"), warm_offset=1.0, out=None):
+        """kmanip_transition_fd: derivatives.transition_fd -- MuJoCo's mjd_transitionFD, centred finite differences of ONE step (nsub
+        sub-steps; None = the model's) with respect to the inputs named in `wrt` -- in ONE library call of two launches: the nominal
+        rows through rollout()'s kernel, then a kernel that perturbs the rows, steps the +eps and -eps copies side by side in one
+        wave and writes the quotients.  No perturbed row and no perturbed state reaches memory, and no torch arithmetic runs.
+        Rows and their None fields as in rollout(): unlike derivatives.transition_fd a differentiated input may stay None (the named
+        env's stored values are then differentiated about).  Per row the arithmetic is derivatives.transition_fd's, operation for
+        operation: see there for eps, the warm start (`warm`, warm_offset) and the piecewise-smooth caveat.  Returns its dict:
+          qpos [n, nq], qvel [n, nv], qacc_warm [n, nv], contact_mask [n] int32, status [n] uint8      the nominal rows one step on
+          A [n, 2 nv, 2 nv] (wrt holds qpos and qvel; else dnext_dqpos / dnext_dqvel [n, 2 nv, nv]), B [n, 2 nv, nu] (ctrl),
+          dnext_dfrc [n, 2 nv, nv] (qfrc_applied): TRANSPOSED VIEWS, no copy, of the one buffer the kernel writes, also returned as
+          deriv_t [n, ncol, 2 nv] with the columns in the order qpos, qvel, ctrl, qfrc_applied whatever the order of `wrt`
+          status_cols [n, ncol] uint8 and status_fd [n] = its largest entry per row (nonzero: the column is zeros, not a derivative)
+          contact_mask_fd [ncol, 2, n] int32: the mask after the step of every perturbed row, + then -, columns in `wrt` order
+        `out`: a dict of tensors to fill, keyed by the kernel's own outputs (qpos, qvel, qacc_warm, contact_mask, status, deriv_t,
+        status_cols, contact_mask_fd [n, ncol, 2]); only the fields it names are computed -- without contact_mask_fd the perturbed
+        rows skip the kinematics + collision pass -- plus the two the call cannot do without, which are allocated: deriv_t, and
+        qacc_warm when `warm` is None (it is then the warm-start base of the perturbed rows).  A differentiated qfrc_applied left
+        None is rows of zeros, as in derivatives.transition_fd (also while a force is bound: pass its rows to differentiate about it)."""
+        torch = _torch()
+        cm = self.cm
+        wrt = tuple(wrt)
+        unknown = set(wrt) - set(_libmod.KM_WRT)
+        if unknown:
+            raise ValueError("unknown wrt name(s) %s" % sorted(unknown))
+        if len(set(wrt)) != len(wrt):
+            raise ValueError("transition_fd: a name is repeated in wrt %s" % (wrt,))
+        width = {"qpos": cm.nv, "qvel": cm.nv, "ctrl": cm.nu, "qfrc_applied": cm.nv}
+        order = [name for name in _libmod.KM_WRT if name in wrt]             # the kernel's column order
+        ncol = sum(width[name] for name in order)
+        fi = _libmod.KTransFdIn()
+        given = [("qpos", qpos, (cm.nq,)), ("qvel", qvel, (cm.nv,)), ("qacc_warm", warm, (cm.nv,)), ("ctrl", ctrl, (cm.nu,)),
+                 ("qfrc_applied", qfrc_applied, (cm.nv,))]
+        n, idx = self._query_rows(envs, given, fi)
+        if "qfrc_applied" in wrt and qfrc_applied is None and self.applied_force is not None and n > 0:
+            qfrc_applied = torch.zeros((n, cm.nv), dtype=torch.float64, device=self.device)
+            fi.qfrc_applied = qfrc_applied.data_ptr()
+        fi.wrt, fi.eps, fi.warm_offset = sum(_libmod.KM_WRT[name] for name in order), float(eps), float(warm_offset)
+        fd_fields = ("deriv_t", "status_cols", "contact_mask_fd")
+        names = list(self._TRANSFD_FIELDS) if out is None else list(out)
+        if ncol == 0 or n == 0:              # nothing to differentiate: the nominal rows only, as derivatives.transition_fd returns them
+            names = [name for name in names if name not in fd_fields]
+        else:
+            names += [name for name in ("deriv_t",) + (("qacc_warm",) if warm is None else ()) if name not in names]
+        dims = {"nq": cm.nq, "nv": cm.nv, "ncol": ncol, "nx": 2 * cm.nv}
+        res = {}
+        for name in names:
+            if out is not None and name in out:
+                res[name] = out[name]
+            elif name in self._TRANSFD_FIELDS:
+                shp, dt = self._TRANSFD_FIELDS[name]
+                res[name] = torch.empty((n,) + tuple(dims[d] if isinstance(d, str) else d for d in shp), dtype=getattr(torch, dt), device=self.device)
+            else:
+                res[name] = None             # (_query_out names it in its error)
+        fd = _libmod.KTransFdDev()
+        self._query_out(self._TRANSFD_FIELDS, (n,), dims, res, None, fd, "transition_fd")
+        self._check(self.L.kmanip_transition_fd(self.h, C.byref(fi), n, 0 if nsub is None else int(nsub), C.byref(fd), self._stream()),
+                    "kmanip_transition_fd")
+        if "deriv_t" not in res:
+            return res
+        d = res["deriv_t"].transpose(1, 2)                                   # [n, 2 nv, ncol], a view
+        blocks, c = {}, 0
+        for name in order:
+            blocks[name] = d[:, :, c:c + width[name]]
+            c += width[name]
+        if "qpos" in blocks and "qvel" in blocks:
+            res["A"] = d[:, :, :2 * cm.nv]
+        else:
+            for name in ("qpos", "qvel"):
+                if name in blocks:
+                    res["dnext_d" + name] = blocks[name]
+        if "ctrl" in blocks:
+            res["B"] = blocks["ctrl"]
+        if "qfrc_applied" in blocks:
+            res["dnext_dfrc"] = blocks["qfrc_applied"]
+        if "status_cols" in res:
+            res["status_fd"] = res["status_cols"].amax(dim=1)
+        if "contact_mask_fd" in res:
+            m = res["contact_mask_fd"]
+            if list(wrt) != order:           # the caller's column order
+                start = {name: sum(width[o] for o in order[:order.index(name)]) for name in order}
+                cols = torch.cat([torch.arange(start[name], start[name] + width[name], device=self.device) for name in wrt])
+                m = m[:, cols]
+            res["contact_mask_fd"] = m.permute(1, 2, 0)
+        return res
+
     def normal_by_bit(self, f):
         """[n, 32] float64: the normal force of the contact at each KM_CON_* mask bit of a forces() / forward() / inverse() result
         (it needs contact_force and contact_bit; n = the result's rows), 0 where the bit is clear.  Device-side indexing only: no

@@ -1,13 +1,14 @@
 #!/usr/bin/env python3
 """iLQR in ctrl space to a joint-space goal (gym_kmanip_amd.ilqr): every env plans for itself from the state its handle holds.
 
-    python -m gym_kmanip_amd.examples.ilqr_reach [--env KManipSoloArmQPos] [--num-envs 8] [--horizon 8] [--iters 5] [--alphas 1 0.5 0.25]
+    python -m gym_kmanip_amd.examples.ilqr_reach [--env KManipSoloArmQPos] [--num-envs 8] [--horizon 8] [--iters 5] [--alphas 1 0.5 0.25] [--fused]
 
 The goal of env e is its own joint configuration moved by `--reach` radians on every joint (signs alternate); the cost weighs the
 joints' distance to it, the joint velocities and the servo targets' distance from the goal, and leaves the cube alone.  Per
 iteration the device sees three calls whatever the horizon: the nominal rollout, transition_fd over all num_envs x horizon steps as
 rows, and ONE rollout_feedback launch that runs the backward pass's time-varying policy closed loop for every step size at once
-(num_envs x len(alphas) rows sharing num_envs gain trajectories).  The handle itself takes no step.  Printed: the mean cost per
+(num_envs x len(alphas) rows sharing num_envs gain trajectories).  With --fused the linearisation is KManipEnvHip.transition_fd, the rows perturbed and differenced inside the kernel, in place of
+derivatives.transition_fd's torch arithmetic around two rollout launches.  The handle itself takes no step.  Printed: the mean cost per
 iteration, then the record as JSON."""
 import argparse
 import json
@@ -16,11 +17,11 @@ from gym_kmanip_amd import env_hip, ilqr
 
 
 class _Count:
-    """The env as ilqr sees it -- .cm, .rollout, .rollout_feedback -- counting the feedback launches and their rows."""
+    """The env as ilqr sees it -- .cm, .rollout, .transition_fd, .rollout_feedback -- counting the feedback launches and their rows."""
 
     def __init__(self, env):
         self.env, self.cm, self.rows = env, env.cm, []
-        self.rollout = env.rollout
+        self.rollout, self.transition_fd = env.rollout, env.transition_fd
 
     def rollout_feedback(self, **kw):
         self.rows.append(int(kw["ctrl"].shape[0]))
@@ -38,6 +39,7 @@ def main(argv=None):
     ap.add_argument("--alphas", type=float, nargs="+", default=[1.0, 0.5, 0.25])
     ap.add_argument("--reach", type=float, default=0.1)
     ap.add_argument("--seed", type=int, default=3)
+    ap.add_argument("--fused", action="store_true", help="linearise with KManipEnvHip.transition_fd (kmanip_transition_fd)")
     args = ap.parse_args(argv)
     env = env_hip.make(args.env, num_envs=args.num_envs, seed=args.seed)
     cm, n, T = env.cm, args.num_envs, args.horizon
@@ -57,13 +59,13 @@ def main(argv=None):
                               torch.full((cm.nu,), 1e-3, dtype=torch.float64, device=dev), 10.0 * wq)
     guess = st["ctrl"][:, None, :].repeat(1, T, 1)
     counted = _Count(env)
-    res = ilqr.ilqr(counted, None, st["qpos"], st["qvel"], st["warm"], guess, cost, iters=args.iters, alphas=args.alphas)
+    res = ilqr.ilqr(counted, None, st["qpos"], st["qvel"], st["warm"], guess, cost, iters=args.iters, alphas=args.alphas, fused=args.fused)
     after = env.state_tensors()
     assert all(torch.equal(st[k], after[k]) for k in st)                                 # the handle was only read
     per_env = res["cost"].cpu()
     for it, c in enumerate(per_env.mean(dim=1).tolist()):
         print("iteration %d: mean cost %.6f" % (it, c))
-    out = {"env": args.env, "num_envs": n, "horizon": T, "alphas": list(args.alphas), "cost": per_env.mean(dim=1).tolist(),
+    out = {"env": args.env, "num_envs": n, "horizon": T, "alphas": list(args.alphas), "fused": bool(args.fused), "cost": per_env.mean(dim=1).tolist(),
            "cost_per_env": per_env.tolist(), "accepted": res["accepted"].cpu().tolist(), "feedback_launches": len(counted.rows),
            "rows_per_line_search": counted.rows[0] if counted.rows else 0, "first_ctrl_moved_by": float((res["ctrl"][:, 0] - st["ctrl"]).abs().max())}
     print(json.dumps(out))

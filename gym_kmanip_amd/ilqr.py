@@ -8,6 +8,8 @@ of n len(alphas) rows that share the n gain trajectories through gain_index.
 The state is (qpos in the tangent space, qvel), 2 nv wide, as transition_fd defines it; differences of states are
 derivatives.tangent_diff's.  Everything is torch arithmetic on the device of the caller's tensors and needs only env.rollout,
 env.rollout_feedback, env.cm and that device, so a CPU stand-in (tests/tools/feedback_oracle.py OracleFeedback) runs the same code."""
+import functools
+
 from .derivatives import tangent_diff, transition_fd
 
 
@@ -17,14 +19,16 @@ def _start_states(first, records):
     return torch.cat([first[:, None], records[:, :-1]], dim=1)
 
 
-def trajectory_fd(env, envs, qpos0, qvel0, warm0, ctrl, qfrc_applied=None, nsub=None, eps=1e-6):
+def trajectory_fd(env, envs, qpos0, qvel0, warm0, ctrl, qfrc_applied=None, nsub=None, eps=1e-6, fused=False):
     """The nominal trajectory of ctrl [n, T, nu] from (qpos0, qvel0, warm0) and its linearisation at every step.  One rollout launch,
     then ONE transition_fd call over the n T start-of-step states as rows (row e T + t names env envs[e]; its warm start is the
     trajectory's qacc_warm before that step).  envs None: row e is env e.  qfrc_applied [n, nv], held, or None.  Returns a dict:
       A [n, T, 2 nv, 2 nv], B [n, T, 2 nv, nu]       d x_{t+1} / d x_t, d x_{t+1} / d u_t
       qpos [n, T + 1, nq], qvel [n, T + 1, nv]       x_0 .. x_T (x_t: the state before step t)
       warm [n, T, nv]                                 the warm start of every step
-      status [n] uint8                                the nominal rollout's; status_fd [n]: the largest over the row's steps"""
+      status [n] uint8                                the nominal rollout's; status_fd [n]: the largest over the row's steps
+    fused=True: the linearisation is env.transition_fd (kmanip_transition_fd: the rows perturbed and differenced inside the kernel,
+    DESIGN.md section 31) in place of derivatives.transition_fd over env.rollout; the same rows, the same arithmetic per row."""
     import torch
     cm = env.cm
     n, T = int(ctrl.shape[0]), int(ctrl.shape[1])
@@ -34,8 +38,9 @@ def trajectory_fd(env, envs, qpos0, qvel0, warm0, ctrl, qfrc_applied=None, nsub=
                        fields=("qpos", "qvel", "qacc_warm", "status"))
     qs, vs, ws = _start_states(qpos0, roll["qpos"]), _start_states(qvel0, roll["qvel"]), _start_states(warm0, roll["qacc_warm"])
     flat = lambda t: t.reshape(n * T, t.shape[-1]).contiguous()
-    d = transition_fd(env, envs=idx.repeat_interleave(T), qpos=flat(qs), qvel=flat(vs), ctrl=flat(ctrl), warm=flat(ws),
-                      qfrc_applied=None if qfrc_applied is None else qfrc_applied.repeat_interleave(T, dim=0), nsub=nsub, eps=eps)
+    linearise = env.transition_fd if fused else functools.partial(transition_fd, env)
+    d = linearise(envs=idx.repeat_interleave(T), qpos=flat(qs), qvel=flat(vs), ctrl=flat(ctrl), warm=flat(ws),
+                  qfrc_applied=None if qfrc_applied is None else qfrc_applied.repeat_interleave(T, dim=0), nsub=nsub, eps=eps)
     nx = 2 * cm.nv
     return {"A": d["A"].reshape(n, T, nx, nx), "B": d["B"].reshape(n, T, nx, cm.nu),
             "qpos": torch.cat([qpos0[:, None], roll["qpos"]], dim=1), "qvel": torch.cat([qvel0[:, None], roll["qvel"]], dim=1), "warm": ws,
@@ -147,12 +152,12 @@ def forward_pass(env, envs, qpos0, qvel0, warm0, ctrl, k, K, qpos_ref, qvel_ref,
 
 
 def ilqr(env, envs, qpos0, qvel0, warm0, ctrl, cost, iters=10, alphas=(1.0, 0.5, 0.25), reg=1e-6, reg_factor=10.0, qfrc_applied=None,
-         nsub=None, eps=1e-6):
+         nsub=None, eps=1e-6, fused=False):
     """iLQR from the initial rows (qpos0, qvel0, warm0) [n, ..] and the control guess ctrl [n, T, nu]: per iteration trajectory_fd,
     cost.derivatives, backward_pass and forward_pass.  An env accepts the cheapest of its line-search rows if it is cheaper than its
     nominal trajectory, and divides its regularisation by reg_factor; otherwise it keeps its controls and multiplies it.  Returns a
     dict: ctrl [n, T, nu]; cost [iters + 1, n], the accepted cost after every iteration (entry 0: the guess's), never increasing;
-    accepted [iters, n] bool; k, K of the last backward pass; reg [n]."""
+    accepted [iters, n] bool; k, K of the last backward pass; reg [n].  fused: trajectory_fd's."""
     import torch
     n = int(ctrl.shape[0])
     ctrl = ctrl.clone()
@@ -160,7 +165,7 @@ def ilqr(env, envs, qpos0, qvel0, warm0, ctrl, cost, iters=10, alphas=(1.0, 0.5,
     history, accepted = [], []
     k = K = None
     for _ in range(iters):
-        fd = trajectory_fd(env, envs, qpos0, qvel0, warm0, ctrl, qfrc_applied=qfrc_applied, nsub=nsub, eps=eps)
+        fd = trajectory_fd(env, envs, qpos0, qvel0, warm0, ctrl, qfrc_applied=qfrc_applied, nsub=nsub, eps=eps, fused=fused)
         if not history:
             history.append(cost.total(fd["qpos"], fd["qvel"], ctrl))
         k, K, _ = backward_pass(fd["A"], fd["B"], *cost.derivatives(fd["qpos"], fd["qvel"], ctrl), reg=reg)
