@@ -328,6 +328,12 @@ int kmanip_create(const KModelDesc* desc, int num_envs, int device, uint64_t see
   KDeviceModel hm;
   hm.d = *desc;
   if (validate(desc, h->err) != 0 || build_aux(desc, &hm.x, h->err) != 0) { g_create_error = h->err; delete h; return -2; }
+  // solver_iterations = 0 means no iteration: qacc is the solver's start point (MuJoCo's `while (iter < opt.iterations)`; the PGS
+  // loop's `iter < maxit`).  The Newton loop tests its cap only after an iteration, so a Newton model with a cap of 0 gets an
+  // infinite tolerance in the DEVICE copy instead: the loop's entry test (scaled gradient < tolerance) then accepts every start
+  // point, of every problem of every kernel that holds the loop, and the kernels themselves stay as they are (a test of the cap
+  // inside the loop, one scalar compare, moved the step time by 0.5-1 %: DESIGN.md section 32).  h->desc keeps the caller's value.
+  if (desc->solver == KM_SOLVER_NEWTON && desc->solver_iterations == 0) hm.d.solver_tolerance = INFINITY;
   hm.trace_robot = trace_robot_of(*desc);
   build_sphere_arm(desc, hm.sphere_arm);
   int ndev = 0;

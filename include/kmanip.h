@@ -86,7 +86,13 @@ typedef struct KModelDesc {
   int32_t obs_dim;               /* 2*nlink + 7                                                    */
   int32_t max_episode_steps;     /* 64, __init__.py:28                                             */
   int32_t n_sub_steps;           /* control_timestep / timestep = 10, __init__.py:30, env_sim.py:210 */
-  int32_t solver_iterations;     /* PGS sweeps cap (MuJoCo default 100)                            */
+  /* Cap on the solver's iterations per solve, MuJoCo's opt.iterations (default 100): PGS sweeps, or Newton iterations of each
+   * problem a solve runs (the whole problem of a coupled env; the arm problem, then the cube problem of an uncoupled one, each with
+   * a count of its own).  0 = no iteration: qacc is the start point, the cheaper of qacc_warmstart and qacc_smooth (Newton) or
+   * qacc_smooth + M^-1 J^T f of the kept warm-start forces (PGS), as in MuJoCo.  (The Newton kernels test the cap after an iteration;
+   * for a Newton model with a cap of 0 kmanip_create therefore puts an infinite solver_tolerance into the device's copy of the model,
+   * at which the solver's entry test accepts every start point.)  Negative: kmanip_create refuses the descriptor. */
+  int32_t solver_iterations;
   int32_t touch_reward_enabled;  /* 0 reproduces the reference's dead touch/lift terms (SURVEY finding 4) */
   int32_t auto_reset;            /* 1: envs whose done byte is set are reset inside kmanip_step    */
   int32_t act_col[KM_ACT_NKEYS]; /* first column of each action key, -1 if the key is absent       */

@@ -205,9 +205,14 @@ def test_wave_mates_order_and_chunk_change_no_bit(asset, solver, monkeypatch):
     for bit the same.  In the interleaved order every wave of every forced shape that holds a coupled env holds an uncoupled one
     too, at least 9 such waves (asserted from the permutation).  step_chunk(3), which launches at the widest envs per wave, equals the three step_flat
     calls in cell-major and in interleaved order."""
+    _wave_mates_change_no_bit(model(asset, solver), asset, monkeypatch)
+
+
+def _wave_mates_change_no_bit(cm, asset, monkeypatch):
+    """The body of test_wave_mates_order_and_chunk_change_no_bit for a compiled model of the asset (tests/test_solver_caps_gpu.py
+    runs it with the Newton solver capped)."""
     torch = _torch()
     from oracle.oracle import Oracle
-    cm = model(asset, solver)
     qpos, qvel, ctrl, labels = cells(asset)
     n = len(labels)
     warm = R.warm_start(cm, Oracle(cm, 1), qpos, qvel, ctrl)
