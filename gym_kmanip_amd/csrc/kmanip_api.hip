@@ -618,6 +618,28 @@ static KVisArgs vis_args(KHandle h, int src) {
   return v;
 }
 
+// the state a render reads: the live one, or the snapshot kmanip_set_render_source chose
+static KDeviceState render_state(KHandle h) {
+  KDeviceState st = h->st;
+  if (h->render_src >= 0) st.qpos = h->qpos_snap[h->render_src];
+  return st;
+}
+// the handle's capsule list as the launchers take it; for the depth renders and the point clouds only while the depth flag is on
+static KLinkArgs link_args(KHandle h) { return KLinkArgs{h->links_buf, (int)h->links.size()}; }
+static KLinkArgs depth_link_args(KHandle h) { return h->depth_links && !h->links.empty() ? link_args(h) : KLinkArgs{nullptr, 0}; }
+
+// the end of an RGB / label render entry.  Kernel timing (kmanip_enable_timing): the camera observations rendered right after a timed step are that step's render leg --
+// its start is the event the step recorded after k_step, so the render costs the stream ONE more event, not a pair around it
+// (a render of a SNAPSHOT runs behind the steps, on a stream of its own: it is no leg of the step's stream)
+static int render_done(KHandle h, void* stream) {
+  if (h->timing && h->render_src < 0 && h->last_step_timed && h->timed_steps > 0 && !h->ev_render[h->timed_steps - 1]) {
+    HIPCHK(h, hipEventRecord(h->ev[3 * (size_t)(h->timed_steps - 1) + 2], (hipStream_t)stream));
+    h->ev_render[h->timed_steps - 1] = 1;
+  }
+  HIPCHK(h, hipGetLastError());
+  return 0;
+}
+
 static int step_impl(KHandle h, int nchunk, const float* act_dev, double* obs_dev, double* reward_dev, uint8_t* done_dev, void* stream) {
   if (!h) { g_create_error = "kmanip_step: null handle"; return -1; }
   if (!act_dev || !obs_dev || !reward_dev || !done_dev) { h->err = "kmanip_step: null buffer"; return -1; }
@@ -646,9 +668,8 @@ static int step_impl(KHandle h, int nchunk, const float* act_dev, double* obs_de
   if (tm) HIPCHK(h, hipEventRecord(ev[1], s));
   const bool render = h->step_depth && nchunk == 1;
   if (render) {                           // the observation's camera branch (env_sim.py:140-145) of the state just produced
-    if (h->depth_links && !h->links.empty())
-      kmanip_launch_render_depth_links(h->dmodel, h->st, h->step_cam, h->step_h, h->step_w, h->step_depth, KLinkArgs{h->links_buf, (int)h->links.size()},
-                                       vis_args(h, -1), s);
+    const KLinkArgs links = depth_link_args(h);
+    if (links.n > 0) kmanip_launch_render_depth_links(h->dmodel, h->st, h->step_cam, h->step_h, h->step_w, h->step_depth, links, vis_args(h, -1), s);
     else
       kmanip_launch_render_depth(h->dmodel, h->st, h->step_cam, h->step_h, h->step_w, h->step_depth, vis_args(h, -1), s);
   }
@@ -674,11 +695,9 @@ int kmanip_render_depth(KHandle h, int cam, int height, int width, float* depth_
   if (!h || !depth_dev || cam < 0 || cam >= KM_MAX_CAMS || height <= 0 || width <= 0) { if (h) h->err = "kmanip_render_depth: bad arguments"; return -1; }
   if (!h->desc.cam_present[cam]) { h->err = "kmanip_render_depth: this model has no such camera"; return -1; }
   KM_ENTER(h);
-  KDeviceState st = h->st;
-  if (h->render_src >= 0) st.qpos = h->qpos_snap[h->render_src];
-  if (h->depth_links && !h->links.empty())
-    kmanip_launch_render_depth_links(h->dmodel, st, cam, height, width, depth_dev, KLinkArgs{h->links_buf, (int)h->links.size()}, vis_args(h, h->render_src),
-                                     (hipStream_t)stream);
+  const KDeviceState st = render_state(h);
+  const KLinkArgs links = depth_link_args(h);
+  if (links.n > 0) kmanip_launch_render_depth_links(h->dmodel, st, cam, height, width, depth_dev, links, vis_args(h, h->render_src), (hipStream_t)stream);
   else
     kmanip_launch_render_depth(h->dmodel, st, cam, height, width, depth_dev, vis_args(h, h->render_src), (hipStream_t)stream);
   HIPCHK(h, hipGetLastError());
@@ -690,8 +709,7 @@ int kmanip_get_camera_poses(KHandle h, int cam, double* pose_dev, void* stream) 
   if (!pose_dev) { h->err = "kmanip_get_camera_poses: pose_dev is NULL"; return -1; }
   if (cam < 0 || cam >= KM_MAX_CAMS || !h->desc.cam_present[cam]) { h->err = "kmanip_get_camera_poses: this model has no such camera"; return -1; }
   KM_ENTER(h);
-  KDeviceState st = h->st;
-  if (h->render_src >= 0) st.qpos = h->qpos_snap[h->render_src];
+  const KDeviceState st = render_state(h);
   kmanip_launch_camera_poses(h->dmodel, st, cam, pose_dev, vis_args(h, h->render_src), (hipStream_t)stream);
   HIPCHK(h, hipGetLastError());
   return 0;
@@ -704,11 +722,8 @@ int kmanip_render_points(KHandle h, int cam, int height, int width, int frame, f
   if (height <= 0 || width <= 0) { h->err = "kmanip_render_points: height and width must be positive"; return -1; }
   if (frame != KM_POINTS_CAMERA && frame != KM_POINTS_WORLD) { h->err = "kmanip_render_points: frame must be KM_POINTS_CAMERA or KM_POINTS_WORLD"; return -1; }
   KM_ENTER(h);
-  KDeviceState st = h->st;
-  if (h->render_src >= 0) st.qpos = h->qpos_snap[h->render_src];
-  // the scene kmanip_render_depth draws on this handle now: the capsule list only while the depth flag is on
-  const KLinkArgs links = h->depth_links && !h->links.empty() ? KLinkArgs{h->links_buf, (int)h->links.size()} : KLinkArgs{nullptr, 0};
-  kmanip_launch_render_points(h->dmodel, st, cam, height, width, frame == KM_POINTS_WORLD, xyz_dev, depth_dev, links, vis_args(h, h->render_src),
+  const KDeviceState st = render_state(h);
+  kmanip_launch_render_points(h->dmodel, st, cam, height, width, frame == KM_POINTS_WORLD, xyz_dev, depth_dev, depth_link_args(h), vis_args(h, h->render_src),
                               (hipStream_t)stream);
   HIPCHK(h, hipGetLastError());
   return 0;
@@ -761,25 +776,16 @@ int kmanip_render_rgb_multi(KHandle h, int ncam, const int* cams, const int* hei
     jobs.cam[i] = cams[i]; jobs.height[i] = heights[i]; jobs.width[i] = widths[i]; jobs.rgb[i] = rgb_dev[i];
   }
   KM_ENTER(h);
-  KDeviceState st = h->st;
-  if (h->render_src >= 0) st.qpos = h->qpos_snap[h->render_src];
+  const KDeviceState st = render_state(h);
   if (!h->links.empty()) {
     // link capsules: the kernel that draws them, with no label output
     KLabelJobs lj{};
     lj.n = ncam;
     for (int i = 0; i < ncam; i++) { lj.cam[i] = jobs.cam[i]; lj.height[i] = jobs.height[i]; lj.width[i] = jobs.width[i]; lj.rgb[i] = jobs.rgb[i]; lj.seg[i] = nullptr; }
-    kmanip_launch_render_links(h->dmodel, st, lj, true, KLinkArgs{h->links_buf, (int)h->links.size()}, vis_args(h, h->render_src), (hipStream_t)stream);
+    kmanip_launch_render_links(h->dmodel, st, lj, true, link_args(h), vis_args(h, h->render_src), (hipStream_t)stream);
   } else
     kmanip_launch_render_rgb(h->dmodel, st, jobs, vis_args(h, h->render_src), (hipStream_t)stream);
-  // kernel timing (kmanip_enable_timing): the camera observations rendered right after a timed step are that step's render leg --
-  // its start is the event the step recorded after k_step, so the render costs the stream ONE more event, not a pair around it
-  // (a render of a SNAPSHOT runs behind the steps, on a stream of its own: it is no leg of the step's stream)
-  if (h->timing && h->render_src < 0 && h->last_step_timed && h->timed_steps > 0 && !h->ev_render[h->timed_steps - 1]) {
-    HIPCHK(h, hipEventRecord(h->ev[3 * (size_t)(h->timed_steps - 1) + 2], (hipStream_t)stream));
-    h->ev_render[h->timed_steps - 1] = 1;
-  }
-  HIPCHK(h, hipGetLastError());
-  return 0;
+  return render_done(h, stream);
 }
 
 int kmanip_render_rgb(KHandle h, int cam, int height, int width, uint8_t* rgb_dev, void* stream) {
@@ -805,20 +811,13 @@ int kmanip_render_labels_multi(KHandle h, int ncam, const int* cams, const int* 
   // no label wanted anywhere: this is the RGB render
   if (nseg == 0) return kmanip_render_rgb_multi(h, ncam, cams, heights, widths, rgb_dev, stream);
   KM_ENTER(h);
-  KDeviceState st = h->st;
-  if (h->render_src >= 0) st.qpos = h->qpos_snap[h->render_src];
+  const KDeviceState st = render_state(h);
   // labels only in every job: the kernel that does not shade; anything else: the one that writes what each job asks for
   if (!h->links.empty())
-    kmanip_launch_render_links(h->dmodel, st, jobs, nrgb > 0, KLinkArgs{h->links_buf, (int)h->links.size()}, vis_args(h, h->render_src), (hipStream_t)stream);
+    kmanip_launch_render_links(h->dmodel, st, jobs, nrgb > 0, link_args(h), vis_args(h, h->render_src), (hipStream_t)stream);
   else
     kmanip_launch_render_labels(h->dmodel, st, jobs, nrgb > 0, vis_args(h, h->render_src), (hipStream_t)stream);
-  // (kmanip_enable_timing: the render after the step, as in kmanip_render_rgb_multi)
-  if (h->timing && h->render_src < 0 && h->last_step_timed && h->timed_steps > 0 && !h->ev_render[h->timed_steps - 1]) {
-    HIPCHK(h, hipEventRecord(h->ev[3 * (size_t)(h->timed_steps - 1) + 2], (hipStream_t)stream));
-    h->ev_render[h->timed_steps - 1] = 1;
-  }
-  HIPCHK(h, hipGetLastError());
-  return 0;
+  return render_done(h, stream);
 }
 
 int kmanip_render_seg(KHandle h, int cam, int height, int width, uint8_t* seg_dev, void* stream) {
