@@ -1015,9 +1015,11 @@ static int step1(const KModelDesc* m, const double* qpos, const double* qvel, Dy
 }
 
 static int solve_newton(const KModelDesc* m, const Dyn* D, const double* a_s, const double* qacc_warm, double* a);
-/* mj_step2 minus integration: actuation, smooth acceleration, constraint solve.  Returns solver iterations. */
-static int step2_accel(const KModelDesc* m, const Dyn* D, const double* ctrl, int actuation, double* qacc_warm,
-                       double* qacc) {
+/* mj_step2 minus integration: actuation, smooth acceleration, constraint solve.  Returns solver iterations.  applied: NULL, or
+ * MuJoCo's data.qfrc_applied in the dof order of qM (ko_physics_step_applied); it acts with the actuation, outside the servos'
+ * clamps, and a zero component leaves its dof's sum untouched (as the device's add_applied does). */
+static int step2_accel(const KModelDesc* m, const Dyn* D, const double* ctrl, int actuation, const double* applied,
+                       double* qacc_warm, double* qacc) {
   int nl = m->nlink, nv = nl + 6, ne = D->nefc;
   double a_s[NVMAX];
   for (int j = 0; j < nv; j++) a_s[j] = -D->bias[j];
@@ -1027,6 +1029,7 @@ static int step2_accel(const KModelDesc* m, const Dyn* D, const double* ctrl, in
     if (m->forcelimited[i]) force = fmin(fmax(force, m->forcerange[i][0]), m->forcerange[i][1]);
     a_s[i] += force;
   }
+  if (actuation && applied) for (int j = 0; j < nv; j++) if (applied[j] != 0) a_s[j] += applied[j];
   minv_mul(m, D, a_s);
   if (ne == 0) { memcpy(qacc, a_s, sizeof(double) * nv); memcpy(qacc_warm, a_s, sizeof(double) * nv); return 0; }
   if (m->solver == KM_SOLVER_NEWTON) {
@@ -1376,7 +1379,7 @@ int ko_after_reset(const KModelDesc* m, KoState* s) {
   int rc = step1(m, s->qpos, s->qvel, D, 1);
   if (rc == 0) {
     double qacc[NVMAX];
-    step2_accel(m, D, s->ctrl, 0, s->qacc_warm, qacc);
+    step2_accel(m, D, s->ctrl, 0, NULL, s->qacc_warm, qacc);
   }
   free(D);
   return rc;
@@ -1449,12 +1452,12 @@ static void before_step(const KModelDesc* m, KoState* s, const Dyn* P0, const fl
 /* dm_control Physics.step(n), legacy order (mj_step2; (n-1) x mj_step; mj_step1): D holds the mj_step1 products the first
  * mj_step2 consumes (those of the state BEFORE the IK moved qpos); the trailing mj_step1 is left to the caller.  Returns 1 on
  * mjWARN_BADQACC / a non-finite qpos. */
-static int physics_step(const KModelDesc* m, KoState* s, Dyn* D, int nsub, KoDiag* dg) {
+static int physics_step(const KModelDesc* m, KoState* s, Dyn* D, int nsub, const double* applied, KoDiag* dg) {
   int nl = m->nlink, nv = nl + 6, bad = 0;
   double qacc[NVMAX];
   for (int sub = 0; sub < nsub && !bad; sub++) {
     if (sub > 0 && step1(m, s->qpos, s->qvel, D, 1) != 0) { bad = 1; break; }
-    int it = step2_accel(m, D, s->ctrl, 1, s->qacc_warm, qacc);
+    int it = step2_accel(m, D, s->ctrl, 1, applied, s->qacc_warm, qacc);
     if (dg) { dg->solver_iter += it; dg->nefc = D->nefc; }
     for (int j = 0; j < nv; j++) if (!isfinite(qacc[j]) || fabs(qacc[j]) > 1e10) bad = 1;   /* mjWARN_BADQACC */
     if (bad) break;
@@ -1469,11 +1472,11 @@ static int physics_step(const KModelDesc* m, KoState* s, Dyn* D, int nsub, KoDia
 /* Physics.step(nsub) alone, for tests/tools/refrun.py (the reference's own Python running over this physics): qpos_step1 = the
  * qpos the previous mj_step1 saw (the IK has since written data.qpos: ik_mujoco.py:34,67).  contact_mask / touch flags are the
  * trailing mj_step1's.  Returns 1 if the state diverged. */
-int ko_physics_step(const KModelDesc* m, KoState* s, const double* qpos_step1, int nsub, uint32_t* contact_mask,
-                    int32_t* touch_finger_cube, int32_t* touch_cube_table) {
+static int physics_step_alone(const KModelDesc* m, KoState* s, const double* qpos_step1, int nsub, const double* applied,
+                              KoDiag* dg, uint32_t* contact_mask, int32_t* touch_finger_cube, int32_t* touch_cube_table) {
   Dyn* D = (Dyn*)malloc(sizeof(Dyn));
   int bad = step1(m, qpos_step1, s->qvel, D, 1) != 0;
-  if (!bad) bad = physics_step(m, s, D, nsub, NULL);
+  if (!bad) bad = physics_step(m, s, D, nsub, applied, dg);
   if (!bad) {
     step1(m, s->qpos, s->qvel, D, 0);
     if (contact_mask) *contact_mask = D->contact_mask;
@@ -1482,6 +1485,17 @@ int ko_physics_step(const KModelDesc* m, KoState* s, const double* qpos_step1, i
   }
   free(D);
   return bad;
+}
+int ko_physics_step(const KModelDesc* m, KoState* s, const double* qpos_step1, int nsub, uint32_t* contact_mask,
+                    int32_t* touch_finger_cube, int32_t* touch_cube_table) {
+  return physics_step_alone(m, s, qpos_step1, nsub, NULL, NULL, contact_mask, touch_finger_cube, touch_cube_table);
+}
+/* The same under a constant applied force (applied[nv]: data.qfrc_applied, the dof order of qM): the reference of the device's
+ * bound force at sweep caps the NumPy restatement of tests/tools/applied_oracle.py cannot reach in a test's time.  dg (may be
+ * NULL) gets the summed solver iterations and the last nefc; the caller zeroes it. */
+int ko_physics_step_applied(const KModelDesc* m, KoState* s, const double* qpos_step1, int nsub, const double* applied,
+                            uint32_t* contact_mask, KoDiag* dg) {
+  return physics_step_alone(m, s, qpos_step1, nsub, applied, dg, contact_mask, NULL, NULL);
 }
 /* collision at a state (what a trailing mj_step1 / mj_forward leaves in data.contact) */
 void ko_contact_mask(const KModelDesc* m, const double* qpos, uint32_t* contact_mask, int32_t* touch_finger_cube,
@@ -1517,7 +1531,7 @@ int ko_step(const KModelDesc* m, uint64_t seed, int64_t env_id, KoState* s, cons
   if (step1(m, s->qpos, s->qvel, D, 1) != 0) bad = 1;
   if (!bad) {
     before_step(m, s, D, act, dg);
-    bad = physics_step(m, s, D, m->n_sub_steps, dg);
+    bad = physics_step(m, s, D, m->n_sub_steps, NULL, dg);
   }
   uint8_t dn = 0;
   if (!bad) {
@@ -1607,10 +1621,10 @@ int ko_dynamics(const KModelDesc* m, const double* qpos, const double* qvel, con
     memcpy(D0, D, sizeof(Dyn));
     D0->nefc = 0;
     double w0[NVMAX]; memset(w0, 0, sizeof w0);
-    step2_accel(m, D0, ctrl, 1, w0, qacc_smooth);
+    step2_accel(m, D0, ctrl, 1, NULL, w0, qacc_smooth);
     free(D0);
     memset(w0, 0, sizeof w0);
-    step2_accel(m, D, ctrl, 1, w0, qacc);
+    step2_accel(m, D, ctrl, 1, NULL, w0, qacc);
     *nefc = D->nefc;
     if (efc_J) for (int i = 0; i < D->nefc; i++) { memcpy(efc_J + (size_t)i * nv, D->J[i], sizeof(double) * nv); efc_aref[i] = D->aref[i]; efc_R[i] = D->Rr[i]; }
   }

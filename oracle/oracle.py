@@ -207,6 +207,21 @@ class Oracle:
         return (np.array(st.qpos[:nq]), np.array(st.qvel[:nv]), np.array(st.qacc_warm[:nv]), int(bad), mask.value,
                 tf.value, tt.value)
 
+    def physics_step_applied(self, qpos, qvel, ctrl, warm, applied, nsub):
+        """physics_step of ONE env under the constant applied force `applied` [nv] (MuJoCo's data.qfrc_applied, the dof order of
+        qM), from the state's own mj_step1 products.  Returns (qpos, qvel, warm, bad, mask, solver_iter), solver_iter summed over
+        the sub-steps.  The call releases the GIL: envs may run in threads."""
+        st = KoState()
+        nq, nv, nu = self.cm.nq, self.cm.nv, self.cm.nu
+        st.qpos[:nq] = list(qpos); st.qvel[:nv] = list(qvel); st.ctrl[:nu] = list(ctrl); st.qacc_warm[:nv] = list(warm)
+        mask = C.c_uint32(); dg = KoDiag()
+        tau = _f64(applied)
+        assert tau.shape == (nv,)
+        bad = self.L.ko_physics_step_applied(C.byref(self.desc), C.byref(st), _p(_f64(qpos)), int(nsub), _p(tau), C.byref(mask),
+                                             C.byref(dg))
+        return (np.array(st.qpos[:nq]), np.array(st.qvel[:nv]), np.array(st.qacc_warm[:nv]), int(bad), mask.value,
+                int(dg.solver_iter))
+
     def after_reset(self, qpos, qvel, ctrl):
         """mj_forward with actuation disabled: returns qacc_warmstart."""
         st = KoState()

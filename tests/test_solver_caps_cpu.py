@@ -51,9 +51,10 @@ def actions(cm, n):
     return np.random.default_rng(3).uniform(-0.2, 0.2, (3, n, cm.act_dim)).astype(np.float32)
 
 
-def control_steps(asset, solver, cap, tol, kind="zero", twin=False):
+def control_steps(asset, solver, cap, tol, kind="zero", twin=False, nthreads=1):
     """The cells one control step on under a zero action (kind "zero") or three steps on under actions() ("random"), on the oracle
-    of capped_model: a list of dict(qpos, qvel, obs, reward, done, mask, iters) per step, computed once.  twin: from qvel (1 + 1e-15)."""
+    of capped_model: a list of dict(qpos, qvel, obs, reward, done, mask, iters) per step, computed once.  twin: from qvel (1 + 1e-15).
+    nthreads: the oracle's threads over the envs (an env's result does not depend on it)."""
     key = (asset, solver, cap, tol, kind, twin)
     if key not in _RUNS:
         cm = capped_model(asset, solver, cap, tol)
@@ -63,7 +64,7 @@ def control_steps(asset, solver, cap, tol, kind="zero", twin=False):
         acts = np.zeros((1, n, cm.act_dim), dtype=np.float32) if kind == "zero" else actions(cm, n)
         out = []
         for act in acts:
-            obs, rew, done = orc.step(act)
+            obs, rew, done = orc.step(act, nthreads)
             q, v = orc.get_state()[:2]
             out.append(dict(qpos=q, qvel=v, obs=obs.copy(), reward=rew.copy(), done=done.copy(), mask=orc.get_diag()[0],
                             iters=np.array([d.solver_iter for d in orc.diag])))

@@ -1,5 +1,7 @@
 """The physics step with an applied force (MuJoCo's data.qfrc_applied), restated in NumPy from what oracle.Oracle returns: the
-reference of kmanip_bind_applied_force.  oracle/ itself knows no applied force and stays as it is.
+reference of kmanip_bind_applied_force.  The oracle's control step knows no applied force; Oracle.physics_step_applied (the physics
+sub-steps alone, for sweep caps this module cannot reach in a test's time) is held to this restatement by
+tests/test_pgs_fixed_point_cpu.py.
 
 Per sub-step: dyn = Oracle.dynamics(qpos, qvel, ctrl) gives M, bias, qacc_smooth and the constraint rows J, aref, R of the state,
 Oracle.constraint_rows their types and friction-loss bounds.  The force enters in one place,
