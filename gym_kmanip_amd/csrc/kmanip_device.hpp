@@ -618,7 +618,8 @@ struct KLinkArgs { const KLinkCapsule* caps; int n; };
 void kmanip_launch_render_links(const KDeviceModel* dm, const KDeviceState& st, const KLabelJobs& jobs, bool rgb, const KLinkArgs& links, const KVisArgs& vis,
                                 hipStream_t stream);
 // the depth render with the same list drawn (kmanip_set_depth_links; kmanip_render_depth_links.hip): kmanip_launch_render_depth's
-// arguments and its COLFIXED rule, plus the list
+// arguments and its COLFIXED rule, plus the list.  (The three float64 depth kernels -- this one, k_render_depth and k_render_points
+// below -- are built from one text, kmanip_render_depth_cast.inc)
 void kmanip_launch_render_depth_links(const KDeviceModel* dm, const KDeviceState& st, int cam, int height, int width, float* depth,
                                       const KLinkArgs& links, const KVisArgs& vis, hipStream_t stream);
 // camera geometry out of the library (kmanip_render_points.hip): camera `cam`'s pose of every env into pose

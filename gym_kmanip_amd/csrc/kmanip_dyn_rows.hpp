@@ -1,6 +1,7 @@
 // kmanip_dyn_rows.hpp -- what the queries that solve share beyond the phase headers: the decode of the Newton path's registers into a
 // KForcesDev row, its writer and the bad-qacc test (k_forces, k_forward; k_rollout's and k_feedback's sub-step spells the test out) and
-// the entry of a kernel over rows the caller passes (k_forward, k_rollout, k_feedback, k_transfd).  Included by kmanip_forces.hip,
+// the entry of a kernel over rows the caller passes (k_forward, k_rollout, k_feedback, k_transfd), and the quaternion log map of
+// k_feedback and k_transfd (quat_log_diff).  Included by kmanip_forces.hip,
 // kmanip_forward.hip, kmanip_rollout.hip (the source of k_rollout and k_feedback) and kmanip_transfd.hip only, right after kmanip_dyn_variant.hpp
 // and so inside the build's namespace: the other per-variant objects never see it and stay the ones they were (DESIGN.md sections 25 and 28).
 #pragma once
@@ -150,4 +151,24 @@ __device__ __forceinline__ int row_load(Ws<NL>& w, const KDeviceState& st, const
 #endif
   GSYNC();
   return lb;
+}
+
+// ---- the log map of k_feedback's state difference (a = the reference's quaternion) and of k_transfd's quotient (a = the -eps row's)
+// The rotation part of derivatives.tangent_diff (MuJoCo's mj_differentiatePos): the body-frame log of conj(a) (x) b, a = the
+// reference's quaternion, b = the state's, operation for operation as the Python spells it.  No contraction: the vector part is two
+// differences of separately rounded products, so that equal quaternions give exactly zero (with an FMA, wa xb - xa wb would be the
+// rounding error of a product).
+__device__ __forceinline__ void quat_log_diff(const real (&a)[4], const real (&b)[4], real (&r)[3]) {
+#pragma clang fp contract(off)
+  const real wa = a[0], xa = a[1], ya = a[2], za = a[3], wb = b[0], xb = b[1], yb = b[2], zb = b[3];
+  const real w = ((wa * wb + xa * xb) + ya * yb) + za * zb;
+  const real x = (wa * xb - xa * wb) + (za * yb - ya * zb);
+  const real y = (wa * yb - ya * wb) + (xa * zb - za * xb);
+  const real z = (wa * zb - za * wb) + (ya * xb - xa * yb);
+  const real s = sqrt((x * x + y * y) + z * z);
+  real ang = 2.0 * atan2(s, w);
+  if (ang > 3.141592653589793) ang = ang - 6.283185307179586;
+  // angle / sin(angle / 2) -> 2 / w as the vector part vanishes
+  const real k = s > 0 ? ang / s : 2.0 / (w != 0 ? w : 1.0);
+  r[0] = k * x; r[1] = k * y; r[2] = k * z;
 }

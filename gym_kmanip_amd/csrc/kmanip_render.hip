@@ -17,7 +17,8 @@
 // One workgroup (256 lanes) per env.  Forward kinematics run one link per lane with ceil(log2(depth)) rounds of pointer
 // jumping through LDS (the same scheme as k_step's fk_parallel), lane 0 builds the camera frame, then the lanes ray-cast.
 //   depth (k_render_depth): 128 lanes per env, pixels p = lane, lane + 128, ...; float64 ray maths -- the depth parity bar
-//     against the float64 oracle is 1e-6 m, which float32 intersection arithmetic (cancellation ~1e-5 m) would not meet.
+//     against the float64 oracle is 1e-6 m, which float32 intersection arithmetic (cancellation ~1e-5 m) would not meet.  The
+//     kernel's text is kmanip_render_depth_cast.inc, included below.
 //   rgb (k_render_rgb, round 3): the *Vision observations are 480 x 640 x 3 + 40 x 60 x 3 bytes per env-step (__init__.py:
 //     158-161), 929 KB -- the one genuinely HBM-sized output of the path.  Round 2 cast every pixel in float64 (~150 FP64
 //     operations per pixel: 5 x the time the stores need) and wrote three separate bytes per pixel.  Now: (1) float32 ray
@@ -31,204 +32,18 @@
 // VIS build a few lanes of the second wave load the env's KM_VP_N values (or evaluate their Philox draw) into LDS while the FK
 // loads are in flight; lane 0 adds the camera offset when it builds the camera frame, and the RGB kernel shades with the env's
 // colours and light terms (RgbVis).
-#include "kmanip_render_scene.hpp"
+#include "kmanip_render_depth_cast.hpp"
 
 // ---- depth (BASELINE config 5) -------------------------------------------------------------------------------------
-// float64 ray maths (the parity bar against the float64 oracle is 1e-6 m; float32 intersection arithmetic cancels to ~1e-5 m).
-// Round 4: the pixel loop was bound by what it FETCHED per pixel, not by its arithmetic -- scene constants re-read from LDS and
-// model scalars from global memory inside the loop, a walk over all twelve collider spheres testing each one's `visible` flag.
-// Now the per-env scene a ray meets is hoisted into registers once (camera basis and the same basis turned into the cube frame,
-// so the slab test's direction is linear in the pixel coordinates; the visible spheres' centres from the host-built list), the
-// divides are reciprocal + Newton steps, and nothing but the image is touched inside the loop.  (A float32 pre-classification
-// with a float64 evaluation of the winner was built and measured first: 12 % of the pixels fell within its margins, i.e. nearly
-// every wave ran both paths -- 0.155 ms against round 3's 0.089; dropped.)
-struct DepthScene { real ol[3], DX[3], DY[3], DZ[3]; real oc[KM_RENDER_MAXVIS][3], cc[KM_RENDER_MAXVIS]; int nvis; };
-
-// COLFIXED: blockDim.x is a whole number of image rows (the launcher knows).  VIS = false: the default kernel (no VA);
-// VIS = true: VA = KVisArgs, one more argument, and the camera offset applied
-template <bool COLFIXED, bool VIS, class... VA>
-__global__ __launch_bounds__(256, 4) void k_render_depth(const KDeviceModel* __restrict__ dm, KDeviceState st, int cam, int height, int width,
-                                                      float* __restrict__ depth, VA... vargs) {
-  static_assert(sizeof...(VA) == (VIS ? 1 : 0), "the VIS kernel takes one KVisArgs, the default kernel none");
-  __shared__ RenderScene sc;
-  __shared__ DepthScene ds;
-  __shared__ double vsv_[KM_VP_N];           // (VIS only: the default kernel never references it)
-  KVisArgs va{};
-  double* vsv = nullptr;
-  if constexpr (VIS) { ((va = vargs), ...); vsv = vsv_; }
-  const KModelDesc* m = &dm->d;
-  const int env = blockIdx.x;
-  // model scalars of the pixel loop: wave-uniform reads, issued in front of the set-up (they used to start after its last barrier)
-  const real zfar = m->cam_zfar, znear = m->cam_znear, tabz = m->table_z;
-  const real rx0 = m->table_rect[0], rx1 = m->table_rect[1], ry0 = m->table_rect[2], ry1 = m->table_rect[3];
-  const real hf0 = m->cube_half[0], hf1 = m->cube_half[1], hf2 = m->cube_half[2];
-  RenderPre pre;
-  render_fk<VIS>(dm, st, env, cam, &sc, pre, va, vsv);
-  render_camera<VIS>(dm, st, env, cam, height, &sc, pre, vsv);
-  __syncthreads();
-  if (threadIdx.x < 4) {
-    // ray origin and basis in the cube frame, one vector per lane
-    const int k = threadIdx.x;
-    const real rel[3] = {sc.cam_o[0] - sc.cube_p[0], sc.cam_o[1] - sc.cube_p[1], sc.cam_o[2] - sc.cube_p[2]};
-    const real* src = k == 0 ? rel : (k == 1 ? sc.cam_x : (k == 2 ? sc.cam_y : sc.cam_z));
-    real* dst = k == 0 ? ds.ol : (k == 1 ? ds.DX : (k == 2 ? ds.DY : ds.DZ));
-    matT_vec3(dst, sc.cube_R, src);
-  } else if (threadIdx.x >= 64 && threadIdx.x < 64 + KM_RENDER_MAXVIS) {
-    const int ns = threadIdx.x - 64;
-    if (ns == 0) ds.nvis = dm->x.nvis;
-    if (ns < dm->x.nvis) {
-      const int sp = dm->x.vis_sphere[ns];
-      const real rad = m->sphere_radius[sp];
-      const real oc[3] = {sc.cam_o[0] - sc.sph[sp][0], sc.cam_o[1] - sc.sph[sp][1], sc.cam_o[2] - sc.sph[sp][2]};
-      ds.oc[ns][0] = oc[0]; ds.oc[ns][1] = oc[1]; ds.oc[ns][2] = oc[2];
-      ds.cc[ns] = dot3(oc, oc) - rad * rad;
-    }
-  }
-  __syncthreads();
-  // ---- everything the pixel loop reads, in registers
-  const real k0 = tabz - sc.cam_o[2], ox = sc.cam_o[0], oy = sc.cam_o[1];
-  real X[3], Y[3], Z[3], ol[3], DX[3], DY[3], DZ[3];
-  const real hf[3] = {hf0, hf1, hf2};
-#pragma unroll
-  for (int c = 0; c < 3; c++) {
-    X[c] = sc.cam_x[c]; Y[c] = sc.cam_y[c]; Z[c] = sc.cam_z[c];
-    ol[c] = ds.ol[c]; DX[c] = ds.DX[c]; DY[c] = ds.DY[c]; DZ[c] = ds.DZ[c];
-  }
-  // |camera - cube centre|^2 - (bounding radius)^2, the radius padded by a relative 1e-9 so that roundoff never rejects a grazing ray
-  const real cube_cc = (ol[0] * ol[0] + ol[1] * ol[1] + ol[2] * ol[2]) - (hf[0] * hf[0] + hf[1] * hf[1] + hf[2] * hf[2]) * (1.0 + 1e-9);
-  const int nvis = ds.nvis;
-  real soc[KM_RENDER_MAXVIS][3], scc[KM_RENDER_MAXVIS];
-#pragma unroll
-  for (int s = 0; s < KM_RENDER_MAXVIS; s++) {
-    const int k = s < nvis ? s : 0;                      // (unused entries: finite copies, never tested)
-    soc[s][0] = ds.oc[k][0]; soc[s][1] = ds.oc[k][1]; soc[s][2] = ds.oc[k][2]; scc[s] = ds.cc[k];
-  }
-  const int npix = height * width;
-  const real inv_f = 1.0 / sc.focal, hw = 0.5 * width, hh = 0.5 * height;
-  float* __restrict__ out = depth + (size_t)env * npix;
-  int r = threadIdx.x / width, c = threadIdx.x - r * width;         // row / column advance incrementally (no division in the loop)
-  const int dr = blockDim.x / width, dc = blockDim.x - dr * width;
-  // Round 5: when the workgroup's stride is a whole number of image rows (64-wide images: 128 lanes = two rows) a lane keeps its
-  // COLUMN for the whole loop, so everything that is linear in the pixel coordinates has a per-lane constant part.
-  // The loop is bound by the NUMBER of float64 instructions a pixel issues (a wave is one image row): what a ray rarely needs is
-  // computed where it is needed -- the direction in the cube frame and the slab reciprocals behind the bounding-sphere test (itself
-  // in the world frame: a rotation changes neither dot product), reciprocals take one Newton step (v_rcp_f64 is good to 2^-23: one
-  // step gives 2^-46, the depth bar is 1e-6 m), and the final clamp is one v_med3_f32 after the conversion (rounding is monotonic).
-  // Round 6 (column kept): the ray direction is d = e + Y dy with e fixed per lane, so every dot product with d is ONE FMA in dy
-  // against two per-lane constants (|d|^2: two) instead of three; dy itself advances by a constant; the table's rectangle is
-  // tested as half-width minus |offset from its centre| (three instructions for the four edges' seven).
-  constexpr bool colfixed = COLFIXED;
-  const real dxl = (c + 0.5 - hw) * inv_f;
-  real ex[3], bx[3];
-#pragma unroll
-  for (int a = 0; a < 3; a++) { ex[a] = X[a] * dxl - Z[a]; bx[a] = DX[a] * dxl - DZ[a]; }
-  const real rel[3] = {sc.cam_o[0] - sc.cube_p[0], sc.cam_o[1] - sc.cube_p[1], sc.cam_o[2] - sc.cube_p[2]};   // (|rel| = |ol|)
-  real A0 = 0, A1 = 0, A2 = 0, B0 = 0, B1 = 0, S0[KM_RENDER_MAXVIS], S1[KM_RENDER_MAXVIS];
-#pragma unroll
-  for (int s = 0; s < KM_RENDER_MAXVIS; s++) { S0[s] = 0; S1[s] = 0; }
-  if constexpr (colfixed) {
-    A0 = dot3(ex, ex); A1 = 2.0 * dot3(ex, Y); A2 = dot3(Y, Y);
-    B0 = dot3(ex, rel); B1 = dot3(Y, rel);
-#pragma unroll
-    for (int s = 0; s < KM_RENDER_MAXVIS; s++) { S0[s] = dot3(ex, soc[s]); S1[s] = dot3(Y, soc[s]); }
-  }
-  // table rectangle by centre and half-widths (an unbounded side: the four-edge form below)
-  const bool centred = isfinite(rx0) && isfinite(rx1) && isfinite(ry0) && isfinite(ry1);
-  const real tcx = centred ? 0.5 * (rx0 + rx1) : 0.0, tcy = centred ? 0.5 * (ry0 + ry1) : 0.0;
-  const real thx = 0.5 * (rx1 - rx0), thy = 0.5 * (ry1 - ry0);
-  const real oxc = ox - tcx, oyc = oy - tcy;
-  const float znf = (float)znear, zff = (float)zfar;
-  const real row0 = hh - 0.5;                            // dy = (row0 - r) / f
-  real rd = (real)r;
-  const real drd = (real)dr;
-  real dyc = (row0 - rd) * inv_f;
-  const real ddy = drd * inv_f;
-  real zfv = zfar;
-  asm volatile("" : "+v"(zfv));                          // (kept in a register pair: the selects below cannot take it from SGPRs next to VCC)
-  auto rcp1 = [](real x) { real q = __builtin_amdgcn_rcp(x); return q + q * (1.0 - x * q); };
-  // sqrt(x), x > 0, to 2^-46: v_rsq_f64 (2^-23) and one coupled step (g ~ sqrt x, h ~ 1 / (2 sqrt x): g += g (1/2 - g h)).
-  // x = 0 gives NaN, which fails the comparisons of the hit it would have been (a ray tangent to a sphere to the last bit)
-  auto sqrt1 = [](real x) { const real y = __builtin_amdgcn_rsq(x); const real g = x * y, h = 0.5 * y; return g + g * (0.5 - g * h); };
-  // (a wave-uniform trip count: the loop control is scalar, the lane's pixel index one add)
-  const int nit = (npix + (int)blockDim.x - 1) / (int)blockDim.x;
-  float* __restrict__ op = out + threadIdx.x;
-  const int pstep = blockDim.x;
-  int p = threadIdx.x;
-  for (int it = 0; it < nit; it++, p += pstep, op += pstep) {
-    real dx, dy, d0, d1, d2, a2, bc;
-    if constexpr (colfixed) {
-      dx = dxl; dy = dyc; dyc -= ddy;
-      d0 = __builtin_fma(Y[0], dy, ex[0]); d1 = __builtin_fma(Y[1], dy, ex[1]); d2 = __builtin_fma(Y[2], dy, ex[2]);
-      a2 = __builtin_fma(dy, __builtin_fma(dy, A2, A1), A0);
-      bc = __builtin_fma(dy, B1, B0);
-    } else {
-      dx = (c + 0.5 - hw) * inv_f; dy = -(r + 0.5 - hh) * inv_f;
-      c += dc; r += dr;
-      if (c >= width) { c -= width; r++; }
-      d0 = X[0] * dx + Y[0] * dy - Z[0]; d1 = X[1] * dx + Y[1] * dy - Z[1]; d2 = X[2] * dx + Y[2] * dy - Z[2];
-      a2 = d0 * d0 + d1 * d1 + d2 * d2;
-      bc = d0 * rel[0] + d1 * rel[1] + d2 * rel[2];
-    }
-    // table top: the rectangle table_rect at z = table_z.  d2 == 0 makes t infinite or NaN, which fails `t > 0 && t < zfar`; the
-    // rectangle test is then never looked at (table_rect holds no NaN: kmanip_create checks)
-    real best = zfv;
-    {
-      const real t = k0 * rcp1(d2);
-      real in;
-      if (centred) {
-        const real hx = __builtin_fma(t, d0, oxc), hy = __builtin_fma(t, d1, oyc);
-        in = fmin(thx - fabs(hx), thy - fabs(hy));
-      } else {
-        const real hx = __builtin_fma(t, d0, ox), hy = __builtin_fma(t, d1, oy);
-        in = fmin(fmin(hx - rx0, rx1 - hx), fmin(hy - ry0, ry1 - hy));
-      }
-      if (t > 0 && t < zfar && in >= 0) best = t;
-    }
-    // cube box: slab test in the cube frame -- only for rays that meet the box's bounding sphere (a wave is one image row or two,
-    // so the test is coherent)
-    if (bc * bc - a2 * cube_cc >= 0) {
-      real dlv[3];
-#pragma unroll
-      for (int a = 0; a < 3; a++) dlv[a] = colfixed ? __builtin_fma(DY[a], dy, bx[a]) : DX[a] * dx + DY[a] * dy - DZ[a];
-      real t0 = -INFINITY, t1 = INFINITY;
-      bool ok = true;
-#pragma unroll
-      for (int a = 0; a < 3; a++) {
-        const real dl = dlv[a];
-        if (dl != 0) {
-          const real inv = rcp1(dl);
-          const real ta = (-hf[a] - ol[a]) * inv, tb = (hf[a] - ol[a]) * inv;
-          t0 = fmax(t0, fmin(ta, tb)); t1 = fmin(t1, fmax(ta, tb));
-        } else if (ol[a] < -hf[a] || ol[a] > hf[a]) ok = false;
-      }
-      if (ok && t0 <= t1 && t1 > 0) {
-        const real t = t0 > 0 ? t0 : t1;
-        if (t < best) best = t;
-      }
-    }
-    // the visible spheres (finger tips): from the gripper camera they fill most of the image, so nearly every wave (one image
-    // row) takes the hit path of every sphere -- 1 / |d|^2 once per pixel, a one-step square root
-    const real ia2 = rcp1(a2);
-#pragma unroll
-    for (int s = 0; s < KM_RENDER_MAXVIS; s++) {
-      if (s < nvis) {
-        const real b = colfixed ? __builtin_fma(dy, S1[s], S0[s]) : d0 * soc[s][0] + d1 * soc[s][1] + d2 * soc[s][2];
-        const real disc = b * b - a2 * scc[s];
-        if (disc >= 0) {
-          // nearest root; compared before the division: t < best  <=>  -b - sqrt(disc) < best * a2  (a2 > 0)
-          const real num = -b - sqrt1(disc);
-          if (num > 0 && num < best * a2) best = num * ia2;
-        }
-      }
-    }
-    if (COLFIXED || p < npix) *op = __builtin_amdgcn_fmed3f((float)best, znf, zff);     // (COLFIXED launches: npix is a multiple of the workgroup, checked by the launcher)
-  }
-}
+// k_render_depth is the float64 depth ray cast of kmanip_render_depth_cast.inc, the one text k_render_depth_links and
+// k_render_points are built from too; what rounds 4 to 6 did to its pixel loop is told there.
+#define KM_CAST_MODE KM_CAST_DEPTH
+#include "kmanip_render_depth_cast.inc"
 
 // one pixel, float32: grey level * 255 of the three channels packed r | g << 8 | b << 16
-// (kmanip_render_labels.hip keeps a copy, seg_pixel, that also returns the material, and its quad loop repeats k_render_rgb's table
-// path: a change to the hit tests or the shading here belongs there too -- DESIGN.md section 13 says why it is a copy;
-// tests/test_label_render_gpu.py holds the two to each other byte for byte)
+// (kmanip_render_label_cast.hpp keeps a copy, label_pixel, that also returns the material and tests the link capsules, and its quad
+// loop repeats k_render_rgb's table path: a change to the hit tests or the shading here belongs there too -- DESIGN.md sections 13
+// and 33 say why it is a copy; tests/test_label_render_gpu.py holds the two to each other byte for byte)
 template <bool VIS>
 __device__ __forceinline__ uint32_t rgb_pixel(const RgbScene& g, const RgbVis* gv, float dx, float dy, uint32_t objs, bool tab) {
   const float dz = g.X[2] * dx + g.Y[2] * dy - g.Z[2];

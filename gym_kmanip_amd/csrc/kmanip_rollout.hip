@@ -30,7 +30,7 @@
 #include "kmanip_ik_coop.hpp"
 #include <stdlib.h>
 #include "kmanip_dyn_variant.hpp"
-#include "kmanip_dyn_rows.hpp"         // (row_env, row_load: shared with k_forward)
+#include "kmanip_dyn_rows.hpp"         // (row_env, row_load: shared with k_forward; quat_log_diff: with k_transfd)
 
 // KM_VAR_FB=1: the closed-loop build of this unit (the Makefile's kmanip_feedback_* objects), next to KM_VAR_PAR and KM_VAR_FRC.  It
 // names the structs (KFeedbackIn / KFeedbackDev begin with KRolloutIn's / KRolloutDev's fields), the kernel and the launcher.
@@ -73,27 +73,6 @@ __device__ __forceinline__ void rollout_finish(const RollDev& out, size_t row, i
     if (out.steps_done) out.steps_done[row] = t0;
   }
 }
-
-#if KM_VAR_FB
-// The rotation part of derivatives.tangent_diff (MuJoCo's mj_differentiatePos): the body-frame log of conj(a) (x) b, a = the
-// reference's quaternion, b = the state's, operation for operation as the Python spells it.  No contraction: the vector part is two
-// differences of separately rounded products, so that equal quaternions give exactly zero (with an FMA, wa xb - xa wb would be the
-// rounding error of a product).
-__device__ __forceinline__ void quat_log_diff(const real (&a)[4], const real (&b)[4], real (&r)[3]) {
-#pragma clang fp contract(off)
-  const real wa = a[0], xa = a[1], ya = a[2], za = a[3], wb = b[0], xb = b[1], yb = b[2], zb = b[3];
-  const real w = ((wa * wb + xa * xb) + ya * yb) + za * zb;
-  const real x = (wa * xb - xa * wb) + (za * yb - ya * zb);
-  const real y = (wa * yb - ya * wb) + (xa * zb - za * xb);
-  const real z = (wa * zb - za * wb) + (ya * xb - xa * yb);
-  const real s = sqrt((x * x + y * y) + z * z);
-  real ang = 2.0 * atan2(s, w);
-  if (ang > 3.141592653589793) ang = ang - 6.283185307179586;
-  // angle / sin(angle / 2) -> 2 / w as the vector part vanishes
-  const real k = s > 0 ? ang / s : 2.0 / (w != 0 ? w : 1.0);
-  r[0] = k * x; r[1] = k * y; r[2] = k * z;
-}
-#endif
 
 template <int NL, int G, int SOLVER, int EPB>
 __global__ __launch_bounds__(64) void KM_KERNEL(KM_ROLL_KERNEL)(const KDeviceModel* __restrict__ dm, KDeviceState st, RollIn in, int n, int nstep,

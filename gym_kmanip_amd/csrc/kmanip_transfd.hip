@@ -12,14 +12,13 @@
 // Per row the arithmetic is derivatives.transition_fd's, operation for operation: +-eps added to one entry, or the cube's quaternion
 // multiplied on the right by [cos(eps / 2), +-sin(eps / 2) e_k] as tangent_perturb spells the product (sin and cos taken once on the
 // host); the warm start of the first sub-step the base (the caller's, else the nominal row's after its step: the first launch wrote
-// it) plus warm_offset; the log map as kmanip_rollout.hip's quat_log_diff writes it (restated here: that unit keeps it to itself, and
-// the k_feedback objects stay the ones they were); a division, not a reciprocal multiply.
+// it) plus warm_offset; the log map is k_feedback's, quat_log_diff of kmanip_dyn_rows.hpp; a division, not a reciprocal multiply.
 // NO GROUP LEAVES BEFORE THE EXCHANGE, except a whole pair without work: a bad index or a row that stops sets the group's status and
 // falls through, where k_rollout returns.
 #include "kmanip_ik_coop.hpp"
 #include <stdlib.h>
 #include "kmanip_dyn_variant.hpp"
-#include "kmanip_dyn_rows.hpp"         // (row_env, row_load: shared with k_forward and k_rollout)
+#include "kmanip_dyn_rows.hpp"         // (row_env, row_load: shared with k_forward and k_rollout; quat_log_diff: with k_feedback)
 
 // what the two groups of a pair hand each other: the state after the step and the row's status
 template <int NL>
@@ -27,23 +26,6 @@ struct TfdXch {
   real qpos[Dim<NL>::NQ], qvel[Dim<NL>::NV];
   int status, pad_;
 };
-
-// kmanip_rollout.hip's quat_log_diff (the rotation part of derivatives.tangent_diff: the body-frame log of conj(a) (x) b), restated.
-// No contraction: the vector part is two differences of separately rounded products, as torch computes them.
-__device__ __forceinline__ void tfd_quat_log_diff(const real (&a)[4], const real (&b)[4], real (&r)[3]) {
-#pragma clang fp contract(off)
-  const real wa = a[0], xa = a[1], ya = a[2], za = a[3], wb = b[0], xb = b[1], yb = b[2], zb = b[3];
-  const real w = ((wa * wb + xa * xb) + ya * yb) + za * zb;
-  const real x = (wa * xb - xa * wb) + (za * yb - ya * zb);
-  const real y = (wa * yb - ya * wb) + (xa * zb - za * xb);
-  const real z = (wa * zb - za * wb) + (ya * xb - xa * yb);
-  const real s = sqrt((x * x + y * y) + z * z);
-  real ang = 2.0 * atan2(s, w);
-  if (ang > 3.141592653589793) ang = ang - 6.283185307179586;
-  // angle / sin(angle / 2) -> 2 / w as the vector part vanishes
-  const real k = s > 0 ? ang / s : 2.0 / (w != 0 ? w : 1.0);
-  r[0] = k * x; r[1] = k * y; r[2] = k * z;
-}
 
 // derivatives.tangent_perturb's rotation columns: q <- q (x) [w1, v1], v1 = sh e_k, every product and sum rounded on its own
 __device__ __forceinline__ void tfd_quat_perturb(real (&q)[4], int k, real w1, real sh) {
@@ -174,7 +156,7 @@ __global__ __launch_bounds__(64) void KM_KERNEL(k_transfd)(const KDeviceModel* _
   real qa[4], qb[4], rot[3];
 #pragma unroll
   for (int k = 0; k < 4; k++) { qa[k] = other.qpos[NL + 3 + k]; qb[k] = mine.qpos[NL + 3 + k]; }
-  tfd_quat_log_diff(qa, qb, rot);
+  quat_log_diff(qa, qb, rot);
   const real den = 2.0 * in.eps;
   for (int i = sub; i < NX; i += G) {
     real d;

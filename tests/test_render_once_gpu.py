@@ -2,7 +2,10 @@
 an MI355X): label_cast<.., LINKS> of kmanip_render_label_cast.hpp is k_render_labels and k_render_links, and
 k_render_points<.., LINKS> has been one template since section 16.  What couples them is checked here: a capsule list that every
 camera masks out (cam_mask = 0: every rectangle is empty, no capsule is ever tested) must give the bytes of no list at all.  The
-library of the commit before section 33 passes all twelve cases too."""
+library of the commit before section 33 passes all twelve cases too.
+Since section 35 k_render_depth, k_render_depth_links and k_render_points are one source text, kmanip_render_depth_cast.inc, and
+the depth images of the four routes through it are held to each other byte for byte (six more cases; the library of the commit
+before section 35, the same device code, passes them)."""
 import ctypes as C
 
 import numpy as np
@@ -92,3 +95,42 @@ def test_masked_list_is_no_list_in_the_point_kernels(handle, shape):
             assert torch.equal(depth1.view(torch.int32), depth0.view(torch.int32)), (cam, h, w, frame, "depth")
     dev.set_depth_links(False)
     dev.set_render_links(None)
+
+
+# The four routes to a depth image that the one text of kmanip_render_depth_cast.inc feeds, by kernel
+DEPTH_ROUTES = ("k_render_depth", "k_render_depth_links", "k_render_points<LINKS=false>", "k_render_points<LINKS=true>")
+# ... and the pairs of them held to each other byte for byte: every pair that is byte-equal on the library of the commit before
+# section 35, whose device code is this one's instruction for instruction.  That is all six: no pair is left out
+DEPTH_PAIRS = [(a, b) for i, a in enumerate(DEPTH_ROUTES) for b in DEPTH_ROUTES[i + 1:]]
+
+
+def _depth_routes(dev, masked, cam, h, w):
+    """The depth image of one camera by each route: render_depth and depth_out of render_points, without a list (the depth flag
+    off) and with the list every camera masks out (the flag on)."""
+    out = {}
+    dev.set_render_links(None)
+    dev.set_depth_links(False)
+    out["k_render_depth"] = dev.render_depth(cam, h, w)
+    out["k_render_points<LINKS=false>"] = _points(dev, cam, h, w, "world")[1]
+    dev.set_render_links(masked)
+    dev.set_depth_links(True)
+    out["k_render_depth_links"] = dev.render_depth(cam, h, w)
+    out["k_render_points<LINKS=true>"] = _points(dev, cam, h, w, "world")[1]
+    dev.set_depth_links(False)
+    dev.set_render_links(None)
+    return out
+
+
+@pytest.mark.parametrize("shape", SHAPES, ids=lambda s: "%dx%d" % s)
+def test_depth_routes_of_the_one_cast_agree(handle, shape):
+    """k_render_depth, k_render_depth_links and both k_render_points instantiations are one text: with no capsule to test, the
+    depth images they write are the same bytes."""
+    torch = _torch()
+    dev, masked = handle
+    h, w = shape
+    for cam in _cams(dev.cm):
+        d = _depth_routes(dev, masked, cam, h, w)
+        for a, b in DEPTH_PAIRS:
+            ne = int((d[a].view(torch.int32) != d[b].view(torch.int32)).sum())
+            print("%s %dx%d  %s | %s: %d pixels differ, max |diff| %.3g" % (cam, h, w, a, b, ne, float((d[a] - d[b]).abs().max())))
+            assert ne == 0, (cam, h, w, a, b)
