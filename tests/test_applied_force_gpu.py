@@ -7,10 +7,9 @@ holds it against the oracle itself).  The "test forces" are applied_oracle.draw_
 +-2 m g on the cube's force components, +-1e-3 on its torque components; they move every env's qpos by more than 1e-5 in one control
 step (test_applied_force_cpu), so no parity test here passes without the feature.
 
-The guard at the end runs without a GPU: the rows of the zero-force, parity and forces() tests launch every force object the
-Makefile compiles."""
+The guard at the end runs without a GPU: the rows of the zero-force, parity and forces() tests launch every force object make
+builds."""
 import os
-import re
 import sys
 
 import numpy as np
@@ -18,10 +17,10 @@ import pytest
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "tools"))
 import applied_oracle as AO  # noqa: E402
+import build_matrix as BM  # noqa: E402
 import force_oracle as FO  # noqa: E402
 import mujoco_pin  # noqa: E402
 import regime_states as R  # noqa: E402
-from conftest import ROOT  # noqa: E402
 from gym_kmanip_amd.model import ENV_PARAMS, KM_DONE_DIVERGED, with_env_params  # noqa: E402
 from test_gpu_parity import TOL_Q, TOL_V  # noqa: E402
 
@@ -492,28 +491,16 @@ def test_refusals_and_state_calls_leave_the_binding_alone():
 
 
 # ------------------------------------------------------------------------------------------------------ 3. a row for every object
-MAKEFILE = os.path.join(ROOT, "gym_kmanip_amd", "csrc", "Makefile")
 SOLVER_OF = {"pgs": 0, "newton": 1}
 
 
-def _variants(makefile_text, name):
-    m = re.search(r"^%s\s*:?=(.*)$" % name, makefile_text, re.M)
-    assert m, "no %s line" % name
-    return [tuple(int(x) for x in tok.split("_")) for tok in m.group(1).split()]
-
-
-def force_objects(makefile_text):
-    """Every force object the Makefile compiles and every launch shape of it: ("dyn", NL, G, SOLVER, per-env parameters, chunk) for the
-    kmanip_dyn_frc_* / kmanip_dyn_ep_frc_* rules over DYN_VARIANTS, ("forces", NL, G, per-env parameters) for the kmanip_forces_frc_*
-    / kmanip_forces_ep_frc_* rules over FORCES_VARIANTS."""
-    out = []
-    for par, stem in ((False, "kmanip_dyn_frc_"), (True, "kmanip_dyn_ep_frc_")):
-        assert re.search(r"^\$\(DYN_VARIANTS:%%=%s%%\.\$\(O\)\):.*kmanip_dyn\.hip" % stem, makefile_text, re.M), stem
-        out += [("dyn", nl, g, s, par, chunk) for nl, g, s in _variants(makefile_text, "DYN_VARIANTS") for chunk in (False, True)]
-    for par, stem in ((False, "kmanip_forces_frc_"), (True, "kmanip_forces_ep_frc_")):
-        assert re.search(r"^\$\(FORCES_VARIANTS:%%=%s%%\.\$\(O\)\):.*kmanip_forces\.hip" % stem, makefile_text, re.M), stem
-        out += [("forces", nl, g, par) for nl, g in _variants(makefile_text, "FORCES_VARIANTS")]
-    return out
+def force_objects(makefile_path):
+    """Every force object of kmanip_dyn and kmanip_forces that make builds and every launch shape of it: ("dyn", NL, G, SOLVER, per-env
+    parameters, chunk) for the kmanip_dyn_frc_* / kmanip_dyn_ep_frc_* objects, ("forces", NL, G, per-env parameters) for the
+    kmanip_forces_frc_* / kmanip_forces_ep_frc_* objects."""
+    objs = [o for o in BM.objects(makefile_path) if o.frc]
+    return ([("dyn", o.NL, o.G, o.solver, o.ep, chunk) for o in objs if o.unit == "dyn" for chunk in (False, True)]
+            + [("forces", o.NL, o.G, o.ep) for o in objs if o.unit == "forces"])
 
 
 def covered(step_rows, parity_rows, forces_rows):
@@ -535,22 +522,20 @@ def _parity_rows():
 
 
 def test_every_compiled_force_object_has_a_row():
-    with open(MAKEFILE) as f:
-        text = f.read()
-    objs = force_objects(text)
+    objs = force_objects(BM.MAKEFILE)
     assert len(objs) >= 2 * 2 * 4 + 2 * 2
     have = covered(STEP_ROWS, _parity_rows(), FORCES_ROWS)
     assert [o for o in objs if o not in have] == []
 
 
 def test_the_guard_fails_for_an_object_without_a_row(tmp_path):
-    with open(MAKEFILE) as f:
-        text = f.read()
-    more = re.sub(r"^(DYN_VARIANTS\s*:?=.*)$", r"\1 30_64_1", text, count=1, flags=re.M)
+    more = BM.copy_with_class(tmp_path / "Makefile", "30_64")
     have = covered(STEP_ROWS, _parity_rows(), FORCES_ROWS)
-    assert [o for o in force_objects(more) if o not in have] == [("dyn", 30, 64, 1, p, c) for p in (False, True) for c in (False, True)]
+    miss = [o for o in force_objects(more) if o not in have]
+    assert sorted(o for o in miss if o[0] == "dyn") == [("dyn", 30, 64, s, p, c) for s in (0, 1) for p in (False, True) for c in (False, True)]
+    assert [o for o in miss if o[0] == "forces"] == [("forces", 30, 64, False), ("forces", 30, 64, True)]
     rows = [r for r in STEP_ROWS if not (r[1] == "pgs" and r[2])]
-    miss = [o for o in force_objects(text) if o not in covered(rows, _parity_rows(), FORCES_ROWS)]
+    miss = [o for o in force_objects(BM.MAKEFILE) if o not in covered(rows, _parity_rows(), FORCES_ROWS)]
     assert ("dyn", 10, 16, 0, True, True) in miss and ("dyn", 20, 32, 0, True, False) in miss
-    miss = [o for o in force_objects(text) if o not in covered(STEP_ROWS, _parity_rows(), [r for r in FORCES_ROWS if not r[1]])]
+    miss = [o for o in force_objects(BM.MAKEFILE) if o not in covered(STEP_ROWS, _parity_rows(), [r for r in FORCES_ROWS if not r[1]])]
     assert miss == [("forces", 10, 16, True), ("forces", 20, 32, True)]

@@ -96,26 +96,20 @@ def test_cam_mask_and_spheres_in_the_reference():
 def test_depth_link_kernel_resources_and_exports():
     """The four k_render_depth_links instantiations (COLFIXED x VIS) exist, the COLFIXED ones do not spill to scratch, k_render_depth
     and k_render_links keep their four instantiations each, and the two new entry points are declared, exported and loadable."""
-    import subprocess
+    import build_matrix as BM
     from gym_kmanip_amd import lib as klib
     if not os.path.exists(klib.LIB_PATH):
         klib.build()
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "kernel_resources.py"), klib.LIB_PATH, "render"],
-                         capture_output=True, text=True, check=True).stdout
-    res = {}
-    for line in out.splitlines():
-        f = line.split()
-        res[f[0]] = {f[i]: int(f[i + 1]) for i in range(1, len(f) - 1, 2) if f[i + 1].isdigit()}
-    dl = {(col, vis): v for k, v in res.items() for col in (0, 1) for vis in (0, 1)
-          if k.startswith("_Z20k_render_depth_linksILb%dELb%dE" % (col, vis))}
-    assert len(dl) == 4 and sum(k.startswith("_Z20k_render_depth_links") for k in res) == 4, sorted(res)
+    all_dl = BM.kernels(klib.LIB_PATH, "k_render_depth_links")
+    dl = {k.args[:2]: k for k in all_dl}                                    # (COLFIXED, VIS)
+    assert len(dl) == 4 and len(all_dl) == 4, all_dl
     for key, v in dl.items():
         print("k_render_depth_links<COLFIXED=%d, VIS=%d>" % key, v)
-        assert v["vgpr"] <= 128, (key, v)                                      # (four waves per SIMD, as k_render_depth)
+        assert v.vgpr <= 128, (key, v)                                         # (four waves per SIMD, as k_render_depth)
         if key[0]:
-            assert v["scratch"] == 0, (key, v)
-    assert sum(k.startswith("_Z14k_render_depthILb") for k in res) == 4
-    assert sum(k.startswith("_Z14k_render_links") for k in res) == 4
+            assert v.scratch == 0, (key, v)
+    assert sum(type(k.args[0]) is bool for k in BM.kernels(klib.LIB_PATH, "k_render_depth")) == 4
+    assert len(BM.kernels(klib.LIB_PATH, "k_render_links")) == 4
     hdr = open(os.path.join(ROOT, "include", "kmanip.h")).read()
     L = klib.load()
     for name in ("kmanip_set_depth_links", "kmanip_get_depth_links"):

@@ -12,6 +12,9 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "gym_kmanip_amd", "csrc")
 sys.path.insert(0, os.path.join(ROOT, "tools"))
+sys.path.insert(0, os.path.join(ROOT, "tests", "tools"))
+import build_matrix as BM  # noqa: E402
+
 HIPCC = "/opt/rocm/bin/hipcc"
 
 
@@ -47,11 +50,11 @@ def test_checker_finds_a_planted_hazard(tmp_path):
 def test_shipped_kernels_have_no_dpp_read_after_write_hazard(tmp_path):
     import check_dpp_hazard as chk
     flags = ["-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-ffp-contract=fast-honor-pragmas", "-S", "--cuda-device-only"]
-    # every kmanip_dyn variant the Makefile links (DYN_VARIANTS) + the stand-alone IK object
+    # every kmanip_dyn variant the Makefile links in the default build + the stand-alone IK object
     jobs = [("kmanip_dyn.hip", ["-DKM_VAR_NL=%d" % nl, "-DKM_VAR_G=%d" % g, "-DKM_VAR_SOLVER=%d" % sv], "dyn_%d_%d_%d.s" % (nl, g, sv))
             for nl, g in ((10, 16), (20, 32)) for sv in (1, 0)] + [("kmanip_ik_coop.hip", [], "ik_coop.s")]
-    mk = open(os.path.join(CSRC, "Makefile")).read()
-    assert "DYN_VARIANTS := 10_16_1 10_16_0 20_32_1 20_32_0" in mk          # (keep this list in step with the Makefile)
+    default_dyn = [o for o in BM.objects(os.path.join(CSRC, "Makefile"), "dyn") if not o.ep and not o.frc]
+    assert [j[2] for j in jobs[:-1]] == ["dyn_%d_%d_%d.s" % (o.NL, o.G, o.solver) for o in default_dyn]
 
     def build(job):
         src, defs, out = job

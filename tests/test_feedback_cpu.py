@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "tools"))
+import build_matrix as BM  # noqa: E402
 import feedback_oracle as FO  # noqa: E402
 import mujoco_pin  # noqa: E402
 import regime_states as R  # noqa: E402
@@ -22,7 +23,6 @@ from test_gpu_parity import TOL_Q, TOL_R, TOL_V  # noqa: E402
 ASSETS = mujoco_pin.ASSETS
 SOLVERS = ("newton", "pgs")
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-MAKEFILE = os.path.join(ROOT, "gym_kmanip_amd", "csrc", "Makefile")
 BARS = {"qpos": TOL_Q, "qvel": TOL_V, "reward": TOL_R}
 # the worst spread of the recorded u between the reference and its qvel (1 + 1e-15) twin over every cell of the three assets, both
 # solvers, 3 steps of the model's sub-steps under the fixed gains (values of size <= 5), measured by the test below and committed; the
@@ -58,16 +58,9 @@ def test_feedback_binding_matches_the_header():
 
 
 def _feedback_table():
-    import contextlib
-    import io
-    sys.path.insert(0, os.path.join(ROOT, "tools"))
-    import kernel_resources as kr
+    """The k_feedback* kernels of the built library; args = (NL, G, SOLVER, rows per wave)."""
     from gym_kmanip_amd import lib as klib
-    buf = io.StringIO()
-    with contextlib.redirect_stdout(buf):
-        kr.main(klib.LIB_PATH, "k_feedback")
-    return [re.search(r"\d+(k_feedback\w*?)ILi(\d+)ELi(\d+)ELi(\d)ELi(\d)E\S*\s+vgpr (\d+) agpr \d+ sgpr \d+ scratch (\d+) lds (\d+)", ln).groups()
-            for ln in buf.getvalue().splitlines()]
+    return BM.kernels(klib.LIB_PATH, r"k_feedback\w*")
 
 
 def test_shipped_feedback_kernels_run_without_scratch():
@@ -77,13 +70,13 @@ def test_shipped_feedback_kernels_run_without_scratch():
     from test_rollout_cpu import _rollout_table
     rows = _feedback_table()
     names = ("k_feedback", "k_feedback_ep", "k_feedback_frc", "k_feedback_ep_frc")
-    assert sorted((r[0], int(r[1]), int(r[3])) for r in rows) == sorted((nm, nl, s) for nm in names for nl in (10, 20) for s in (0, 1))
-    sibling = {(r[0].replace("k_rollout", "k_feedback"), int(r[1]), int(r[3])): int(r[7]) for r in _rollout_table()}
+    assert sorted((r.base, r.args[0], r.args[2]) for r in rows) == sorted((nm, nl, s) for nm in names for nl in (10, 20) for s in (0, 1))
+    sibling = {(r.base.replace("k_rollout", "k_feedback"), r.args[0], r.args[2]): r.lds for r in _rollout_table()}
     for r in rows:
-        nl, epb = int(r[1]), int(r[4])
-        assert (int(r[2]), epb) == ((16, 4) if nl == 10 else (32, 2)), r
-        assert int(r[6]) == 0 and int(r[5]) <= 512, r
-        assert int(r[7]) == sibling[(r[0], nl, int(r[3]))] + epb * 2 * (nl + 6) * 8, r
+        nl, g, solver, epb = r.args
+        assert (g, epb) == ((16, 4) if nl == 10 else (32, 2)), r
+        assert r.scratch == 0 and r.vgpr <= 512, r
+        assert r.lds == sibling[(r.base, nl, solver)] + epb * 2 * (nl + 6) * 8, r
 
 
 # ---------------------------------------------------------------------------------------------------- the reference's own identities
@@ -184,13 +177,6 @@ def test_the_ctrl_bar_is_1000_times_the_committed_spread_one_digit_up():
 
 
 # ------------------------------------------------------------------------------------------ every compiled object runs a parity row
-def fb_variants(makefile_text):
-    """(NL, G, SOLVER) of every FB_VARIANTS entry: each is compiled in the default, _ep_, _frc_ and _ep_frc_ builds."""
-    m = re.search(r"^FB_VARIANTS\s*:?=(.*)$", makefile_text, re.M)
-    assert m, "no FB_VARIANTS line"
-    return [tuple(int(x) for x in tok.split("_")) for tok in m.group(1).split()]
-
-
 def covered(parity_rows):
     """The (NL, G, SOLVER, ep, frc) objects the device's parity runs launch (kmanip_dispatch.hip: the 10-link class for nlink <= 10,
     the parameter build while the handle has per-env parameters, the force build while the call gives a force)."""
@@ -202,29 +188,25 @@ def covered(parity_rows):
     return out
 
 
-def missing_rows(makefile_text, parity_rows):
+def missing_rows(makefile_path, parity_rows):
     have = covered(parity_rows)
-    return [v + (ep, frc) for v in fb_variants(makefile_text) for ep in (False, True) for frc in (False, True) if v + (ep, frc) not in have]
+    return [tuple(o[1:]) for o in BM.objects(makefile_path, "feedback") if tuple(o[1:]) not in have]
 
 
 def test_every_compiled_feedback_object_has_a_parity_row():
     from test_feedback_gpu import PARITY_ROWS
-    with open(MAKEFILE) as f:
-        text = f.read()
-    assert sorted(fb_variants(text)) == sorted([(10, 16, 1), (10, 16, 0), (20, 32, 1), (20, 32, 0)])
-    assert missing_rows(text, PARITY_ROWS) == []
-    assert len(_feedback_table()) == 4 * len(fb_variants(text))          # the objects the Makefile links are the ones the library holds
+    objs = BM.objects(BM.MAKEFILE, "feedback")
+    assert sorted({o[1:4] for o in objs}) == sorted([(10, 16, 1), (10, 16, 0), (20, 32, 1), (20, 32, 0)])
+    assert missing_rows(BM.MAKEFILE, PARITY_ROWS) == []
+    assert len(_feedback_table()) == len(objs)          # the objects the Makefile links are the ones the library holds
 
 
 def test_the_guard_fails_for_a_feedback_variant_without_a_row(tmp_path):
     from test_feedback_gpu import PARITY_ROWS
-    with open(MAKEFILE) as f:
-        text = f.read()
-    copy = tmp_path / "Makefile"
-    copy.write_text(re.sub(r"^(FB_VARIANTS\s*:?=.*)$", r"\1 30_64_1", text, count=1, flags=re.M))
-    assert missing_rows(copy.read_text(), PARITY_ROWS) == [(30, 64, 1, ep, frc) for ep in (False, True) for frc in (False, True)]
+    more = BM.copy_with_class(tmp_path / "Makefile", "30_64")
+    assert sorted(missing_rows(more, PARITY_ROWS)) == [(30, 64, s, ep, frc) for s in (0, 1) for ep in (False, True) for frc in (False, True)]
     rows = [r for r in PARITY_ROWS if not (r[1] == "pgs" and "forced" in r[2])]
-    miss = missing_rows(text, rows)
+    miss = missing_rows(BM.MAKEFILE, rows)
     assert (10, 16, 0, False, True) in miss and (20, 32, 0, True, True) in miss
 
 
@@ -233,7 +215,7 @@ def test_the_feedback_objects_are_the_rollout_source_with_one_more_macro():
     """k_feedback is kmanip_rollout.hip compiled with -DKM_VAR_FB=1 and nothing else: make's dry run (nothing
     is compiled) gives the feedback object and its rollout sibling the same command line but for that flag and the object's name."""
     import subprocess
-    csrc = os.path.dirname(MAKEFILE)
+    csrc = os.path.dirname(BM.MAKEFILE)
     objs = {"feedback": "kmanip_feedback_ep_frc_20_32_0.o", "rollout": "kmanip_rollout_ep_frc_20_32_0.o"}
     lines = {}
     for kind, obj in objs.items():

@@ -75,27 +75,54 @@ def test_kforwardin_binding_matches_the_header():
 def test_shipped_forward_kernels_run_without_scratch():
     """The eight k_forward variants of the built library (parsed from the .so: no GPU): none spills, the LDS of their k_forces
     siblings (the same workspace), registers within the 512 of a single-wave workgroup."""
-    import contextlib
-    import io
-    sys.path.insert(0, os.path.join(ROOT, "tools"))
-    import kernel_resources as kr
+    import build_matrix as BM
     from gym_kmanip_amd import lib as klib
-
-    def table(pat):
-        buf = io.StringIO()
-        with contextlib.redirect_stdout(buf):
-            kr.main(klib.LIB_PATH, pat)
-        return [re.search(r"(k_\w+?)ILi(\d+)ELi(\d+)ELi(\d)E\S*\s+vgpr (\d+) agpr \d+ sgpr \d+ scratch (\d+) lds (\d+)", ln).groups()
-                for ln in buf.getvalue().splitlines()]
-    fwd = {(r[0], int(r[1])): r for r in table("k_forward")}
+    fwd = {(r.base, r.args[0]): r for r in BM.kernels(klib.LIB_PATH, r"k_forward\w*")}
     names = ("k_forward", "k_forward_ep", "k_forward_frc", "k_forward_ep_frc")
     assert sorted(fwd) == sorted((nm, nl) for nm in names for nl in (10, 20))
-    frc = {(r[0], int(r[1])): r for r in table("k_(frc_)?forces")}
+    frc = {(r.base, r.args[0]): r for r in BM.kernels(klib.LIB_PATH, r"k_(frc_)?forces\w*")}
     sibling = dict(zip(names, ("k_forces", "k_forces_ep", "k_frc_forces", "k_frc_forces_ep")))
     for (nm, nl), r in fwd.items():
-        assert (int(r[2]), int(r[3])) == ((16, 4) if nl == 10 else (32, 2)), r
-        assert int(r[5]) == 0 and int(r[4]) <= 512, r
-        assert int(r[6]) == int(frc[(sibling[nm], nl)][6]), (r, frc[(sibling[nm], nl)])
+        assert r.args[1:] == ((16, 4) if nl == 10 else (32, 2)), r
+        assert r.scratch == 0 and r.vgpr <= 512, r
+        assert r.lds == frc[(sibling[nm], nl)].lds, (r, frc[(sibling[nm], nl)])
+
+
+# ------------------------------------------------------------------------------------------ every compiled object runs an identity row
+def covered(identity_rows):
+    """The (NL, G, ep, frc) forward objects that test_forward_gpu's comparison with forces() launches (kmanip_dispatch.hip: the 10-link
+    class for nlink <= 10, the parameter build while the handle has per-env parameters, set or drawn from ranges, the force build
+    while a force is bound)."""
+    out = set()
+    for asset, mode in identity_rows:
+        cls = (10, 16) if R.model(asset).nlink <= 10 else (20, 32)
+        out.add(cls + ("params" in mode or mode == "ranges", "bound" in mode))
+    return out
+
+
+def missing_rows(makefile_path, identity_rows):
+    import build_matrix as BM
+    have = covered(identity_rows)
+    return [(o.NL, o.G, o.ep, o.frc) for o in BM.objects(makefile_path, "forward") if (o.NL, o.G, o.ep, o.frc) not in have]
+
+
+def test_every_compiled_forward_object_has_an_identity_row():
+    import build_matrix as BM
+    from gym_kmanip_amd import lib as klib
+    from test_forward_gpu import IDENTITY_ROWS
+    objs = BM.objects(BM.MAKEFILE, "forward")
+    assert sorted({(o.NL, o.G, o.solver) for o in objs}) == [(10, 16, None), (20, 32, None)]
+    assert missing_rows(BM.MAKEFILE, IDENTITY_ROWS) == []
+    assert len(BM.kernels(klib.LIB_PATH, r"k_forward\w*")) == len(objs)          # the objects the Makefile links are the ones the library holds
+
+
+def test_the_guard_fails_for_a_forward_object_without_a_row(tmp_path):
+    import build_matrix as BM
+    from test_forward_gpu import IDENTITY_ROWS
+    more = BM.copy_with_class(tmp_path / "Makefile", "30_64")
+    assert missing_rows(more, IDENTITY_ROWS) == [(30, 64, ep, frc) for frc in (False, True) for ep in (False, True)]
+    rows = [r for r in IDENTITY_ROWS if "bound" not in r[1]]
+    assert missing_rows(BM.MAKEFILE, rows) == [(nl, g, ep, True) for ep in (False, True) for nl, g in ((10, 16), (20, 32))]
 
 
 # ------------------------------------------------------------------------------------------------------------------ tangent_perturb

@@ -127,6 +127,7 @@ def _diff_under_bars(f, g):
     return bad + [(k, v, bars[k]) for k, v in d.items() if not v <= bars[k]], d
 
 
+# tests/test_forward_cpu.py checks that these rows launch every k_forward object the Makefile compiles.
 IDENTITY_ROWS = [(a, m) for a in ASSETS for m in ("plain", "bound", "params", "params+bound")] + [("solo_arm", "ranges")]
 
 

@@ -196,21 +196,13 @@ def test_kinverse_bindings_match_the_header():
 def test_shipped_inverse_kernels_run_without_scratch():
     """k_inverse / k_inverse_ep of the built library (parsed from the .so: no GPU): four variants, none spills, the LDS of their
     k_forces siblings at most."""
-    import contextlib
-    import io
-    import re
-    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools"))
-    import kernel_resources as kr
+    import build_matrix as BM
     from gym_kmanip_amd import lib as klib
     if not os.path.exists(klib.LIB_PATH):
         klib.build()
-    buf = io.StringIO()
-    with contextlib.redirect_stdout(buf):
-        kr.main(klib.LIB_PATH, "k_inverse")
-    rows = [re.search(r"(k_inverse(?:_ep)?)ILi(\d+)ELi(\d+)ELi(\d)E\S*\s+vgpr (\d+) agpr \d+ sgpr \d+ scratch (\d+) lds (\d+)", ln).groups()
-            for ln in buf.getvalue().splitlines()]
-    assert sorted((r[0], int(r[1]), int(r[2]), int(r[3])) for r in rows) == [("k_inverse", 10, 16, 4), ("k_inverse", 20, 32, 2),
-                                                                             ("k_inverse_ep", 10, 16, 4), ("k_inverse_ep", 20, 32, 2)]
+    rows = BM.kernels(klib.LIB_PATH, r"k_inverse\w*")
+    assert sorted((r.base,) + r.args for r in rows) == [("k_inverse", 10, 16, 4), ("k_inverse", 20, 32, 2),
+                                                        ("k_inverse_ep", 10, 16, 4), ("k_inverse_ep", 20, 32, 2)]
     for r in rows:
-        print("%s<%s,%s,%s> vgpr %s scratch %s lds %s" % r)
-        assert int(r[5]) == 0 and int(r[4]) <= 512 and int(r[6]) <= 40 * 1024, r
+        print("%s<%s,%s,%s> vgpr %s scratch %s lds %s" % ((r.base,) + r.args + (r.vgpr, r.scratch, r.lds)))
+        assert r.scratch == 0 and r.vgpr <= 512 and r.lds <= 40 * 1024, r

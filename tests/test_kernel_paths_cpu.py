@@ -1,25 +1,21 @@
 """CPU guards of tests/test_kernel_paths_gpu.py: its step matrix has a row for every kmanip_dyn object the Makefile compiles, and its
 render shape lists reach every pixel-loop path of k_render_depth and k_render_rgb."""
 import os
-import re
+import sys
 
 from conftest import ROOT
 from gym_kmanip_amd.model import compile_model
 from test_kernel_paths_gpu import DEPTH_SHAPES, RGB_SHAPES, STEP_ROWS
 
-MAKEFILE = os.path.join(ROOT, "gym_kmanip_amd", "csrc", "Makefile")
+sys.path.insert(0, os.path.join(ROOT, "tests", "tools"))
+import build_matrix as BM  # noqa: E402
+
 SOLVER_OF = {"pgs": 0, "newton": 1}
 
 
-def dyn_variants(makefile_text):
-    """(NL, G, SOLVER) of every DYN_VARIANTS entry: each is compiled once without and once with per-env parameters."""
-    m = re.search(r"^DYN_VARIANTS\s*:?=(.*)$", makefile_text, re.M)
-    assert m, "no DYN_VARIANTS line"
-    out = []
-    for tok in m.group(1).split():
-        nl, g, s = (int(x) for x in tok.split("_"))
-        out.append((nl, g, s))
-    return out
+def dyn_objects(makefile_path):
+    """The kmanip_dyn objects without an applied force (tests/test_applied_force_gpu.py's guard answers for the _frc_ ones)."""
+    return [o for o in BM.objects(makefile_path, "dyn") if not o.frc]
 
 
 def covered(rows):
@@ -35,27 +31,22 @@ def covered(rows):
     return out
 
 
-def missing_rows(makefile_text, rows):
+def missing_rows(makefile_path, rows):
     have = covered(rows)
-    return [(nl, g, s, par) for nl, g, s in dyn_variants(makefile_text) for par in (False, True) if (nl, g, s, par) not in have]
+    return [(o.NL, o.G, o.solver, o.ep) for o in dyn_objects(makefile_path) if (o.NL, o.G, o.solver, o.ep) not in have]
 
 
 def test_every_compiled_step_object_has_an_oracle_row():
-    with open(MAKEFILE) as f:
-        text = f.read()
-    assert len(dyn_variants(text)) >= 4
-    assert missing_rows(text, STEP_ROWS) == []
+    assert len(dyn_objects(BM.MAKEFILE)) >= 2 * 4
+    assert missing_rows(BM.MAKEFILE, STEP_ROWS) == []
 
 
 def test_the_guard_fails_for_a_variant_without_a_row(tmp_path):
-    with open(MAKEFILE) as f:
-        text = f.read()
-    copy = tmp_path / "Makefile"
-    copy.write_text(re.sub(r"^(DYN_VARIANTS\s*:?=.*)$", r"\1 30_64_1", text, count=1, flags=re.M))
-    assert missing_rows(copy.read_text(), STEP_ROWS) == [(30, 64, 1, False), (30, 64, 1, True)]
+    more = BM.copy_with_class(tmp_path / "Makefile", "30_64")
+    assert sorted(missing_rows(more, STEP_ROWS)) == [(30, 64, s, par) for s in (0, 1) for par in (False, True)]
     # ... and for a row set that drops one solver's parameter rows
     rows = [r for r in STEP_ROWS if not (r[1] == "pgs" and r[2] != "none")]
-    assert (10, 16, 0, True) in missing_rows(text, rows) and (20, 32, 0, True) in missing_rows(text, rows)
+    assert (10, 16, 0, True) in missing_rows(BM.MAKEFILE, rows) and (20, 32, 0, True) in missing_rows(BM.MAKEFILE, rows)
 
 
 def _colfixed(h, w):

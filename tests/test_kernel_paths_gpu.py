@@ -3,14 +3,15 @@
 The common paths have their own parity tests (test_gpu_parity, test_env_params_gpu, test_visual_params_gpu).  This module covers
 the rest of what the library compiles and the public API reaches:
   - the step matrix: both link classes x both solvers x {no parameters, explicit per-env parameters, ranges mode}, i.e. all eight
-    kmanip_dyn objects (DYN_VARIANTS x {default, KM_VAR_PAR}), one-step samples against the oracle of the env's own values;
+    kmanip_dyn objects without an applied force ({class x solver} x {default, KM_VAR_PAR}), one-step samples against the oracle of
+    the env's own values;
   - kmanip_step_chunk and the forced envs-per-wave launch shapes (KMANIP_EPB) of every variant, bit for bit against single steps
     and the default shape: the oracle parity above then carries over to them (an env's result does not depend on its wave slot);
   - k_render_depth on both instantiations (COLFIXED: a whole number of rows per 128-lane workgroup; general: any other shape),
     with and without the per-env camera offset;
   - k_render_rgb's per-pixel loop (width % 4 != 0), its quad-tile walk with partial tiles, and the multi-job launch, with and
     without per-env colours, lights and camera offset.
-tests/test_kernel_paths_cpu.py keeps STEP_ROWS complete against the Makefile's DYN_VARIANTS."""
+tests/test_kernel_paths_cpu.py keeps STEP_ROWS complete against the kmanip_dyn objects make builds."""
 import ctypes as C
 
 import numpy as np

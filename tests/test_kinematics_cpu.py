@@ -210,18 +210,10 @@ def test_kkindev_binding_matches_the_header():
 def test_shipped_kinematics_kernels_run_without_scratch():
     """k_kinematics / k_kinematics_ep of the built library (parsed from the .so: no GPU): four variants, none spills, the LDS of
     their k_step siblings."""
-    import contextlib
-    import io
-    import re
-    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools"))
-    import kernel_resources as kr
+    import build_matrix as BM
     from gym_kmanip_amd import lib as klib
-    buf = io.StringIO()
-    with contextlib.redirect_stdout(buf):
-        kr.main(klib.LIB_PATH, "k_kinematics")
-    rows = [re.search(r"(k_kinematics(?:_ep)?)ILi(\d+)ELi(\d+)ELi(\d)E\S*\s+vgpr (\d+) agpr \d+ sgpr \d+ scratch (\d+) lds (\d+)", ln).groups()
-            for ln in buf.getvalue().splitlines()]
-    assert sorted((r[0], int(r[1]), int(r[2]), int(r[3])) for r in rows) == [("k_kinematics", 10, 16, 4), ("k_kinematics", 20, 32, 2),
-                                                                             ("k_kinematics_ep", 10, 16, 4), ("k_kinematics_ep", 20, 32, 2)]
+    rows = BM.kernels(klib.LIB_PATH, r"k_kinematics\w*")
+    assert sorted((r.base,) + r.args for r in rows) == [("k_kinematics", 10, 16, 4), ("k_kinematics", 20, 32, 2),
+                                                        ("k_kinematics_ep", 10, 16, 4), ("k_kinematics_ep", 20, 32, 2)]
     for r in rows:
-        assert int(r[5]) == 0 and int(r[4]) <= 512 and int(r[6]) <= 40 * 1024, r
+        assert r.scratch == 0 and r.vgpr <= 512 and r.lds <= 40 * 1024, r

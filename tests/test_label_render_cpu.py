@@ -3,7 +3,6 @@ held to (tests/tools/label_oracle.py, built on the CPU oracle's RGB ray caster),
 the episode logger's label datasets and the label kernels' resources."""
 import os
 import re
-import subprocess
 import sys
 
 import numpy as np
@@ -218,16 +217,11 @@ def test_episode_logger_late_labels(tmp_path):
 def test_label_kernel_resources():
     """Every k_render_labels instantiation keeps the RGB kernel's occupancy: <= 128 VGPR (four waves per SIMD), no scratch; the
     four instantiations (VIS x RGB) exist, and k_render_rgb still has exactly its two."""
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "kernel_resources.py"), LIB, "render"],
-                         capture_output=True, text=True, check=True).stdout
-    res = {}
-    for line in out.splitlines():
-        f = line.split()
-        res[f[0]] = {f[i]: int(f[i + 1]) for i in range(1, len(f) - 1, 2) if f[i + 1].isdigit()}
-    lab = {(vis, rgb): v for k, v in res.items() for vis in (0, 1) for rgb in (0, 1)
-           if k.startswith("_Z15k_render_labelsILb%dELb%dE" % (vis, rgb))}
-    assert len(lab) == 4 and sum(k.startswith("_Z15k_render_labels") for k in res) == 4, sorted(res)
+    import build_matrix as BM
+    all_lab = BM.kernels(LIB, "k_render_labels")
+    lab = {k.args[:2]: k for k in all_lab}                                  # (VIS, RGB)
+    assert len(lab) == 4 and len(all_lab) == 4, all_lab
     for key, v in lab.items():
         print("k_render_labels<VIS=%d, RGB=%d>" % key, v)
-        assert v["vgpr"] <= 128 and v["scratch"] == 0, (key, v)
-    assert sum(k.startswith("_Z12k_render_rgbILb") for k in res) == 2
+        assert v.vgpr <= 128 and v.scratch == 0, (key, v)
+    assert sum(type(k.args[0]) is bool for k in BM.kernels(LIB, "k_render_rgb")) == 2

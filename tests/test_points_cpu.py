@@ -126,26 +126,20 @@ def test_point_kernel_resources():
     """The eight k_render_points instantiations (COLFIXED x VIS x LINKS) and the two k_camera_poses exist; every one fits four
     waves per SIMD (128 vector registers, the depth kernels' budget) without scratch; the existing depth kernels keep their
     four instantiations each."""
-    import subprocess
+    import build_matrix as BM
     from gym_kmanip_amd import lib as klib
     if not os.path.exists(klib.LIB_PATH):
         klib.build()
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "kernel_resources.py"), klib.LIB_PATH, "k_"],
-                         capture_output=True, text=True, check=True).stdout
-    res = {}
-    for line in out.splitlines():
-        f = line.split()
-        res[f[0]] = {f[i]: int(f[i + 1]) for i in range(1, len(f) - 1, 2) if f[i + 1].isdigit()}
-    pts = {(col, vis, ln): v for k, v in res.items() for col in (0, 1) for vis in (0, 1) for ln in (0, 1)
-           if k.startswith("_Z15k_render_pointsILb%dELb%dELb%dE" % (col, vis, ln))}
-    assert len(pts) == 8 and sum(k.startswith("_Z15k_render_points") for k in res) == 8, sorted(res)
+    all_pts = BM.kernels(klib.LIB_PATH, "k_render_points")
+    pts = {k.args[:3]: k for k in all_pts}                  # (COLFIXED, VIS, LINKS)
+    assert len(pts) == 8 and len(all_pts) == 8, all_pts
     for key, v in sorted(pts.items()):
         print("k_render_points<COLFIXED=%d, VIS=%d, LINKS=%d>" % key, v)
-        assert v["vgpr"] <= 128 and v["scratch"] == 0, (key, v)
-    poses = {k: v for k, v in res.items() if k.startswith("_Z14k_camera_poses")}
+        assert v.vgpr <= 128 and v.scratch == 0, (key, v)
+    poses = BM.kernels(klib.LIB_PATH, "k_camera_poses")
     assert len(poses) == 2
-    for k, v in poses.items():
+    for v in poses:
         print("k_camera_poses", v)
-        assert v["vgpr"] <= 128 and v["scratch"] == 0, (k, v)
-    assert sum(k.startswith("_Z14k_render_depthILb") for k in res) == 4
-    assert sum(k.startswith("_Z20k_render_depth_links") for k in res) == 4
+        assert v.vgpr <= 128 and v.scratch == 0, v
+    assert sum(type(k.args[0]) is bool for k in BM.kernels(klib.LIB_PATH, "k_render_depth")) == 4
+    assert len(BM.kernels(klib.LIB_PATH, "k_render_depth_links")) == 4

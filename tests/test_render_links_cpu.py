@@ -202,23 +202,18 @@ def test_a_zero_length_capsule_is_its_sphere():
 def test_link_kernel_resources_and_exports():
     """The four k_render_links instantiations (VIS x RGB) exist and none spills to scratch; the existing render kernels keep their
     instantiation counts; the two new entry points are declared and exported."""
-    import subprocess
+    import build_matrix as BM
     from gym_kmanip_amd import lib as klib
     if not os.path.exists(klib.LIB_PATH):
         klib.build()
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "kernel_resources.py"), klib.LIB_PATH, "render"],
-                         capture_output=True, text=True, check=True).stdout
-    res = {}
-    for line in out.splitlines():
-        f = line.split()
-        res[f[0]] = {f[i]: int(f[i + 1]) for i in range(1, len(f) - 1, 2) if f[i + 1].isdigit()}
-    links = {(vis, rgb): v for k, v in res.items() for vis in (0, 1) for rgb in (0, 1)
-             if k.startswith("_Z14k_render_linksILb%dELb%dE" % (vis, rgb))}
-    assert len(links) == 4 and sum(k.startswith("_Z14k_render_links") for k in res) == 4, sorted(res)
+    all_links = BM.kernels(klib.LIB_PATH, "k_render_links")
+    links = {k.args[:2]: k for k in all_links}                              # (VIS, RGB)
+    assert len(links) == 4 and len(all_links) == 4, all_links
     for key, v in links.items():
         print("k_render_links<VIS=%d, RGB=%d>" % key, v)
-        assert v["scratch"] == 0 and v["vgpr"] <= 168, (key, v)                 # (168 VGPR: three waves per SIMD)
-    assert sum(k.startswith("_Z15k_render_labels") for k in res) == 4 and sum(k.startswith("_Z12k_render_rgbILb") for k in res) == 2
+        assert v.scratch == 0 and v.vgpr <= 168, (key, v)                       # (168 VGPR: three waves per SIMD)
+    assert len(BM.kernels(klib.LIB_PATH, "k_render_labels")) == 4
+    assert sum(type(k.args[0]) is bool for k in BM.kernels(klib.LIB_PATH, "k_render_rgb")) == 2
     hdr = open(os.path.join(ROOT, "include", "kmanip.h")).read()
     for name in ("kmanip_set_render_links", "kmanip_get_render_links"):
         assert name + "(" in hdr and name in klib.EXPORTS and hasattr(klib.load(), name)

@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "tools"))
+import build_matrix as BM  # noqa: E402
 import forward_oracle as FW  # noqa: E402
 import mujoco_pin  # noqa: E402
 import regime_states as R  # noqa: E402
@@ -23,7 +24,6 @@ from test_gpu_parity import TOL_Q, TOL_R, TOL_V  # noqa: E402
 ASSETS = mujoco_pin.ASSETS
 SOLVERS = ("newton", "pgs")
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-MAKEFILE = os.path.join(ROOT, "gym_kmanip_amd", "csrc", "Makefile")
 BARS = {"qpos": TOL_Q, "qvel": TOL_V, "reward": TOL_R}
 
 
@@ -52,16 +52,9 @@ def test_rollout_binding_matches_the_header():
 
 
 def _rollout_table():
-    import contextlib
-    import io
-    sys.path.insert(0, os.path.join(ROOT, "tools"))
-    import kernel_resources as kr
+    """The k_rollout* kernels of the built library; args = (NL, G, SOLVER, rows per wave)."""
     from gym_kmanip_amd import lib as klib
-    buf = io.StringIO()
-    with contextlib.redirect_stdout(buf):
-        kr.main(klib.LIB_PATH, "k_rollout")
-    return [re.search(r"\d+(k_rollout\w*?)ILi(\d+)ELi(\d+)ELi(\d)ELi(\d)E\S*\s+vgpr (\d+) agpr \d+ sgpr \d+ scratch (\d+) lds (\d+)", ln).groups()
-            for ln in buf.getvalue().splitlines()]
+    return BM.kernels(klib.LIB_PATH, r"k_rollout\w*")
 
 
 def test_shipped_rollout_kernels_run_without_scratch():
@@ -69,10 +62,10 @@ def test_shipped_rollout_kernels_run_without_scratch():
     builds, 64 / G rows per wave, none spills, registers within the 512 of a single-wave workgroup."""
     rows = _rollout_table()
     names = ("k_rollout", "k_rollout_ep", "k_rollout_frc", "k_rollout_ep_frc")
-    assert sorted((r[0], int(r[1]), int(r[3])) for r in rows) == sorted((nm, nl, s) for nm in names for nl in (10, 20) for s in (0, 1))
+    assert sorted((r.base, r.args[0], r.args[2]) for r in rows) == sorted((nm, nl, s) for nm in names for nl in (10, 20) for s in (0, 1))
     for r in rows:
-        assert (int(r[2]), int(r[4])) == ((16, 4) if int(r[1]) == 10 else (32, 2)), r
-        assert int(r[6]) == 0 and int(r[5]) <= 512, r
+        assert len(r.args) == 4 and (r.args[1], r.args[3]) == ((16, 4) if r.args[0] == 10 else (32, 2)), r
+        assert r.scratch == 0 and r.vgpr <= 512, r
 
 
 # ------------------------------------------------------------------------------------------------------- the reference's own spread
@@ -375,13 +368,6 @@ def test_the_derivative_bars_are_1000_times_the_references_own_spread(nsub):
 SOLVER_OF = {"pgs": 0, "newton": 1}
 
 
-def roll_variants(makefile_text):
-    """(NL, G, SOLVER) of every ROLL_VARIANTS entry: each is compiled in the default, _ep_, _frc_ and _ep_frc_ builds."""
-    m = re.search(r"^ROLL_VARIANTS\s*:?=(.*)$", makefile_text, re.M)
-    assert m, "no ROLL_VARIANTS line"
-    return [tuple(int(x) for x in tok.split("_")) for tok in m.group(1).split()]
-
-
 def covered(parity_rows, identity_rows):
     """The (NL, G, SOLVER, ep, frc) objects the device tests launch.  kmanip_dispatch.hip picks the 10-link class for nlink <= 10,
     the parameter build while the handle has per-env parameters, the force build while the call gives a force or one is bound."""
@@ -396,29 +382,25 @@ def covered(parity_rows, identity_rows):
     return out
 
 
-def missing_rows(makefile_text, parity_rows, identity_rows):
+def missing_rows(makefile_path, parity_rows, identity_rows):
     have = covered(parity_rows, identity_rows)
-    return [v + (ep, frc) for v in roll_variants(makefile_text) for ep in (False, True) for frc in (False, True) if v + (ep, frc) not in have]
+    return [tuple(o[1:]) for o in BM.objects(makefile_path, "rollout") if tuple(o[1:]) not in have]
 
 
 def test_every_compiled_rollout_object_has_a_parity_row():
     from test_rollout_gpu import IDENTITY_ROWS, PARITY_ROWS
-    with open(MAKEFILE) as f:
-        text = f.read()
-    assert sorted(roll_variants(text)) == sorted([(10, 16, 1), (10, 16, 0), (20, 32, 1), (20, 32, 0)])
-    assert missing_rows(text, PARITY_ROWS, IDENTITY_ROWS) == []
+    objs = BM.objects(BM.MAKEFILE, "rollout")
+    assert sorted({o[1:4] for o in objs}) == sorted([(10, 16, 1), (10, 16, 0), (20, 32, 1), (20, 32, 0)])
+    assert missing_rows(BM.MAKEFILE, PARITY_ROWS, IDENTITY_ROWS) == []
     # the objects the Makefile links are the ones the library holds
-    assert len(_rollout_table()) == 4 * len(roll_variants(text))
+    assert len(_rollout_table()) == len(objs)
 
 
 def test_the_guard_fails_for_a_rollout_variant_without_a_row(tmp_path):
     from test_rollout_gpu import IDENTITY_ROWS, PARITY_ROWS
-    with open(MAKEFILE) as f:
-        text = f.read()
-    copy = tmp_path / "Makefile"
-    copy.write_text(re.sub(r"^(ROLL_VARIANTS\s*:?=.*)$", r"\1 30_64_1", text, count=1, flags=re.M))
-    assert missing_rows(copy.read_text(), PARITY_ROWS, IDENTITY_ROWS) == [(30, 64, 1, ep, frc) for ep in (False, True) for frc in (False, True)]
+    more = BM.copy_with_class(tmp_path / "Makefile", "30_64")
+    assert sorted(missing_rows(more, PARITY_ROWS, IDENTITY_ROWS)) == [(30, 64, s, ep, frc) for s in (0, 1) for ep in (False, True) for frc in (False, True)]
     # ... and for a row set that drops the PGS force rows
     rows = [r for r in PARITY_ROWS if not (r[1] == "pgs" and "forced" in r[2])]
-    miss = missing_rows(text, rows, IDENTITY_ROWS)
+    miss = missing_rows(BM.MAKEFILE, rows, IDENTITY_ROWS)
     assert (10, 16, 0, False, True) in miss and (20, 32, 0, True, True) in miss

@@ -5,35 +5,27 @@ must not need more than it did before its forward kinematics moved its link-fram
 35 168 bytes of LDS per workgroup, no scratch.  The two-arm Newton per-step kernels, which that change does not touch, stay within
 432 + 176 registers without scratch (the compiler this was written with allots them 428 + 172, before that change and after it: the
 figures are ceilings, not equalities)."""
-import contextlib
-import io
 import os
-import re
 import sys
 
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "tools"))
+sys.path.insert(0, os.path.join(ROOT, "tests", "tools"))
 
 ONE_ROW_NEWTON = dict(vgpr=384, agpr=128, lds=35168)
 TWO_ARM = dict(vgpr=432, agpr=176)
 
 
 def _rows():
-    import kernel_resources as kr
+    import build_matrix as BM
     so = os.path.join(ROOT, "gym_kmanip_amd", "libkmanip_hip.so")
     if not os.path.exists(so):
         pytest.skip("library not built")
-    buf = io.StringIO()
-    with contextlib.redirect_stdout(buf):
-        kr.main(so, "^_Z6k_stepILi")
     rows = {}
-    for ln in buf.getvalue().splitlines():
-        m = re.match(r"_Z6k_stepILi(\d+)ELi(\d+)ELi(\d)ELi(\d)ELb(\d)E\S*\s+vgpr (\d+) agpr (\d+) sgpr \d+ scratch (\d+) lds (\d+)", ln)
-        assert m, ln
-        nl, g, solver, epb, chunk, vgpr, agpr, scratch, lds = map(int, m.groups())
-        rows[(nl, g, solver, epb, chunk)] = dict(vgpr=vgpr, agpr=agpr, scratch=scratch, lds=lds)
+    for k in BM.kernels(so, "k_step"):
+        nl, g, solver, epb, chunk = k.args
+        rows[(nl, g, solver, epb, int(chunk))] = dict(vgpr=k.vgpr, agpr=k.agpr, scratch=k.scratch, lds=k.lds)
     return rows
 
 

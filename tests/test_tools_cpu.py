@@ -47,23 +47,16 @@ def test_shipped_step_kernels_scratch_and_lds():
     """The shipped library's k_step variants (parsed from the built .so: no GPU): every per-step variant runs without scratch and a
     four-env single-arm workgroup's LDS lets four workgroups share a CU (one wave per SIMD: DESIGN.md 2, 3.2); the chunk variants are
     pinned at what round 6 left (two-arm Newton: 128 B -- the one shipped kernel that spills)."""
-    import io
-    import contextlib
-    import re
-    import kernel_resources as kr
+    sys.path.insert(0, os.path.join(ROOT, "tests", "tools"))
+    import build_matrix as BM
     so = os.path.join(ROOT, "gym_kmanip_amd", "libkmanip_hip.so")
     if not os.path.exists(so):
         import pytest
         pytest.skip("library not built")
-    buf = io.StringIO()
-    with contextlib.redirect_stdout(buf):
-        kr.main(so, "k_stepILi")
     rows = {}
-    for ln in buf.getvalue().splitlines():
-        m = re.match(r"_Z6k_stepILi(\d+)ELi(\d+)ELi(\d)ELi(\d)ELb(\d)E\S*\s+vgpr (\d+) agpr (\d+) sgpr \d+ scratch (\d+) lds (\d+)", ln)
-        assert m, ln
-        nl, g, solver, epb, chunk, vgpr, agpr, scratch, lds = map(int, m.groups())
-        rows[(nl, solver, epb, chunk)] = (vgpr, scratch, lds)
+    for k in BM.kernels(so, "k_step"):
+        nl, g, solver, epb, chunk = k.args
+        rows[(nl, solver, epb, int(chunk))] = (k.vgpr, k.scratch, k.lds)
     assert len(rows) == 14
     for (nl, solver, epb, chunk), (vgpr, scratch, lds) in rows.items():
         assert vgpr <= 512

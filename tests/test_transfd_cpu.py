@@ -9,12 +9,12 @@ import sys
 import numpy as np
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "tools"))
+import build_matrix as BM  # noqa: E402
 import feedback_oracle as FO  # noqa: E402
 import regime_states as R  # noqa: E402
 import rollout_oracle as RO  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-MAKEFILE = os.path.join(ROOT, "gym_kmanip_amd", "csrc", "Makefile")
 
 
 # ------------------------------------------------------------------------------------------------------------------ the binding
@@ -51,16 +51,9 @@ def test_transfd_binding_matches_the_header():
 
 
 def _transfd_table():
-    import contextlib
-    import io
-    sys.path.insert(0, os.path.join(ROOT, "tools"))
-    import kernel_resources as kr
+    """The k_transfd* kernels of the built library; args = (NL, G, SOLVER, lane groups per wave)."""
     from gym_kmanip_amd import lib as klib
-    buf = io.StringIO()
-    with contextlib.redirect_stdout(buf):
-        kr.main(klib.LIB_PATH, "k_transfd")
-    return [re.search(r"\d+(k_transfd\w*?)ILi(\d+)ELi(\d+)ELi(\d)ELi(\d)E\S*\s+vgpr (\d+) agpr \d+ sgpr \d+ scratch (\d+) lds (\d+)", ln).groups()
-            for ln in buf.getvalue().splitlines()]
+    return BM.kernels(klib.LIB_PATH, r"k_transfd\w*")
 
 
 def test_shipped_transfd_kernels_run_without_scratch():
@@ -72,25 +65,18 @@ def test_shipped_transfd_kernels_run_without_scratch():
     from test_rollout_cpu import _rollout_table
     rows = _transfd_table()
     names = ("k_transfd", "k_transfd_ep", "k_transfd_frc", "k_transfd_ep_frc")
-    assert sorted((r[0], int(r[1]), int(r[3])) for r in rows) == sorted((nm, nl, s) for nm in names for nl in (10, 20) for s in (0, 1))
-    lds = {(r[0].replace("k_rollout", "k_transfd"), int(r[1]), int(r[3])): int(r[7]) for r in _rollout_table()}
-    vgpr = {(r[0].replace("k_feedback", "k_transfd"), int(r[1]), int(r[3])): int(r[5]) for r in _feedback_table()}
+    assert sorted((r.base, r.args[0], r.args[2]) for r in rows) == sorted((nm, nl, s) for nm in names for nl in (10, 20) for s in (0, 1))
+    lds = {(r.base.replace("k_rollout", "k_transfd"), r.args[0], r.args[2]): r.lds for r in _rollout_table()}
+    vgpr = {(r.base.replace("k_feedback", "k_transfd"), r.args[0], r.args[2]): r.vgpr for r in _feedback_table()}
     for r in rows:
-        nl, epb = int(r[1]), int(r[4])
-        key = (r[0], nl, int(r[3]))
-        assert (int(r[2]), epb) == ((16, 4) if nl == 10 else (32, 2)), r
-        assert int(r[6]) == 0 and int(r[5]) <= 512 and int(r[5]) <= vgpr[key], r
-        assert int(r[7]) == lds[key] + epb * ((nl + 7) + (nl + 6) + 1) * 8, r
+        nl, g, solver, epb = r.args
+        key = (r.base, nl, solver)
+        assert (g, epb) == ((16, 4) if nl == 10 else (32, 2)), r
+        assert r.scratch == 0 and r.vgpr <= 512 and r.vgpr <= vgpr[key], r
+        assert r.lds == lds[key] + epb * ((nl + 7) + (nl + 6) + 1) * 8, r
 
 
 # ------------------------------------------------------------------------------------------ every compiled object runs a parity row
-def tfd_variants(makefile_text):
-    """(NL, G, SOLVER) of every TFD_VARIANTS entry: each is compiled in the default, _ep_, _frc_ and _ep_frc_ builds."""
-    m = re.search(r"^TFD_VARIANTS\s*:?=(.*)$", makefile_text, re.M)
-    assert m, "no TFD_VARIANTS line"
-    return [tuple(int(x) for x in tok.split("_")) for tok in m.group(1).split()]
-
-
 def covered(handle_rows):
     """The (NL, G, SOLVER, ep, frc) objects the device's comparison with derivatives.transition_fd launches (kmanip_dispatch.hip: the
     10-link class for nlink <= 10, the parameter build while the handle has per-env parameters, the force build while the call
@@ -103,29 +89,25 @@ def covered(handle_rows):
     return out
 
 
-def missing_rows(makefile_text, handle_rows):
+def missing_rows(makefile_path, handle_rows):
     have = covered(handle_rows)
-    return [v + (ep, frc) for v in tfd_variants(makefile_text) for ep in (False, True) for frc in (False, True) if v + (ep, frc) not in have]
+    return [tuple(o[1:]) for o in BM.objects(makefile_path, "transfd") if tuple(o[1:]) not in have]
 
 
 def test_every_compiled_transfd_object_has_a_row():
     from test_transfd_gpu import HANDLE_ROWS
-    with open(MAKEFILE) as f:
-        text = f.read()
-    assert sorted(tfd_variants(text)) == sorted([(10, 16, 1), (10, 16, 0), (20, 32, 1), (20, 32, 0)])
-    assert missing_rows(text, HANDLE_ROWS) == []
-    assert len(_transfd_table()) == 4 * len(tfd_variants(text))          # the objects the Makefile links are the ones the library holds
+    objs = BM.objects(BM.MAKEFILE, "transfd")
+    assert sorted({o[1:4] for o in objs}) == sorted([(10, 16, 1), (10, 16, 0), (20, 32, 1), (20, 32, 0)])
+    assert missing_rows(BM.MAKEFILE, HANDLE_ROWS) == []
+    assert len(_transfd_table()) == len(objs)          # the objects the Makefile links are the ones the library holds
 
 
 def test_the_guard_fails_for_a_transfd_variant_without_a_row(tmp_path):
     from test_transfd_gpu import HANDLE_ROWS
-    with open(MAKEFILE) as f:
-        text = f.read()
-    copy = tmp_path / "Makefile"
-    copy.write_text(re.sub(r"^(TFD_VARIANTS\s*:?=.*)$", r"\1 30_64_1", text, count=1, flags=re.M))
-    assert missing_rows(copy.read_text(), HANDLE_ROWS) == [(30, 64, 1, ep, frc) for ep in (False, True) for frc in (False, True)]
+    more = BM.copy_with_class(tmp_path / "Makefile", "30_64")
+    assert sorted(missing_rows(more, HANDLE_ROWS)) == [(30, 64, s, ep, frc) for s in (0, 1) for ep in (False, True) for frc in (False, True)]
     rows = [r for r in HANDLE_ROWS if not (r[1] == "pgs" and ("forced" in r[2] or "bound" in r[2]))]
-    miss = missing_rows(text, rows)
+    miss = missing_rows(BM.MAKEFILE, rows)
     assert (10, 16, 0, False, True) in miss and (20, 32, 0, True, True) in miss
 
 

@@ -2,7 +2,6 @@
 definition the camera offset is held to -- the Python setters' validation, and the VIS render kernels' resources."""
 import math
 import os
-import subprocess
 import sys
 
 import numpy as np
@@ -136,15 +135,12 @@ LIB = os.path.join(ROOT, "gym_kmanip_amd", "libkmanip_hip.so")
 def test_vis_kernel_resources():
     """The VIS render kernels keep the default's occupancy: rgb <= 128 VGPR and no scratch; depth no more scratch than the
     default kernels (0 with a whole number of rows per workgroup, 52 B without)."""
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "kernel_resources.py"), LIB, "render"],
-                         capture_output=True, text=True, check=True).stdout
-    res = {}
-    for line in out.splitlines():
-        f = line.split()
-        res[f[0]] = {f[i]: int(f[i + 1]) for i in range(1, len(f) - 1, 2) if f[i + 1].isdigit()}
-    rgb_vis = [v for k, v in res.items() if k.startswith("_Z12k_render_rgbILb1E")]
-    rgb_def = [v for k, v in res.items() if k.startswith("_Z12k_render_rgbILb0E")]
-    d = {(c, vis): v for k, v in res.items() for c in (0, 1) for vis in (0, 1) if k.startswith("_Z14k_render_depthILb%dELb%dE" % (c, vis))}
-    assert len(rgb_vis) == 1 and len(rgb_def) == 1 and len(d) == 4, sorted(res)
-    assert rgb_vis[0]["vgpr"] <= 128 and rgb_vis[0]["scratch"] == 0
-    assert d[(1, 1)]["scratch"] == 0 and d[(0, 1)]["scratch"] <= d[(0, 0)]["scratch"]
+    sys.path.insert(0, os.path.join(ROOT, "tests", "tools"))
+    import build_matrix as BM
+    rgb = BM.kernels(LIB, "k_render_rgb")
+    rgb_vis = [k for k in rgb if k.args[0] is True]
+    rgb_def = [k for k in rgb if k.args[0] is False]
+    d = {k.args[:2]: k for k in BM.kernels(LIB, "k_render_depth")}          # (COLFIXED, VIS)
+    assert len(rgb_vis) == 1 and len(rgb_def) == 1 and len(d) == 4, (rgb, d)
+    assert rgb_vis[0].vgpr <= 128 and rgb_vis[0].scratch == 0
+    assert d[(1, 1)].scratch == 0 and d[(0, 1)].scratch <= d[(0, 0)].scratch

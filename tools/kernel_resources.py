@@ -1,8 +1,10 @@
 #!/usr/bin/env python3
 """Print VGPR/AGPR/scratch/LDS per kernel of a HIP object or shared library (parses the clang offload bundle)."""
-import re, struct, subprocess, sys, tempfile
+import collections, re, struct, subprocess, sys, tempfile
 
 READELF = "/opt/rocm/lib/llvm/bin/llvm-readelf"
+# the figures are the metadata's own text ("?" where a note lacks one)
+Kernel = collections.namedtuple("Kernel", "name vgpr agpr sgpr scratch lds")
 
 
 def code_objects(blob):
@@ -23,7 +25,9 @@ def code_objects(blob):
         pos += 24
 
 
-def main(path, pat="."):
+def kernels(path, pat="."):
+    """One Kernel per kernel of the file whose mangled name matches pat, in the file's order."""
+    out = []
     blob = open(path, "rb").read()
     for triple, co in code_objects(blob):
         with tempfile.NamedTemporaryFile(suffix=".co") as f:
@@ -33,9 +37,14 @@ def main(path, pat="."):
             g = lambda k: (re.search(r"\.%s:\s+(\S+)" % k, blk) or [None, "?"])[1]
             name = g("name")
             if re.search(pat, name):
-                print("%-60s vgpr %s agpr %s sgpr %s scratch %s lds %s" % (
-                    name[:60], g("vgpr_count"), blk.split()[0], g("sgpr_count"), g("private_segment_fixed_size"),
-                    g("group_segment_fixed_size")))
+                out.append(Kernel(name, g("vgpr_count"), blk.split()[0], g("sgpr_count"), g("private_segment_fixed_size"),
+                                  g("group_segment_fixed_size")))
+    return out
+
+
+def main(path, pat="."):
+    for k in kernels(path, pat):
+        print("%-60s vgpr %s agpr %s sgpr %s scratch %s lds %s" % ((k.name[:60],) + k[1:]))
 
 
 if __name__ == "__main__":
