@@ -610,6 +610,35 @@ int kmanip_transition_fd(KHandle h, const KTransFdIn* in, int n, int nsub, const
   return 0;
 }
 
+// The backward pass of iLQR for n problems of T steps (include/kmanip.h KLqrIn / KLqrDev; kmanip_lqr.hip).  One
+// launch; the handle gives the device and the size class and is only read.
+int kmanip_lqr_backward(KHandle h, const KLqrIn* in, int n, int T, const KLqrDev* out, void* stream) {
+  if (!h) { g_create_error = "kmanip_lqr_backward: null handle"; return -1; }
+  if (!in) { h->err = "kmanip_lqr_backward: the KLqrIn pointer is NULL"; return -1; }
+  if (!out) { h->err = "kmanip_lqr_backward: the KLqrDev pointer is NULL"; return -1; }
+  if (n < 0) { h->err = "kmanip_lqr_backward: n is negative"; return -1; }
+  if (T < 0) { h->err = "kmanip_lqr_backward: T is negative"; return -1; }
+  if (n == 0 || T == 0) return 0;      // (tensors of no problems or no steps have no address: nothing below is asked of them)
+  if (!in->a_t) { h->err = "kmanip_lqr_backward: KLqrIn::a_t is NULL"; return -1; }
+  if (!in->b_t) { h->err = "kmanip_lqr_backward: KLqrIn::b_t is NULL"; return -1; }
+  if (!in->lx) { h->err = "kmanip_lqr_backward: KLqrIn::lx is NULL"; return -1; }
+  if (!in->lu) { h->err = "kmanip_lqr_backward: KLqrIn::lu is NULL"; return -1; }
+  if (!in->lxx) { h->err = "kmanip_lqr_backward: KLqrIn::lxx is NULL"; return -1; }
+  if (!in->luu) { h->err = "kmanip_lqr_backward: KLqrIn::luu is NULL"; return -1; }
+  const int64_t nx = h->desc.nlink <= 10 ? 32 : 52, nu = h->desc.nlink <= 10 ? 10 : 20;      // (kmanip_lqr.hip's two classes)
+  if (in->a_stride != 0 && in->a_stride < nx * nx) { h->err = "kmanip_lqr_backward: a_stride is smaller than an [nx, nx] block"; return -1; }
+  if (in->b_stride != 0 && in->b_stride < nu * nx) { h->err = "kmanip_lqr_backward: b_stride is smaller than an [nu, nx] block"; return -1; }
+  if ((long long)n * T > 2147483647LL) { h->err = "kmanip_lqr_backward: n * T steps are more than an int counts"; return -1; }
+  if (!out->k && !out->gain_t && !out->dv && !out->status && !out->fail_step) return 0;
+  KLqrIn li = *in;
+  if (!li.a_stride) li.a_stride = nx * nx;
+  if (!li.b_stride) li.b_stride = nu * nx;
+  KM_ENTER(h);
+  kmanip_launch_lqr_backward(h->desc, li, n, T, *out, (hipStream_t)stream);
+  HIPCHK(h, hipGetLastError());
+  return 0;
+}
+
 // the render launchers' visual inputs for a render of source `src` (-1 live state, 0 / 1 a snapshot): in ranges mode the draw
 // uses the episode counters of that source (a snapshot taken before ranges mode was on has none: the live ones)
 static KVisArgs vis_args(KHandle h, int src) {

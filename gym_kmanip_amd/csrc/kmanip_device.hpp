@@ -597,6 +597,9 @@ void kmanip_launch_feedback(const KDeviceModel* dm, const KModelDesc& hd, const 
 // sh = cos / sin of eps / 2; the applied-force build also while in.wrt has KM_WRT_FRC
 void kmanip_launch_transfd(const KDeviceModel* dm, const KModelDesc& hd, const KDeviceState& st, const KTransFdIn& in, int n, int ncol,
                            int nsub, double ch, double sh, const KTransFdDev& out, hipStream_t stream);
+// kmanip_lqr_backward (kmanip_lqr.hip): n > 0 problems of T > 0 steps, in.a_stride / in.b_stride resolved (never 0); the size class
+// (nx, nu) is the handle's link-count class
+void kmanip_launch_lqr_backward(const KModelDesc& hd, const KLqrIn& in, int n, int T, const KLqrDev& out, hipStream_t stream);
 // The render launchers' visual inputs (kmanip_set_visual_params / _ranges), a kernel argument of the VIS
 // kernels only -- never a KDeviceState field: the step kernels' argument stays as it is.  All NULL: the default kernels.
 //   vp       explicit values double[KM_VP_N][N], read at the render's launch

@@ -503,6 +503,81 @@ class KManipEnvHip:
             res["contact_mask_fd"] = m.permute(1, 2, 0)
         return res
 
+    # KLqrDev field -> (trailing shape in terms of T / nx / nu, or None for the per-problem fields, dtype name)
+    _LQR_FIELDS = {"k": (("T", "nu"), "float64"), "gain_t": (("T", "nx", "nu"), "float64"), "dv": ((2,), "float64"),
+                   "status": (None, "uint8"), "fail_step": (None, "int32")}
+
+    def lqr_backward(self, lx, lu, lxx, luu, A=None, B=None, deriv_t=None, reg=0.0, out=None):
+        """kmanip_lqr_backward: ilqr.backward_pass -- the Riccati recursion of iLQR -- for n problems of T steps in ONE launch on the
+        current stream, a workgroup per problem with the loop over the steps inside the kernel (no synchronisation; the handle gives
+        the device and the sizes nx = 2 nv, nu, and is only read; n has nothing to do with num_envs).
+          deriv_t [n, T, nx + nu, nx]: transition_fd's buffer over the n T rows e T + t with the default wrt, read where it lies (no
+            copy), or A [n, T, nx, nx] and B [n, T, nx, nu], which get one transposed contiguous copy each.
+          lx [n, T + 1, nx], lu [n, T, nu]; lxx [n, T + 1, nx, nx] or [T + 1, nx, nx] shared by the problems, luu [n, T, nu, nu] or
+            [T, nu, nu]; entry T of lx / lxx is the final cost's.  reg: a number or [n], added to the diagonal of Quu for the solve.
+        Returns a dict: k [n, T, nu]; gains_t [n, T, nx, nu], what rollout_feedback(gains_t=...) takes; K [n, T, nu, nx], its
+        transposed view; dV [n, 2]; status [n] uint8 and fail_step [n] int32 -- 0 and -1, or 1 and the step at which Quu + reg I
+        had a Cholesky pivot that was not positive and finite: that problem's k, gains_t and dV are then zeros, all steps.
+        `out`: a dict of tensors to fill, keyed by the kernel's outputs (k, gain_t, dv, status, fail_step); the others are allocated."""
+        torch = _torch()
+        nx, nu, f64 = 2 * self.cm.nv, self.cm.nu, torch.float64
+        if not isinstance(lu, torch.Tensor) or lu.dim() != 3:
+            raise _libmod.KManipError("lqr_backward: lu must be a [n, T, nu] tensor")
+        n, T = int(lu.shape[0]), int(lu.shape[1])
+        li = _libmod.KLqrIn()
+        if (deriv_t is None) == (A is None and B is None) or (A is None) != (B is None):
+            raise _libmod.KManipError("lqr_backward: give deriv_t, or A and B")
+        if deriv_t is not None:
+            self._check_buf(deriv_t, (n, T, nx + nu, nx), f64, "deriv_t")
+            li.a_t, li.b_t = deriv_t.data_ptr(), deriv_t.data_ptr() + 8 * nx * nx
+            li.a_stride = li.b_stride = (nx + nu) * nx
+            keep = (deriv_t,)
+        else:
+            for name, t, shape in (("A", A, (n, T, nx, nx)), ("B", B, (n, T, nx, nu))):
+                if not isinstance(t, torch.Tensor) or tuple(t.shape) != shape:
+                    raise _libmod.KManipError("lqr_backward: %s must be a tensor of shape %s" % (name, shape))
+            a_t, b_t = A.transpose(2, 3).contiguous(), B.transpose(2, 3).contiguous()
+            self._check_buf(a_t, (n, T, nx, nx), f64, "A")
+            self._check_buf(b_t, (n, T, nu, nx), f64, "B")
+            li.a_t, li.b_t, li.a_stride, li.b_stride = a_t.data_ptr(), b_t.data_ptr(), 0, 0
+            keep = (a_t, b_t)
+        # (the cost's derivatives come as torch made them -- QuadraticCost hands an einsum's strided lx and an expanded luu: a view
+        # gets one contiguous copy, everything else about it is checked)
+        dense = lambda t: t.contiguous() if isinstance(t, torch.Tensor) else t
+        for name, t, shape in (("lx", lx, (n, T + 1, nx)), ("lu", lu, (n, T, nu))):
+            t = dense(t)
+            self._check_buf(t, shape, f64, name)
+            setattr(li, name, t.data_ptr())
+            keep += (t,)
+        for name, t, shape in (("lxx", lxx, (T + 1, nx, nx)), ("luu", luu, (T, nu, nu))):
+            per_env = isinstance(t, torch.Tensor) and t.dim() == 4
+            t = dense(t)
+            self._check_buf(t, ((n,) if per_env else ()) + shape, f64, name)
+            setattr(li, name, t.data_ptr())
+            setattr(li, name + "_per_env", int(per_env))
+            keep += (t,)
+        if isinstance(reg, torch.Tensor) or reg != 0.0:
+            reg = torch.as_tensor(reg, dtype=f64, device=self.device)
+            reg = (reg.expand(n) if reg.dim() == 0 else reg).contiguous()
+            self._check_buf(reg, (n,), f64, "reg")
+            li.reg = reg.data_ptr()
+            keep += (reg,)
+        if out is not None and set(out) - set(self._LQR_FIELDS):
+            raise ValueError("unknown lqr_backward field(s) %s" % sorted(set(out) - set(self._LQR_FIELDS)))
+        ld = _libmod.KLqrDev()
+        res = {name: out[name] if out is not None and name in out else
+               torch.empty((n,) + (() if shp is None else tuple({"T": T, "nx": nx, "nu": nu}.get(d, d) for d in shp)), dtype=getattr(torch, dt),
+                           device=self.device) for name, (shp, dt) in self._LQR_FIELDS.items()}
+        if n == 0 or T == 0:                 # (nothing is launched: what a problem of no steps gives)
+            for name in ("k", "gain_t", "dv", "status"):
+                res[name].zero_()
+            res["fail_step"].fill_(-1)
+        self._query_out(self._LQR_FIELDS, (n,), {"T": T, "nx": nx, "nu": nu}, res, None, ld, "lqr_backward")
+        self._check(self.L.kmanip_lqr_backward(self.h, C.byref(li), n, T, C.byref(ld), self._stream()), "kmanip_lqr_backward")
+        del keep                             # (the stream orders the launch before the allocator reuses the copies)
+        return {"k": res["k"], "gains_t": res["gain_t"], "K": res["gain_t"].transpose(2, 3), "dV": res["dv"], "status": res["status"],
+                "fail_step": res["fail_step"]}
+
     def normal_by_bit(self, f):
         """[n, 32] float64: the normal force of the contact at each KM_CON_* mask bit of a forces() / forward() / inverse() result
         (it needs contact_force and contact_bit; n = the result's rows), 0 where the bit is clear.  Device-side indexing only: no

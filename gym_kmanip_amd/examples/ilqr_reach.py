@@ -1,14 +1,15 @@
 #!/usr/bin/env python3
 """iLQR in ctrl space to a joint-space goal (gym_kmanip_amd.ilqr): every env plans for itself from the state its handle holds.
 
-    python -m gym_kmanip_amd.examples.ilqr_reach [--env KManipSoloArmQPos] [--num-envs 8] [--horizon 8] [--iters 5] [--alphas 1 0.5 0.25] [--fused]
+    python -m gym_kmanip_amd.examples.ilqr_reach [--env KManipSoloArmQPos] [--num-envs 8] [--horizon 8] [--iters 5] [--alphas 1 0.5 0.25] [--fused] [--device-backward]
 
 The goal of env e is its own joint configuration moved by `--reach` radians on every joint (signs alternate); the cost weighs the
 joints' distance to it, the joint velocities and the servo targets' distance from the goal, and leaves the cube alone.  Per
 iteration the device sees three calls whatever the horizon: the nominal rollout, transition_fd over all num_envs x horizon steps as
 rows, and ONE rollout_feedback launch that runs the backward pass's time-varying policy closed loop for every step size at once
 (num_envs x len(alphas) rows sharing num_envs gain trajectories).  With --fused the linearisation is KManipEnvHip.transition_fd, the rows perturbed and differenced inside the kernel, in place of
-derivatives.transition_fd's torch arithmetic around two rollout launches.  The handle itself takes no step.  Printed: the mean cost per
+derivatives.transition_fd's torch arithmetic around two rollout launches; with --device-backward the backward pass is
+KManipEnvHip.lqr_backward, one launch, in place of ilqr.backward_pass's torch loop over the steps.  The handle itself takes no step.  Printed: the mean cost per
 iteration, then the record as JSON."""
 import argparse
 import json
@@ -17,11 +18,12 @@ from gym_kmanip_amd import env_hip, ilqr
 
 
 class _Count:
-    """The env as ilqr sees it -- .cm, .rollout, .transition_fd, .rollout_feedback -- counting the feedback launches and their rows."""
+    """The env as ilqr sees it -- .cm, .rollout, .transition_fd, .lqr_backward, .rollout_feedback -- counting the feedback launches and
+    their rows."""
 
     def __init__(self, env):
         self.env, self.cm, self.rows = env, env.cm, []
-        self.rollout, self.transition_fd = env.rollout, env.transition_fd
+        self.rollout, self.transition_fd, self.lqr_backward = env.rollout, env.transition_fd, env.lqr_backward
 
     def rollout_feedback(self, **kw):
         self.rows.append(int(kw["ctrl"].shape[0]))
@@ -40,6 +42,7 @@ def main(argv=None):
     ap.add_argument("--reach", type=float, default=0.1)
     ap.add_argument("--seed", type=int, default=3)
     ap.add_argument("--fused", action="store_true", help="linearise with KManipEnvHip.transition_fd (kmanip_transition_fd)")
+    ap.add_argument("--device-backward", action="store_true", help="the backward pass in one launch: KManipEnvHip.lqr_backward (kmanip_lqr_backward)")
     args = ap.parse_args(argv)
     env = env_hip.make(args.env, num_envs=args.num_envs, seed=args.seed)
     cm, n, T = env.cm, args.num_envs, args.horizon
@@ -59,13 +62,15 @@ def main(argv=None):
                               torch.full((cm.nu,), 1e-3, dtype=torch.float64, device=dev), 10.0 * wq)
     guess = st["ctrl"][:, None, :].repeat(1, T, 1)
     counted = _Count(env)
-    res = ilqr.ilqr(counted, None, st["qpos"], st["qvel"], st["warm"], guess, cost, iters=args.iters, alphas=args.alphas, fused=args.fused)
+    res = ilqr.ilqr(counted, None, st["qpos"], st["qvel"], st["warm"], guess, cost, iters=args.iters, alphas=args.alphas, fused=args.fused,
+                    device_backward=args.device_backward)
     after = env.state_tensors()
     assert all(torch.equal(st[k], after[k]) for k in st)                                 # the handle was only read
     per_env = res["cost"].cpu()
     for it, c in enumerate(per_env.mean(dim=1).tolist()):
         print("iteration %d: mean cost %.6f" % (it, c))
-    out = {"env": args.env, "num_envs": n, "horizon": T, "alphas": list(args.alphas), "fused": bool(args.fused), "cost": per_env.mean(dim=1).tolist(),
+    out = {"env": args.env, "num_envs": n, "horizon": T, "alphas": list(args.alphas), "fused": bool(args.fused), "device_backward": bool(args.device_backward),
+           "backward_failures": int(res["backward_status"].ne(0).sum()) if args.device_backward else 0, "cost": per_env.mean(dim=1).tolist(),
            "cost_per_env": per_env.tolist(), "accepted": res["accepted"].cpu().tolist(), "feedback_launches": len(counted.rows),
            "rows_per_line_search": counted.rows[0] if counted.rows else 0, "first_ctrl_moved_by": float((res["ctrl"][:, 0] - st["ctrl"]).abs().max())}
     print(json.dumps(out))

@@ -28,7 +28,9 @@ def trajectory_fd(env, envs, qpos0, qvel0, warm0, ctrl, qfrc_applied=None, nsub=
       warm [n, T, nv]                                 the warm start of every step
       status [n] uint8                                the nominal rollout's; status_fd [n]: the largest over the row's steps
     fused=True: the linearisation is env.transition_fd (kmanip_transition_fd: the rows perturbed and differenced inside the kernel,
-    DESIGN.md section 31) in place of derivatives.transition_fd over env.rollout; the same rows, the same arithmetic per row."""
+    DESIGN.md section 31) in place of derivatives.transition_fd over env.rollout; the same rows, the same arithmetic per row.  Where
+    that call returns its buffer, the dict also has deriv_t [n, T, 2 nv + nu, 2 nv], a view of it: what A and B are transposed views
+    of, and what env.lqr_backward reads without a copy."""
     import torch
     cm = env.cm
     n, T = int(ctrl.shape[0]), int(ctrl.shape[1])
@@ -42,9 +44,12 @@ def trajectory_fd(env, envs, qpos0, qvel0, warm0, ctrl, qfrc_applied=None, nsub=
     d = linearise(envs=idx.repeat_interleave(T), qpos=flat(qs), qvel=flat(vs), ctrl=flat(ctrl), warm=flat(ws),
                   qfrc_applied=None if qfrc_applied is None else qfrc_applied.repeat_interleave(T, dim=0), nsub=nsub, eps=eps)
     nx = 2 * cm.nv
-    return {"A": d["A"].reshape(n, T, nx, nx), "B": d["B"].reshape(n, T, nx, cm.nu),
-            "qpos": torch.cat([qpos0[:, None], roll["qpos"]], dim=1), "qvel": torch.cat([qvel0[:, None], roll["qvel"]], dim=1), "warm": ws,
-            "status": roll["status"], "status_fd": torch.maximum(d["status"], d["status_fd"]).reshape(n, T).max(dim=1).values}
+    out = {"A": d["A"].reshape(n, T, nx, nx), "B": d["B"].reshape(n, T, nx, cm.nu),
+           "qpos": torch.cat([qpos0[:, None], roll["qpos"]], dim=1), "qvel": torch.cat([qvel0[:, None], roll["qvel"]], dim=1), "warm": ws,
+           "status": roll["status"], "status_fd": torch.maximum(d["status"], d["status_fd"]).reshape(n, T).max(dim=1).values}
+    if fused and "deriv_t" in d:
+        out["deriv_t"] = d["deriv_t"].reshape(n, T, nx + cm.nu, nx)
+    return out
 
 
 class QuadraticCost:
@@ -124,12 +129,13 @@ def backward_pass(A, B, lx, lu, lxx, luu, reg=0.0):
     return k, K, dV
 
 
-def forward_pass(env, envs, qpos0, qvel0, warm0, ctrl, k, K, qpos_ref, qvel_ref, cost, alphas, qfrc_applied=None, nsub=None):
+def forward_pass(env, envs, qpos0, qvel0, warm0, ctrl, k, K, qpos_ref, qvel_ref, cost, alphas, qfrc_applied=None, nsub=None, K_t=None):
     """The line search in ONE rollout_feedback launch of n len(alphas) rows: row a n + e starts at env e's initial state, carries the
     open-loop term ctrl[e] + alphas[a] k[e] and follows gain trajectory e (gain_index), i.e. K[e] about the nominal states
     qpos_ref / qvel_ref [n, T, ..] before each step.  Returns a dict: cost [len(alphas), n] (inf where the row stopped early),
     best [n] the index of the cheapest alpha per env, best_cost [n], ctrl [n, T, nu] the controls the best row applied, rows: the
-    launch's result."""
+    launch's result.  K_t [n, T, 2 nv, nu]: the gains transposed (env.lqr_backward's gains_t), handed to the launch as they are in
+    place of K, which then is not read."""
     import torch
     n, T, nu = ctrl.shape
     dev = ctrl.device
@@ -138,7 +144,8 @@ def forward_pass(env, envs, qpos0, qvel0, warm0, ctrl, k, K, qpos_ref, qvel_ref,
     idx = torch.arange(n, dtype=torch.int32, device=dev) if envs is None else torch.as_tensor(envs).to(device=dev, dtype=torch.int32)
     open_loop = (ctrl[None] + al[:, None, None, None] * k[None]).reshape(na * n, T, nu).contiguous()
     rows = env.rollout_feedback(envs=idx.repeat(na), qpos=qpos0.repeat(na, 1), qvel=qvel0.repeat(na, 1), warm=warm0.repeat(na, 1),
-                                ctrl=open_loop, qfrc_applied=None if qfrc_applied is None else qfrc_applied.repeat(na, 1), gains=K,
+                                ctrl=open_loop, qfrc_applied=None if qfrc_applied is None else qfrc_applied.repeat(na, 1),
+                                **(dict(gains=K) if K_t is None else dict(gains_t=K_t)),
                                 qpos_ref=qpos_ref.contiguous(), qvel_ref=qvel_ref.contiguous(),
                                 gain_index=torch.arange(n, dtype=torch.int32, device=dev).repeat(na), nsub=nsub,
                                 fields=("qpos", "qvel", "ctrl", "status"))
@@ -152,28 +159,45 @@ def forward_pass(env, envs, qpos0, qvel0, warm0, ctrl, k, K, qpos_ref, qvel_ref,
 
 
 def ilqr(env, envs, qpos0, qvel0, warm0, ctrl, cost, iters=10, alphas=(1.0, 0.5, 0.25), reg=1e-6, reg_factor=10.0, qfrc_applied=None,
-         nsub=None, eps=1e-6, fused=False):
+         nsub=None, eps=1e-6, fused=False, device_backward=False):
     """iLQR from the initial rows (qpos0, qvel0, warm0) [n, ..] and the control guess ctrl [n, T, nu]: per iteration trajectory_fd,
     cost.derivatives, backward_pass and forward_pass.  An env accepts the cheapest of its line-search rows if it is cheaper than its
     nominal trajectory, and divides its regularisation by reg_factor; otherwise it keeps its controls and multiplies it.  Returns a
     dict: ctrl [n, T, nu]; cost [iters + 1, n], the accepted cost after every iteration (entry 0: the guess's), never increasing;
-    accepted [iters, n] bool; k, K of the last backward pass; reg [n].  fused: trajectory_fd's."""
+    accepted [iters, n] bool; k, K of the last backward pass; reg [n].  fused: trajectory_fd's.
+    device_backward: the backward pass is env.lqr_backward (kmanip_lqr_backward, one launch) on deriv_t where
+    fused gives it, else on A and B, and the line search takes its transposed gains as they are.  It factorises Quu + reg I by
+    Cholesky: an env whose factorisation fails (status != 0; its k and K are zeros) counts as not accepted -- it keeps its controls and
+    its reg is multiplied by reg_factor.  The dict then also has backward_status [iters, n] uint8."""
     import torch
     n = int(ctrl.shape[0])
     ctrl = ctrl.clone()
     reg = torch.full((n,), float(reg), dtype=ctrl.dtype, device=ctrl.device)
     history, accepted = [], []
     k = K = None
+    statuses = []
     for _ in range(iters):
         fd = trajectory_fd(env, envs, qpos0, qvel0, warm0, ctrl, qfrc_applied=qfrc_applied, nsub=nsub, eps=eps, fused=fused)
         if not history:
             history.append(cost.total(fd["qpos"], fd["qvel"], ctrl))
-        k, K, _ = backward_pass(fd["A"], fd["B"], *cost.derivatives(fd["qpos"], fd["qvel"], ctrl), reg=reg)
+        K_t = solved = None
+        if device_backward:
+            dyn = dict(deriv_t=fd["deriv_t"]) if "deriv_t" in fd else dict(A=fd["A"], B=fd["B"])
+            bp = env.lqr_backward(*cost.derivatives(fd["qpos"], fd["qvel"], ctrl), reg=reg, **dyn)
+            k, K, K_t, solved = bp["k"], bp["K"], bp["gains_t"], bp["status"] == 0
+            statuses.append(bp["status"])
+        else:
+            k, K, _ = backward_pass(fd["A"], fd["B"], *cost.derivatives(fd["qpos"], fd["qvel"], ctrl), reg=reg)
         fp = forward_pass(env, envs, qpos0, qvel0, warm0, ctrl, k, K, fd["qpos"][:, :-1], fd["qvel"][:, :-1], cost, alphas,
-                          qfrc_applied=qfrc_applied, nsub=nsub)
+                          qfrc_applied=qfrc_applied, nsub=nsub, K_t=K_t)
         ok = fp["best_cost"] < history[-1]
+        if solved is not None:
+            ok = ok & solved
         ctrl = torch.where(ok[:, None, None], fp["ctrl"], ctrl)
         reg = torch.where(ok, reg / reg_factor, reg * reg_factor)
         history.append(torch.where(ok, fp["best_cost"], history[-1]))
         accepted.append(ok)
-    return {"ctrl": ctrl, "cost": torch.stack(history), "accepted": torch.stack(accepted), "k": k, "K": K, "reg": reg}
+    res = {"ctrl": ctrl, "cost": torch.stack(history), "accepted": torch.stack(accepted), "k": k, "K": K, "reg": reg}
+    if device_backward:
+        res["backward_status"] = torch.stack(statuses)
+    return res
