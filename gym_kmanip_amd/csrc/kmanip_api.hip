@@ -639,6 +639,24 @@ int kmanip_lqr_backward(KHandle h, const KLqrIn* in, int n, int T, const KLqrDev
   return 0;
 }
 
+// One helper of the kernels' math headers over n rows (include/kmanip_debug.h; kmanip_mathprobe.hip).  One
+// launch; the handle gives the device and is only read.
+int kmanip_dbg_math(KHandle h, int fn, int n, const double* in_dev, int in_cols, double* out_dev, int out_cols, void* stream) {
+  if (!h) { g_create_error = "kmanip_dbg_math: null handle"; return -1; }
+  int ic = 0, oc = 0;
+  if (!kmanip_math_probe_cols(fn, &ic, &oc)) { h->err = "kmanip_dbg_math: no such function"; return -1; }
+  if (in_cols != ic) { h->err = "kmanip_dbg_math: in_cols is not the function's argument count"; return -1; }
+  if (out_cols != oc) { h->err = "kmanip_dbg_math: out_cols is not the function's result count"; return -1; }
+  if (n < 0) { h->err = "kmanip_dbg_math: n is negative"; return -1; }
+  if (n == 0) return 0;
+  if (!in_dev) { h->err = "kmanip_dbg_math: in_dev is NULL"; return -1; }
+  if (!out_dev) { h->err = "kmanip_dbg_math: out_dev is NULL"; return -1; }
+  KM_ENTER(h);
+  kmanip_launch_math_probe(fn, n, in_dev, out_dev, (hipStream_t)stream);
+  HIPCHK(h, hipGetLastError());
+  return 0;
+}
+
 // the render launchers' visual inputs for a render of source `src` (-1 live state, 0 / 1 a snapshot): in ranges mode the draw
 // uses the episode counters of that source (a snapshot taken before ranges mode was on has none: the live ones)
 static KVisArgs vis_args(KHandle h, int src) {

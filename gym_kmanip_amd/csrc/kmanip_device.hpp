@@ -600,6 +600,9 @@ void kmanip_launch_transfd(const KDeviceModel* dm, const KModelDesc& hd, const K
 // kmanip_lqr_backward (kmanip_lqr.hip): n > 0 problems of T > 0 steps, in.a_stride / in.b_stride resolved (never 0); the size class
 // (nx, nu) is the handle's link-count class
 void kmanip_launch_lqr_backward(const KModelDesc& hd, const KLqrIn& in, int n, int T, const KLqrDev& out, hipStream_t stream);
+// kmanip_dbg_math (kmanip_mathprobe.hip): the columns of function fn (false: no such function), and its launch over n > 0 rows
+bool kmanip_math_probe_cols(int fn, int* in_cols, int* out_cols);
+void kmanip_launch_math_probe(int fn, int n, const double* in, double* out, hipStream_t stream);
 // The render launchers' visual inputs (kmanip_set_visual_params / _ranges), a kernel argument of the VIS
 // kernels only -- never a KDeviceState field: the step kernels' argument stays as it is.  All NULL: the default kernels.
 //   vp       explicit values double[KM_VP_N][N], read at the render's launch

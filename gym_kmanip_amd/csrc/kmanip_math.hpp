@@ -1,12 +1,25 @@
 // kmanip_math.hpp -- lean double-precision elementary functions for the kernels' bounded arguments (gfx950).
 // The ROCm device library's sincos / atan2 / sqrt carry large-argument (Payne-Hanek) paths, inf / nan / signed-zero handling and
 // IEEE-correct rounding sequences: 150-270 instructions per call, 10 % of k_step's dynamic instructions in round 2.  Joint angles,
-// Euler angles and unit-quaternion components need none of that: these versions are branch-free, 30-45 instructions, and accurate
-// to <= 2 ulp on their stated domains (tools/libm_check.hip compares them with the device library on the GPU).
+// Euler angles and unit-quaternion components need none of that: these versions are branch-free, 30-45 instructions.
+//
+// CONTRACT, as measured against a 50-digit reference on tests/golden/math_edges.npz (tests/test_math_gpu.py on the device,
+// tests/test_math_cpu.py on a host twin of this file; the bars are tools/libm_check.hip's exit criteria; DESIGN.md section 38 has the
+// call sites' argument ranges).  An ulp is the spacing of the doubles at the true value; "abs" is in units of 2^-53.
+//   km_sincos  |x| <= 2^17.  |x| <= pi/4 (reduction index 0): relative, < 4 ulp (measured 0.57 / 0.66 sin / cos; subnormal x exact).
+//              Elsewhere ABSOLUTE, < 4 abs (measured 0.90 / 0.92): the two-term reduction keeps no relative accuracy next to a zero
+//              of the function (1781 ulp at x = -92133.487751827866, an error of 3.3e-27).  sin(-0.0) is +0.0, not -0.0.
+//              Beyond 4e9 the quadrant is lost ((int)k leaves its range): a unit (sin, cos) pair of the wrong angle.
+//   km_atan2   max(|y|, |x|) in [1e-300, 1e300], or both zero (-> 0).  Relative, < 4 ulp (measured 2.19; 2.74 in a host emulation over larger random
+//              samples); (-pi, pi]: y = -0.0 counts as +0.0.  Both magnitudes below 1e-300: the fmax clamp makes the result ~ min / 1e-300,
+//              not the angle; above ~9e307 mn + mx overflows and the result is NaN.
+//   km_sqrt    0 or 2.3e-308 <= x < inf.  Relative, < 2 ulp (measured 0.50; perfect squares exact); 0, -0.0 and negative x give 0.
+//              Subnormal x: off by up to 25 %; +inf: NaN (below).
+//   km_rcp     2^-300 <= |x| <= 2^300 measured.  Relative, < 2 ulp (measured 0.50).
 #pragma once
 #include <hip/hip_runtime.h>
 
-// sin(x), cos(x) for |x| <~ 1e5 (joint and Euler angles are within a few pi): Cody-Waite reduction by pi/2 with two FMA steps
+// sin(x), cos(x) for |x| <= 2^17 (joint and Euler angles are within a few pi): Cody-Waite reduction by pi/2 with two FMA steps
 // (the product k * pi/2_hi is never rounded by itself), fdlibm's __kernel_sin / __kernel_cos polynomials on |r| <= pi/4, then the
 // quadrant swap / signs as selects.
 __device__ __forceinline__ void km_sincos(double x, double* sn, double* cs) {
@@ -54,7 +67,7 @@ __device__ __forceinline__ double km_sqrt(double x) {
   return x > 0 ? s : 0.0;
 }
 
-// atan2(y, x) in (-pi, pi], finite arguments, (0, 0) -> 0: a = min / max of the magnitudes, one division after folding the
+// atan2(y, x) in (-pi, pi], the larger magnitude in [1e-300, 1e300], (0, 0) -> 0: a = min / max of the magnitudes, one division after folding the
 // reduction atan(a) = pi/4 + atan((a - 1) / (a + 1)) for a > tan(pi/8) into its numerator and denominator, a degree-11 polynomial
 // in t^2 (Chebyshev-node fit computed with 60-digit arithmetic: 2e-19 relative on |t| <= tan(pi/8)), octant fix-ups as selects.
 __device__ __forceinline__ double km_atan2(double y, double x) {

@@ -1251,6 +1251,19 @@ class KManipEnvHip:
         self._check(self.L.kmanip_ik_eval(self.h, arm, n, p(qpos), p(gp), p(gq), p(res), p(jac)), "kmanip_ik_eval")
         return res, jac
 
+    def dbg_math(self, fn, rows):
+        """Diagnostic (include/kmanip_debug.h kmanip_dbg_math): the helper `fn` of the kernels' math headers (a key of lib.MATH_FNS)
+        on every row of `rows`, a contiguous float64 device tensor [n, arguments].  Returns the device tensor [n, results]; one launch
+        on the current stream, no synchronisation; the handle is only read."""
+        torch = _torch()
+        code, ic, oc = _libmod.MATH_FNS[fn]
+        n = int(rows.shape[0])
+        self._check_buf(rows, (n, ic), torch.float64, "dbg_math rows")
+        out = torch.empty((n, oc), dtype=torch.float64, device=self.device)
+        self._check(self.L.kmanip_dbg_math(self.h, code, n, C.c_void_p(rows.data_ptr()), ic, C.c_void_p(out.data_ptr()), oc, self._stream()),
+                    "kmanip_dbg_math")
+        return out
+
     def enable_timing(self, on=True):
         """on = True / 1: events around every step; an int k > 1: around every k-th step (the sampled average; an event pair costs
         the stream about 5 us); False / 0: off."""

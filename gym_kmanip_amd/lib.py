@@ -26,7 +26,12 @@ EXPORTS = [
 
 
 # include/kmanip_debug.h: diagnostics, not part of the boundary (product build; the -DKM_PROFILE build adds kmanip_dbg_prof*)
-DEBUG_EXPORTS = ["kmanip_dbg_wave_clocks"]
+DEBUG_EXPORTS = ["kmanip_dbg_wave_clocks", "kmanip_dbg_math"]
+
+# include/kmanip_debug.h KM_MATH_*: name -> (fn, arguments per row, results per row) of kmanip_dbg_math
+MATH_FNS = {"km_sincos": (0, 1, 2), "km_atan2": (1, 2, 1), "km_sqrt": (2, 1, 1), "km_rcp": (3, 1, 1), "frcp": (4, 1, 1), "rsqrt_nr": (5, 1, 1),
+            "normalize3_fast": (6, 3, 4), "normalize4_fast": (7, 4, 4), "axis_angle2quat": (8, 4, 4), "mat2quat": (9, 9, 4),
+            "sub_quat": (10, 8, 3), "sub_quat_sc": (11, 8, 5), "quat_log_diff": (12, 8, 3)}
 
 
 class KManipError(RuntimeError):
@@ -222,6 +227,7 @@ def load():
     lib.kmanip_destroy.argtypes = [vp]
     lib.kmanip_destroy.restype = None
     lib.kmanip_dbg_wave_clocks.argtypes = [vp, C.POINTER(C.c_ulonglong), i32p, i32p]
+    lib.kmanip_dbg_math.argtypes = [vp, C.c_int, C.c_int, vp, C.c_int, vp, C.c_int, vp]
     if lib.kmanip_model_desc_size() != C.sizeof(KModelDesc):
         raise KManipError("KModelDesc layout mismatch: lib %d vs python %d"
                           % (lib.kmanip_model_desc_size(), C.sizeof(KModelDesc)))

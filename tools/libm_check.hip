@@ -1,5 +1,7 @@
 // tools/libm_check.hip -- accuracy of kmanip_math.hpp against the ROCm device library, on the GPU.
 //   hipcc -O3 --offload-arch=gfx950 tools/libm_check.hip -o tools/_build/libm_check && tools/_build/libm_check
+// (a hand tool: random samples against the device library.  The suite's check is tests/test_math_gpu.py and tests/test_math_cpu.py: the
+// same functions through kmanip_dbg_math against a 50-digit reference at their edges)
 #include "../gym_kmanip_amd/csrc/kmanip_math.hpp"
 #include <cmath>
 #include <cstdio>

@@ -1,6 +1,8 @@
 // Accuracy of the hardware estimates v_rsq_f64 / v_rcp_f64 on gfx950 and of one / two Newton steps on top of them (rsqrt_nr, frcp in
 // kmanip_device.hpp use two): max relative error over 2^24 samples spread over 40 binades, against host long double.
 // hipcc -O3 --offload-arch=gfx950 -o tools/_build/rsq_check tools/rsq_check.hip && tools/_build/rsq_check
+// (a hand tool.  The suite's check of rsqrt_nr / frcp / km_sqrt / km_rcp is tests/test_math_gpu.py: binades 2^-300 .. 2^300, powers of two
+// +-1 ulp and perfect squares through kmanip_dbg_math against a 50-digit reference)
 #include <hip/hip_runtime.h>
 #include <cmath>
 #include <cstdio>
