@@ -572,6 +572,26 @@ int kmanip_feedback(KHandle h, const KFeedbackIn* in, int n, int nstep, int nsub
   return 0;
 }
 
+// kmanip_feedback with the policy's output clamped to a box (include/kmanip.h KFeedbackBoxIn; kmanip_rollout.hip built with KM_VAR_FB=2,
+// the kmanip_boxfb_* objects).  One launch; the handle is only read; the handle's solver.
+int kmanip_feedback_box(KHandle h, const KFeedbackBoxIn* in, int n, int nstep, int nsub, const KFeedbackDev* out, void* stream) {
+  if (!h) { g_create_error = "kmanip_feedback_box: null handle"; return -1; }
+  if (stepped_args(h, "kmanip_feedback_box", "KFeedbackBoxIn", "KFeedbackDev", in, out, n, nstep, nsub)) return -1;
+  if (!in->qpos_ref) { h->err = "kmanip_feedback_box: KFeedbackBoxIn::qpos_ref is NULL"; return -1; }
+  if (!in->qvel_ref) { h->err = "kmanip_feedback_box: KFeedbackBoxIn::qvel_ref is NULL"; return -1; }
+  if (!in->gain_t) { h->err = "kmanip_feedback_box: KFeedbackBoxIn::gain_t is NULL"; return -1; }
+  if (!in->lo) { h->err = "kmanip_feedback_box: KFeedbackBoxIn::lo is NULL"; return -1; }
+  if (!in->hi) { h->err = "kmanip_feedback_box: KFeedbackBoxIn::hi is NULL"; return -1; }
+  if (in->ng <= 0) { h->err = "kmanip_feedback_box: ng is not positive"; return -1; }
+  if (!in->gain_index && in->ng < n) { h->err = "kmanip_feedback_box: more rows than gain trajectories need KFeedbackBoxIn::gain_index"; return -1; }
+  if (n == 0 || nstep == 0) return 0;
+  if (!out->qpos && !out->qvel && !out->qacc_warm && !out->contact_mask && !out->reward && !out->status && !out->steps_done && !out->ctrl) return 0;
+  KM_ENTER(h);
+  kmanip_launch_boxfb(h->dmodel, h->desc, h->st, *in, n, nstep, nsub ? nsub : h->desc.n_sub_steps, *out, (hipStream_t)stream);
+  HIPCHK(h, hipGetLastError());
+  return 0;
+}
+
 // MuJoCo's mjd_transitionFD at rows the caller passes (include/kmanip.h KTransFdIn / KTransFdDev; kmanip_transfd.hip; DESIGN.md section
 // 31).  Two launches ordered by the stream: the nominal rows through kmanip_rollout's kernel, then the column pairs, which read the
 // nominal qacc_warm the first wrote.  The handle is only read; the handle's solver.
@@ -635,6 +655,40 @@ int kmanip_lqr_backward(KHandle h, const KLqrIn* in, int n, int T, const KLqrDev
   if (!li.b_stride) li.b_stride = nu * nx;
   KM_ENTER(h);
   kmanip_launch_lqr_backward(h->desc, li, n, T, *out, (hipStream_t)stream);
+  HIPCHK(h, hipGetLastError());
+  return 0;
+}
+
+// The backward pass of control-limited DDP for n problems of T steps (include/kmanip.h KLqrBoxIn / KLqrBoxDev; kmanip_lqr_box.hip;
+// DESIGN.md section 39).  One launch; the handle gives the device and the size class and is only read.
+int kmanip_lqr_backward_box(KHandle h, const KLqrBoxIn* in, int n, int T, const KLqrBoxDev* out, void* stream) {
+  if (!h) { g_create_error = "kmanip_lqr_backward_box: null handle"; return -1; }
+  if (!in) { h->err = "kmanip_lqr_backward_box: the KLqrBoxIn pointer is NULL"; return -1; }
+  if (!out) { h->err = "kmanip_lqr_backward_box: the KLqrBoxDev pointer is NULL"; return -1; }
+  if (n < 0) { h->err = "kmanip_lqr_backward_box: n is negative"; return -1; }
+  if (T < 0) { h->err = "kmanip_lqr_backward_box: T is negative"; return -1; }
+  if (n == 0 || T == 0) return 0;      // (tensors of no problems or no steps have no address: nothing below is asked of them)
+  const KLqrIn& l = in->lqr;
+  if (!l.a_t) { h->err = "kmanip_lqr_backward_box: KLqrIn::a_t is NULL"; return -1; }
+  if (!l.b_t) { h->err = "kmanip_lqr_backward_box: KLqrIn::b_t is NULL"; return -1; }
+  if (!l.lx) { h->err = "kmanip_lqr_backward_box: KLqrIn::lx is NULL"; return -1; }
+  if (!l.lu) { h->err = "kmanip_lqr_backward_box: KLqrIn::lu is NULL"; return -1; }
+  if (!l.lxx) { h->err = "kmanip_lqr_backward_box: KLqrIn::lxx is NULL"; return -1; }
+  if (!l.luu) { h->err = "kmanip_lqr_backward_box: KLqrIn::luu is NULL"; return -1; }
+  if (!in->u) { h->err = "kmanip_lqr_backward_box: KLqrBoxIn::u is NULL"; return -1; }
+  if (!in->lo) { h->err = "kmanip_lqr_backward_box: KLqrBoxIn::lo is NULL"; return -1; }
+  if (!in->hi) { h->err = "kmanip_lqr_backward_box: KLqrBoxIn::hi is NULL"; return -1; }
+  const int64_t nx = h->desc.nlink <= 10 ? 32 : 52, nu = h->desc.nlink <= 10 ? 10 : 20;      // (kmanip_lqr_box.hip's two classes)
+  if (l.a_stride != 0 && l.a_stride < nx * nx) { h->err = "kmanip_lqr_backward_box: a_stride is smaller than an [nx, nx] block"; return -1; }
+  if (l.b_stride != 0 && l.b_stride < nu * nx) { h->err = "kmanip_lqr_backward_box: b_stride is smaller than an [nu, nx] block"; return -1; }
+  if ((long long)n * T > 2147483647LL) { h->err = "kmanip_lqr_backward_box: n * T steps are more than an int counts"; return -1; }
+  const KLqrDev& o = out->lqr;
+  if (!o.k && !o.gain_t && !o.dv && !o.status && !o.fail_step && !out->clamped && !out->qp_iters) return 0;
+  KLqrBoxIn li = *in;
+  if (!li.lqr.a_stride) li.lqr.a_stride = nx * nx;
+  if (!li.lqr.b_stride) li.lqr.b_stride = nu * nx;
+  KM_ENTER(h);
+  kmanip_launch_lqr_backward_box(h->desc, li, n, T, *out, (hipStream_t)stream);
   HIPCHK(h, hipGetLastError());
   return 0;
 }

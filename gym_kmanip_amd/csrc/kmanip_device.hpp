@@ -593,6 +593,9 @@ void kmanip_launch_rollout(const KDeviceModel* dm, const KModelDesc& hd, const K
 // kmanip_feedback: kmanip_launch_rollout's arguments and choice of build
 void kmanip_launch_feedback(const KDeviceModel* dm, const KModelDesc& hd, const KDeviceState& st, const KFeedbackIn& in, int n, int nstep,
                             int nsub, const KFeedbackDev& out, hipStream_t stream);
+// kmanip_feedback_box (kmanip_rollout.hip built with KM_VAR_FB=2): kmanip_launch_feedback's arguments and choice of build
+void kmanip_launch_boxfb(const KDeviceModel* dm, const KModelDesc& hd, const KDeviceState& st, const KFeedbackBoxIn& in, int n, int nstep,
+                         int nsub, const KFeedbackDev& out, hipStream_t stream);
 // kmanip_transition_fd's second launch (either solver: the handle's): the n * ncol > 0 column pairs of n rows, nsub > 0 sub-steps, ch /
 // sh = cos / sin of eps / 2; the applied-force build also while in.wrt has KM_WRT_FRC
 void kmanip_launch_transfd(const KDeviceModel* dm, const KModelDesc& hd, const KDeviceState& st, const KTransFdIn& in, int n, int ncol,
@@ -600,6 +603,8 @@ void kmanip_launch_transfd(const KDeviceModel* dm, const KModelDesc& hd, const K
 // kmanip_lqr_backward (kmanip_lqr.hip): n > 0 problems of T > 0 steps, in.a_stride / in.b_stride resolved (never 0); the size class
 // (nx, nu) is the handle's link-count class
 void kmanip_launch_lqr_backward(const KModelDesc& hd, const KLqrIn& in, int n, int T, const KLqrDev& out, hipStream_t stream);
+// kmanip_lqr_backward_box (kmanip_lqr_box.hip): likewise
+void kmanip_launch_lqr_backward_box(const KModelDesc& hd, const KLqrBoxIn& in, int n, int T, const KLqrBoxDev& out, hipStream_t stream);
 // kmanip_dbg_math (kmanip_mathprobe.hip): the columns of function fn (false: no such function), and its launch over n > 0 rows
 bool kmanip_math_probe_cols(int fn, int* in_cols, int* out_cols);
 void kmanip_launch_math_probe(int fn, int n, const double* in, double* out, hipStream_t stream);

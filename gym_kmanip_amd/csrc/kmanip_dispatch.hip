@@ -20,6 +20,7 @@ typedef void InverseFn(const KDeviceModel*, const KDeviceState&, const KInverseI
 typedef void ForwardFn(const KDeviceModel*, const KDeviceState&, const KForwardIn&, int, const KForcesDev&, hipStream_t);
 typedef void RolloutFn(const KDeviceModel*, const KDeviceState&, const KRolloutIn&, int, int, int, const KRolloutDev&, hipStream_t);
 typedef void FeedbackFn(const KDeviceModel*, const KDeviceState&, const KFeedbackIn&, int, int, int, const KFeedbackDev&, hipStream_t);
+typedef void BoxFbFn(const KDeviceModel*, const KDeviceState&, const KFeedbackBoxIn&, int, int, int, const KFeedbackDev&, hipStream_t);
 typedef void TransFdFn(const KDeviceModel*, const KDeviceState&, const KTransFdIn&, int, int, int, double, double, const KTransFdDev&, hipStream_t);
 
 // kmanip_dyn.hip: step per solver in every build, reset per solver in the parameter builds; observe and prepare are
@@ -30,6 +31,8 @@ typedef void TransFdFn(const KDeviceModel*, const KDeviceState&, const KTransFdI
 #define KM_ROLLOUT_ROW(B, NL, G) {KM_NAME(rollout, B, NL, G, _0), KM_NAME(rollout, B, NL, G, _1)},
 // kmanip_rollout.hip built with KM_VAR_FB (the kmanip_feedback_* objects): likewise
 #define KM_FEEDBACK_ROW(B, NL, G) {KM_NAME(feedback, B, NL, G, _0), KM_NAME(feedback, B, NL, G, _1)},
+// kmanip_rollout.hip built with KM_VAR_FB=2 (the kmanip_boxfb_* objects): likewise
+#define KM_BOXFB_ROW(B, NL, G) {KM_NAME(boxfb, B, NL, G, _0), KM_NAME(boxfb, B, NL, G, _1)},
 // kmanip_transfd.hip: likewise
 #define KM_TRANSFD_ROW(B, NL, G) {KM_NAME(transfd, B, NL, G, _0), KM_NAME(transfd, B, NL, G, _1)},
 #define KM_OBSERVE_ROW(B, NL, G) KM_NAME(observe, B, NL, G, _1),
@@ -42,7 +45,7 @@ typedef void TransFdFn(const KDeviceModel*, const KDeviceState&, const KTransFdI
 #define KM_FORWARD_ROW(B, NL, G) KM_NAME(forward, B, NL, G, ),
 
 #define KM_DECL_SOLVERS(Fn, kind, B, NL, G) Fn KM_NAME(kind, B, NL, G, _0), KM_NAME(kind, B, NL, G, _1);
-#define KM_DECL_FRC(B, NL, G) KM_DECL_SOLVERS(StepFn, step, B, NL, G) KM_DECL_SOLVERS(RolloutFn, rollout, B, NL, G) KM_DECL_SOLVERS(FeedbackFn, feedback, B, NL, G) KM_DECL_SOLVERS(TransFdFn, transfd, B, NL, G) ForcesFn KM_NAME(forces, B, NL, G, ); ForwardFn KM_NAME(forward, B, NL, G, );
+#define KM_DECL_FRC(B, NL, G) KM_DECL_SOLVERS(StepFn, step, B, NL, G) KM_DECL_SOLVERS(RolloutFn, rollout, B, NL, G) KM_DECL_SOLVERS(FeedbackFn, feedback, B, NL, G) KM_DECL_SOLVERS(BoxFbFn, boxfb, B, NL, G) KM_DECL_SOLVERS(TransFdFn, transfd, B, NL, G) ForcesFn KM_NAME(forces, B, NL, G, ); ForwardFn KM_NAME(forward, B, NL, G, );
 #define KM_DECL_PAR(B, NL, G) KM_DECL_SOLVERS(ResetFn, reset, B, NL, G) KinFn KM_NAME(kinematics, B, NL, G, ); InverseFn KM_NAME(inverse, B, NL, G, );
 #define KM_DECL_ONCE(B, NL, G) ObserveFn KM_NAME(observe, B, NL, G, _1); PrepareFn KM_NAME(prepare, B, NL, G, _1);
 #define KM_DECL_BUILD_FRC(B) KM_CLASSES(KM_DECL_FRC, B)
@@ -58,6 +61,7 @@ KM_BUILDS(KM_DECL_BUILD_FRC) KM_BUILDS_PAR(KM_DECL_BUILD_PAR) KM_CLASSES(KM_DECL
 #define KM_FORWARD_BUILD(B) {KM_CLASSES(KM_FORWARD_ROW, B)},
 #define KM_ROLLOUT_BUILD(B) {KM_CLASSES(KM_ROLLOUT_ROW, B)},
 #define KM_FEEDBACK_BUILD(B) {KM_CLASSES(KM_FEEDBACK_ROW, B)},
+#define KM_BOXFB_BUILD(B) {KM_CLASSES(KM_BOXFB_ROW, B)},
 #define KM_TRANSFD_BUILD(B) {KM_CLASSES(KM_TRANSFD_ROW, B)},
 static constexpr StepFn* step_tab[4][2][2] = {KM_BUILDS(KM_STEP_BUILD)};
 static constexpr ResetFn* reset_tab[2][2][2] = {KM_BUILDS_PAR(KM_RESET_BUILD)};
@@ -69,6 +73,7 @@ static constexpr InverseFn* inverse_tab[2][2] = {KM_BUILDS_PAR(KM_INVERSE_BUILD)
 static constexpr ForwardFn* forward_tab[4][2] = {KM_BUILDS(KM_FORWARD_BUILD)};
 static constexpr RolloutFn* rollout_tab[4][2][2] = {KM_BUILDS(KM_ROLLOUT_BUILD)};
 static constexpr FeedbackFn* feedback_tab[4][2][2] = {KM_BUILDS(KM_FEEDBACK_BUILD)};
+static constexpr BoxFbFn* boxfb_tab[4][2][2] = {KM_BUILDS(KM_BOXFB_BUILD)};
 static constexpr TransFdFn* transfd_tab[4][2][2] = {KM_BUILDS(KM_TRANSFD_BUILD)};
 
 static int cls(const KModelDesc& hd) { return hd.nlink <= 10 ? 0 : 1; }
@@ -113,6 +118,10 @@ void kmanip_launch_rollout(const KDeviceModel* dm, const KModelDesc& hd, const K
 void kmanip_launch_feedback(const KDeviceModel* dm, const KModelDesc& hd, const KDeviceState& st, const KFeedbackIn& in, int n, int nstep,
                             int nsub, const KFeedbackDev& out, hipStream_t stream) {
   feedback_tab[row_build(st, in)][cls(hd)][newton(hd)](dm, st, in, n, nstep, nsub, out, stream);
+}
+void kmanip_launch_boxfb(const KDeviceModel* dm, const KModelDesc& hd, const KDeviceState& st, const KFeedbackBoxIn& in, int n, int nstep,
+                         int nsub, const KFeedbackDev& out, hipStream_t stream) {
+  boxfb_tab[row_build(st, in)][cls(hd)][newton(hd)](dm, st, in, n, nstep, nsub, out, stream);
 }
 // (the force build also for a differentiated force nobody gave: the kernel then perturbs rows of zeros)
 void kmanip_launch_transfd(const KDeviceModel* dm, const KModelDesc& hd, const KDeviceState& st, const KTransFdIn& in, int n, int ncol,

@@ -1,5 +1,6 @@
 // kmanip_rollout.hip -- rollouts in ctrl space from rows the CALLER passes, as many as it likes, in ONE launch (gfx950, wave64): the
-// source of two kernels, open-loop kmanip_rollout (k_rollout) and, compiled with -DKM_VAR_FB=1, closed-loop kmanip_feedback (k_feedback).
+// source of three kernels, open-loop kmanip_rollout (k_rollout), compiled with -DKM_VAR_FB=1 closed-loop kmanip_feedback (k_feedback)
+// and, with -DKM_VAR_FB=2, kmanip_feedback_box (k_boxfb): k_feedback with the policy's output clamped to a box.
 //
 // MuJoCo's `rollout`: row r names an env (KRolloutIn::env_index; NULL = row r is env r), takes that env's model parameters and, per
 // field, either the caller's row of qpos / qvel / qacc_warm / ctrl / qfrc_applied or what the env stores, and is integrated for nstep
@@ -27,6 +28,11 @@
 // lane requests its 2 nv entries before the tangent difference is computed, and they are dead before the first sub-step starts
 // (the 20-link Newton variant has no room for 52 doubles across the loop).  dx goes through a small LDS array of this unit's own
 // (Ws is every kernel's and stays as it is); the lanes of a group read the same dx_j: a broadcast.
+//
+// KM_VAR_FB=2 is KM_VAR_FB=1 with  u_i = min(max(u_i, lo[b, i]), hi[b, i]),  b = box_per_traj ? g : 0,  after the finite-u test
+// (DESIGN.md section 39): the clamped u acts and is recorded.  The lane's two bounds are requested with its gain column, every step:
+// nothing of the box is kept across the sub-steps.  A box with lo_i <= hi_i false stops the row before its first step, status 1.
+// The clamp statements stand in #if KM_VAR_FB == 2 regions of their own: k_feedback's text after preprocessing is what it was.
 #include "kmanip_ik_coop.hpp"
 #include <stdlib.h>
 #include "kmanip_dyn_variant.hpp"
@@ -37,7 +43,12 @@
 #ifndef KM_VAR_FB
 #define KM_VAR_FB 0
 #endif
-#if KM_VAR_FB
+#if KM_VAR_FB == 2
+typedef KFeedbackBoxIn RollIn;
+typedef KFeedbackDev RollDev;
+#define KM_ROLL_KERNEL k_boxfb
+#define KM_ROLL_LAUNCHER KM_LAUNCHER3(boxfb)
+#elif KM_VAR_FB
 typedef KFeedbackIn RollIn;
 typedef KFeedbackDev RollDev;
 #define KM_ROLL_KERNEL k_feedback
@@ -118,6 +129,11 @@ __global__ __launch_bounds__(64) void KM_KERNEL(KM_ROLL_KERNEL)(const KDeviceMod
   // entry (g, t) of the references and the gain: t = 0 throughout while one gain is held
   const size_t gT = (size_t)g * (in.gain_per_step ? (size_t)nstep : (size_t)1);
 #endif
+#if KM_VAR_FB == 2
+  // this actuator's bounds: an empty box or a NaN bound anywhere in the row's box is status 1, no step
+  const size_t bx = (in.box_per_traj ? (size_t)g : (size_t)0) * NL + ia;
+  if (gor<G>(!(in.lo[bx] <= in.hi[bx]))) { rollout_finish<NL, G>(out, r, sub, nstep, 0, 1); return; }
+#endif
   Prof pf;
   pf.start();
   const bool trail = out.contact_mask || out.reward;       // (kernel arguments: uniform over the launch)
@@ -147,6 +163,9 @@ __global__ __launch_bounds__(64) void KM_KERNEL(KM_ROLL_KERNEL)(const KDeviceMod
       real kg[NX];
 #pragma unroll
       for (int j = 0; j < NX; j++) kg[j] = kcol[(size_t)j * NL];
+#if KM_VAR_FB == 2
+      const real bl = in.lo[bx], bh = in.hi[bx];
+#endif
       const double* qr = in.qpos_ref + gt * NQ;
       real rq[KQ], ra[4], qb[4], rot[3];
 #pragma unroll
@@ -167,7 +186,11 @@ __global__ __launch_bounds__(64) void KM_KERNEL(KM_ROLL_KERNEL)(const KDeviceMod
       const real u = oc + acc;
       // a non-finite u (a non-finite reference or gain entry the row uses, or an overflow): the row stops, t steps recorded
       if (gor<G>(!isfinite(u))) { status = 1; break; }
+#if KM_VAR_FB == 2
+      if (sub < NL) w.ctrl[sub] = fmin(fmax(u, bl), bh);
+#else
       if (sub < NL) w.ctrl[sub] = u;
+#endif
       GSYNC();
     }
 #endif
@@ -248,7 +271,7 @@ static void launch_rollout_t(const KDeviceModel* dm, const KDeviceState& st, con
   hipLaunchKernelGGL((KM_KERNEL(KM_ROLL_KERNEL)<NL, G, SOLVER, EPB>), dim3((n + EPB - 1) / EPB), dim3(64), 0, stream, dm, st, in, n, nstep, nsub, out);
 }
 KM_VARIANT_END
-// ---- one (NL, G, SOLVER[, PAR][, FRC][, FB]) variant per translation unit (the Makefile compiles this file thirty-two times)
+// ---- one (NL, G, SOLVER[, PAR][, FRC][, FB]) variant per translation unit (the Makefile compiles this file forty-eight times)
 void KM_ROLL_LAUNCHER(const KDeviceModel* dm, const KDeviceState& st, const RollIn& in, int n, int nstep, int nsub, const RollDev& out,
                       hipStream_t stream) {
   launch_rollout_t<KM_VAR_NL, KM_VAR_G, KM_VAR_SOLVER>(dm, st, in, n, nstep, nsub, out, stream);

@@ -364,7 +364,8 @@ class KManipEnvHip:
     _FEEDBACK_FIELDS = dict(_ROLLOUT_FIELDS, ctrl=(("nu",), "float64"))
 
     def rollout_feedback(self, envs=None, qpos=None, qvel=None, ctrl=None, warm=None, qfrc_applied=None, gains=None, qpos_ref=None,
-                         qvel_ref=None, gain_index=None, nstep=None, nsub=None, out=None, fields=None, gains_t=None):
+                         qvel_ref=None, gain_index=None, nstep=None, nsub=None, out=None, fields=None, gains_t=None, ctrl_lo=None,
+                         ctrl_hi=None):
         """kmanip_feedback: rollout() with a per-step affine state feedback evaluated on the device, in the same ONE launch -- the
         policy of an iLQR / DDP backward pass, a regulator, or the stabilising feedback under MPPI samples.  At the START of every
         step t, with (q, v) the row's state there,
@@ -379,7 +380,10 @@ class KManipEnvHip:
           gain_index: int32 [n], row r follows trajectory gain_index[r] (repeats allowed); None = row r follows trajectory r.
         Returns rollout()'s dict plus ctrl [n, nstep, nu], the u of every step; status 1 also for a non-finite u (steps_done = the
         step it was computed for), status 2 also for a gain index outside 0 .. ng-1 (never used as an address).  With zero gains
-        the result is rollout()'s, bit for bit."""
+        the result is rollout()'s, bit for bit.
+        ctrl_lo / ctrl_hi [nu], or [ng, nu] a box per gain trajectory (one of them None: that side is unbounded): kmanip_feedback_box,
+        the same launch with u = clip(u, ctrl_lo, ctrl_hi) after the finite-u test -- the clamped u acts and is what `ctrl` records;
+        a row whose box has lo <= hi false somewhere (a NaN bound too) gets status 1 and no step.  Both None: kmanip_feedback."""
         torch = _torch()
         if (gains is None) == (gains_t is None):
             raise _libmod.KManipError("rollout_feedback: give gains or gains_t (one of them)")
@@ -391,7 +395,8 @@ class KManipEnvHip:
             raise _libmod.KManipError("rollout_feedback: gains_t must be a [ng, nstep, 2 nv, nu] or [ng, 2 nv, nu] tensor")
         per_step = gains_t.dim() == 4
         ng = int(gains_t.shape[0])
-        fi = _libmod.KFeedbackIn()
+        boxed = ctrl_lo is not None or ctrl_hi is not None
+        fi = _libmod.KFeedbackBoxIn() if boxed else _libmod.KFeedbackIn()
         n, nstep, nsub, idx = self._stepped_rows("rollout_feedback", envs, qpos, qvel, ctrl, warm, qfrc_applied, nstep, nsub, fi,
                                                  per_step_lengths=(gains_t.shape[1],) if per_step else ())
         lead = (ng, nstep) if per_step else (ng,)
@@ -408,8 +413,31 @@ class KManipEnvHip:
         fd = _libmod.KFeedbackDev()
         out = self._query_out(self._FEEDBACK_FIELDS, (n, nstep), {"nq": self.cm.nq, "nv": self.cm.nv, "nu": self.cm.nu}, out, fields, fd,
                               "rollout_feedback")
+        if boxed:
+            box = self._box("rollout_feedback", ctrl_lo, ctrl_hi, ng)
+            fi.lo, fi.hi, fi.box_per_traj = box[0].data_ptr(), box[1].data_ptr(), int(box[0].dim() == 2)
+            self._check(self.L.kmanip_feedback_box(self.h, C.byref(fi), n, nstep, nsub, C.byref(fd), self._stream()), "kmanip_feedback_box")
+            return out
         self._check(self.L.kmanip_feedback(self.h, C.byref(fi), n, nstep, nsub, C.byref(fd), self._stream()), "kmanip_feedback")
         return out
+
+    def _box(self, what, lo, hi, rows):
+        """(lo, hi) of a control box as checked float64 device tensors, both [nu] or both [rows, nu]; a None side is -inf / +inf."""
+        torch = _torch()
+        nu = self.cm.nu
+        shape = next(tuple(t.shape) for t in (lo, hi) if isinstance(t, torch.Tensor)) if any(isinstance(t, torch.Tensor) for t in (lo, hi)) else (nu,)
+        if shape not in ((nu,), (rows, nu)):
+            raise _libmod.KManipError("%s: the box must be [nu] or [%d, nu] tensors, got %s" % (what, rows, shape))
+        res = []
+        for name, t, fill in (("lo", lo, float("-inf")), ("hi", hi, float("inf"))):
+            if t is None:
+                t = torch.full(shape, fill, dtype=torch.float64, device=self.device)
+            elif not isinstance(t, torch.Tensor):
+                t = torch.as_tensor(t, dtype=torch.float64, device=self.device)
+            t = t.contiguous()
+            self._check_buf(t, shape, torch.float64, "%s: %s" % (what, name))
+            res.append(t)
+        return tuple(res)
 
     # KTransFdDev field -> (trailing shape in terms of nq / nv / ncol / nx = 2 nv, dtype name)
     _TRANSFD_FIELDS = {"qpos": (("nq",), "float64"), "qvel": (("nv",), "float64"), "qacc_warm": (("nv",), "float64"),
@@ -507,26 +535,16 @@ class KManipEnvHip:
     _LQR_FIELDS = {"k": (("T", "nu"), "float64"), "gain_t": (("T", "nx", "nu"), "float64"), "dv": ((2,), "float64"),
                    "status": (None, "uint8"), "fail_step": (None, "int32")}
 
-    def lqr_backward(self, lx, lu, lxx, luu, A=None, B=None, deriv_t=None, reg=0.0, out=None):
-        """kmanip_lqr_backward: ilqr.backward_pass -- the Riccati recursion of iLQR -- for n problems of T steps in ONE launch on the
-        current stream, a workgroup per problem with the loop over the steps inside the kernel (no synchronisation; the handle gives
-        the device and the sizes nx = 2 nv, nu, and is only read; n has nothing to do with num_envs).
-          deriv_t [n, T, nx + nu, nx]: transition_fd's buffer over the n T rows e T + t with the default wrt, read where it lies (no
-            copy), or A [n, T, nx, nx] and B [n, T, nx, nu], which get one transposed contiguous copy each.
-          lx [n, T + 1, nx], lu [n, T, nu]; lxx [n, T + 1, nx, nx] or [T + 1, nx, nx] shared by the problems, luu [n, T, nu, nu] or
-            [T, nu, nu]; entry T of lx / lxx is the final cost's.  reg: a number or [n], added to the diagonal of Quu for the solve.
-        Returns a dict: k [n, T, nu]; gains_t [n, T, nx, nu], what rollout_feedback(gains_t=...) takes; K [n, T, nu, nx], its
-        transposed view; dV [n, 2]; status [n] uint8 and fail_step [n] int32 -- 0 and -1, or 1 and the step at which Quu + reg I
-        had a Cholesky pivot that was not positive and finite: that problem's k, gains_t and dV are then zeros, all steps.
-        `out`: a dict of tensors to fill, keyed by the kernel's outputs (k, gain_t, dv, status, fail_step); the others are allocated."""
+    def _lqr_in(self, what, li, lx, lu, lxx, luu, A, B, deriv_t, reg):
+        """The checked inputs of lqr_backward() / lqr_backward_box() set in the KLqrIn `li`.  Returns (n, T, the tensors the caller
+        holds until the launch)."""
         torch = _torch()
         nx, nu, f64 = 2 * self.cm.nv, self.cm.nu, torch.float64
         if not isinstance(lu, torch.Tensor) or lu.dim() != 3:
-            raise _libmod.KManipError("lqr_backward: lu must be a [n, T, nu] tensor")
+            raise _libmod.KManipError("%s: lu must be a [n, T, nu] tensor" % what)
         n, T = int(lu.shape[0]), int(lu.shape[1])
-        li = _libmod.KLqrIn()
         if (deriv_t is None) == (A is None and B is None) or (A is None) != (B is None):
-            raise _libmod.KManipError("lqr_backward: give deriv_t, or A and B")
+            raise _libmod.KManipError("%s: give deriv_t, or A and B" % what)
         if deriv_t is not None:
             self._check_buf(deriv_t, (n, T, nx + nu, nx), f64, "deriv_t")
             li.a_t, li.b_t = deriv_t.data_ptr(), deriv_t.data_ptr() + 8 * nx * nx
@@ -535,7 +553,7 @@ class KManipEnvHip:
         else:
             for name, t, shape in (("A", A, (n, T, nx, nx)), ("B", B, (n, T, nx, nu))):
                 if not isinstance(t, torch.Tensor) or tuple(t.shape) != shape:
-                    raise _libmod.KManipError("lqr_backward: %s must be a tensor of shape %s" % (name, shape))
+                    raise _libmod.KManipError("%s: %s must be a tensor of shape %s" % (what, name, shape))
             a_t, b_t = A.transpose(2, 3).contiguous(), B.transpose(2, 3).contiguous()
             self._check_buf(a_t, (n, T, nx, nx), f64, "A")
             self._check_buf(b_t, (n, T, nu, nx), f64, "B")
@@ -562,6 +580,65 @@ class KManipEnvHip:
             self._check_buf(reg, (n,), f64, "reg")
             li.reg = reg.data_ptr()
             keep += (reg,)
+        return n, T, keep
+
+    _LQR_BOX_FIELDS = dict(_LQR_FIELDS, clamped=(("T",), "int32"), qp_iters=(("T",), "int32"))
+
+    def lqr_backward_box(self, lx, lu, lxx, luu, u, lo, hi, A=None, B=None, deriv_t=None, reg=0.0, out=None):
+        """kmanip_lqr_backward_box: ilqr.backward_pass_box -- the backward pass of control-limited DDP -- for n problems of T steps in
+        ONE launch: lqr_backward() with the box lo <= u + du <= hi on the controls, a projected-Newton box QP per step inside the
+        kernel (include/kmanip.h KLqrBoxIn states the iteration and its scale-free termination rule).  lqr_backward()'s arguments,
+        and u [n, T, nu] the nominal controls; lo, hi [nu] shared or [n, nu] per problem (None or +-inf: unbounded on that side).
+        Returns lqr_backward()'s dict plus clamped [n, T] int32 (the uint32 mask's bits: bit i set where actuator i ended the
+        step's QP on a bound -- those rows of K are exact zeros) and qp_iters [n, T] int32.  status: 1 also for a box with lo <= hi
+        false somewhere (a NaN bound, a non-finite u), 3 for a QP that hit its iteration cap; such a problem's outputs are zeros.
+        `out`: as in lqr_backward(), keyed by k, gain_t, dv, status, fail_step, clamped, qp_iters."""
+        torch = _torch()
+        nx, nu = 2 * self.cm.nv, self.cm.nu
+        li = _libmod.KLqrBoxIn()
+        n, T, keep = self._lqr_in("lqr_backward_box", li.lqr, lx, lu, lxx, luu, A, B, deriv_t, reg)
+        u = u.contiguous() if isinstance(u, torch.Tensor) else u
+        self._check_buf(u, (n, T, nu), torch.float64, "u")
+        box = self._box("lqr_backward_box", lo, hi, n)
+        li.u, li.lo, li.hi, li.box_per_env = u.data_ptr(), box[0].data_ptr(), box[1].data_ptr(), int(box[0].dim() == 2)
+        keep += (u,) + box
+        table = self._LQR_BOX_FIELDS
+        if out is not None and set(out) - set(table):
+            raise ValueError("unknown lqr_backward_box field(s) %s" % sorted(set(out) - set(table)))
+        dims = {"T": T, "nx": nx, "nu": nu}
+        res = {name: out[name] if out is not None and name in out else
+               torch.empty((n,) + (() if shp is None else tuple(dims.get(d, d) for d in shp)), dtype=getattr(torch, dt), device=self.device)
+               for name, (shp, dt) in table.items()}
+        if n == 0 or T == 0:                 # (nothing is launched: what a problem of no steps gives)
+            for name in ("k", "gain_t", "dv", "status", "clamped", "qp_iters"):
+                res[name].zero_()
+            res["fail_step"].fill_(-1)
+        ld = _libmod.KLqrBoxDev()
+        for name, t in res.items():
+            shp, dt = table[name]
+            self._check_buf(t, (n,) + (() if shp is None else tuple(dims.get(d, d) for d in shp)), getattr(torch, dt), name)
+            setattr(ld if name in ("clamped", "qp_iters") else ld.lqr, name, t.data_ptr())
+        self._check(self.L.kmanip_lqr_backward_box(self.h, C.byref(li), n, T, C.byref(ld), self._stream()), "kmanip_lqr_backward_box")
+        del keep                             # (the stream orders the launch before the allocator reuses the copies)
+        return {"k": res["k"], "gains_t": res["gain_t"], "K": res["gain_t"].transpose(2, 3), "dV": res["dv"], "status": res["status"],
+                "fail_step": res["fail_step"], "clamped": res["clamped"], "qp_iters": res["qp_iters"]}
+
+    def lqr_backward(self, lx, lu, lxx, luu, A=None, B=None, deriv_t=None, reg=0.0, out=None):
+        """kmanip_lqr_backward: ilqr.backward_pass -- the Riccati recursion of iLQR -- for n problems of T steps in ONE launch on the
+        current stream, a workgroup per problem with the loop over the steps inside the kernel (no synchronisation; the handle gives
+        the device and the sizes nx = 2 nv, nu, and is only read; n has nothing to do with num_envs).
+          deriv_t [n, T, nx + nu, nx]: transition_fd's buffer over the n T rows e T + t with the default wrt, read where it lies (no
+            copy), or A [n, T, nx, nx] and B [n, T, nx, nu], which get one transposed contiguous copy each.
+          lx [n, T + 1, nx], lu [n, T, nu]; lxx [n, T + 1, nx, nx] or [T + 1, nx, nx] shared by the problems, luu [n, T, nu, nu] or
+            [T, nu, nu]; entry T of lx / lxx is the final cost's.  reg: a number or [n], added to the diagonal of Quu for the solve.
+        Returns a dict: k [n, T, nu]; gains_t [n, T, nx, nu], what rollout_feedback(gains_t=...) takes; K [n, T, nu, nx], its
+        transposed view; dV [n, 2]; status [n] uint8 and fail_step [n] int32 -- 0 and -1, or 1 and the step at which Quu + reg I
+        had a Cholesky pivot that was not positive and finite: that problem's k, gains_t and dV are then zeros, all steps.
+        `out`: a dict of tensors to fill, keyed by the kernel's outputs (k, gain_t, dv, status, fail_step); the others are allocated."""
+        torch = _torch()
+        nx, nu = 2 * self.cm.nv, self.cm.nu
+        li = _libmod.KLqrIn()
+        n, T, keep = self._lqr_in("lqr_backward", li, lx, lu, lxx, luu, A, B, deriv_t, reg)
         if out is not None and set(out) - set(self._LQR_FIELDS):
             raise ValueError("unknown lqr_backward field(s) %s" % sorted(set(out) - set(self._LQR_FIELDS)))
         ld = _libmod.KLqrDev()

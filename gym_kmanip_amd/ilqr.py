@@ -129,13 +129,149 @@ def backward_pass(A, B, lx, lu, lxx, luu, reg=0.0):
     return k, K, dV
 
 
-def forward_pass(env, envs, qpos0, qvel0, warm0, ctrl, k, K, qpos_ref, qvel_ref, cost, alphas, qfrc_applied=None, nsub=None, K_t=None):
+# the constants of the box QP (Tassa, Mansard, Todorov, "Control-limited differential dynamic programming", ICRA 2014): parameters of the
+# published algorithm, the same in kmanip_lqr_box.hip
+BOXQP_ITERS, BOXQP_TRIALS, BOXQP_ARMIJO, BOXQP_STEP = 100, 100, 0.1, 0.6
+
+
+def box_qp(H, q, bl, bh):
+    """min_d 0.5 d'H d + q'd subject to bl <= d <= bh for n problems at once, H [n, nu, nu], the rest [n, nu]: the projected-Newton
+    box QP of control-limited DDP, the iteration include/kmanip.h KLqrBoxIn states -- from d = clip(0, bl, bh): the gradient, the
+    clamped set c, the Cholesky factor of H with the unit row and column at c, the Newton step on the free coordinates, a projected
+    Armijo line search.  A problem has converged when its last step was a full one that the clip left alone and c is the set that
+    step was factorised for, when every coordinate is clamped, or when the step is no descent direction (s . g >= 0: the face's exact
+    minimiser).  No gradient threshold enters.  A Python loop over the iterations, every problem masked once it is done.
+    Returns (d [n, nu], c [n, nu] bool, L [n, nu, nu] the factor for the final c, iters [n], status [n]: 0, 1 a pivot that is
+    not > 0 or not finite / a box with bl <= bh false / a step that is not finite, 3 the iteration or line-search cap)."""
+    import torch
+    n, nu = q.shape
+    eye = torch.eye(nu, dtype=q.dtype, device=q.device).expand(n, nu, nu)
+    value = lambda x: (x * (0.5 * (H @ x[:, :, None])[:, :, 0] + q)).sum(dim=1)
+    clip = lambda x: torch.where(x < bl, bl, torch.where(x > bh, bh, x))
+    status = torch.where((bl <= bh).all(dim=1), 0, 1).to(torch.uint8)
+    done = status != 0
+    d = clip(torch.zeros_like(q))
+    v = value(d)
+    moved = torch.ones(n, dtype=torch.bool, device=q.device)
+    have = torch.zeros_like(moved)                       # a factor exists, for the set cf
+    c = cf = torch.zeros_like(q, dtype=torch.bool)
+    L = eye.clone()
+    iters = torch.zeros(n, dtype=torch.int32, device=q.device)
+    for it in range(BOXQP_ITERS + 1):
+        g = q + (H @ d[:, :, None])[:, :, 0]
+        c = torch.where(done[:, None], c, ((d == bl) & (g > 0)) | ((d == bh) & (g < 0)))
+        done = done | (~done & ~moved & have & (c == cf).all(dim=1))
+        if bool(done.all()):
+            break
+        if it == BOXQP_ITERS:
+            status[~done] = 3
+            break
+        unit = c[:, :, None] | c[:, None, :]
+        Lnew, info = torch.linalg.cholesky_ex(torch.where(unit, eye, torch.where(done[:, None, None], eye, H)))
+        bad = ~done & ((info != 0) | ~torch.isfinite(Lnew).all(dim=2).all(dim=1))
+        status[bad] = 1
+        done = done | bad
+        L = torch.where(done[:, None, None], L, Lnew)
+        cf, have = torch.where(done[:, None], cf, c), have | ~done
+        done = done | (~done & c.all(dim=1))
+        s = torch.cholesky_solve(torch.where(c, torch.zeros_like(g), -g)[:, :, None], L)[:, :, 0]
+        s = torch.where(c, torch.zeros_like(s), s)
+        sg = (s * g).sum(dim=1)
+        bad = ~done & ~torch.isfinite(sg)
+        status[bad] = 1
+        done = done | bad | (~done & ~(sg < 0))
+        if bool(done.all()):
+            break
+        a = torch.ones_like(v)
+        found = done.clone()
+        xc, vc, clipped = d, v, torch.zeros_like(done)
+        for _ in range(BOXQP_TRIALS):
+            y = d + a[:, None] * s
+            xt = clip(y)
+            vt = value(xt)
+            ok = ~found & ((vt - v) / (a * sg) >= BOXQP_ARMIJO)
+            xc, vc = torch.where(ok[:, None], xt, xc), torch.where(ok, vt, vc)
+            clipped = torch.where(ok, (xt != y).any(dim=1), clipped)
+            found = found | ok
+            if bool(found.all()):
+                break
+            a = torch.where(found, a, a * BOXQP_STEP)
+        status[~found] = 3
+        done = done | ~found
+        run = ~done
+        moved = torch.where(run, clipped | (a != 1.0), moved)
+        d, v = torch.where(run[:, None], xc, d), torch.where(run, vc, v)
+        iters = iters + run.to(iters.dtype)
+    bad = (status == 0) & ~torch.isfinite(d).all(dim=1)
+    status[bad] = 1
+    return d, c, L, iters, status
+
+
+def backward_pass_box(A, B, lx, lu, lxx, luu, u, lo, hi, reg=0.0, info=None):
+    """The backward pass of control-limited DDP: backward_pass with the box lo <= u_t + du <= hi on the controls -- THE DEFINITION
+    kmanip_lqr_backward_box is held to.  backward_pass's arguments, u [n, T, nu] the nominal controls, lo and
+    hi [nu] or [n, nu] (-inf / +inf: unbounded on that side).  Per step, with H = Quu + reg I: k = box_qp(H, Qu, lo - u_t, hi - u_t);
+    on the free set K_f = -H_ff^-1 Qux_f, the rows of K at the clamped actuators zeros; Vx, Vxx and dV by backward_pass's formulas
+    with these k and K (Quu without reg).  A problem whose QP fails at step t (box_qp's status) stops there: all its k, K, dV and
+    masks are zeros.  Returns (k [n, T, nu], K [n, T, nu, nx], dV [n, 2], clamped [n, T] int32: bit i set where actuator i ended
+    step t on a bound); a dict given as `info` receives status [n] uint8, fail_step [n] int32 (-1: none) and qp_iters [n, T] int32."""
+    import torch
+    n, T, nx, nu = B.shape
+    if lxx.dim() == 3:
+        lxx = lxx[None]
+    if luu.dim() == 3:
+        luu = luu[None]
+    dev, dt = A.device, A.dtype
+    reg = torch.as_tensor(reg, dtype=dt, device=dev).reshape(-1, 1, 1)
+    lo = torch.as_tensor(lo, dtype=dt, device=dev).reshape(-1, nu).expand(n, nu)
+    hi = torch.as_tensor(hi, dtype=dt, device=dev).reshape(-1, nu).expand(n, nu)
+    eye = torch.eye(nu, dtype=dt, device=dev)
+    bits = (2 ** torch.arange(nu, device=dev)).to(torch.int64)
+    Vx, Vxx = lx[:, T], lxx[:, T].expand(n, nx, nx)
+    k, K = torch.zeros_like(lu), torch.zeros((n, T, nu, nx), dtype=dt, device=dev)
+    dV = torch.zeros((n, 2), dtype=dt, device=dev)
+    clamped = torch.zeros((n, T), dtype=torch.int32, device=dev)
+    qp_iters = torch.zeros((n, T), dtype=torch.int32, device=dev)
+    status = torch.zeros(n, dtype=torch.uint8, device=dev)
+    fail_step = torch.full((n,), -1, dtype=torch.int32, device=dev)
+    for t in range(T - 1, -1, -1):
+        At, Bt = A[:, t], B[:, t]
+        AtT, BtT = At.transpose(1, 2), Bt.transpose(1, 2)
+        Qx = lx[:, t] + (AtT @ Vx[:, :, None])[:, :, 0]
+        Qu = lu[:, t] + (BtT @ Vx[:, :, None])[:, :, 0]
+        Qxx = lxx[:, t] + AtT @ Vxx @ At
+        Quu = luu[:, t] + BtT @ Vxx @ Bt
+        Qux = BtT @ Vxx @ At
+        kt, c, L, its, st = box_qp(Quu + reg * eye, Qu, lo - u[:, t], hi - u[:, t])
+        Kt = -torch.cholesky_solve(torch.where(c[:, :, None], torch.zeros_like(Qux), Qux), L)
+        Kt = torch.where(c[:, :, None], torch.zeros_like(Kt), Kt)
+        st = torch.where((st == 0) & ~torch.isfinite(Kt).all(dim=2).all(dim=1), torch.ones_like(st), st)
+        new = (status == 0) & (st != 0)
+        status, fail_step = torch.where(new, st, status), torch.where(new, torch.full_like(fail_step, t), fail_step)
+        KtT = Kt.transpose(1, 2)
+        Vx = Qx + (KtT @ (Quu @ kt[:, :, None] + Qu[:, :, None]) + Qux.transpose(1, 2) @ kt[:, :, None])[:, :, 0]
+        Vxx = Qxx + KtT @ Quu @ Kt + KtT @ Qux + Qux.transpose(1, 2) @ Kt
+        Vxx = 0.5 * (Vxx + Vxx.transpose(1, 2))
+        dV[:, 0] += (kt * Qu).sum(dim=1)
+        dV[:, 1] += 0.5 * (kt * (Quu @ kt[:, :, None])[:, :, 0]).sum(dim=1)
+        k[:, t], K[:, t] = kt, Kt
+        clamped[:, t], qp_iters[:, t] = (c.to(torch.int64) * bits).sum(dim=1).to(torch.int32), its
+    ok = status == 0
+    zero = lambda x: torch.where(ok.reshape((n,) + (1,) * (x.dim() - 1)), x, torch.zeros_like(x))
+    if info is not None:
+        info.update(status=status, fail_step=fail_step, qp_iters=zero(qp_iters))
+    return zero(k), zero(K), zero(dV), zero(clamped)
+
+
+def forward_pass(env, envs, qpos0, qvel0, warm0, ctrl, k, K, qpos_ref, qvel_ref, cost, alphas, qfrc_applied=None, nsub=None, K_t=None,
+                 ctrl_lo=None, ctrl_hi=None):
     """The line search in ONE rollout_feedback launch of n len(alphas) rows: row a n + e starts at env e's initial state, carries the
     open-loop term ctrl[e] + alphas[a] k[e] and follows gain trajectory e (gain_index), i.e. K[e] about the nominal states
     qpos_ref / qvel_ref [n, T, ..] before each step.  Returns a dict: cost [len(alphas), n] (inf where the row stopped early),
     best [n] the index of the cheapest alpha per env, best_cost [n], ctrl [n, T, nu] the controls the best row applied, rows: the
     launch's result.  K_t [n, T, 2 nv, nu]: the gains transposed (env.lqr_backward's gains_t), handed to the launch as they are in
-    place of K, which then is not read."""
+    place of K, which then is not read.  ctrl_lo / ctrl_hi [nu] or [n, nu]: the launch clamps the policy's output to the box
+    (rollout_feedback's ctrl_lo / ctrl_hi), and `ctrl` is the clamped controls; both None: today's call."""
     import torch
     n, T, nu = ctrl.shape
     dev = ctrl.device
@@ -148,7 +284,8 @@ def forward_pass(env, envs, qpos0, qvel0, warm0, ctrl, k, K, qpos_ref, qvel_ref,
                                 **(dict(gains=K) if K_t is None else dict(gains_t=K_t)),
                                 qpos_ref=qpos_ref.contiguous(), qvel_ref=qvel_ref.contiguous(),
                                 gain_index=torch.arange(n, dtype=torch.int32, device=dev).repeat(na), nsub=nsub,
-                                fields=("qpos", "qvel", "ctrl", "status"))
+                                fields=("qpos", "qvel", "ctrl", "status"),
+                                **({} if ctrl_lo is None and ctrl_hi is None else dict(ctrl_lo=ctrl_lo, ctrl_hi=ctrl_hi)))
     q = torch.cat([qpos0.repeat(na, 1)[:, None], rows["qpos"]], dim=1)
     v = torch.cat([qvel0.repeat(na, 1)[:, None], rows["qvel"]], dim=1)
     c = cost.total(q, v, rows["ctrl"])
@@ -159,7 +296,7 @@ def forward_pass(env, envs, qpos0, qvel0, warm0, ctrl, k, K, qpos_ref, qvel_ref,
 
 
 def ilqr(env, envs, qpos0, qvel0, warm0, ctrl, cost, iters=10, alphas=(1.0, 0.5, 0.25), reg=1e-6, reg_factor=10.0, qfrc_applied=None,
-         nsub=None, eps=1e-6, fused=False, device_backward=False):
+         nsub=None, eps=1e-6, fused=False, device_backward=False, ctrl_lo=None, ctrl_hi=None):
     """iLQR from the initial rows (qpos0, qvel0, warm0) [n, ..] and the control guess ctrl [n, T, nu]: per iteration trajectory_fd,
     cost.derivatives, backward_pass and forward_pass.  An env accepts the cheapest of its line-search rows if it is cheaper than its
     nominal trajectory, and divides its regularisation by reg_factor; otherwise it keeps its controls and multiplies it.  Returns a
@@ -168,10 +305,22 @@ def ilqr(env, envs, qpos0, qvel0, warm0, ctrl, cost, iters=10, alphas=(1.0, 0.5,
     device_backward: the backward pass is env.lqr_backward (kmanip_lqr_backward, one launch) on deriv_t where
     fused gives it, else on A and B, and the line search takes its transposed gains as they are.  It factorises Quu + reg I by
     Cholesky: an env whose factorisation fails (status != 0; its k and K are zeros) counts as not accepted -- it keeps its controls and
-    its reg is multiplied by reg_factor.  The dict then also has backward_status [iters, n] uint8."""
+    its reg is multiplied by reg_factor.  The dict then also has backward_status [iters, n] uint8.
+    ctrl_lo / ctrl_hi [nu] or [n, nu] (one of them None: that side unbounded): CONTROL-LIMITED iLQR -- the guess
+    is clipped into the box, the backward pass is backward_pass_box or, with device_backward, env.lqr_backward_box, and the line search
+    clamps the policy's output, so every control applied lies in the box.  An env whose backward pass has status 1 or 3 counts as
+    not accepted, as above; backward_status is returned on either path, clamped [n, T] (the last pass's masks) with it.  Both None:
+    today's code path."""
     import torch
     n = int(ctrl.shape[0])
     ctrl = ctrl.clone()
+    boxed = ctrl_lo is not None or ctrl_hi is not None
+    if boxed:
+        inf = torch.full((ctrl.shape[2],), float("inf"), dtype=ctrl.dtype, device=ctrl.device)
+        ctrl_lo = -inf if ctrl_lo is None else torch.as_tensor(ctrl_lo, dtype=ctrl.dtype, device=ctrl.device)
+        ctrl_hi = inf if ctrl_hi is None else torch.as_tensor(ctrl_hi, dtype=ctrl.dtype, device=ctrl.device)
+        ctrl = torch.minimum(torch.maximum(ctrl, ctrl_lo.reshape(-1, 1, ctrl.shape[2])), ctrl_hi.reshape(-1, 1, ctrl.shape[2]))
+    clamped = None
     reg = torch.full((n,), float(reg), dtype=ctrl.dtype, device=ctrl.device)
     history, accepted = [], []
     k = K = None
@@ -181,7 +330,19 @@ def ilqr(env, envs, qpos0, qvel0, warm0, ctrl, cost, iters=10, alphas=(1.0, 0.5,
         if not history:
             history.append(cost.total(fd["qpos"], fd["qvel"], ctrl))
         K_t = solved = None
-        if device_backward:
+        if boxed:
+            derivs = cost.derivatives(fd["qpos"], fd["qvel"], ctrl)
+            if device_backward:
+                dyn = dict(deriv_t=fd["deriv_t"]) if "deriv_t" in fd else dict(A=fd["A"], B=fd["B"])
+                bp = env.lqr_backward_box(*derivs, ctrl, ctrl_lo, ctrl_hi, reg=reg, **dyn)
+                k, K, K_t, clamped, status = bp["k"], bp["K"], bp["gains_t"], bp["clamped"], bp["status"]
+            else:
+                bp = {}
+                k, K, _, clamped = backward_pass_box(fd["A"], fd["B"], *derivs, ctrl, ctrl_lo, ctrl_hi, reg=reg, info=bp)
+                status = bp["status"]
+            solved = status == 0
+            statuses.append(status)
+        elif device_backward:
             dyn = dict(deriv_t=fd["deriv_t"]) if "deriv_t" in fd else dict(A=fd["A"], B=fd["B"])
             bp = env.lqr_backward(*cost.derivatives(fd["qpos"], fd["qvel"], ctrl), reg=reg, **dyn)
             k, K, K_t, solved = bp["k"], bp["K"], bp["gains_t"], bp["status"] == 0
@@ -189,7 +350,7 @@ def ilqr(env, envs, qpos0, qvel0, warm0, ctrl, cost, iters=10, alphas=(1.0, 0.5,
         else:
             k, K, _ = backward_pass(fd["A"], fd["B"], *cost.derivatives(fd["qpos"], fd["qvel"], ctrl), reg=reg)
         fp = forward_pass(env, envs, qpos0, qvel0, warm0, ctrl, k, K, fd["qpos"][:, :-1], fd["qvel"][:, :-1], cost, alphas,
-                          qfrc_applied=qfrc_applied, nsub=nsub, K_t=K_t)
+                          qfrc_applied=qfrc_applied, nsub=nsub, K_t=K_t, ctrl_lo=ctrl_lo, ctrl_hi=ctrl_hi)
         ok = fp["best_cost"] < history[-1]
         if solved is not None:
             ok = ok & solved
@@ -198,6 +359,8 @@ def ilqr(env, envs, qpos0, qvel0, warm0, ctrl, cost, iters=10, alphas=(1.0, 0.5,
         history.append(torch.where(ok, fp["best_cost"], history[-1]))
         accepted.append(ok)
     res = {"ctrl": ctrl, "cost": torch.stack(history), "accepted": torch.stack(accepted), "k": k, "K": K, "reg": reg}
-    if device_backward:
+    if device_backward or boxed:
         res["backward_status"] = torch.stack(statuses)
+    if boxed:
+        res["clamped"] = clamped
     return res

@@ -19,7 +19,7 @@ _lib = None
 # every symbol include/kmanip.h declares (tests check the library exports all of them)
 EXPORTS = [
     "kmanip_model_desc_size", "kmanip_create", "kmanip_reset", "kmanip_step", "kmanip_step_chunk", "kmanip_get_state",
-    "kmanip_set_state", "kmanip_get_episode", "kmanip_set_episode", "kmanip_get_counters", "kmanip_bind_sim_time", "kmanip_bind_applied_force", "kmanip_bind_reward_done_record", "kmanip_select_reward_done_record", "kmanip_observe", "kmanip_forces", "kmanip_kinematics", "kmanip_inverse", "kmanip_forward", "kmanip_rollout", "kmanip_feedback", "kmanip_transition_fd", "kmanip_lqr_backward", "kmanip_set_seed", "kmanip_get_diag", "kmanip_timing_summary", "kmanip_enable_timing", "kmanip_ik", "kmanip_ik_eval",
+    "kmanip_set_state", "kmanip_get_episode", "kmanip_set_episode", "kmanip_get_counters", "kmanip_bind_sim_time", "kmanip_bind_applied_force", "kmanip_bind_reward_done_record", "kmanip_select_reward_done_record", "kmanip_observe", "kmanip_forces", "kmanip_kinematics", "kmanip_inverse", "kmanip_forward", "kmanip_rollout", "kmanip_feedback", "kmanip_feedback_box", "kmanip_transition_fd", "kmanip_lqr_backward", "kmanip_lqr_backward_box", "kmanip_set_seed", "kmanip_get_diag", "kmanip_timing_summary", "kmanip_enable_timing", "kmanip_ik", "kmanip_ik_eval",
     "kmanip_render_depth", "kmanip_render_rgb", "kmanip_render_rgb_multi", "kmanip_render_labels_multi", "kmanip_render_seg", "kmanip_set_render_links", "kmanip_get_render_links", "kmanip_set_depth_links", "kmanip_get_depth_links", "kmanip_get_camera_poses", "kmanip_render_points", "kmanip_snapshot_render_state", "kmanip_set_render_source", "kmanip_bind_step_depth", "kmanip_scripted_action", "kmanip_sample_action", "kmanip_set_env_params", "kmanip_get_env_params", "kmanip_set_env_param_ranges", "kmanip_set_visual_params", "kmanip_get_visual_params", "kmanip_set_visual_param_ranges",
     "kmanip_get_state_dev", "kmanip_set_state_dev", "kmanip_copy_envs", "kmanip_state_index_errors", "kmanip_num_envs", "kmanip_last_error", "kmanip_version", "kmanip_destroy",
 ]
@@ -107,6 +107,12 @@ class KFeedbackDev(C.Structure):
     _fields_ = KRolloutDev._fields_ + [("ctrl", C.c_void_p)]
 
 
+class KFeedbackBoxIn(C.Structure):
+    """include/kmanip.h KFeedbackBoxIn: KFeedbackIn's fields, then the DEVICE pointers of the box [ng or 1, nu] that clamps the
+    policy's output and the flag that says whether every gain trajectory has its own."""
+    _fields_ = KFeedbackIn._fields_ + [("lo", C.c_void_p), ("hi", C.c_void_p), ("box_per_traj", C.c_int32)]
+
+
 class KTransFdIn(C.Structure):
     """include/kmanip.h KTransFdIn: the DEVICE pointers of KRolloutIn's rows (one step, everything held), the KM_WRT_* mask of the
     differentiated inputs, eps and the offset of the perturbed rows' warm start."""
@@ -131,6 +137,16 @@ class KLqrIn(C.Structure):
 class KLqrDev(C.Structure):
     """include/kmanip.h KLqrDev: DEVICE pointers of kmanip_lqr_backward's outputs, any of them NULL."""
     _fields_ = [("k", C.c_void_p), ("gain_t", C.c_void_p), ("dv", C.c_void_p), ("status", C.c_void_p), ("fail_step", C.c_void_p)]
+
+
+class KLqrBoxIn(C.Structure):
+    """include/kmanip.h KLqrBoxIn: KLqrIn, then the DEVICE pointers of the nominal controls [n, T, nu] and of the box [n or 1, nu]."""
+    _fields_ = [("lqr", KLqrIn), ("u", C.c_void_p), ("lo", C.c_void_p), ("hi", C.c_void_p), ("box_per_env", C.c_int32)]
+
+
+class KLqrBoxDev(C.Structure):
+    """include/kmanip.h KLqrBoxDev: KLqrDev, then the clamped-set masks [n, T] uint32 and the QP's step counts [n, T] int32."""
+    _fields_ = [("lqr", KLqrDev), ("clamped", C.c_void_p), ("qp_iters", C.c_void_p)]
 
 
 KM_WRT = {"qpos": 1, "qvel": 2, "ctrl": 4, "qfrc_applied": 8}     # include/kmanip.h KM_WRT_*: the columns always run in this order
@@ -186,8 +202,10 @@ def load():
     lib.kmanip_forward.argtypes = [vp, C.POINTER(KForwardIn), C.c_int, C.POINTER(KForcesDev), vp]
     lib.kmanip_rollout.argtypes = [vp, C.POINTER(KRolloutIn), C.c_int, C.c_int, C.c_int, C.POINTER(KRolloutDev), vp]
     lib.kmanip_feedback.argtypes = [vp, C.POINTER(KFeedbackIn), C.c_int, C.c_int, C.c_int, C.POINTER(KFeedbackDev), vp]
+    lib.kmanip_feedback_box.argtypes = [vp, C.POINTER(KFeedbackBoxIn), C.c_int, C.c_int, C.c_int, C.POINTER(KFeedbackDev), vp]
     lib.kmanip_transition_fd.argtypes = [vp, C.POINTER(KTransFdIn), C.c_int, C.c_int, C.POINTER(KTransFdDev), vp]
     lib.kmanip_lqr_backward.argtypes = [vp, C.POINTER(KLqrIn), C.c_int, C.c_int, C.POINTER(KLqrDev), vp]
+    lib.kmanip_lqr_backward_box.argtypes = [vp, C.POINTER(KLqrBoxIn), C.c_int, C.c_int, C.POINTER(KLqrBoxDev), vp]
     lib.kmanip_set_seed.argtypes = [vp, C.c_uint64, C.c_int]
     lib.kmanip_get_diag.argtypes = [vp, C.POINTER(C.c_uint32), i32p, i32p]
     lib.kmanip_timing_summary.argtypes = [vp, f64p, f64p, f64p, i32p]

@@ -614,6 +614,14 @@ def draw_visual_params(seed: int, genv: int, episode: int, lo, hi) -> np.ndarray
     return out
 
 
+def ctrl_range(cm: CompiledModel, device=None):
+    """(lo, hi): the compiled model's ctrlrange as float64 torch tensors [nu], actuator i's in entry i -- the box that
+    KManipEnvHip.lqr_backward_box, rollout_feedback(ctrl_lo=, ctrl_hi=) and ilqr.ilqr(ctrl_lo=, ctrl_hi=) take."""
+    import torch
+    r = torch.tensor([[cm.desc.ctrlrange[i][0], cm.desc.ctrlrange[i][1]] for i in range(cm.nu)], dtype=torch.float64, device=device)
+    return r[:, 0].contiguous(), r[:, 1].contiguous()
+
+
 def contact_slots(nlink: int) -> int:
     """include/kmanip.h KM_CONTACT_SLOTS: 4 cube corners + KM_SPHERE_SLOTS sphere-cube + KM_SPHERE_TABLE_SLOTS sphere-table (8 / 14)."""
     return 4 + 2 * (nlink // 10) + (6 if nlink >= 20 else 2)

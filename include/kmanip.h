@@ -618,9 +618,37 @@ typedef struct KFeedbackDev {
  * ONE kernel launch, asynchronous on `stream`: no allocation, no synchronisation, no host copy.  THE HANDLE IS READ ONLY.
  * ERRORS: everything kmanip_rollout refuses, a NULL qpos_ref, qvel_ref or gain_t, ng <= 0, or a NULL gain_index with ng < n return
  * nonzero with kmanip_last_error set and launch nothing.
- * OUT OF SCOPE: clamped or box-constrained policies, nonlinear policies, feedback per sub-step other than through nsub == 1,
+ * OUT OF SCOPE: nonlinear policies, feedback per sub-step other than through nsub == 1 (a policy clamped to a box: kmanip_feedback_box),
  * analytic derivatives (gym_kmanip_amd/ilqr.py builds the iLQR loop from kmanip_rollout, transition_fd and this entry). */
 KMANIP_API int kmanip_feedback(KHandle h, const KFeedbackIn* in, int n, int nstep, int nsub, const KFeedbackDev* out, void* stream);
+
+/* kmanip_feedback with the policy's output clamped to a box -- the forward pass of control-limited DDP: at
+ * every step boundary, after kmanip_feedback's finite-u test,
+ *   u_i = min(max(ctrl[r, t, i] + sum_j gain_t[g, t, j, i] * dx_j, lo[b, i]), hi[b, i]),     b = box_per_traj ? g : 0
+ * and the clamped u is what acts and what KFeedbackDev::ctrl records.  -inf / +inf leave a side open; with every bound infinite every
+ * output byte is kmanip_feedback's.  A row whose box has lo_i <= hi_i false for some i (lo > hi, a NaN bound) gets status 1 and no
+ * step.  Everything else, the refusals included, is kmanip_feedback's; a NULL lo or hi is refused as well.  The kernels are
+ * kmanip_rollout.hip built a third time (KM_VAR_FB=2, the kmanip_boxfb_* objects): kmanip_feedback's own objects are untouched. */
+typedef struct KFeedbackBoxIn { /* KFeedbackIn's fields, in its order and with its meanings, then the box */
+  const int32_t* env_index;
+  const double*  qpos;
+  const double*  qvel;
+  const double*  qacc_warm;
+  const double*  ctrl;
+  const double*  qfrc_applied;
+  int32_t ctrl_per_step;
+  int32_t frc_per_step;
+  const int32_t* gain_index;
+  const double*  qpos_ref;
+  const double*  qvel_ref;
+  const double*  gain_t;
+  int32_t ng;
+  int32_t gain_per_step;
+  const double* lo;            /* [box_per_traj ? ng : 1, nu] DEVICE */
+  const double* hi;            /* [box_per_traj ? ng : 1, nu] DEVICE */
+  int32_t box_per_traj;        /* 1: gain trajectory g has its own box (row g of lo / hi); 0: one box for all */
+} KFeedbackBoxIn;
+KMANIP_API int kmanip_feedback_box(KHandle h, const KFeedbackBoxIn* in, int n, int nstep, int nsub, const KFeedbackDev* out, void* stream);
 
 /* Finite-difference derivatives of ONE step at rows the caller passes, MuJoCo's mjd_transitionFD: what
  * gym_kmanip_amd/derivatives.py transition_fd assembles from two kmanip_rollout calls and torch arithmetic, with the perturbation of
@@ -713,9 +741,45 @@ typedef struct KLqrDev {    /* any field may be NULL */
  * the device, nx and nu).  n == 0 or T == 0 succeeds and launches nothing (the fields of `in` are then not looked at).
  * ERRORS: a NULL handle, `in` or `out`, a NULL a_t, b_t, lx, lu, lxx or luu, n < 0 or T < 0, a nonzero stride smaller than its
  * block, or n * T beyond int return nonzero with kmanip_last_error set, launch nothing and leave the outputs untouched.
- * OUT OF SCOPE: a cross term lux, box-constrained or clamped policies (control-limited DDP), second-order dynamics terms (DDP), nx /
+ * OUT OF SCOPE: a cross term lux, second-order dynamics terms (DDP), nx /
  * nu other than the handle's model's, the cost's derivatives. */
 KMANIP_API int kmanip_lqr_backward(KHandle h, const KLqrIn* in, int n, int T, const KLqrDev* out, void* stream);
+
+/* The backward pass of CONTROL-LIMITED DDP (Tassa, Mansard, Todorov, ICRA 2014): kmanip_lqr_backward with a box
+ * lo <= u_t + du <= hi on the controls, gym_kmanip_amd/ilqr.py backward_pass_box, in ONE launch.  Qx, Qu, Qxx, Quu, Qux as above; with
+ * H = Quu + reg I, bl = lo - u_t, bh = hi - u_t the step solves   min_d 0.5 d'H d + Qu'd,  bl <= d <= bh   by projected Newton steps:
+ *   d = clip(0, bl, bh);  repeat:
+ *     g = Qu + H d;  c = { i : d_i == bl_i and g_i > 0 } u { i : d_i == bh_i and g_i < 0 }  (the clamped set; the rest is free)
+ *     CONVERGED if the last step was a full one (step 1) that the clip left alone, and c is the set that step was factorised for
+ *     H_ff = L L' (Cholesky; row and column i of H replaced by the unit row for i in c), only when c changed
+ *     CONVERGED if every actuator is clamped
+ *     s_f = -H_ff^-1 g_f, s_c = 0;  sg = s . g;  CONVERGED if sg >= 0 (an exact minimiser of the face: nothing left to descend)
+ *     step a = 1, 0.6, 0.36, ..: the first with  [v(clip(d + a s)) - v(d)] / (a sg) >= 0.1;  d = clip(d + a s)
+ * (Armijo 0.1, step factor 0.6, at most 100 iterations: the paper's constants.)  No gradient threshold enters: the rule compares
+ * sets and steps, so it is scale-free.  Then k = d, K_f = -H_ff^-1 Qux_f, the rows of K at the clamped actuators EXACT ZEROS, and Vx,
+ * Vxx, dv by kmanip_lqr_backward's formulas with these k and K (Quu without reg). */
+typedef struct KLqrBoxIn {
+  KLqrIn lqr;               /* kmanip_lqr_backward's inputs */
+  const double* u;          /* [n, T, nu] the nominal controls */
+  const double* lo;         /* [box_per_env ? n : 1, nu]; -inf = unbounded below */
+  const double* hi;         /* [box_per_env ? n : 1, nu]; +inf = unbounded above */
+  int32_t box_per_env;
+} KLqrBoxIn;
+typedef struct KLqrBoxDev { /* any field may be NULL */
+  KLqrDev   lqr;            /* kmanip_lqr_backward's outputs */
+  uint32_t* clamped;        /* [n, T] bit i set: actuator i ended step t's QP on a bound (clamped) */
+  int32_t*  qp_iters;       /* [n, T] the projected-Newton steps step t's QP took */
+} KLqrBoxDev;
+/* STATUS per problem, with kmanip_lqr_backward's rule (the problem stops, fail_step t, ALL of its k, gain_t, dv, clamped and qp_iters
+ * entries zeros): 1 when a pivot of a free block's factorisation is not > 0 or not finite, when an entry of the step's k or K (or
+ * the step's descent s . g) is not finite, or when the step's box has bl_i <= bh_i false for some i -- lo > hi or a NaN bound (at the
+ * first step solved, t = T - 1), a non-finite u_t; 3 when a step's QP reached the iteration cap, or one of its line searches ran out
+ * of its 100 trials (0.6^100 < 1e-22: the paper's smallest step).  Every loop of the kernel has such a cap.
+ * With every bound infinite the result is kmanip_lqr_backward's to rounding (the solve is the same factorisation; qp_iters is 1).
+ * ONE kernel launch, asynchronous on `stream`; THE HANDLE IS READ ONLY; n == 0 or T == 0 succeeds and launches nothing.
+ * ERRORS: everything kmanip_lqr_backward refuses, and a NULL u, lo or hi.
+ * OUT OF SCOPE: per-step bounds, a cross term lux, a warm start of the QP from an earlier pass, forcerange-aware planning. */
+KMANIP_API int kmanip_lqr_backward_box(KHandle h, const KLqrBoxIn* in, int n, int T, const KLqrBoxDev* out, void* stream);
 
 /* KManipEnv.reset(seed=...) (env_base.py:219-220): re-key the cube-spawn stream.  restart_episodes != 0 also rewinds every
  * env's episode counter so that the next kmanip_reset draws episode 0 of the new seed (reset(seed=s) is then reproducible). */
