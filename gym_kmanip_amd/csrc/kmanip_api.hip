@@ -235,7 +235,7 @@ static void build_sphere_arm(const KModelDesc* d, uint8_t* out) {
   }
 }
 
-// the row arguments of kmanip_forward / kmanip_rollout / kmanip_feedback (`what`; `in_t` / `out_t`: the names of its structs)
+// the row arguments of kmanip_forward / kmanip_rollout / kmanip_feedback / kmanip_kinematics_rows / kmanip_site_cost (`what`; `in_t` / `out_t`: the names of its structs)
 template <class In, class Out>
 static int row_args(KHandle h, const char* what, const char* in_t, const char* out_t, const In* in, const Out* out, int n) {
   const std::string w = std::string(what) + ": ";
@@ -535,6 +535,35 @@ int kmanip_forward(KHandle h, const KForwardIn* in, int n, const KForcesDev* out
   if (forces_out_empty(*out)) return 0;
   KM_ENTER(h);
   kmanip_launch_forward(h->dmodel, h->desc, h->st, *in, n, *out, (hipStream_t)stream);
+  HIPCHK(h, hipGetLastError());
+  return 0;
+}
+
+// kmanip_kinematics at rows the caller passes (include/kmanip.h KKinRowsIn; kmanip_sitekin.hip).  One launch; the
+// handle is only read; either solver.
+int kmanip_kinematics_rows(KHandle h, const KKinRowsIn* in, int n, const KKinDev* out, void* stream) {
+  if (!h) { g_create_error = "kmanip_kinematics_rows: null handle"; return -1; }
+  if (row_args(h, "kmanip_kinematics_rows", "KKinRowsIn", "KKinDev", in, out, n)) return -1;
+  if (n == 0) return 0;
+  if (!out->link_xpos && !out->link_xmat && !out->site_xpos && !out->site_xmat && !out->site_jacp && !out->site_jacr && !out->site_vel &&
+      !out->qM && !out->qfrc_bias && !out->status) return 0;
+  KM_ENTER(h);
+  kmanip_launch_kinrows(h->dmodel, h->desc, h->st, *in, n, *out, (hipStream_t)stream);
+  HIPCHK(h, hipGetLastError());
+  return 0;
+}
+
+// the site-pose cost of n rows, its gradient and Gauss-Newton Hessian (include/kmanip.h KSiteCostIn / KSiteCostDev; kmanip_sitekin.hip;
+// DESIGN.md section 40).  One launch; the handle is only read; either solver.
+int kmanip_site_cost(KHandle h, const KSiteCostIn* in, int n, const KSiteCostDev* out, void* stream) {
+  if (!h) { g_create_error = "kmanip_site_cost: null handle"; return -1; }
+  if (row_args(h, "kmanip_site_cost", "KSiteCostIn", "KSiteCostDev", in, out, n)) return -1;
+  if (!in->target_pos) { h->err = "kmanip_site_cost: KSiteCostIn::target_pos is NULL"; return -1; }
+  if (!in->weight) { h->err = "kmanip_site_cost: KSiteCostIn::weight is NULL"; return -1; }
+  if (n == 0) return 0;
+  if (!out->cost && !out->lx && !out->lxx && !out->site_xpos && !out->resid && !out->status) return 0;
+  KM_ENTER(h);
+  kmanip_launch_sitecost(h->dmodel, h->desc, h->st, *in, n, *out, (hipStream_t)stream);
   HIPCHK(h, hipGetLastError());
   return 0;
 }

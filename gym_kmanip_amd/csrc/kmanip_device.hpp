@@ -586,6 +586,11 @@ void kmanip_launch_inverse(const KDeviceModel* dm, const KModelDesc& hd, const K
 // applied-force build while in.qfrc_applied or KDeviceState::qfrc_applied is set
 void kmanip_launch_forward(const KDeviceModel* dm, const KModelDesc& hd, const KDeviceState& st, const KForwardIn& in, int n,
                            const KForcesDev& out, hipStream_t stream);
+// kmanip_kinematics_rows and kmanip_site_cost (either solver), n > 0 rows; the per-env parameter build while KDeviceState::envp is set
+void kmanip_launch_kinrows(const KDeviceModel* dm, const KModelDesc& hd, const KDeviceState& st, const KKinRowsIn& in, int n,
+                           const KKinDev& out, hipStream_t stream);
+void kmanip_launch_sitecost(const KDeviceModel* dm, const KModelDesc& hd, const KDeviceState& st, const KSiteCostIn& in, int n,
+                            const KSiteCostDev& out, hipStream_t stream);
 // kmanip_rollout (either solver: the handle's), n > 0 rows, nstep > 0 steps of nsub > 0 sub-steps; the builds are picked as
 // kmanip_launch_forward picks them
 void kmanip_launch_rollout(const KDeviceModel* dm, const KModelDesc& hd, const KDeviceState& st, const KRolloutIn& in, int n, int nstep,

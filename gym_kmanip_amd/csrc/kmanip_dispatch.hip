@@ -18,6 +18,8 @@ typedef void ForcesFn(const KDeviceModel*, const KDeviceState&, const KForcesDev
 typedef void KinFn(const KDeviceModel*, const KDeviceState&, const KKinDev&, hipStream_t);
 typedef void InverseFn(const KDeviceModel*, const KDeviceState&, const KInverseIn&, const KInverseDev&, hipStream_t);
 typedef void ForwardFn(const KDeviceModel*, const KDeviceState&, const KForwardIn&, int, const KForcesDev&, hipStream_t);
+typedef void KinRowsFn(const KDeviceModel*, const KDeviceState&, const KKinRowsIn&, int, const KKinDev&, hipStream_t);
+typedef void SiteCostFn(const KDeviceModel*, const KDeviceState&, const KSiteCostIn&, int, const KSiteCostDev&, hipStream_t);
 typedef void RolloutFn(const KDeviceModel*, const KDeviceState&, const KRolloutIn&, int, int, int, const KRolloutDev&, hipStream_t);
 typedef void FeedbackFn(const KDeviceModel*, const KDeviceState&, const KFeedbackIn&, int, int, int, const KFeedbackDev&, hipStream_t);
 typedef void BoxFbFn(const KDeviceModel*, const KDeviceState&, const KFeedbackBoxIn&, int, int, int, const KFeedbackDev&, hipStream_t);
@@ -43,10 +45,13 @@ typedef void TransFdFn(const KDeviceModel*, const KDeviceState&, const KTransFdI
 #define KM_KIN_ROW(B, NL, G) KM_NAME(kinematics, B, NL, G, ),
 #define KM_INVERSE_ROW(B, NL, G) KM_NAME(inverse, B, NL, G, ),
 #define KM_FORWARD_ROW(B, NL, G) KM_NAME(forward, B, NL, G, ),
+// kmanip_sitekin.hip: two launchers per object, one object per class, the parameter builds
+#define KM_KINROWS_ROW(B, NL, G) KM_NAME(kinrows, B, NL, G, ),
+#define KM_SITECOST_ROW(B, NL, G) KM_NAME(sitecost, B, NL, G, ),
 
 #define KM_DECL_SOLVERS(Fn, kind, B, NL, G) Fn KM_NAME(kind, B, NL, G, _0), KM_NAME(kind, B, NL, G, _1);
 #define KM_DECL_FRC(B, NL, G) KM_DECL_SOLVERS(StepFn, step, B, NL, G) KM_DECL_SOLVERS(RolloutFn, rollout, B, NL, G) KM_DECL_SOLVERS(FeedbackFn, feedback, B, NL, G) KM_DECL_SOLVERS(BoxFbFn, boxfb, B, NL, G) KM_DECL_SOLVERS(TransFdFn, transfd, B, NL, G) ForcesFn KM_NAME(forces, B, NL, G, ); ForwardFn KM_NAME(forward, B, NL, G, );
-#define KM_DECL_PAR(B, NL, G) KM_DECL_SOLVERS(ResetFn, reset, B, NL, G) KinFn KM_NAME(kinematics, B, NL, G, ); InverseFn KM_NAME(inverse, B, NL, G, );
+#define KM_DECL_PAR(B, NL, G) KM_DECL_SOLVERS(ResetFn, reset, B, NL, G) KinFn KM_NAME(kinematics, B, NL, G, ); InverseFn KM_NAME(inverse, B, NL, G, ); KinRowsFn KM_NAME(kinrows, B, NL, G, ); SiteCostFn KM_NAME(sitecost, B, NL, G, );
 #define KM_DECL_ONCE(B, NL, G) ObserveFn KM_NAME(observe, B, NL, G, _1); PrepareFn KM_NAME(prepare, B, NL, G, _1);
 #define KM_DECL_BUILD_FRC(B) KM_CLASSES(KM_DECL_FRC, B)
 #define KM_DECL_BUILD_PAR(B) KM_CLASSES(KM_DECL_PAR, B)
@@ -59,6 +64,8 @@ KM_BUILDS(KM_DECL_BUILD_FRC) KM_BUILDS_PAR(KM_DECL_BUILD_PAR) KM_CLASSES(KM_DECL
 #define KM_KIN_BUILD(B) {KM_CLASSES(KM_KIN_ROW, B)},
 #define KM_INVERSE_BUILD(B) {KM_CLASSES(KM_INVERSE_ROW, B)},
 #define KM_FORWARD_BUILD(B) {KM_CLASSES(KM_FORWARD_ROW, B)},
+#define KM_KINROWS_BUILD(B) {KM_CLASSES(KM_KINROWS_ROW, B)},
+#define KM_SITECOST_BUILD(B) {KM_CLASSES(KM_SITECOST_ROW, B)},
 #define KM_ROLLOUT_BUILD(B) {KM_CLASSES(KM_ROLLOUT_ROW, B)},
 #define KM_FEEDBACK_BUILD(B) {KM_CLASSES(KM_FEEDBACK_ROW, B)},
 #define KM_BOXFB_BUILD(B) {KM_CLASSES(KM_BOXFB_ROW, B)},
@@ -71,6 +78,8 @@ static constexpr ForcesFn* forces_tab[4][2] = {KM_BUILDS(KM_FORCES_BUILD)};
 static constexpr KinFn* kin_tab[2][2] = {KM_BUILDS_PAR(KM_KIN_BUILD)};
 static constexpr InverseFn* inverse_tab[2][2] = {KM_BUILDS_PAR(KM_INVERSE_BUILD)};
 static constexpr ForwardFn* forward_tab[4][2] = {KM_BUILDS(KM_FORWARD_BUILD)};
+static constexpr KinRowsFn* kinrows_tab[2][2] = {KM_BUILDS_PAR(KM_KINROWS_BUILD)};
+static constexpr SiteCostFn* sitecost_tab[2][2] = {KM_BUILDS_PAR(KM_SITECOST_BUILD)};
 static constexpr RolloutFn* rollout_tab[4][2][2] = {KM_BUILDS(KM_ROLLOUT_BUILD)};
 static constexpr FeedbackFn* feedback_tab[4][2][2] = {KM_BUILDS(KM_FEEDBACK_BUILD)};
 static constexpr BoxFbFn* boxfb_tab[4][2][2] = {KM_BUILDS(KM_BOXFB_BUILD)};
@@ -110,6 +119,14 @@ void kmanip_launch_inverse(const KDeviceModel* dm, const KModelDesc& hd, const K
 void kmanip_launch_forward(const KDeviceModel* dm, const KModelDesc& hd, const KDeviceState& st, const KForwardIn& in, int n,
                            const KForcesDev& out, hipStream_t stream) {
   forward_tab[row_build(st, in)][cls(hd)](dm, st, in, n, out, stream);
+}
+void kmanip_launch_kinrows(const KDeviceModel* dm, const KModelDesc& hd, const KDeviceState& st, const KKinRowsIn& in, int n,
+                           const KKinDev& out, hipStream_t stream) {
+  kinrows_tab[par(st)][cls(hd)](dm, st, in, n, out, stream);
+}
+void kmanip_launch_sitecost(const KDeviceModel* dm, const KModelDesc& hd, const KDeviceState& st, const KSiteCostIn& in, int n,
+                            const KSiteCostDev& out, hipStream_t stream) {
+  sitecost_tab[par(st)][cls(hd)](dm, st, in, n, out, stream);
 }
 void kmanip_launch_rollout(const KDeviceModel* dm, const KModelDesc& hd, const KDeviceState& st, const KRolloutIn& in, int n, int nstep,
                            int nsub, const KRolloutDev& out, hipStream_t stream) {

@@ -692,6 +692,51 @@ class KManipEnvHip:
         self._check(self.L.kmanip_kinematics(self.h, C.byref(kd), self._stream()), "kmanip_kinematics")
         return out
 
+    def kinematics_at(self, envs=None, qpos=None, qvel=None, out=None, fields=None):
+        """kmanip_kinematics_rows: kinematics() at rows the CALLER passes, as many as it likes -- the states of a nominal trajectory,
+        the rows of a line search (one launch on the current stream, no synchronisation; the handle is only read; either solver).
+        Row r takes the per-env parameters of env envs[r] (forward()'s rules: repeats allowed, more rows than envs allowed; None =
+        row r is env r, and then at most num_envs rows) and the caller's row of qpos [n, nq] / qvel [n, nv] or, for None, what that
+        env stores.  n = len(envs), else the rows of the first given tensor, else num_envs.  With everything None it returns
+        kinematics()' bits.  Returns kinematics()' dict with n leading rows; status [n] uint8: 0 ok; 1 a non-finite qpos or qvel the
+        row uses, given or stored; 2 an env index outside 0 .. num_envs-1 (never used as an address) -- every other output of such a
+        row is 0.  `fields`, `out`: as in kinematics(); without qM and qfrc_bias the kernel stops after the forward kinematics, and
+        the other fields' bits are the same."""
+        ki = _libmod.KKinRowsIn()
+        n, idx = self._query_rows(envs, (("qpos", qpos, (self.cm.nq,)), ("qvel", qvel, (self.cm.nv,))), ki)
+        dims = {"nl": self.cm.nlink, "nv": self.cm.nv, "na": 2}
+        kd = _libmod.KKinDev()
+        out = self._query_out(self._KIN_FIELDS, (n,), dims, out, fields, kd, "kinematics")
+        self._check(self.L.kmanip_kinematics_rows(self.h, C.byref(ki), n, C.byref(kd), self._stream()), "kmanip_kinematics_rows")
+        return out
+
+    # KSiteCostDev field -> (trailing shape in terms of nx = 2 nv, na = KM_MAX_ARMS, dtype name)
+    _SITE_COST_FIELDS = {"cost": ((), "float64"), "lx": (("nx",), "float64"), "lxx": (("nx", "nx"), "float64"),
+                         "site_xpos": (("na", 3), "float64"), "resid": (("na", 6), "float64"), "status": ((), "uint8")}
+
+    def site_cost(self, target_pos, weight, envs=None, qpos=None, target_quat=None, follow_cube=(False, False), out=None, fields=None):
+        """kmanip_site_cost: a site-pose cost of n rows of states, its gradient and Gauss-Newton Hessian in ONE launch (the handle is
+        only read; either solver).  Per row r, over the present arms a, in transition_fd's tangent x = [dq ; qvel], nx = 2 nv:
+          e_pos = site_xpos - (target_pos[r, a] + follow_cube[a] * cube position); e_rot = the world-frame rotation vector (|.| <= pi)
+          of R_site R_target^T, R_target from target_quat[r, a] (wxyz, normalised; read only where weight[r, a, 1] != 0)
+          cost = 1/2 sum_a (weight[r, a, 0] |e_pos|^2 + weight[r, a, 1] |e_rot|^2); lx = sum_a (w0 Jp' e_pos + w1 Jr' e_rot) with Jp =
+          site_jacp and -follow_cube[a] I on the cube's position columns, Jr = site_jacr; lxx = sum_a (w0 Jp' Jp + w1 Jr' Jr)
+        target_pos [n, 2, 3] and weight [n, 2, 2] float64, required; target_quat [n, 2, 4] or None (no rotation term); envs, qpos:
+        kinematics_at()'s rows; qvel does not enter.  follow_cube: a bool, or one per arm.  Returns a dict of device tensors:
+          cost [n]; lx [n, nx] (exact zeros from nv on); lxx [n, nx, nx] (bitwise symmetric, exact zeros outside the nv x nv block);
+          site_xpos [n, 2, 3]; resid [n, 2, 6] (e_pos, e_rot); status [n] uint8: 0 ok; 1 a non-finite qpos the row uses, or a
+          non-finite target or weight of a present arm; 2 an env index out of range -- every other output of such a row is 0
+        `fields`: the names wanted (default: all); `out`: a dict of such tensors to fill, returned as given."""
+        si = _libmod.KSiteCostIn()
+        n, idx = self._query_rows(envs, (("qpos", qpos, (self.cm.nq,)), ("target_pos", target_pos, (2, 3)), ("weight", weight, (2, 2)),
+                                         ("target_quat", target_quat, (2, 4))), si)
+        fc = (follow_cube, follow_cube) if isinstance(follow_cube, (bool, int)) else tuple(follow_cube)
+        si.follow_cube[0], si.follow_cube[1] = int(bool(fc[0])), int(bool(fc[1]))
+        sd = _libmod.KSiteCostDev()
+        out = self._query_out(self._SITE_COST_FIELDS, (n,), {"nx": 2 * self.cm.nv, "na": 2}, out, fields, sd, "site cost")
+        self._check(self.L.kmanip_site_cost(self.h, C.byref(si), n, C.byref(sd), self._stream()), "kmanip_site_cost")
+        return out
+
     def site_jacobian(self, k, arm):
         """[n, 6, nv] float64: the 6 x nv site Jacobian of `arm` (0 = right) from a kinematics() result (it needs site_jacp and
         site_jacr), jacp over jacr: one cat, no further C call."""

@@ -6,7 +6,8 @@ u_t = u_t + alpha k_t + K_t (x_t - x_t_nominal) rolled out CLOSED LOOP for every
 of n len(alphas) rows that share the n gain trajectories through gain_index.
 
 The state is (qpos in the tangent space, qvel), 2 nv wide, as transition_fd defines it; differences of states are
-derivatives.tangent_diff's.  Everything is torch arithmetic on the device of the caller's tensors and needs only env.rollout,
+derivatives.tangent_diff's.  The cost is an object with total() and derivatives(): QuadraticCost (a goal state in joint space), SiteCost (a
+goal pose of the end-effector sites in task space) or a SumCost of such.  Everything is torch arithmetic on the device of the caller's tensors and needs only env.rollout,
 env.rollout_feedback, env.cm and that device, so a CPU stand-in (tests/tools/feedback_oracle.py OracleFeedback) runs the same code."""
 import functools
 
@@ -90,6 +91,193 @@ class QuadraticCost:
         lxx = torch.cat([self.Q[None].expand(T, -1, -1), self.Qf[None]], dim=0)
         lx = torch.einsum("tij,ntj->nti", lxx, d)
         return lx, ctrl @ self.R.transpose(0, 1), lxx, self.R[None].expand(T, -1, -1)
+
+
+def _mat2quat(m):
+    """wxyz [.., 4] of rotation matrices [.., 9] (row-major), normalised: mju_mat2Quat's four cases, chosen as the kernels' mat2quat
+    chooses them (the trace if positive, else the largest diagonal entry)."""
+    import torch
+    m0, m1, m2, m3, m4, m5, m6, m7, m8 = m.unbind(dim=-1)
+    tr = m0 + m4 + m8
+    case = torch.where(tr > 0, 0, torch.where((m0 > m4) & (m0 > m8), 1, torch.where(m4 > m8, 2, 3)))
+    arg = torch.stack([1 + tr, 1 + m0 - m4 - m8, 1 - m0 + m4 - m8, 1 - m0 - m4 + m8], dim=-1).gather(-1, case[..., None])[..., 0]
+    r = 0.5 * torch.sqrt(arg)
+    s = 0.25 / r
+    d75, d26, d31, s13, s26, s57 = s * (m7 - m5), s * (m2 - m6), s * (m3 - m1), s * (m1 + m3), s * (m2 + m6), s * (m5 + m7)
+    cands = torch.stack([torch.stack([r, d75, d26, d31], dim=-1), torch.stack([d75, r, s13, s26], dim=-1),
+                         torch.stack([d26, s13, r, s57], dim=-1), torch.stack([d31, s26, s57, r], dim=-1)], dim=-2)
+    q = cands.gather(-2, case[..., None, None].expand(case.shape + (1, 4)))[..., 0, :]
+    return q / q.norm(dim=-1, keepdim=True)
+
+
+def _rotation_error(qs, qt):
+    """[.., 3]: the world-frame rotation vector (angle in (-pi, pi]) of qs (x) conj(qt), unit quaternions wxyz -- the rotation that
+    takes the frame qt to the frame qs.  derivatives.tangent_diff's atan2 form (no division by zero at the identity) on a = conj(qs),
+    b = conj(qt): conj(a) (x) b is that product."""
+    import math
+    import torch
+    wa, xa, ya, za = qs[..., 0], -qs[..., 1], -qs[..., 2], -qs[..., 3]
+    wb, xb, yb, zb = qt[..., 0], -qt[..., 1], -qt[..., 2], -qt[..., 3]
+    w = wa * wb + xa * xb + ya * yb + za * zb
+    x = (wa * xb - xa * wb) + (za * yb - ya * zb)
+    y = (wa * yb - ya * wb) + (xa * zb - za * xb)
+    z = (wa * zb - za * wb) + (ya * xb - xa * yb)
+    sn = torch.sqrt(x * x + y * y + z * z)
+    ang = 2.0 * torch.atan2(sn, w)
+    ang = torch.where(ang > math.pi, ang - 2.0 * math.pi, ang)
+    k = torch.where(sn > 0, ang / torch.where(sn > 0, sn, torch.ones_like(sn)), 2.0 / torch.where(w != 0, w, torch.ones_like(w)))
+    return torch.stack([k * x, k * y, k * z], dim=-1)
+
+
+def site_cost_rows(env, envs, qpos, qvel, target_pos, target_quat, weight, follow_cube, want_derivatives=True):
+    """THE DEFINITION kmanip_site_cost is held to (include/kmanip.h KSiteCostIn states the formulas): one
+    env.kinematics_at call over the N rows (envs [N] int32, qpos [N, nq], qvel [N, nv]) and torch arithmetic on target_pos [N, 2, 3],
+    target_quat [N, 2, 4] or None, weight [N, 2, 2] and follow_cube (two bools).  Returns dict(cost [N], status [N] and, if wanted, lx
+    [N, 2 nv], lxx [N, 2 nv, 2 nv]); a row with status != 0 is zeros."""
+    import torch
+    cm = env.cm
+    nl, nv = cm.nlink, cm.nv
+    q, tp, tq, w = qpos, target_pos, target_quat, weight
+    N = int(q.shape[0])
+    present = torch.tensor([bool(cm.desc.arm_present[a]) for a in range(2)], device=q.device)
+    k = env.kinematics_at(envs=envs, qpos=q, qvel=qvel, fields=SiteCost.FIELDS)
+    ok = (k["status"] == 0)
+    f = torch.tensor([float(bool(x)) for x in follow_cube], dtype=q.dtype, device=q.device)
+    zero = torch.zeros((), dtype=q.dtype, device=q.device)
+    w0 = torch.where(present[None], w[:, :, 0], zero)
+    w1 = torch.where(present[None], w[:, :, 1], zero) if tq is not None else torch.zeros_like(w0)
+    e_pos = torch.where(present[None, :, None], k["site_xpos"] - (tp + f[None, :, None] * q[:, None, nl:nl + 3]), zero)
+    if tq is None:
+        e_rot = torch.zeros_like(e_pos)
+    else:
+        eye = torch.eye(3, dtype=q.dtype, device=q.device).reshape(1, 1, 9)
+        use = ok[:, None] & (w1 != 0)
+        unit = torch.tensor([1.0, 0.0, 0.0, 0.0], dtype=q.dtype, device=q.device)
+        qt = torch.where(use[:, :, None], tq, unit)
+        e_rot = _rotation_error(_mat2quat(torch.where(use[:, :, None], k["site_xmat"], eye)), qt / qt.norm(dim=-1, keepdim=True))
+        e_rot = torch.where(use[:, :, None], e_rot, zero)
+    cost = 0.5 * (w0 * (e_pos * e_pos).sum(dim=-1) + w1 * (e_rot * e_rot).sum(dim=-1)).sum(dim=1)
+    bad = ~(torch.isfinite(cost))
+    status = torch.where(ok & bad, torch.ones_like(k["status"]), k["status"])      # (a non-finite target or weight of a present arm)
+    ok = status == 0
+    out = {"cost": torch.where(ok, cost, zero), "status": status}
+    if want_derivatives:
+        Jp, Jr = k["site_jacp"].clone(), k["site_jacr"]
+        for c in range(3):
+            Jp[:, :, c, nl + c] = -f * present.to(q.dtype)
+        lx = torch.zeros((N, 2 * nv), dtype=q.dtype, device=q.device)
+        lxx = torch.zeros((N, 2 * nv, 2 * nv), dtype=q.dtype, device=q.device)
+        lx[:, :nv] = torch.einsum("ra,rac,racj->rj", w0, e_pos, Jp) + torch.einsum("ra,rac,racj->rj", w1, e_rot, Jr)
+        lxx[:, :nv, :nv] = torch.einsum("ra,raci,racj->rij", w0, Jp, Jp) + torch.einsum("ra,raci,racj->rij", w1, Jr, Jr)
+        out.update(lx=torch.where(ok[:, None], lx, zero), lxx=torch.where(ok[:, None, None], lxx, zero))
+    return out
+
+
+class SiteCost:
+    """sum_{t <= T} 1/2 sum_a (w_pos[a] |e_pos_a(x_t)|^2 + w_rot[a] |e_rot_a(x_t)|^2) over the present arms a, the final state with
+    wf_pos / wf_rot: the distance of the end-effector sites to a target pose, in task space (DESIGN.md section 40;
+    include/kmanip.h KSiteCostIn states e_pos, e_rot, the gradient and the Gauss-Newton Hessian).
+    target_pos [n0, arms, 3], or [n0, T + 1, arms, 3] for a trajectory to track; target_quat likewise with 4 (wxyz), or None: no
+    rotation term.  arms: the present arms in order, or 2 (the slots of an absent arm are ignored).  Problem e is env e (n0 <=
+    num_envs); rows beyond n0 repeat the targets as QuadraticCost.dx repeats its goal: row a n0 + e uses entry e.  w_pos, w_rot: a
+    number or one per arm; wf_pos, wf_rot: the final state's, default the running ones.  follow_cube (a bool or one per arm): the
+    target position is an offset from the cube's position, and the cost then also pulls on the cube's position columns.
+    device=False: env.kinematics_at and torch arithmetic -- the definition kmanip_site_cost is held to; it needs only
+    env.kinematics_at and env.cm, so a CPU stand-in serves it.  device=True: one env.site_cost launch per call."""
+
+    FIELDS = ("site_xpos", "site_xmat", "site_jacp", "site_jacr", "status")
+
+    def __init__(self, env, target_pos, target_quat=None, w_pos=1.0, w_rot=0.0, wf_pos=None, wf_rot=None, follow_cube=False, device=False):
+        import torch
+        self.env, self.cm, self.device = env, env.cm, bool(device)
+        present = [a for a in range(2) if self.cm.desc.arm_present[a]]
+        dt, dev = target_pos.dtype, target_pos.device
+
+        def slots(t, width):                      # [n0, (T + 1,) arms, width] -> [n0, T + 1 or 1, 2, width]
+            if t.dim() == 3:
+                t = t[:, None]
+            if t.shape[2] == 2:
+                return t
+            assert t.shape[2] == len(present), "one target per present arm, or two"
+            out = torch.zeros(t.shape[:2] + (2, width), dtype=dt, device=dev)
+            out[:, :, present] = t
+            if width == 4:
+                out[..., 0] = torch.where(out.abs().sum(dim=-1) == 0, torch.ones_like(out[..., 0]), out[..., 0])
+            return out
+
+        def per_arm(v):                           # a number or [arms] -> [2], zeros at an absent arm
+            v = torch.as_tensor(v, dtype=dt, device=dev).reshape(-1)
+            out = torch.zeros(2, dtype=dt, device=dev)
+            out[present] = v.expand(len(present)) if v.numel() == 1 else (v if v.numel() == len(present) else v[present])
+            return out
+        self.target_pos = slots(target_pos, 3)
+        self.target_quat = None if target_quat is None else slots(target_quat, 4)
+        wr = per_arm(w_rot) if target_quat is not None else torch.zeros(2, dtype=dt, device=dev)
+        wfr = wr if wf_rot is None or target_quat is None else per_arm(wf_rot)
+        wp = per_arm(w_pos)
+        self.w_run, self.w_final = torch.stack([wp, wr], dim=1), torch.stack([wp if wf_pos is None else per_arm(wf_pos), wfr], dim=1)
+        fc = (follow_cube, follow_cube) if isinstance(follow_cube, (bool, int)) else tuple(follow_cube)
+        self.follow_cube = tuple(bool(f) and a in present for a, f in zip(range(2), fc))
+
+    def _rows(self, n, L):
+        """(env index [n L] int32, target_pos [n L, 2, 3], target_quat [n L, 2, 4] or None, weight [n L, 2, 2]) of n trajectories of
+        L states, the last one the final state."""
+        import torch
+        n0 = int(self.target_pos.shape[0])
+        reps = n // n0
+        assert reps * n0 == n, "the rows are a multiple of the targets"
+        spread = lambda t: t.repeat(reps, 1, 1, 1).expand(n, L, 2, t.shape[-1]).reshape(n * L, 2, t.shape[-1]).contiguous()
+        w = torch.cat([self.w_run[None].expand(L - 1, 2, 2), self.w_final[None]], dim=0)
+        idx = torch.arange(n0, dtype=torch.int32, device=self.target_pos.device).repeat(reps).repeat_interleave(L)
+        return idx, spread(self.target_pos), None if self.target_quat is None else spread(self.target_quat), \
+            w[None].expand(n, L, 2, 2).reshape(n * L, 2, 2).contiguous()
+
+    def _evaluate(self, qpos, qvel, want_derivatives):
+        """dict(cost [n, L], status [n, L] and, if wanted, lx [n, L, nx], lxx [n, L, nx, nx]) of states qpos [n, L, nq], qvel [n, L, nv]."""
+        n, L = int(qpos.shape[0]), int(qpos.shape[1])
+        idx, tp, tq, w = self._rows(n, L)
+        q = qpos.reshape(n * L, -1).contiguous()
+        if self.device:
+            r = self.env.site_cost(tp, w, envs=idx, qpos=q, target_quat=tq, follow_cube=self.follow_cube,
+                                   fields=("cost", "lx", "lxx", "status") if want_derivatives else ("cost", "status"))
+            return {k: v.reshape((n, L) + tuple(v.shape[1:])) for k, v in r.items()}
+        r = site_cost_rows(self.env, idx, q, qvel.reshape(n * L, -1).contiguous(), tp, tq, w, self.follow_cube, want_derivatives)
+        return {k: v.reshape((n, L) + tuple(v.shape[1:])) for k, v in r.items()}
+
+    def total(self, qpos, qvel, ctrl):
+        """[n]: the cost of trajectories qpos [n, T + 1, nq], qvel [n, T + 1, nv]; inf where any state of the trajectory has status != 0."""
+        import torch
+        r = self._evaluate(qpos, qvel, False)
+        c = r["cost"].sum(dim=1)
+        return torch.where((r["status"] == 0).all(dim=1), c, torch.full_like(c, float("inf")))
+
+    def derivatives(self, qpos, qvel, ctrl):
+        """(lx [n, T + 1, 2 nv], lu zeros [n, T, nu], lxx [n, T + 1, 2 nv, 2 nv] per problem, luu zeros [T, nu, nu])."""
+        import torch
+        r = self._evaluate(qpos, qvel, True)
+        T, nu = int(ctrl.shape[1]), int(ctrl.shape[2])
+        return r["lx"], torch.zeros_like(ctrl), r["lxx"], torch.zeros((T, nu, nu), dtype=ctrl.dtype, device=ctrl.device)
+
+
+class SumCost:
+    """The sum of costs with QuadraticCost's two methods: totals and derivatives added, a shared lxx [T + 1, nx, nx] / luu [T, nu, nu]
+    broadcast against a per-problem [n, T + 1, nx, nx] / [n, T, nu, nu]."""
+
+    def __init__(self, *costs):
+        assert costs, "at least one cost"
+        self.costs = costs
+
+    def total(self, qpos, qvel, ctrl):
+        out = self.costs[0].total(qpos, qvel, ctrl)
+        for c in self.costs[1:]:
+            out = out + c.total(qpos, qvel, ctrl)
+        return out
+
+    def derivatives(self, qpos, qvel, ctrl):
+        out = self.costs[0].derivatives(qpos, qvel, ctrl)
+        for c in self.costs[1:]:
+            out = tuple(a + b for a, b in zip(out, c.derivatives(qpos, qvel, ctrl)))
+        return out
 
 
 def backward_pass(A, B, lx, lu, lxx, luu, reg=0.0):

@@ -19,7 +19,7 @@ _lib = None
 # every symbol include/kmanip.h declares (tests check the library exports all of them)
 EXPORTS = [
     "kmanip_model_desc_size", "kmanip_create", "kmanip_reset", "kmanip_step", "kmanip_step_chunk", "kmanip_get_state",
-    "kmanip_set_state", "kmanip_get_episode", "kmanip_set_episode", "kmanip_get_counters", "kmanip_bind_sim_time", "kmanip_bind_applied_force", "kmanip_bind_reward_done_record", "kmanip_select_reward_done_record", "kmanip_observe", "kmanip_forces", "kmanip_kinematics", "kmanip_inverse", "kmanip_forward", "kmanip_rollout", "kmanip_feedback", "kmanip_feedback_box", "kmanip_transition_fd", "kmanip_lqr_backward", "kmanip_lqr_backward_box", "kmanip_set_seed", "kmanip_get_diag", "kmanip_timing_summary", "kmanip_enable_timing", "kmanip_ik", "kmanip_ik_eval",
+    "kmanip_set_state", "kmanip_get_episode", "kmanip_set_episode", "kmanip_get_counters", "kmanip_bind_sim_time", "kmanip_bind_applied_force", "kmanip_bind_reward_done_record", "kmanip_select_reward_done_record", "kmanip_observe", "kmanip_forces", "kmanip_kinematics", "kmanip_inverse", "kmanip_forward", "kmanip_kinematics_rows", "kmanip_site_cost", "kmanip_rollout", "kmanip_feedback", "kmanip_feedback_box", "kmanip_transition_fd", "kmanip_lqr_backward", "kmanip_lqr_backward_box", "kmanip_set_seed", "kmanip_get_diag", "kmanip_timing_summary", "kmanip_enable_timing", "kmanip_ik", "kmanip_ik_eval",
     "kmanip_render_depth", "kmanip_render_rgb", "kmanip_render_rgb_multi", "kmanip_render_labels_multi", "kmanip_render_seg", "kmanip_set_render_links", "kmanip_get_render_links", "kmanip_set_depth_links", "kmanip_get_depth_links", "kmanip_get_camera_poses", "kmanip_render_points", "kmanip_snapshot_render_state", "kmanip_set_render_source", "kmanip_bind_step_depth", "kmanip_scripted_action", "kmanip_sample_action", "kmanip_set_env_params", "kmanip_get_env_params", "kmanip_set_env_param_ranges", "kmanip_set_visual_params", "kmanip_get_visual_params", "kmanip_set_visual_param_ranges",
     "kmanip_get_state_dev", "kmanip_set_state_dev", "kmanip_copy_envs", "kmanip_state_index_errors", "kmanip_num_envs", "kmanip_last_error", "kmanip_version", "kmanip_destroy",
 ]
@@ -80,6 +80,24 @@ class KForwardIn(C.Structure):
     NULL = what the named env stores."""
     _fields_ = [("env_index", C.c_void_p), ("qpos", C.c_void_p), ("qvel", C.c_void_p), ("ctrl", C.c_void_p), ("qacc_warm", C.c_void_p),
                 ("qfrc_applied", C.c_void_p)]
+
+
+class KKinRowsIn(C.Structure):
+    """include/kmanip.h KKinRowsIn: DEVICE pointers of kmanip_kinematics_rows' inputs (KForwardIn's NULL semantics)."""
+    _fields_ = [("env_index", C.c_void_p), ("qpos", C.c_void_p), ("qvel", C.c_void_p)]
+
+
+class KSiteCostIn(C.Structure):
+    """include/kmanip.h KSiteCostIn: DEVICE pointers of kmanip_site_cost's inputs (env_index / qpos: KForwardIn's NULL semantics;
+    target_quat NULL: no rotation term) and, per arm, whether its target position rides on the cube."""
+    _fields_ = [("env_index", C.c_void_p), ("qpos", C.c_void_p), ("target_pos", C.c_void_p), ("target_quat", C.c_void_p),
+                ("weight", C.c_void_p), ("follow_cube", C.c_int32 * 2)]
+
+
+class KSiteCostDev(C.Structure):
+    """include/kmanip.h KSiteCostDev: DEVICE pointers of kmanip_site_cost's outputs, any of them NULL."""
+    _fields_ = [("cost", C.c_void_p), ("lx", C.c_void_p), ("lxx", C.c_void_p), ("site_xpos", C.c_void_p), ("resid", C.c_void_p),
+                ("status", C.c_void_p)]
 
 
 class KRolloutIn(C.Structure):
@@ -200,6 +218,8 @@ def load():
     lib.kmanip_kinematics.argtypes = [vp, C.POINTER(KKinDev), vp]
     lib.kmanip_inverse.argtypes = [vp, C.POINTER(KInverseIn), C.POINTER(KInverseDev), vp]
     lib.kmanip_forward.argtypes = [vp, C.POINTER(KForwardIn), C.c_int, C.POINTER(KForcesDev), vp]
+    lib.kmanip_kinematics_rows.argtypes = [vp, C.POINTER(KKinRowsIn), C.c_int, C.POINTER(KKinDev), vp]
+    lib.kmanip_site_cost.argtypes = [vp, C.POINTER(KSiteCostIn), C.c_int, C.POINTER(KSiteCostDev), vp]
     lib.kmanip_rollout.argtypes = [vp, C.POINTER(KRolloutIn), C.c_int, C.c_int, C.c_int, C.POINTER(KRolloutDev), vp]
     lib.kmanip_feedback.argtypes = [vp, C.POINTER(KFeedbackIn), C.c_int, C.c_int, C.c_int, C.POINTER(KFeedbackDev), vp]
     lib.kmanip_feedback_box.argtypes = [vp, C.POINTER(KFeedbackBoxIn), C.c_int, C.c_int, C.c_int, C.POINTER(KFeedbackDev), vp]
