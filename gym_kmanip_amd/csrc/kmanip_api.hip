@@ -722,6 +722,33 @@ int kmanip_lqr_backward_box(KHandle h, const KLqrBoxIn* in, int n, int T, const 
   return 0;
 }
 
+// The adjoint sweep of a rollout for n problems of T steps and m cotangent vectors each (include/kmanip.h KAdjointIn / KAdjointDev;
+// kmanip_adjoint.hip).  One launch; the handle gives the device and the size class and is only read.
+int kmanip_adjoint(KHandle h, const KAdjointIn* in, int n, int T, int m, const KAdjointDev* out, void* stream) {
+  if (!h) { g_create_error = "kmanip_adjoint: null handle"; return -1; }
+  if (!in) { h->err = "kmanip_adjoint: the KAdjointIn pointer is NULL"; return -1; }
+  if (!out) { h->err = "kmanip_adjoint: the KAdjointDev pointer is NULL"; return -1; }
+  if (n < 0) { h->err = "kmanip_adjoint: n is negative"; return -1; }
+  if (T < 0) { h->err = "kmanip_adjoint: T is negative"; return -1; }
+  if (m < 0) { h->err = "kmanip_adjoint: m is negative"; return -1; }
+  if (n == 0 || T == 0 || m == 0) return 0;      // (tensors of no problems, steps or vectors have no address: nothing below is asked of them)
+  if (!in->a_t) { h->err = "kmanip_adjoint: KAdjointIn::a_t is NULL"; return -1; }
+  if (!in->b_t) { h->err = "kmanip_adjoint: KAdjointIn::b_t is NULL"; return -1; }
+  if (!in->gx) { h->err = "kmanip_adjoint: KAdjointIn::gx is NULL"; return -1; }
+  const int64_t nx = h->desc.nlink <= 10 ? 32 : 52, nu = h->desc.nlink <= 10 ? 10 : 20;      // (kmanip_adjoint.hip's two classes)
+  if (in->a_stride != 0 && in->a_stride < nx * nx) { h->err = "kmanip_adjoint: a_stride is smaller than an [nx, nx] block"; return -1; }
+  if (in->b_stride != 0 && in->b_stride < nu * nx) { h->err = "kmanip_adjoint: b_stride is smaller than an [nu, nx] block"; return -1; }
+  if ((long long)n * m > 2147483647LL || (long long)n * m * T > 2147483647LL) { h->err = "kmanip_adjoint: n * m * T row steps are more than an int counts"; return -1; }
+  if (!out->lam && !out->mu) return 0;
+  KAdjointIn ai = *in;
+  if (!ai.a_stride) ai.a_stride = nx * nx;
+  if (!ai.b_stride) ai.b_stride = nu * nx;
+  KM_ENTER(h);
+  kmanip_launch_adjoint(h->desc, ai, n, T, m, *out, (hipStream_t)stream);
+  HIPCHK(h, hipGetLastError());
+  return 0;
+}
+
 // One helper of the kernels' math headers over n rows (include/kmanip_debug.h; kmanip_mathprobe.hip).  One
 // launch; the handle gives the device and is only read.
 int kmanip_dbg_math(KHandle h, int fn, int n, const double* in_dev, int in_cols, double* out_dev, int out_cols, void* stream) {

@@ -610,6 +610,8 @@ void kmanip_launch_transfd(const KDeviceModel* dm, const KModelDesc& hd, const K
 void kmanip_launch_lqr_backward(const KModelDesc& hd, const KLqrIn& in, int n, int T, const KLqrDev& out, hipStream_t stream);
 // kmanip_lqr_backward_box (kmanip_lqr_box.hip): likewise
 void kmanip_launch_lqr_backward_box(const KModelDesc& hd, const KLqrBoxIn& in, int n, int T, const KLqrBoxDev& out, hipStream_t stream);
+// kmanip_adjoint (kmanip_adjoint.hip): n > 0 problems of T > 0 steps and m > 0 vectors each, the strides resolved; the class likewise
+void kmanip_launch_adjoint(const KModelDesc& hd, const KAdjointIn& in, int n, int T, int m, const KAdjointDev& out, hipStream_t stream);
 // kmanip_dbg_math (kmanip_mathprobe.hip): the columns of function fn (false: no such function), and its launch over n > 0 rows
 bool kmanip_math_probe_cols(int fn, int* in_cols, int* out_cols);
 void kmanip_launch_math_probe(int fn, int n, const double* in, double* out, hipStream_t stream);

@@ -157,6 +157,42 @@ def transition_fd(env, envs=None, qpos=None, qvel=None, ctrl=None, qfrc_applied=
     return out
 
 
+def adjoint_pass(A, B, gx, gu=None, gains=None, m=1):
+    """The adjoint sweep of a rollout: THE DEFINITION kmanip_adjoint is held to (include/kmanip.h KAdjointIn).
+    A [n, T, nx, nx], B [n, T, nx, nu] the step Jacobians (trajectory_fd's); m >= 1 cotangent vectors per problem, row e m + j
+    carrying vector j through the dynamics of problem e; gx [n m, T + 1, nx] the loss's direct partials with respect to the tangent
+    state x_t (entry 0: x_0, entry T: the final state), gu [n m, T, nu] those with respect to u_t or None (zeros); gains
+    [n, T, nu, nx] the feedback K_t of a closed-loop rollout u_t = ctrl_t + K_t dx_t, or None (open loop).  lam[T] = gx[T]; for
+    t = T-1 .. 0
+        mu[t]  = gu[t] + B_t' lam[t+1]
+        lam[t] = gx[t] + A_t' lam[t+1] + K_t' mu[t]
+    the direct term added last.  Returns (lam [n m, T + 1, nx], mu [n m, T, nu]): lam[:, 0] is the gradient with respect to the
+    initial tangent state, mu the gradient with respect to the control that acted (the open-loop term); the gradient with respect to
+    K_t is the outer product mu[t] (x) dx_t.  With gains, dx_t is taken as linear in the state (QuadraticCost's Gauss-Newton
+    habit): exact when the cube-rotation columns of K are zero.  A torch loop over the T steps, on the device of the tensors."""
+    import torch
+    n, T, nx, nu = B.shape
+    m = int(m)
+    if tuple(gx.shape) != (n * m, T + 1, nx):
+        raise ValueError("adjoint_pass: gx must be [n m, T + 1, nx] = %s, not %s" % ((n * m, T + 1, nx), tuple(gx.shape)))
+    g = gx.reshape(n, m, T + 1, nx)
+    h = None if gu is None else gu.reshape(n, m, T, nu)
+    lam = torch.empty((n, m, T + 1, nx), dtype=A.dtype, device=A.device)
+    mu = torch.empty((n, m, T, nu), dtype=A.dtype, device=A.device)
+    nxt = g[:, :, T]
+    lam[:, :, T] = nxt
+    for t in range(T - 1, -1, -1):
+        u = nxt @ B[:, t]                                 # rows of lam[t+1]' B_t = (B_t' lam[t+1])'
+        if h is not None:
+            u = u + h[:, :, t]
+        s = nxt @ A[:, t]
+        if gains is not None:
+            s = s + u @ gains[:, t]
+        nxt = s + g[:, :, t]
+        mu[:, :, t], lam[:, :, t] = u, nxt
+    return lam.reshape(n * m, T + 1, nx), mu.reshape(n * m, T, nu)
+
+
 def forward_fd(env, envs=None, qpos=None, qvel=None, ctrl=None, qfrc_applied=None, eps=1e-6,
                wrt=("qpos", "qvel", "ctrl", "qfrc_applied"), warm_offset=1.0):
     """Centred finite differences of env.forward's qacc and qfrc_constraint with respect to the inputs named in `wrt`, at the rows

@@ -535,6 +535,85 @@ class KManipEnvHip:
     _LQR_FIELDS = {"k": (("T", "nu"), "float64"), "gain_t": (("T", "nx", "nu"), "float64"), "dv": ((2,), "float64"),
                    "status": (None, "uint8"), "fail_step": (None, "int32")}
 
+    def _dyn_in(self, what, li, n, T, A, B, deriv_t, ncol=None):
+        """The step Jacobians of n problems of T steps set in `li` (a_t, b_t, a_stride, b_stride: KLqrIn's and KAdjointIn's first four
+        fields): deriv_t [n, T, ncol, nx] read where it lies (ncol = nx + nu unless the caller allows more columns after them), or A
+        and B through one transposed contiguous copy each.  Returns the tensors the caller holds until the launch."""
+        torch = _torch()
+        nx, nu, f64 = 2 * self.cm.nv, self.cm.nu, torch.float64
+        if (deriv_t is None) == (A is None and B is None) or (A is None) != (B is None):
+            raise _libmod.KManipError("%s: give deriv_t, or A and B" % what)
+        if deriv_t is not None:
+            ncol = nx + nu if ncol is None else ncol
+            self._check_buf(deriv_t, (n, T, ncol, nx), f64, "deriv_t")
+            li.a_t, li.b_t = deriv_t.data_ptr(), deriv_t.data_ptr() + 8 * nx * nx
+            li.a_stride = li.b_stride = ncol * nx
+            return (deriv_t,)
+        for name, t, shape in (("A", A, (n, T, nx, nx)), ("B", B, (n, T, nx, nu))):
+            if not isinstance(t, torch.Tensor) or tuple(t.shape) != shape:
+                raise _libmod.KManipError("%s: %s must be a tensor of shape %s" % (what, name, shape))
+        a_t, b_t = A.transpose(2, 3).contiguous(), B.transpose(2, 3).contiguous()
+        self._check_buf(a_t, (n, T, nx, nx), f64, "A")
+        self._check_buf(b_t, (n, T, nu, nx), f64, "B")
+        li.a_t, li.b_t, li.a_stride, li.b_stride = a_t.data_ptr(), b_t.data_ptr(), 0, 0
+        return (a_t, b_t)
+
+    # KAdjointDev field -> (trailing shape, dtype name); the leading dimension is n m rows
+    _ADJOINT_FIELDS = {"lam": (("T1", "nx"), "float64"), "mu": (("T", "nu"), "float64")}
+
+    def adjoint(self, gx, gu=None, A=None, B=None, deriv_t=None, gains=None, gains_t=None, m=1, out=None):
+        """kmanip_adjoint: derivatives.adjoint_pass -- the adjoint sweep of a rollout, the gradient of a scalar loss with respect to
+        the controls and the initial state -- for n problems of T steps and m cotangent vectors each in ONE launch on the current
+        stream, a workgroup per problem with the loop over the steps inside the kernel and each step's Jacobians read once for all
+        m vectors (no synchronisation; the handle gives the device and the sizes and is only read).
+          gx [n m, T + 1, nx], gu [n m, T, nu] or None (zeros): the loss's direct partials, row e m + j vector j of problem e.
+          deriv_t [n, T, ncol >= nx + nu, nx]: transition_fd's buffer, read where it lies (columns after ctrl's are skipped by the
+            stride), or A [n, T, nx, nx] and B [n, T, nx, nu], which get one transposed contiguous copy each.
+          gains [n, T, nu, nx] (one transposed copy) or gains_t [n, T, nx, nu] (rollout_feedback's, lqr_backward's; no copy), or
+            neither: open loop.
+        Returns dict(lam [n m, T + 1, nx], mu [n m, T, nu]) by adjoint_pass's recursion; include/kmanip.h KAdjointIn states the
+        order of every sum.  `out`: a dict of tensors to fill, keyed lam / mu; only the fields it names are computed."""
+        torch = _torch()
+        nx, nu, f64 = 2 * self.cm.nv, self.cm.nu, torch.float64
+        m = int(m)
+        if m < 1:
+            raise _libmod.KManipError("adjoint: m must be at least 1")
+        if not isinstance(gx, torch.Tensor) or gx.dim() != 3 or gx.shape[0] % m or gx.shape[1] < 1:
+            raise _libmod.KManipError("adjoint: gx must be a [n m, T + 1, nx] tensor")
+        n, T = int(gx.shape[0]) // m, int(gx.shape[1]) - 1
+        ai = _libmod.KAdjointIn()
+        ncol = None
+        if isinstance(deriv_t, torch.Tensor) and deriv_t.dim() == 4 and deriv_t.shape[2] > nx + nu:
+            ncol = int(deriv_t.shape[2])
+        keep = self._dyn_in("adjoint", ai, n, T, A, B, deriv_t, ncol=ncol)
+        gx = gx.contiguous()
+        self._check_buf(gx, (n * m, T + 1, nx), f64, "gx")
+        ai.gx = gx.data_ptr()
+        keep += (gx,)
+        if gu is not None:
+            gu = gu.contiguous() if isinstance(gu, torch.Tensor) else gu
+            self._check_buf(gu, (n * m, T, nu), f64, "gu")
+            ai.gu = gu.data_ptr()
+            keep += (gu,)
+        if gains is not None and gains_t is not None:
+            raise _libmod.KManipError("adjoint: give gains or gains_t, not both")
+        if gains is not None:
+            if not isinstance(gains, torch.Tensor) or tuple(gains.shape) != (n, T, nu, nx):
+                raise _libmod.KManipError("adjoint: gains must be a tensor of shape %s" % ((n, T, nu, nx),))
+            gains_t = gains.transpose(2, 3)
+        if gains_t is not None:
+            gains_t = gains_t.contiguous() if isinstance(gains_t, torch.Tensor) else gains_t
+            self._check_buf(gains_t, (n, T, nx, nu), f64, "gains_t")
+            ai.gain_t = gains_t.data_ptr()
+            keep += (gains_t,)
+        ad = _libmod.KAdjointDev()
+        res = self._query_out(self._ADJOINT_FIELDS, (n * m,), {"T": T, "T1": T + 1, "nx": nx, "nu": nu}, out, None, ad, "adjoint")
+        if n > 0 and T == 0 and "lam" in res:          # (nothing is launched: lam[T] = gx[T] is all there is)
+            res["lam"].copy_(gx)
+        self._check(self.L.kmanip_adjoint(self.h, C.byref(ai), n, T, m, C.byref(ad), self._stream()), "kmanip_adjoint")
+        del keep                             # (the stream orders the launch before the allocator reuses the copies)
+        return res
+
     def _lqr_in(self, what, li, lx, lu, lxx, luu, A, B, deriv_t, reg):
         """The checked inputs of lqr_backward() / lqr_backward_box() set in the KLqrIn `li`.  Returns (n, T, the tensors the caller
         holds until the launch)."""
@@ -543,22 +622,7 @@ class KManipEnvHip:
         if not isinstance(lu, torch.Tensor) or lu.dim() != 3:
             raise _libmod.KManipError("%s: lu must be a [n, T, nu] tensor" % what)
         n, T = int(lu.shape[0]), int(lu.shape[1])
-        if (deriv_t is None) == (A is None and B is None) or (A is None) != (B is None):
-            raise _libmod.KManipError("%s: give deriv_t, or A and B" % what)
-        if deriv_t is not None:
-            self._check_buf(deriv_t, (n, T, nx + nu, nx), f64, "deriv_t")
-            li.a_t, li.b_t = deriv_t.data_ptr(), deriv_t.data_ptr() + 8 * nx * nx
-            li.a_stride = li.b_stride = (nx + nu) * nx
-            keep = (deriv_t,)
-        else:
-            for name, t, shape in (("A", A, (n, T, nx, nx)), ("B", B, (n, T, nx, nu))):
-                if not isinstance(t, torch.Tensor) or tuple(t.shape) != shape:
-                    raise _libmod.KManipError("%s: %s must be a tensor of shape %s" % (what, name, shape))
-            a_t, b_t = A.transpose(2, 3).contiguous(), B.transpose(2, 3).contiguous()
-            self._check_buf(a_t, (n, T, nx, nx), f64, "A")
-            self._check_buf(b_t, (n, T, nu, nx), f64, "B")
-            li.a_t, li.b_t, li.a_stride, li.b_stride = a_t.data_ptr(), b_t.data_ptr(), 0, 0
-            keep = (a_t, b_t)
+        keep = self._dyn_in(what, li, n, T, A, B, deriv_t)
         # (the cost's derivatives come as torch made them -- QuadraticCost hands an einsum's strided lx and an expanded luu: a view
         # gets one contiguous copy, everything else about it is checked)
         dense = lambda t: t.contiguous() if isinstance(t, torch.Tensor) else t

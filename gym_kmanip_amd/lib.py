@@ -19,7 +19,7 @@ _lib = None
 # every symbol include/kmanip.h declares (tests check the library exports all of them)
 EXPORTS = [
     "kmanip_model_desc_size", "kmanip_create", "kmanip_reset", "kmanip_step", "kmanip_step_chunk", "kmanip_get_state",
-    "kmanip_set_state", "kmanip_get_episode", "kmanip_set_episode", "kmanip_get_counters", "kmanip_bind_sim_time", "kmanip_bind_applied_force", "kmanip_bind_reward_done_record", "kmanip_select_reward_done_record", "kmanip_observe", "kmanip_forces", "kmanip_kinematics", "kmanip_inverse", "kmanip_forward", "kmanip_kinematics_rows", "kmanip_site_cost", "kmanip_rollout", "kmanip_feedback", "kmanip_feedback_box", "kmanip_transition_fd", "kmanip_lqr_backward", "kmanip_lqr_backward_box", "kmanip_set_seed", "kmanip_get_diag", "kmanip_timing_summary", "kmanip_enable_timing", "kmanip_ik", "kmanip_ik_eval",
+    "kmanip_set_state", "kmanip_get_episode", "kmanip_set_episode", "kmanip_get_counters", "kmanip_bind_sim_time", "kmanip_bind_applied_force", "kmanip_bind_reward_done_record", "kmanip_select_reward_done_record", "kmanip_observe", "kmanip_forces", "kmanip_kinematics", "kmanip_inverse", "kmanip_forward", "kmanip_kinematics_rows", "kmanip_site_cost", "kmanip_rollout", "kmanip_feedback", "kmanip_feedback_box", "kmanip_transition_fd", "kmanip_lqr_backward", "kmanip_lqr_backward_box", "kmanip_adjoint", "kmanip_set_seed", "kmanip_get_diag", "kmanip_timing_summary", "kmanip_enable_timing", "kmanip_ik", "kmanip_ik_eval",
     "kmanip_render_depth", "kmanip_render_rgb", "kmanip_render_rgb_multi", "kmanip_render_labels_multi", "kmanip_render_seg", "kmanip_set_render_links", "kmanip_get_render_links", "kmanip_set_depth_links", "kmanip_get_depth_links", "kmanip_get_camera_poses", "kmanip_render_points", "kmanip_snapshot_render_state", "kmanip_set_render_source", "kmanip_bind_step_depth", "kmanip_scripted_action", "kmanip_sample_action", "kmanip_set_env_params", "kmanip_get_env_params", "kmanip_set_env_param_ranges", "kmanip_set_visual_params", "kmanip_get_visual_params", "kmanip_set_visual_param_ranges",
     "kmanip_get_state_dev", "kmanip_set_state_dev", "kmanip_copy_envs", "kmanip_state_index_errors", "kmanip_num_envs", "kmanip_last_error", "kmanip_version", "kmanip_destroy",
 ]
@@ -167,6 +167,18 @@ class KLqrBoxDev(C.Structure):
     _fields_ = [("lqr", KLqrDev), ("clamped", C.c_void_p), ("qp_iters", C.c_void_p)]
 
 
+class KAdjointIn(C.Structure):
+    """include/kmanip.h KAdjointIn: DEVICE pointers of kmanip_adjoint's inputs -- KLqrIn's transposed step Jacobians and strides, the
+    loss's direct partials gx [n m, T + 1, nx] and gu [n m, T, nu] (NULL: zeros), and the transposed gains [n, T, nx, nu] (NULL: open loop)."""
+    _fields_ = [("a_t", C.c_void_p), ("b_t", C.c_void_p), ("a_stride", C.c_int64), ("b_stride", C.c_int64), ("gx", C.c_void_p),
+                ("gu", C.c_void_p), ("gain_t", C.c_void_p)]
+
+
+class KAdjointDev(C.Structure):
+    """include/kmanip.h KAdjointDev: DEVICE pointers of kmanip_adjoint's outputs lam [n m, T + 1, nx] and mu [n m, T, nu], either NULL."""
+    _fields_ = [("lam", C.c_void_p), ("mu", C.c_void_p)]
+
+
 KM_WRT = {"qpos": 1, "qvel": 2, "ctrl": 4, "qfrc_applied": 8}     # include/kmanip.h KM_WRT_*: the columns always run in this order
 KM_MAX_LINK_CAPSULES = 24
 KM_COPY_EPISODE, KM_COPY_ENV_PARAMS = 1, 2       # include/kmanip.h: flags of kmanip_copy_envs
@@ -226,6 +238,7 @@ def load():
     lib.kmanip_transition_fd.argtypes = [vp, C.POINTER(KTransFdIn), C.c_int, C.c_int, C.POINTER(KTransFdDev), vp]
     lib.kmanip_lqr_backward.argtypes = [vp, C.POINTER(KLqrIn), C.c_int, C.c_int, C.POINTER(KLqrDev), vp]
     lib.kmanip_lqr_backward_box.argtypes = [vp, C.POINTER(KLqrBoxIn), C.c_int, C.c_int, C.POINTER(KLqrBoxDev), vp]
+    lib.kmanip_adjoint.argtypes = [vp, C.POINTER(KAdjointIn), C.c_int, C.c_int, C.c_int, C.POINTER(KAdjointDev), vp]
     lib.kmanip_set_seed.argtypes = [vp, C.c_uint64, C.c_int]
     lib.kmanip_get_diag.argtypes = [vp, C.POINTER(C.c_uint32), i32p, i32p]
     lib.kmanip_timing_summary.argtypes = [vp, f64p, f64p, f64p, i32p]

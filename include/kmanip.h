@@ -851,6 +851,46 @@ typedef struct KLqrBoxDev { /* any field may be NULL */
  * OUT OF SCOPE: per-step bounds, a cross term lux, a warm start of the QP from an earlier pass, forcerange-aware planning. */
 KMANIP_API int kmanip_lqr_backward_box(KHandle h, const KLqrBoxIn* in, int n, int T, const KLqrBoxDev* out, void* stream);
 
+/* The ADJOINT sweep of a rollout -- the first-order use of the step Jacobians (gym_kmanip_amd/derivatives.py
+ * adjoint_pass is the definition, gym_kmanip_amd/grad.py builds rollout_grad, rollout_jacobian and diff_rollout on it): the gradient
+ * of a scalar loss on a trajectory with respect to the controls and the initial state, for n problems of T steps and m >= 1
+ * COTANGENT VECTORS per problem in ONE launch.  Row r = e * m + j carries vector j through the dynamics of problem e, which are
+ * addressed exactly as in KLqrIn (a_t, b_t, a_stride, b_stride, transposed blocks: kmanip_transition_fd's deriv_t is read where it
+ * lies, and a deriv_t that also carries the qfrc_applied columns works through the stride alone).  With gx the loss's direct partials
+ * with respect to the tangent state x_t, gu those with respect to u_t, lam[T] = gx[T], for t = T-1 .. 0:
+ *   mu[t]_i  = gu[t]_i + sum_k B_t[k][i] lam[t+1]_k
+ *   lam[t]_j = gx[t]_j + sum_k A_t[k][j] lam[t+1]_k + sum_i K_t[i][j] mu[t]_i         (the last sum only when gains are given)
+ * lam[0] is the gradient with respect to the initial tangent state, mu[t] the gradient with respect to the control that ACTED at
+ * step t -- the gradient with respect to ctrl of an open-loop rollout, and with respect to the open-loop term of kmanip_feedback's
+ * policy u = ctrl + K dx.  The gradient with respect to K_t is the outer product mu[t] (x) dx_t: torch arithmetic for the caller.
+ * THE ORDER OF EVERY SUM: one FMA chain from 0 over k ascending, for lam continued over i ascending, then ONE add of the direct term
+ * (gx or gu; a NULL gu adds 0.0).  A row's result does not depend on n, on m or on the row's place; with every gain entry zero the
+ * bytes are the open-loop ones.
+ * THE ONE APPROXIMATION: with gains, dx_t = tangent_diff(x_t, ref_t) is taken as linear in the state (the log map's Jacobian at the
+ * cube's rotation as the identity, QuadraticCost's Gauss-Newton habit): exact when the cube-rotation columns of K (those rows of gain_t) are zero. */
+typedef struct KAdjointIn {
+  const double* a_t;        /* KLqrIn::a_t: block (e, t) at a_t + (e*T + t) * a_stride, [nx, nx] TRANSPOSED */
+  const double* b_t;        /* KLqrIn::b_t: block (e, t) at b_t + (e*T + t) * b_stride, [nu, nx] */
+  int64_t a_stride, b_stride; /* in doubles; 0 = dense (nx*nx, nu*nx) */
+  const double* gx;         /* [n*m, T+1, nx]; entry 0 belongs to x_0, entry T to the final state */
+  const double* gu;         /* [n*m, T, nu], or NULL = zeros */
+  const double* gain_t;     /* [n, T, nx, nu]: KFeedbackIn::gain_t's layout, a trajectory per problem; NULL = open loop */
+} KAdjointIn;
+typedef struct KAdjointDev { /* either field may be NULL */
+  double* lam;              /* [n*m, T+1, nx] */
+  double* mu;               /* [n*m, T, nu] */
+} KAdjointDev;
+/* NO STATUS: nothing is factorised, and a non-finite input propagates as IEEE arithmetic propagates it, into the outputs of the rows
+ * that read it only (a NaN in one row's gx stays in that row; one in A_t reaches every row of its problem).
+ * ONE kernel launch, asynchronous on `stream`: no allocation, no synchronisation, no host copy.  THE HANDLE IS READ ONLY (it gives
+ * the device, nx and nu).  n == 0, T == 0 or m == 0 succeeds and launches nothing (the fields of `in` are then not looked at).
+ * ERRORS: a NULL handle, `in` or `out`, a NULL a_t, b_t or gx, n < 0, T < 0 or m < 0, a nonzero stride smaller than its block, or
+ * n * m * T beyond int return nonzero with kmanip_last_error set, launch nothing and leave the outputs untouched.
+ * OUT OF SCOPE: gradients through the clamped policy of kmanip_feedback_box, with respect to qfrc_applied, the model's parameters or
+ * the warm start (the solver's starting point, not a state), second-order terms, the gradient with respect to the references of the
+ * policy (-K' mu: one line for the caller), analytic step derivatives. */
+KMANIP_API int kmanip_adjoint(KHandle h, const KAdjointIn* in, int n, int T, int m, const KAdjointDev* out, void* stream);
+
 /* KManipEnv.reset(seed=...) (env_base.py:219-220): re-key the cube-spawn stream.  restart_episodes != 0 also rewinds every
  * env's episode counter so that the next kmanip_reset draws episode 0 of the new seed (reset(seed=s) is then reproducible). */
 KMANIP_API int kmanip_set_seed(KHandle h, uint64_t seed, int restart_episodes);
