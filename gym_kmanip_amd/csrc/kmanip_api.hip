@@ -269,11 +269,7 @@ static double trace_robot_of(const KModelDesc& d) {
   const double nv = d.nlink + 6;
   return d.meaninertia * nv - (3.0 * d.cube_mass + ((d.cube_inertia[0] + d.cube_inertia[1]) + d.cube_inertia[2]));
 }
-// the limits every parameter value must meet (the ranges' lo and hi as well)
-__host__ __device__ static inline bool ep_value_ok(int k, double v) {
-  if (!(v - v == 0.0)) return false;           // NaN or infinite (host and device alike)
-  return (k == KM_EP_CUBE_MASS || k == KM_EP_KP_SCALE) ? v > 0 : v >= 0;
-}
+// (the limits every parameter value must meet, the ranges' lo and hi as well: ep_value_ok of kmanip_device.hpp)
 __global__ void k_ep_validate(const double* __restrict__ p, int n, int* __restrict__ bad) {
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
     bool ok = true;
@@ -656,6 +652,36 @@ int kmanip_transition_fd(KHandle h, const KTransFdIn* in, int n, int nsub, const
     kmanip_launch_transfd(h->dmodel, h->desc, h->st, *in, n, ncol, ns, cos(0.5 * in->eps), sin(0.5 * in->eps), *out, s);
     HIPCHK(h, hipGetLastError());
   }
+  return 0;
+}
+
+// Centred finite differences of ONE step in the per-env physics parameters at rows the caller passes (include/kmanip.h KParamFdIn /
+// KParamFdDev; kmanip_paramfd.hip).  One launch; the handle is only read; the handle's solver; always a
+// per-env parameter build, on a handle without parameters over the compiled model's values.
+int kmanip_param_fd(KHandle h, const KParamFdIn* in, int n, int nsub, const KParamFdDev* out, void* stream) {
+  if (!h) { g_create_error = "kmanip_param_fd: null handle"; return -1; }
+  if (row_args(h, "kmanip_param_fd", "KParamFdIn", "KParamFdDev", in, out, n)) return -1;
+  if (nsub < 0) { h->err = "kmanip_param_fd: nsub is negative"; return -1; }
+  const int wrt = in->wrt;
+  if (wrt & ~((1 << KM_EP_N) - 1)) { h->err = "kmanip_param_fd: wrt has bits outside the KM_EP_* parameters"; return -1; }
+  if (!(in->warm_offset - in->warm_offset == 0.0)) { h->err = "kmanip_param_fd: warm_offset is not finite"; return -1; }
+  int npar = 0;
+  for (int k = 0; k < KM_EP_N; k++) {
+    if (!((wrt >> k) & 1)) continue;
+    npar++;
+    if (!(in->eps[k] - in->eps[k] == 0.0) || !(in->eps[k] > 0.0)) {
+      h->err = "kmanip_param_fd: eps[" + std::to_string(k) + "] of a selected parameter is not a finite positive number";
+      return -1;
+    }
+  }
+  if (n == 0 || wrt == 0) return 0;    // (tensors of no rows have no address: nothing below is asked of them)
+  if (!out->deriv_t) { h->err = "kmanip_param_fd: wrt is set and KParamFdDev::deriv_t is NULL"; return -1; }
+  if (2LL * npar * n > 2147483647LL) { h->err = "kmanip_param_fd: 2 npar n perturbed rows are more than an int counts"; return -1; }
+  KM_ENTER(h);
+  const KModelDesc& d = h->desc;
+  const KEnvParamDefaults model{{d.cube_mass, d.con_cube_friction[0], d.cube_frictionloss, 1.0}};
+  kmanip_launch_paramfd(h->dmodel, h->desc, h->st, *in, model, n, npar, nsub ? nsub : d.n_sub_steps, *out, (hipStream_t)stream);
+  HIPCHK(h, hipGetLastError());
   return 0;
 }
 

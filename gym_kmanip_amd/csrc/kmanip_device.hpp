@@ -605,6 +605,18 @@ void kmanip_launch_boxfb(const KDeviceModel* dm, const KModelDesc& hd, const KDe
 // sh = cos / sin of eps / 2; the applied-force build also while in.wrt has KM_WRT_FRC
 void kmanip_launch_transfd(const KDeviceModel* dm, const KModelDesc& hd, const KDeviceState& st, const KTransFdIn& in, int n, int ncol,
                            int nsub, double ch, double sh, const KTransFdDev& out, hipStream_t stream);
+// the limits every per-env parameter value must meet (kmanip_set_env_params, the ranges' lo and hi, k_paramfd's rows and perturbed values)
+__host__ __device__ static inline bool ep_value_ok(int k, double v) {
+  if (!(v - v == 0.0)) return false;           // NaN or infinite (host and device alike)
+  return (k == KM_EP_CUBE_MASS || k == KM_EP_KP_SCALE) ? v > 0 : v >= 0;
+}
+// the compiled model's KM_EP_* values, by value: what a NULL parameter source means on a handle without per-env parameters
+struct KEnvParamDefaults { double v[KM_EP_N]; };
+// kmanip_param_fd (kmanip_paramfd.hip; either solver: the handle's): the n * npar > 0 column pairs of n rows, nsub > 0 sub-steps.  ALWAYS
+// a per-env parameter build, whatever KDeviceState::envp says (model: the values of a handle that has none); the applied-force build
+// while the caller gives a force or one is bound
+void kmanip_launch_paramfd(const KDeviceModel* dm, const KModelDesc& hd, const KDeviceState& st, const KParamFdIn& in,
+                           const KEnvParamDefaults& model, int n, int npar, int nsub, const KParamFdDev& out, hipStream_t stream);
 // kmanip_lqr_backward (kmanip_lqr.hip): n > 0 problems of T > 0 steps, in.a_stride / in.b_stride resolved (never 0); the size class
 // (nx, nu) is the handle's link-count class
 void kmanip_launch_lqr_backward(const KModelDesc& hd, const KLqrIn& in, int n, int T, const KLqrDev& out, hipStream_t stream);
@@ -683,7 +695,6 @@ struct KStateSide {
   int stride, range, staged;
 };
 struct KStateShape { int K[KS_NFIELD]; };
-struct KEnvParamDefaults { double v[KM_EP_N]; };
 // state -> tensors (import = false) or tensors -> state, rows 0 .. n-1 of the tensors, ONE launch
 void kmanip_launch_state_io(const KModelDesc& hd, const KStateSide& state, const KStateSide& tensors, int n, bool import, unsigned long long* errors,
                             hipStream_t stream);

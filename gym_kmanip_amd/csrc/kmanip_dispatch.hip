@@ -8,6 +8,8 @@
 // KDeviceState::qfrc_applied is set), both.  A reset ignores the force, and so do kmanip_kinematics and kmanip_inverse: no force builds.
 #define KM_BUILDS_PAR(X) X() X(ep_)
 #define KM_BUILDS(X) KM_BUILDS_PAR(X) X(frc_) X(ep_frc_)
+// the builds of kmanip_paramfd.hip, always a parameter build (index = FRC)
+#define KM_BUILDS_EP(X) X(ep_) X(ep_frc_)
 #define KM_NAME(kind, B, NL, G, S) kmanip_launch_##kind##_##B##NL##_##G##S
 
 typedef void StepFn(const KDeviceModel*, const KDeviceState&, const float*, double*, double*, uint8_t*, int, int, hipStream_t);
@@ -23,6 +25,7 @@ typedef void SiteCostFn(const KDeviceModel*, const KDeviceState&, const KSiteCos
 typedef void RolloutFn(const KDeviceModel*, const KDeviceState&, const KRolloutIn&, int, int, int, const KRolloutDev&, hipStream_t);
 typedef void FeedbackFn(const KDeviceModel*, const KDeviceState&, const KFeedbackIn&, int, int, int, const KFeedbackDev&, hipStream_t);
 typedef void BoxFbFn(const KDeviceModel*, const KDeviceState&, const KFeedbackBoxIn&, int, int, int, const KFeedbackDev&, hipStream_t);
+typedef void ParamFdFn(const KDeviceModel*, const KDeviceState&, const KParamFdIn&, const KEnvParamDefaults&, int, int, int, const KParamFdDev&, hipStream_t);
 typedef void TransFdFn(const KDeviceModel*, const KDeviceState&, const KTransFdIn&, int, int, int, double, double, const KTransFdDev&, hipStream_t);
 
 // kmanip_dyn.hip: step per solver in every build, reset per solver in the parameter builds; observe and prepare are
@@ -37,6 +40,8 @@ typedef void TransFdFn(const KDeviceModel*, const KDeviceState&, const KTransFdI
 #define KM_BOXFB_ROW(B, NL, G) {KM_NAME(boxfb, B, NL, G, _0), KM_NAME(boxfb, B, NL, G, _1)},
 // kmanip_transfd.hip: likewise
 #define KM_TRANSFD_ROW(B, NL, G) {KM_NAME(transfd, B, NL, G, _0), KM_NAME(transfd, B, NL, G, _1)},
+// kmanip_paramfd.hip: per solver, the two parameter builds
+#define KM_PARAMFD_ROW(B, NL, G) {KM_NAME(paramfd, B, NL, G, _0), KM_NAME(paramfd, B, NL, G, _1)},
 #define KM_OBSERVE_ROW(B, NL, G) KM_NAME(observe, B, NL, G, _1),
 #define KM_PREPARE_ROW(B, NL, G) KM_NAME(prepare, B, NL, G, _1),
 // kmanip_forces.hip and kmanip_forward.hip (the Newton classes, every build), kmanip_kinematics.hip and kmanip_inverse.hip (one object per class serves both
@@ -53,9 +58,11 @@ typedef void TransFdFn(const KDeviceModel*, const KDeviceState&, const KTransFdI
 #define KM_DECL_FRC(B, NL, G) KM_DECL_SOLVERS(StepFn, step, B, NL, G) KM_DECL_SOLVERS(RolloutFn, rollout, B, NL, G) KM_DECL_SOLVERS(FeedbackFn, feedback, B, NL, G) KM_DECL_SOLVERS(BoxFbFn, boxfb, B, NL, G) KM_DECL_SOLVERS(TransFdFn, transfd, B, NL, G) ForcesFn KM_NAME(forces, B, NL, G, ); ForwardFn KM_NAME(forward, B, NL, G, );
 #define KM_DECL_PAR(B, NL, G) KM_DECL_SOLVERS(ResetFn, reset, B, NL, G) KinFn KM_NAME(kinematics, B, NL, G, ); InverseFn KM_NAME(inverse, B, NL, G, ); KinRowsFn KM_NAME(kinrows, B, NL, G, ); SiteCostFn KM_NAME(sitecost, B, NL, G, );
 #define KM_DECL_ONCE(B, NL, G) ObserveFn KM_NAME(observe, B, NL, G, _1); PrepareFn KM_NAME(prepare, B, NL, G, _1);
+#define KM_DECL_EP(B, NL, G) KM_DECL_SOLVERS(ParamFdFn, paramfd, B, NL, G)
 #define KM_DECL_BUILD_FRC(B) KM_CLASSES(KM_DECL_FRC, B)
+#define KM_DECL_BUILD_EP(B) KM_CLASSES(KM_DECL_EP, B)
 #define KM_DECL_BUILD_PAR(B) KM_CLASSES(KM_DECL_PAR, B)
-KM_BUILDS(KM_DECL_BUILD_FRC) KM_BUILDS_PAR(KM_DECL_BUILD_PAR) KM_CLASSES(KM_DECL_ONCE, )
+KM_BUILDS(KM_DECL_BUILD_FRC) KM_BUILDS_PAR(KM_DECL_BUILD_PAR) KM_BUILDS_EP(KM_DECL_BUILD_EP) KM_CLASSES(KM_DECL_ONCE, )
 
 // the tables: [build][class][solver], [build][class] or [class]
 #define KM_STEP_BUILD(B) {KM_CLASSES(KM_STEP_ROW, B)},
@@ -70,6 +77,7 @@ KM_BUILDS(KM_DECL_BUILD_FRC) KM_BUILDS_PAR(KM_DECL_BUILD_PAR) KM_CLASSES(KM_DECL
 #define KM_FEEDBACK_BUILD(B) {KM_CLASSES(KM_FEEDBACK_ROW, B)},
 #define KM_BOXFB_BUILD(B) {KM_CLASSES(KM_BOXFB_ROW, B)},
 #define KM_TRANSFD_BUILD(B) {KM_CLASSES(KM_TRANSFD_ROW, B)},
+#define KM_PARAMFD_BUILD(B) {KM_CLASSES(KM_PARAMFD_ROW, B)},
 static constexpr StepFn* step_tab[4][2][2] = {KM_BUILDS(KM_STEP_BUILD)};
 static constexpr ResetFn* reset_tab[2][2][2] = {KM_BUILDS_PAR(KM_RESET_BUILD)};
 static constexpr ObserveFn* observe_tab[2] = {KM_CLASSES(KM_OBSERVE_ROW, )};
@@ -84,6 +92,7 @@ static constexpr RolloutFn* rollout_tab[4][2][2] = {KM_BUILDS(KM_ROLLOUT_BUILD)}
 static constexpr FeedbackFn* feedback_tab[4][2][2] = {KM_BUILDS(KM_FEEDBACK_BUILD)};
 static constexpr BoxFbFn* boxfb_tab[4][2][2] = {KM_BUILDS(KM_BOXFB_BUILD)};
 static constexpr TransFdFn* transfd_tab[4][2][2] = {KM_BUILDS(KM_TRANSFD_BUILD)};
+static constexpr ParamFdFn* paramfd_tab[2][2][2] = {KM_BUILDS_EP(KM_PARAMFD_BUILD)};
 
 static int cls(const KModelDesc& hd) { return hd.nlink <= 10 ? 0 : 1; }
 static int newton(const KModelDesc& hd) { return hd.solver == KM_SOLVER_NEWTON ? 1 : 0; }
@@ -145,6 +154,11 @@ void kmanip_launch_transfd(const KDeviceModel* dm, const KModelDesc& hd, const K
                            int nsub, double ch, double sh, const KTransFdDev& out, hipStream_t stream) {
   const int build = par(st) + ((in.qfrc_applied || st.qfrc_applied || (in.wrt & KM_WRT_FRC)) ? 2 : 0);
   transfd_tab[build][cls(hd)][newton(hd)](dm, st, in, n, ncol, nsub, ch, sh, out, stream);
+}
+// (a parameter build whatever par(st) says: the kernel takes the parameters from its arguments)
+void kmanip_launch_paramfd(const KDeviceModel* dm, const KModelDesc& hd, const KDeviceState& st, const KParamFdIn& in,
+                           const KEnvParamDefaults& model, int n, int npar, int nsub, const KParamFdDev& out, hipStream_t stream) {
+  paramfd_tab[(in.qfrc_applied || st.qfrc_applied) ? 1 : 0][cls(hd)][newton(hd)](dm, st, in, model, n, npar, nsub, out, stream);
 }
 void kmanip_launch_prepare_model(KDeviceModel* dm, const KModelDesc& hd, hipStream_t stream) {
   prepare_tab[cls(hd)](dm, stream);

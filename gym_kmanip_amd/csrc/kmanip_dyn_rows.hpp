@@ -1,8 +1,8 @@
 // kmanip_dyn_rows.hpp -- what the queries that solve share beyond the phase headers: the decode of the Newton path's registers into a
 // KForcesDev row, its writer and the bad-qacc test (k_forces, k_forward; k_rollout's and k_feedback's sub-step spells the test out) and
-// the entry of a kernel over rows the caller passes (k_forward, k_rollout, k_feedback, k_transfd, k_kinrows, k_sitecost), and the quaternion log map of
-// k_feedback, k_transfd and k_sitecost (quat_log_diff).  Included by kmanip_forces.hip,
-// kmanip_forward.hip, kmanip_rollout.hip (the source of k_rollout and k_feedback), kmanip_transfd.hip and kmanip_sitekin.hip only, right after kmanip_dyn_variant.hpp
+// the entry of a kernel over rows the caller passes (k_forward, k_rollout, k_feedback, k_transfd, k_paramfd, k_kinrows, k_sitecost), and the quaternion log map of
+// k_feedback, k_transfd, k_paramfd and k_sitecost (quat_log_diff).  Included by kmanip_forces.hip,
+// kmanip_forward.hip, kmanip_rollout.hip (the source of k_rollout and k_feedback), kmanip_transfd.hip, kmanip_paramfd.hip and kmanip_sitekin.hip only, right after kmanip_dyn_variant.hpp
 // and so inside the build's namespace: the other per-variant objects never see it and stay the ones they were (DESIGN.md sections 25 and 28).
 #pragma once
 

@@ -1,7 +1,7 @@
 // kmanip_dyn_variant.hpp -- the build macros of one per-variant object and the device code of one step, by phase.  Included once,
 // after kmanip_ik_coop.hpp, by each translation unit the Makefile compiles per (links, lanes per env[, solver]) variant:
 // kmanip_dyn.hip, kmanip_forces.hip, kmanip_kinematics.hip, kmanip_inverse.hip, kmanip_forward.hip, kmanip_rollout.hip (the
-// kmanip_feedback_* objects are its too, built with its own KM_VAR_FB), kmanip_transfd.hip and kmanip_sitekin.hip.  It opens the build's namespace; KM_VARIANT_END,
+// kmanip_feedback_* objects are its too, built with its own KM_VAR_FB), kmanip_transfd.hip, kmanip_paramfd.hip (KM_VAR_PAR builds only) and kmanip_sitekin.hip.  It opens the build's namespace; KM_VARIANT_END,
 // after the unit's kernels and launch templates, closes it.
 #pragma once
 #ifndef KM_VAR_NL

@@ -531,7 +531,86 @@ class KManipEnvHip:
             res["contact_mask_fd"] = m.permute(1, 2, 0)
         return res
 
-    # KLqrDev field -> (trailing shape in terms of T / nx / nu, or None for the per-problem fields, dtype name)
+    # KParamFdDev field -> (trailing shape in terms of npar / nx = 2 nv, dtype name)
+    _PARAMFD_FIELDS = {"deriv_t": (("npar", "nx"), "float64"), "status_cols": (("npar",), "uint8"), "contact_mask_fd": (("npar", 2), "int32")}
+
+    def param_fd(self, envs=None, qpos=None, qvel=None, ctrl=None, qfrc_applied=None, warm=None, params=None, nsub=None, eps=1e-4,
+                 relative=True, wrt=ENV_PARAMS, warm_offset=1.0, out=None):
+        """kmanip_param_fd: centred finite differences of ONE step (nsub sub-steps; None = the model's) with respect to the per-env
+        physics parameters named in `wrt` (model.ENV_PARAMS names), in ONE launch: the + and - rows of a column step side by side in
+        one wave with the parameter replaced in the kernel's workspace.  The handle is only read -- its own parameters included --
+        and the call works on a handle that never called set_env_params.  Rows and their None fields as in rollout(); warm None is
+        the named env's stored warm start (there is no nominal launch), and warm + warm_offset starts both rows' first sub-step, as in
+        transition_fd and for its reason.
+          params: {name: [n] tensor or scalar} (unnamed: what the row's env has in force) or an [n, KM_EP_N] tensor, the parameters
+            the rows are differentiated ABOUT; None: the values in force for the named envs (the compiled model's without any).
+          eps: a scalar or {name: value}; relative: e = eps * p_k, else e = eps.  Per column plus = p_k + e, minus = p_k - e and the
+            quotient [tangent_diff(qpos+, qpos-) ; qvel+ - qvel-] / (2.0 * e), every operation rounded on its own.
+        Returns a dict of device tensors:
+          P [n, 2 nv, npar] = d x' / d p, a TRANSPOSED VIEW of deriv_t [n, npar, 2 nv]; the columns in ENV_PARAMS order whatever the
+            order of `wrt`, named by the entry wrt (a tuple)
+          status_cols [n, npar] uint8 and status_fd [n] = its largest entry per row: 0 a derivative; 1 the + or - row stopped; 2 an
+            env index outside the handle; 3 the row's parameters or a perturbed value outside the parameter's limits (the derivative
+            in cube_frictionloss AT 0 is refused: its rows exist only above 0).  Nonzero: the column is zeros
+          contact_mask_fd [npar, 2, n] int32: the mask after the step of every perturbed row, + then - (transition_fd's layout)
+        `out`: a dict of tensors to fill, keyed by the kernel's own outputs (deriv_t, status_cols, contact_mask_fd [n, npar, 2]); only
+        the fields it names are computed, plus deriv_t, which is allocated if missing."""
+        torch = _torch()
+        cm = self.cm
+        wrt = (wrt,) if isinstance(wrt, str) else tuple(wrt)
+        unknown = set(wrt) - set(ENV_PARAMS)
+        if unknown:
+            raise ValueError("unknown env parameter(s) %s (known: %s)" % (sorted(unknown), ", ".join(ENV_PARAMS)))
+        if len(set(wrt)) != len(wrt):
+            raise ValueError("param_fd: a name is repeated in wrt %s" % (wrt,))
+        order = tuple(name for name in ENV_PARAMS if name in wrt)            # the kernel's column order
+        npar = len(order)
+        fi = _libmod.KParamFdIn()
+        given = [("qpos", qpos, (cm.nq,)), ("qvel", qvel, (cm.nv,)), ("qacc_warm", warm, (cm.nv,)), ("ctrl", ctrl, (cm.nu,)),
+                 ("qfrc_applied", qfrc_applied, (cm.nv,))]
+        n, idx = self._query_rows(envs, given, fi)
+        if isinstance(params, dict):
+            unknown = set(params) - set(ENV_PARAMS)
+            if unknown:
+                raise ValueError("unknown env parameter(s) %s (known: %s)" % (sorted(unknown), ", ".join(ENV_PARAMS)))
+            cur = self.get_env_params()
+            rows = torch.arange(n, device=self.device) if idx is None else idx.long().clamp(0, self.num_envs - 1)
+            cols = [cur[name][rows] if params.get(name) is None else
+                    torch.as_tensor(params[name], dtype=torch.float64).to(self.device).expand(n) for name in ENV_PARAMS]
+            params = torch.stack(cols, dim=1).contiguous()
+        if params is not None:
+            self._check_buf(params, (n, len(ENV_PARAMS)), torch.float64, "params")
+            fi.params = params.data_ptr()
+        fi.wrt = sum(1 << ENV_PARAMS.index(name) for name in order)
+        for k, name in enumerate(ENV_PARAMS):
+            fi.eps[k] = float(eps.get(name, 1e-4) if isinstance(eps, dict) else eps)
+        fi.eps_relative, fi.warm_offset = int(bool(relative)), float(warm_offset)
+        names = list(self._PARAMFD_FIELDS) if out is None else list(out)
+        if "deriv_t" not in names:
+            names.append("deriv_t")
+        dims = {"npar": npar, "nx": 2 * cm.nv}
+        res = {}
+        for name in names:
+            if out is not None and name in out:
+                res[name] = out[name]
+            elif name in self._PARAMFD_FIELDS:
+                shp, dt = self._PARAMFD_FIELDS[name]
+                res[name] = torch.empty((n,) + tuple(dims[d] if isinstance(d, str) else d for d in shp), dtype=getattr(torch, dt), device=self.device)
+            else:
+                res[name] = None             # (_query_out names it in its error)
+        fd = _libmod.KParamFdDev()
+        self._query_out(self._PARAMFD_FIELDS, (n,), dims, res, None, fd, "param_fd")
+        self._check(self.L.kmanip_param_fd(self.h, C.byref(fi), n, 0 if nsub is None else int(nsub), C.byref(fd), self._stream()),
+                    "kmanip_param_fd")
+        res["P"] = res["deriv_t"].transpose(1, 2)
+        if "status_cols" in res:
+            res["status_fd"] = res["status_cols"].amax(dim=1) if npar else torch.zeros((n,), dtype=torch.uint8, device=self.device)
+        if "contact_mask_fd" in res:
+            res["contact_mask_fd"] = res["contact_mask_fd"].permute(1, 2, 0)
+        res["wrt"] = order
+        return res
+
+    # KLqrDev field ->(trailing shape in terms of T / nx / nu, or None for the per-problem fields, dtype name)
     _LQR_FIELDS = {"k": (("T", "nu"), "float64"), "gain_t": (("T", "nx", "nu"), "float64"), "dv": ((2,), "float64"),
                    "status": (None, "uint8"), "fail_step": (None, "int32")}
 

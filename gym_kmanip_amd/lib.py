@@ -19,7 +19,7 @@ _lib = None
 # every symbol include/kmanip.h declares (tests check the library exports all of them)
 EXPORTS = [
     "kmanip_model_desc_size", "kmanip_create", "kmanip_reset", "kmanip_step", "kmanip_step_chunk", "kmanip_get_state",
-    "kmanip_set_state", "kmanip_get_episode", "kmanip_set_episode", "kmanip_get_counters", "kmanip_bind_sim_time", "kmanip_bind_applied_force", "kmanip_bind_reward_done_record", "kmanip_select_reward_done_record", "kmanip_observe", "kmanip_forces", "kmanip_kinematics", "kmanip_inverse", "kmanip_forward", "kmanip_kinematics_rows", "kmanip_site_cost", "kmanip_rollout", "kmanip_feedback", "kmanip_feedback_box", "kmanip_transition_fd", "kmanip_lqr_backward", "kmanip_lqr_backward_box", "kmanip_adjoint", "kmanip_set_seed", "kmanip_get_diag", "kmanip_timing_summary", "kmanip_enable_timing", "kmanip_ik", "kmanip_ik_eval",
+    "kmanip_set_state", "kmanip_get_episode", "kmanip_set_episode", "kmanip_get_counters", "kmanip_bind_sim_time", "kmanip_bind_applied_force", "kmanip_bind_reward_done_record", "kmanip_select_reward_done_record", "kmanip_observe", "kmanip_forces", "kmanip_kinematics", "kmanip_inverse", "kmanip_forward", "kmanip_kinematics_rows", "kmanip_site_cost", "kmanip_rollout", "kmanip_feedback", "kmanip_feedback_box", "kmanip_transition_fd", "kmanip_param_fd", "kmanip_lqr_backward", "kmanip_lqr_backward_box", "kmanip_adjoint", "kmanip_set_seed", "kmanip_get_diag", "kmanip_timing_summary", "kmanip_enable_timing", "kmanip_ik", "kmanip_ik_eval",
     "kmanip_render_depth", "kmanip_render_rgb", "kmanip_render_rgb_multi", "kmanip_render_labels_multi", "kmanip_render_seg", "kmanip_set_render_links", "kmanip_get_render_links", "kmanip_set_depth_links", "kmanip_get_depth_links", "kmanip_get_camera_poses", "kmanip_render_points", "kmanip_snapshot_render_state", "kmanip_set_render_source", "kmanip_bind_step_depth", "kmanip_scripted_action", "kmanip_sample_action", "kmanip_set_env_params", "kmanip_get_env_params", "kmanip_set_env_param_ranges", "kmanip_set_visual_params", "kmanip_get_visual_params", "kmanip_set_visual_param_ranges",
     "kmanip_get_state_dev", "kmanip_set_state_dev", "kmanip_copy_envs", "kmanip_state_index_errors", "kmanip_num_envs", "kmanip_last_error", "kmanip_version", "kmanip_destroy",
 ]
@@ -144,6 +144,19 @@ class KTransFdDev(C.Structure):
                 ("deriv_t", C.c_void_p), ("status_cols", C.c_void_p), ("contact_mask_fd", C.c_void_p)]
 
 
+class KParamFdIn(C.Structure):
+    """include/kmanip.h KParamFdIn: the DEVICE pointers of KRolloutIn's rows, the rows' parameters [n, KM_EP_N] (NULL: the named env's),
+    the mask of the differentiated KM_EP_* parameters, their perturbations and the offset of the perturbed rows' warm start."""
+    _fields_ = KRolloutIn._fields_[:6] + [("params", C.c_void_p), ("wrt", C.c_int32), ("eps", C.c_double * 4), ("eps_relative", C.c_int32),
+                                          ("warm_offset", C.c_double)]
+
+
+class KParamFdDev(C.Structure):
+    """include/kmanip.h KParamFdDev: DEVICE pointers of kmanip_param_fd's outputs -- the transposed derivative [n, npar, 2 nv], the status
+    of every column and the contact masks of its + / - rows."""
+    _fields_ = [("deriv_t", C.c_void_p), ("status_cols", C.c_void_p), ("contact_mask_fd", C.c_void_p)]
+
+
 class KLqrIn(C.Structure):
     """include/kmanip.h KLqrIn: DEVICE pointers of kmanip_lqr_backward's inputs -- the transposed step Jacobians with their block
     strides in doubles (0 = dense), the cost's derivatives, shared by the problems or one set each, and the regularisation."""
@@ -236,6 +249,7 @@ def load():
     lib.kmanip_feedback.argtypes = [vp, C.POINTER(KFeedbackIn), C.c_int, C.c_int, C.c_int, C.POINTER(KFeedbackDev), vp]
     lib.kmanip_feedback_box.argtypes = [vp, C.POINTER(KFeedbackBoxIn), C.c_int, C.c_int, C.c_int, C.POINTER(KFeedbackDev), vp]
     lib.kmanip_transition_fd.argtypes = [vp, C.POINTER(KTransFdIn), C.c_int, C.c_int, C.POINTER(KTransFdDev), vp]
+    lib.kmanip_param_fd.argtypes = [vp, C.POINTER(KParamFdIn), C.c_int, C.c_int, C.POINTER(KParamFdDev), vp]
     lib.kmanip_lqr_backward.argtypes = [vp, C.POINTER(KLqrIn), C.c_int, C.c_int, C.POINTER(KLqrDev), vp]
     lib.kmanip_lqr_backward_box.argtypes = [vp, C.POINTER(KLqrBoxIn), C.c_int, C.c_int, C.POINTER(KLqrBoxDev), vp]
     lib.kmanip_adjoint.argtypes = [vp, C.POINTER(KAdjointIn), C.c_int, C.c_int, C.c_int, C.POINTER(KAdjointDev), vp]

@@ -1091,6 +1091,48 @@ KMANIP_API int kmanip_get_env_params(KHandle h, double* params_dev, void* stream
 #define KM_EP_CTR3 2u
 KMANIP_API int kmanip_set_env_param_ranges(KHandle h, const double* lo, const double* hi);
 
+/* Finite-difference derivatives of ONE step with respect to the per-env physics parameters, at rows the caller passes (DESIGN.md
+ * section 42): P = d s' / d p, s = (qpos in the tangent space, qvel) as in kmanip_transition_fd, whose sibling this is.  The columns
+ * are the parameters named by `wrt` (bit k = KM_EP_* k) in ascending k: npar = the number of bits set.  The +e and -e rows of a
+ * column are stepped side by side in one wave with the parameter replaced in the kernel's workspace, and the quotient is formed there:
+ * no perturbed parameter and no perturbed state reaches memory, and the handle's parameters are not touched. */
+typedef struct KParamFdIn {
+  const int32_t* env_index;    /* [n] DEVICE or NULL: KRolloutIn::env_index */
+  const double*  qpos;         /* [n, nq] or NULL: the named env's stored qpos */
+  const double*  qvel;         /* [n, nv] or NULL */
+  const double*  qacc_warm;    /* [n, nv] or NULL: the named env's stored warm start; the BASE of both rows' first sub-step */
+  const double*  ctrl;         /* [n, nu] or NULL: the named env's stored ctrl, used exactly as given / stored */
+  const double*  qfrc_applied; /* [n, nv] or NULL: the named env's row of a bound applied force, none if nothing is bound */
+  const double*  params;       /* [n, KM_EP_N] DEVICE or NULL: row r's parameters (ROW-major, unlike the handle's storage).  NULL: the
+                                  values in force for env env_index[r] (in ranges mode the drawn ones); on a handle without per-env
+                                  parameters the compiled model's */
+  int32_t wrt;                 /* bit k = differentiate KM_EP_* k */
+  double  eps[KM_EP_N];        /* the perturbation of each parameter (read for the selected ones only) */
+  int32_t eps_relative;        /* 1: e = fl(eps[k] * p_k); 0: e = eps[k] */
+  double  warm_offset;         /* added on every dof to the base of both rows' first warm start (KTransFdIn::warm_offset) */
+} KParamFdIn;
+/* OUTPUTS; status_cols and contact_mask_fd may be NULL. */
+typedef struct KParamFdDev {
+  double*   deriv_t;         /* [n, npar, 2 nv] entry (r, c, i) = d s'_i / d p_c, TRANSPOSED like KTransFdDev::deriv_t.  Must be given */
+  uint8_t*  status_cols;     /* [n, npar] 0 a derivative; 1 the + or - row stopped (KRolloutDev::status 1); 2 the row's env index is
+                                outside the handle (compared before it is used as an address); 3 the row's parameters or either
+                                perturbed value are outside the parameter's limits (mass, kp scale > 0; friction, frictionloss >= 0;
+                                all finite), or e is zero or not finite: nothing is stepped.  Nonzero: the column is zeros */
+  uint32_t* contact_mask_fd; /* [n, npar, 2] the contact mask after the step of the + and of the - row (0 for a column that did not
+                                step); the trailing kinematics + collision pass is skipped when this is NULL */
+} KParamFdDev;
+/* PER COLUMN: e as above, plus = fl(p_k + e), minus = fl(p_k - e); the two rows run kmanip_rollout's sub-step loop for one step (nsub
+ * == 0: the model's n_sub_steps; the handle's solver) from the row's state and warm start + warm_offset, with every constant derived
+ * from the parameters exactly as kmanip_set_env_params derives it; entry (r, c, .) = [tangent_diff(qpos+, qpos-) ; qvel+ - qvel-] /
+ * fl(2.0 * e), a division.  The derivative in the friction loss AT 0 is refused (status 3), not faked: its rows exist only above 0.
+ * ONE launch on `stream`.  No allocation, no synchronisation, no host copy.  THE HANDLE IS READ ONLY, and the call works on a handle
+ * that never had per-env parameters without changing which kernels its steps use.  n == 0 or wrt == 0 succeeds and does nothing.
+ * ERRORS: a NULL handle, `in` or `out`, n < 0, nsub < 0, n > num_envs with a NULL env_index, wrt bits outside the KM_EP_N lowest, a
+ * non-finite warm_offset, an eps[k] of a selected parameter that is not finite or not > 0, wrt != 0 with a NULL deriv_t, or
+ * 2 * npar * n beyond int return nonzero with kmanip_last_error set, launch nothing and leave the outputs untouched.
+ * OUT OF SCOPE: parameters outside KM_EP_*, analytic derivatives, more than one step. */
+KMANIP_API int kmanip_param_fd(KHandle h, const KParamFdIn* in, int n, int nsub, const KParamFdDev* out, void* stream);
+
 /* Per-env visual parameters (visual domain randomisation of the camera renders).  Storage is
  * double[KM_VP_N][num_envs], struct-of-arrays like KM_EP_*: element (k, env) at k * num_envs + env.
  *   index  name                  default        meaning
