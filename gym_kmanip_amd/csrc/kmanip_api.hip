@@ -775,6 +775,37 @@ int kmanip_adjoint(KHandle h, const KAdjointIn* in, int n, int T, int m, const K
   return 0;
 }
 
+// The forward sensitivity sweep of a rollout for n problems of T steps and m tangent columns each, optionally with its Gauss-Newton
+// terms (include/kmanip.h KTangentIn / KTangentDev; kmanip_tangent.hip).  One launch; the handle gives the device
+// and the size class and is only read.
+int kmanip_tangent(KHandle h, const KTangentIn* in, int n, int T, int m, const KTangentDev* out, void* stream) {
+  if (!h) { g_create_error = "kmanip_tangent: null handle"; return -1; }
+  if (!in) { h->err = "kmanip_tangent: the KTangentIn pointer is NULL"; return -1; }
+  if (!out) { h->err = "kmanip_tangent: the KTangentDev pointer is NULL"; return -1; }
+  if (n < 0) { h->err = "kmanip_tangent: n is negative"; return -1; }
+  if (T < 0) { h->err = "kmanip_tangent: T is negative"; return -1; }
+  if (m < 0) { h->err = "kmanip_tangent: m is negative"; return -1; }
+  if (n == 0 || T == 0 || m == 0) return 0;      // (tensors of no problems, steps or columns have no address: nothing below is asked of them)
+  if (!in->a_t) { h->err = "kmanip_tangent: KTangentIn::a_t is NULL"; return -1; }
+  if (!in->b_t) { h->err = "kmanip_tangent: KTangentIn::b_t is NULL"; return -1; }
+  const int64_t nx = h->desc.nlink <= 10 ? 32 : 52, nu = h->desc.nlink <= 10 ? 10 : 20;      // (kmanip_tangent.hip's two classes)
+  if (in->a_stride != 0 && in->a_stride < nx * nx) { h->err = "kmanip_tangent: a_stride is smaller than an [nx, nx] block"; return -1; }
+  if (in->b_stride != 0 && in->b_stride < nu * nx) { h->err = "kmanip_tangent: b_stride is smaller than an [nu, nx] block"; return -1; }
+  if (in->src_stride != 0 && in->src_stride < m * nx) { h->err = "kmanip_tangent: src_stride is smaller than an [m, nx] block"; return -1; }
+  if ((long long)n * m > 2147483647LL || (long long)n * m * T > 2147483647LL) { h->err = "kmanip_tangent: n * m * T column steps are more than an int counts"; return -1; }
+  if ((out->h || out->g) && m > KM_TANGENT_MC) { h->err = "kmanip_tangent: H and g need m <= KM_TANGENT_MC columns (no Gram across chunks)"; return -1; }
+  if (out->g && !in->r) { h->err = "kmanip_tangent: g is asked for and KTangentIn::r is NULL"; return -1; }
+  if (!out->s_t && !out->du_acted_t && !out->h && !out->g) return 0;
+  KTangentIn ti = *in;
+  if (!ti.a_stride) ti.a_stride = nx * nx;
+  if (!ti.b_stride) ti.b_stride = nu * nx;
+  if (!ti.src_stride) ti.src_stride = m * nx;
+  KM_ENTER(h);
+  kmanip_launch_tangent(h->desc, ti, n, T, m, *out, (hipStream_t)stream);
+  HIPCHK(h, hipGetLastError());
+  return 0;
+}
+
 // One helper of the kernels' math headers over n rows (include/kmanip_debug.h; kmanip_mathprobe.hip).  One
 // launch; the handle gives the device and is only read.
 int kmanip_dbg_math(KHandle h, int fn, int n, const double* in_dev, int in_cols, double* out_dev, int out_cols, void* stream) {

@@ -624,6 +624,9 @@ void kmanip_launch_lqr_backward(const KModelDesc& hd, const KLqrIn& in, int n, i
 void kmanip_launch_lqr_backward_box(const KModelDesc& hd, const KLqrBoxIn& in, int n, int T, const KLqrBoxDev& out, hipStream_t stream);
 // kmanip_adjoint (kmanip_adjoint.hip): n > 0 problems of T > 0 steps and m > 0 vectors each, the strides resolved; the class likewise
 void kmanip_launch_adjoint(const KModelDesc& hd, const KAdjointIn& in, int n, int T, int m, const KAdjointDev& out, hipStream_t stream);
+// kmanip_tangent (kmanip_tangent.hip): n > 0 problems of T > 0 steps and m > 0 columns each, the strides resolved; H or g only with
+// m <= KM_TANGENT_MC; the class likewise
+void kmanip_launch_tangent(const KModelDesc& hd, const KTangentIn& in, int n, int T, int m, const KTangentDev& out, hipStream_t stream);
 // kmanip_dbg_math (kmanip_mathprobe.hip): the columns of function fn (false: no such function), and its launch over n > 0 rows
 bool kmanip_math_probe_cols(int fn, int* in_cols, int* out_cols);
 void kmanip_launch_math_probe(int fn, int n, const double* in, double* out, hipStream_t stream);

@@ -193,6 +193,54 @@ def adjoint_pass(A, B, gx, gu=None, gains=None, m=1):
     return lam.reshape(n * m, T + 1, nx), mu.reshape(n * m, T, nu)
 
 
+def tangent_pass(A, B, src=None, du=None, s0=None, gains=None, m=None):
+    """The forward sensitivity sweep of a rollout: THE DEFINITION kmanip_tangent is held to (include/kmanip.h
+    KTangentIn), adjoint_pass's forward-mode twin.  A [n, T, nx, nx], B [n, T, nx, nu] the step Jacobians; m >= 1 tangent columns per
+    problem: src [n, T, nx, m] the step's direct source (sysid's P_t), du [n, T, nu, m] the open-loop control direction, s0
+    [n, nx, m] the initial tangent, each None = zeros (m then says the columns); gains [n, T, nu, nx] the feedback K_t, or None
+    (open loop).  S_0 = s0; for t = 0 .. T-1
+        du_t    = K_t S_t + dU_t
+        S_{t+1} = A_t S_t + B_t du_t + src_t
+    the direct terms added last; open loop without du the B product is not formed.  Returns (S [n, T + 1, nx, m], du_acted
+    [n, T, nu, m]).  With gains, dx is taken as linear in the state (adjoint_pass's one approximation).  A torch loop over the T
+    steps, on the device of the tensors."""
+    import torch
+    n, T, nx, nu = B.shape
+    cols = [int(t.shape[-1]) for t in (src, du, s0) if t is not None] + ([int(m)] if m is not None else [])
+    if not cols or min(cols) != max(cols):
+        raise ValueError("tangent_pass: src, du, s0 and m must give one column count")
+    m = cols[0]
+    for name, t, shape in (("src", src, (n, T, nx, m)), ("du", du, (n, T, nu, m)), ("s0", s0, (n, nx, m))):
+        if t is not None and tuple(t.shape) != shape:
+            raise ValueError("tangent_pass: %s must be %s, not %s" % (name, shape, tuple(t.shape)))
+    S = torch.zeros((n, T + 1, nx, m), dtype=A.dtype, device=A.device)
+    acted = torch.zeros((n, T, nu, m), dtype=A.dtype, device=A.device)
+    if s0 is not None:
+        S[:, 0] = s0
+    cur = S[:, 0]
+    for t in range(T):
+        u = None if gains is None else gains[:, t] @ cur
+        if du is not None:
+            u = du[:, t] if u is None else u + du[:, t]
+        cur = A[:, t] @ cur
+        if u is not None:
+            cur = cur + B[:, t] @ u
+            acted[:, t] = u
+        if src is not None:
+            cur = cur + src[:, t]
+        S[:, t + 1] = cur
+    return S, acted
+
+
+def gauss_newton_products(S, resid=None, weight=None):
+    """(H [n, m, m], g [n, m] or None) of kmanip_tangent's Gauss-Newton terms: y_t = W S_t, H = sum_t S_t' y_t, g = sum_t y_t' r_t for
+    S [n, T + 1, nx, m], resid [n, T + 1, nx], weight [nx, nx] (None: the identity), in torch."""
+    import torch
+    y = S if weight is None else weight @ S
+    H = torch.einsum("ntja,ntjb->nab", S, y)
+    return H, None if resid is None else torch.einsum("ntja,ntj->na", y, resid)
+
+
 def forward_fd(env, envs=None, qpos=None, qvel=None, ctrl=None, qfrc_applied=None, eps=1e-6,
                wrt=("qpos", "qvel", "ctrl", "qfrc_applied"), warm_offset=1.0):
     """Centred finite differences of env.forward's qacc and qfrc_constraint with respect to the inputs named in `wrt`, at the rows

@@ -693,6 +693,102 @@ class KManipEnvHip:
         del keep                             # (the stream orders the launch before the allocator reuses the copies)
         return res
 
+    # result name -> (KTangentDev field, trailing shape after n, dtype name)
+    _TANGENT_FIELDS = {"S": ("s_t", ("T1", "m", "nx"), "float64"), "du_acted": ("du_acted_t", ("T", "m", "nu"), "float64"),
+                       "H": ("h", ("m", "m"), "float64"), "g": ("g", ("m",), "float64")}
+
+    def tangent(self, A=None, B=None, deriv_t=None, src=None, src_t=None, du=None, s0=None, gains=None, gains_t=None, m=None, weight=None,
+                resid=None, fields=("S",), out=None):
+        """kmanip_tangent: derivatives.tangent_pass -- the forward sensitivity sweep of a rollout, adjoint()'s forward-mode twin -- for
+        n problems of T steps and m tangent columns each in ONE launch on the current stream, and from the same launch the
+        Gauss-Newton terms H = sum_t S_t' W S_t and g = sum_t S_t' W r_t (no synchronisation; the handle is only read).
+          deriv_t [n, T, ncol >= nx + nu, nx] read where it lies, or A [n, T, nx, nx] and B [n, T, nx, nu] (one transposed copy each).
+          src [n, T, nx, m] (param_fd's P over the n T rows: its transpose(2, 3) is contiguous and is passed by pointer; anything else
+            is copied once) or src_t [n, T, m, nx]; du [n, T, nu, m] the control direction; s0 [n, nx, m]; each None = zeros.
+          gains [n, T, nu, nx] or gains_t [n, T, nx, nu], or neither: open loop.  m: the columns, when no column tensor says it.
+          weight [nx, nx] (symmetrised as TrackingCost.derivatives does) or its diagonal [nx], None = the identity; resid [n, T + 1, nx].
+        Returns a dict of the requested `fields` among S [n, T + 1, nx, m] and du_acted [n, T, nu, m] (transposed views of the
+        kernel's buffers, as param_fd returns P), H [n, m, m] and g [n, m] (m <= KM_TANGENT_MC; g needs resid).  A caller that asks
+        for H and g only has no S written.  `out`: tensors to fill, keyed by the KERNEL's layouts s_t [n, T + 1, m, nx], du_acted_t
+        [n, T, m, nu], h, g; they are returned under those names' result keys.  include/kmanip.h KTangentIn states every sum's order."""
+        torch = _torch()
+        nx, nu, f64 = 2 * self.cm.nv, self.cm.nu, torch.float64
+        dyn = deriv_t if deriv_t is not None else B
+        if not isinstance(dyn, torch.Tensor) or dyn.dim() != 4:
+            raise _libmod.KManipError("tangent: give deriv_t, or A and B")
+        n, T = int(dyn.shape[0]), int(dyn.shape[1])
+        if src is not None and src_t is not None:
+            raise _libmod.KManipError("tangent: give src or src_t, not both")
+        cols = [int(t.shape[-1]) for t in (src, du, s0) if isinstance(t, torch.Tensor) and t.dim() >= 3]
+        cols += [int(src_t.shape[2])] if isinstance(src_t, torch.Tensor) and src_t.dim() == 4 else []
+        cols += [int(m)] if m is not None else []
+        if not cols or min(cols) != max(cols) or cols[0] < 1:
+            raise _libmod.KManipError("tangent: the column count m >= 1 must be given by src, src_t, du, s0 or m, and alike by all")
+        m = cols[0]
+        ti = _libmod.KTangentIn()
+        ncol = int(deriv_t.shape[2]) if isinstance(deriv_t, torch.Tensor) and deriv_t.dim() == 4 and deriv_t.shape[2] > nx + nu else None
+        keep = self._dyn_in("tangent", ti, n, T, A, B, deriv_t, ncol=ncol)
+        colt = {}                            # the column tensors in the kernel's layout, held until the launch
+        for field, t, shape in (("src_t", src, (n, T, nx, m)), ("du_t", du, (n, T, nu, m)), ("s0_t", s0, (n, nx, m))):
+            if t is not None:
+                if not isinstance(t, torch.Tensor) or tuple(t.shape) != shape:
+                    raise _libmod.KManipError("tangent: %s must be a tensor of shape %s" % (field[:-2], shape))
+                t = t.transpose(-1, -2).contiguous()         # (no copy where the transposed view is contiguous already)
+                self._check_buf(t, shape[:-2] + (shape[-1], shape[-2]), f64, field[:-2])
+                setattr(ti, field, t.data_ptr())
+                colt[field] = t
+        if src_t is not None:
+            self._check_buf(src_t, (n, T, m, nx), f64, "src_t")
+            ti.src_t = src_t.data_ptr()
+            keep += (src_t,)
+        if gains is not None and gains_t is not None:
+            raise _libmod.KManipError("tangent: give gains or gains_t, not both")
+        if gains is not None:
+            if not isinstance(gains, torch.Tensor) or tuple(gains.shape) != (n, T, nu, nx):
+                raise _libmod.KManipError("tangent: gains must be a tensor of shape %s" % ((n, T, nu, nx),))
+            gains_t = gains.transpose(2, 3)
+        if gains_t is not None:
+            gains_t = gains_t.contiguous() if isinstance(gains_t, torch.Tensor) else gains_t
+            self._check_buf(gains_t, (n, T, nx, nu), f64, "gains_t")
+            ti.gain_t = gains_t.data_ptr()
+            keep += (gains_t,)
+        if weight is not None:
+            w = torch.diag(weight) if isinstance(weight, torch.Tensor) and weight.dim() == 1 else weight
+            w = (0.5 * (w + w.transpose(0, 1))).contiguous() if isinstance(w, torch.Tensor) and tuple(w.shape) == (nx, nx) else w
+            self._check_buf(w, (nx, nx), f64, "weight")
+            ti.w = w.data_ptr()
+            keep += (w,)
+        if resid is not None:
+            resid = resid.contiguous() if isinstance(resid, torch.Tensor) else resid
+            self._check_buf(resid, (n, T + 1, nx), f64, "resid")
+            ti.r = resid.data_ptr()
+            keep += (resid,)
+        table = {dev: (shp, dt) for dev, shp, dt in self._TANGENT_FIELDS.values()}
+        if out is None:
+            unknown = set(fields) - set(self._TANGENT_FIELDS)
+            if unknown:
+                raise ValueError("unknown tangent field(s) %s" % sorted(unknown))
+        wanted = [self._TANGENT_FIELDS[name][0] for name in fields] if out is None else None
+        if ("g" in (out if out is not None else wanted)) and resid is None:
+            raise _libmod.KManipError("tangent: g needs resid")
+        if m > _libmod.KM_TANGENT_MC and {"h", "g"} & set(out if out is not None else wanted):
+            raise _libmod.KManipError("tangent: H and g need m <= %d columns" % _libmod.KM_TANGENT_MC)
+        td = _libmod.KTangentDev()
+        raw = self._query_out(table, (n,), {"T": T, "T1": T + 1, "m": m, "nx": nx, "nu": nu}, out, wanted, td, "tangent")
+        if n > 0 and T == 0:                 # (nothing is launched: s_0 is all there is, and its terms of H and g)
+            s_0 = colt["s0_t"] if s0 is not None else torch.zeros((n, m, nx), dtype=f64, device=self.device)
+            y_0 = s_0 if weight is None else s_0 @ w
+            for name, val in (("s_t", s_0[:, None]), ("h", s_0 @ y_0.transpose(1, 2)), ("g", None if resid is None else (y_0 @ resid[:, 0, :, None])[:, :, 0])):
+                if name in raw:
+                    raw[name].copy_(val)
+        self._check(self.L.kmanip_tangent(self.h, C.byref(ti), n, T, m, C.byref(td), self._stream()), "kmanip_tangent")
+        del keep, colt                       # (the stream orders the launch before the allocator reuses the copies)
+        res = {name: raw[dev] for name, (dev, _, _) in self._TANGENT_FIELDS.items() if dev in raw}
+        for name in ("S", "du_acted"):
+            if name in res:
+                res[name] = res[name].transpose(2, 3)
+        return res
+
     def _lqr_in(self, what, li, lx, lu, lxx, luu, A, B, deriv_t, reg):
         """The checked inputs of lqr_backward() / lqr_backward_box() set in the KLqrIn `li`.  Returns (n, T, the tensors the caller
         holds until the launch)."""

@@ -3,7 +3,7 @@
 trajectory per env by a second handle that starts at the model's defaults.
 
     python -m gym_kmanip_amd.examples.system_identification [--num-envs 4] [--horizon 6] [--iters 8] [--wrt kp_scale cube_mass ...]
-        [--fused] [--device-adjoint] [--no-contact]
+        [--fused] [--device-adjoint] [--device-sensitivity] [--no-contact]
 
 The task is KManipSoloArmQPos.  The real handle gets hidden parameters (per env: the check values of DESIGN.md section 42 spread by a
 few per cent) and is stepped open loop with a control sequence; the states it passes through are the log.  The second handle then
@@ -17,7 +17,8 @@ model's defaults the default eight iterations do not always reach the hidden val
 arm alone shows kp_scale and nothing else, and the example says so -- a singular value below RATIO times the largest marks a
 direction in parameter space that this log does not determine.
 --device-adjoint also prints the gradient of the tracking loss in the parameters at the start (sysid.rollout_param_grad with the
-adjoint sweep in one launch, kmanip_adjoint).
+adjoint sweep in one launch, kmanip_adjoint).  --device-sensitivity takes the sensitivity recursion, J'J and J'r from one launch
+(sysid.identify(device_sensitivity=True): kmanip_tangent); it prints the same parameters and losses.
 identify_log() is the loop itself on any env with rollout, param_fd and set_env_params: tests run it on the CPU oracle's stand-in."""
 import argparse
 import json
@@ -36,7 +37,8 @@ def log_trajectory(env, envs, st, ctrl, nsub=None):
     return torch.cat([st["qpos"][:, None], roll["qpos"]], dim=1), torch.cat([st["qvel"][:, None], roll["qvel"]], dim=1), roll["status"]
 
 
-def identify_log(real, model, st, ctrl, wrt=ENV_PARAMS, iters=8, nsub=None, fused=False, device_adjoint=False, verbose=print):
+def identify_log(real, model, st, ctrl, wrt=ENV_PARAMS, iters=8, nsub=None, fused=False, device_adjoint=False, device_sensitivity=False,
+                 verbose=print):
     """The example's loop: `real` (a handle with hidden parameters) logs the trajectory of ctrl [n, T, nu] from the states st (qpos,
     qvel, warm: [n, ..] tensors; problem e is env e of both handles), `model` identifies `wrt` from it.  Returns sysid.identify's dict
     plus hidden {name: [n]}, error {name: [n]} (relative), observable [n] bool (the smallest singular value against RATIO) and, with
@@ -60,7 +62,7 @@ def identify_log(real, model, st, ctrl, wrt=ENV_PARAMS, iters=8, nsub=None, fuse
 
     order = tuple(name for name in ENV_PARAMS if name in wrt)
     res = sysid.identify(model, envs, st["qpos"], st["qvel"], st["warm"], ctrl, qpos_obs, qvel_obs, wrt=order, iters=iters, nsub=nsub,
-                         fused=fused, callback=show)
+                         fused=fused, callback=show, device_sensitivity=device_sensitivity)
     hidden = {name: v[envs.long()] for name, v in real.get_env_params().items()}
     res.update(extra, hidden=hidden, status=torch.maximum(res["status"], status.to(res["status"].device)),
                error={name: (res["params"][name] / hidden[name].to(res["params"][name].device) - 1.0).abs() for name in ENV_PARAMS},
@@ -122,6 +124,7 @@ def main(argv=None):
     ap.add_argument("--wrt", nargs="+", default=list(ENV_PARAMS), choices=ENV_PARAMS, help="the parameters to identify")
     ap.add_argument("--fused", action="store_true", help="linearise with KManipEnvHip.transition_fd (kmanip_transition_fd)")
     ap.add_argument("--device-adjoint", action="store_true", help="print the loss's parameter gradient from KManipEnvHip.adjoint (kmanip_adjoint)")
+    ap.add_argument("--device-sensitivity", action="store_true", help="the sensitivity recursion, J'J and J'r in one launch: KManipEnvHip.tangent (kmanip_tangent)")
     ap.add_argument("--no-contact", action="store_true", help="leave the cube where the reset spawned it: only kp_scale is observable")
     args = ap.parse_args(argv)
     real = env_hip.make("KManipSoloArmQPos", num_envs=args.num_envs, seed=args.seed)
@@ -134,9 +137,11 @@ def main(argv=None):
     if not args.no_contact:
         st = contact_states(model, st)
     ctrl = sweep_controls(model.cm, st, args.horizon)
-    res = identify_log(real, model, st, ctrl, wrt=args.wrt, iters=args.iters, fused=args.fused, device_adjoint=args.device_adjoint)
+    res = identify_log(real, model, st, ctrl, wrt=args.wrt, iters=args.iters, fused=args.fused, device_adjoint=args.device_adjoint,
+                       device_sensitivity=args.device_sensitivity)
     rec = {"env": "KManipSoloArmQPos", "num_envs": args.num_envs, "horizon": args.horizon, "iters": args.iters, "wrt": list(res["wrt"]),
-           "fused": bool(args.fused), "device_adjoint": bool(args.device_adjoint), "contact": not args.no_contact,
+           "fused": bool(args.fused), "device_adjoint": bool(args.device_adjoint),
+           "device_sensitivity": bool(args.device_sensitivity), "contact": not args.no_contact,
            "hidden": {k: v.tolist() for k, v in hidden.items()}, "params": {k: v.cpu().tolist() for k, v in res["params"].items()},
            "error": {k: v.cpu().tolist() for k, v in res["error"].items()}, "loss": res["loss"].cpu().tolist(),
            "singular_values": res["singular_values"].cpu().tolist(), "observable": res["observable"].cpu().tolist(),

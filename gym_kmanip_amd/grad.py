@@ -3,6 +3,7 @@
 rollout_grad      the gradient of a cost on a rollout with respect to the controls, the initial state and, closed loop, the gains
 rollout_jacobian  d x_T / d u_0..T-1 and d x_T / d x_0, nx cotangent vectors per problem through one adjoint
 diff_rollout      env.rollout as a torch.autograd.Function: loss.backward() passes through it
+rollout_jvp       the directional derivative of a rollout's states along a control (and initial-state) direction: forward mode
 
 The state is (qpos in the tangent space, qvel), 2 nv wide, as transition_fd defines it.  The sweep itself is
 derivatives.adjoint_pass (a torch loop over the steps) or, with device=True, env.adjoint (kmanip_adjoint: one launch).  With
@@ -10,7 +11,7 @@ device=False everything needs only env.rollout, env.rollout_feedback and env.cm,
 (tests/tools/feedback_oracle.py OracleFeedback) runs the same code, as it runs ilqr."""
 import functools
 
-from .derivatives import adjoint_pass, tangent_diff
+from .derivatives import adjoint_pass, tangent_diff, tangent_pass
 from .ilqr import trajectory_fd
 
 
@@ -85,6 +86,31 @@ def rollout_jacobian(env, envs, qpos0, qvel0, warm0, ctrl, qfrc_applied=None, ns
     gx[:, :, T] = torch.eye(nx, dtype=ctrl.dtype, device=ctrl.device)
     lam, mu = _sweep(env, fd, gx.reshape(n * nx, T + 1, nx), None, None, None, nx, device)
     return {"dxT_du": mu.reshape(n, nx, T, -1), "dxT_dx0": lam[:, 0].reshape(n, nx, nx), "qpos": fd["qpos"], "qvel": fd["qvel"],
+            "status": fd["status"], "status_fd": fd["status_fd"]}
+
+
+def rollout_jvp(env, envs, qpos0, qvel0, warm0, ctrl, dctrl, dx0=None, gains=None, gains_t=None, qfrc_applied=None, nsub=None, eps=1e-6,
+                fused=False, device=False):
+    """The directional derivative of the states of the rollout of ctrl [n, T, nu] from (qpos0, qvel0, warm0) along dctrl [n, T, nu]
+    (or [n, T, nu, m]: m directions at once) and dx0 [n, 2 nv] (or [n, 2 nv, m]; None: the initial state is held): ONE
+    ilqr.trajectory_fd call and ONE forward sweep ds_{t+1} = A_t ds_t + B_t du_t, du_t = dctrl_t + K_t ds_t -- the linearised
+    forward pass, the first half of a Gauss-Newton Hessian-vector product, the predicted change of a line search.
+    gains [n, T, nu, nx] or gains_t [n, T, nx, nu]: the policy u_t = ctrl_t + K_t dx_t of rollout_feedback, ctrl then the controls
+    that ACTED (rollout_feedback's record: replayed open loop they give the trajectory); dx is taken as linear in the state.
+    Returns a dict: dx [n, T + 1, 2 nv] (or [.., m]) the tangent of x_t; du [n, T, nu] (or [.., m]) the change of the control that
+    acts; qpos, qvel, status, status_fd: trajectory_fd's.  fused: trajectory_fd's.  device: the sweep is env.tangent (kmanip_tangent,
+    one launch) on deriv_t where fused gives it, else on A and B; False: derivatives.tangent_pass."""
+    fd = trajectory_fd(env, envs, qpos0, qvel0, warm0, ctrl, qfrc_applied=qfrc_applied, nsub=nsub, eps=eps, fused=fused)
+    single = dctrl.dim() == 3
+    du = dctrl[..., None] if single else dctrl
+    s0 = None if dx0 is None else (dx0[..., None] if dx0.dim() == 2 else dx0)
+    if device:
+        dyn = dict(deriv_t=fd["deriv_t"]) if "deriv_t" in fd else dict(A=fd["A"], B=fd["B"])
+        r = env.tangent(du=du, s0=s0, gains=gains if gains_t is None else None, gains_t=gains_t, fields=("S", "du_acted"), **dyn)
+        S, acted = r["S"], r["du_acted"]
+    else:
+        S, acted = tangent_pass(fd["A"], fd["B"], du=du, s0=s0, gains=gains if gains_t is None else gains_t.transpose(2, 3))
+    return {"dx": S[..., 0] if single else S, "du": acted[..., 0] if single else acted, "qpos": fd["qpos"], "qvel": fd["qvel"],
             "status": fd["status"], "status_fd": fd["status_fd"]}
 
 

@@ -19,7 +19,7 @@ _lib = None
 # every symbol include/kmanip.h declares (tests check the library exports all of them)
 EXPORTS = [
     "kmanip_model_desc_size", "kmanip_create", "kmanip_reset", "kmanip_step", "kmanip_step_chunk", "kmanip_get_state",
-    "kmanip_set_state", "kmanip_get_episode", "kmanip_set_episode", "kmanip_get_counters", "kmanip_bind_sim_time", "kmanip_bind_applied_force", "kmanip_bind_reward_done_record", "kmanip_select_reward_done_record", "kmanip_observe", "kmanip_forces", "kmanip_kinematics", "kmanip_inverse", "kmanip_forward", "kmanip_kinematics_rows", "kmanip_site_cost", "kmanip_rollout", "kmanip_feedback", "kmanip_feedback_box", "kmanip_transition_fd", "kmanip_param_fd", "kmanip_lqr_backward", "kmanip_lqr_backward_box", "kmanip_adjoint", "kmanip_set_seed", "kmanip_get_diag", "kmanip_timing_summary", "kmanip_enable_timing", "kmanip_ik", "kmanip_ik_eval",
+    "kmanip_set_state", "kmanip_get_episode", "kmanip_set_episode", "kmanip_get_counters", "kmanip_bind_sim_time", "kmanip_bind_applied_force", "kmanip_bind_reward_done_record", "kmanip_select_reward_done_record", "kmanip_observe", "kmanip_forces", "kmanip_kinematics", "kmanip_inverse", "kmanip_forward", "kmanip_kinematics_rows", "kmanip_site_cost", "kmanip_rollout", "kmanip_feedback", "kmanip_feedback_box", "kmanip_transition_fd", "kmanip_param_fd", "kmanip_lqr_backward", "kmanip_lqr_backward_box", "kmanip_adjoint", "kmanip_tangent", "kmanip_set_seed", "kmanip_get_diag", "kmanip_timing_summary", "kmanip_enable_timing", "kmanip_ik", "kmanip_ik_eval",
     "kmanip_render_depth", "kmanip_render_rgb", "kmanip_render_rgb_multi", "kmanip_render_labels_multi", "kmanip_render_seg", "kmanip_set_render_links", "kmanip_get_render_links", "kmanip_set_depth_links", "kmanip_get_depth_links", "kmanip_get_camera_poses", "kmanip_render_points", "kmanip_snapshot_render_state", "kmanip_set_render_source", "kmanip_bind_step_depth", "kmanip_scripted_action", "kmanip_sample_action", "kmanip_set_env_params", "kmanip_get_env_params", "kmanip_set_env_param_ranges", "kmanip_set_visual_params", "kmanip_get_visual_params", "kmanip_set_visual_param_ranges",
     "kmanip_get_state_dev", "kmanip_set_state_dev", "kmanip_copy_envs", "kmanip_state_index_errors", "kmanip_num_envs", "kmanip_last_error", "kmanip_version", "kmanip_destroy",
 ]
@@ -192,6 +192,23 @@ class KAdjointDev(C.Structure):
     _fields_ = [("lam", C.c_void_p), ("mu", C.c_void_p)]
 
 
+class KTangentIn(C.Structure):
+    """include/kmanip.h KTangentIn: DEVICE pointers of kmanip_tangent's inputs -- KLqrIn's transposed step Jacobians and strides, the
+    transposed gains [n, T, nx, nu] (NULL: open loop), the sources [n, T, m, nx] with their block stride in doubles (0 = dense), the
+    control direction [n, T, m, nu], the initial tangent [n, m, nx] (NULL: zeros, each), the residual [n, T + 1, nx] and the weight
+    [nx, nx] (NULL: the identity) of the Gauss-Newton terms."""
+    _fields_ = [("a_t", C.c_void_p), ("b_t", C.c_void_p), ("a_stride", C.c_int64), ("b_stride", C.c_int64), ("gain_t", C.c_void_p),
+                ("src_t", C.c_void_p), ("src_stride", C.c_int64), ("du_t", C.c_void_p), ("s0_t", C.c_void_p), ("r", C.c_void_p),
+                ("w", C.c_void_p)]
+
+
+class KTangentDev(C.Structure):
+    """include/kmanip.h KTangentDev: DEVICE pointers of kmanip_tangent's outputs s_t [n, T + 1, m, nx], du_acted_t [n, T, m, nu],
+    h [n, m, m] and g [n, m], any of them NULL."""
+    _fields_ = [("s_t", C.c_void_p), ("du_acted_t", C.c_void_p), ("h", C.c_void_p), ("g", C.c_void_p)]
+
+
+KM_TANGENT_MC = 16               # include/kmanip.h: H and g need m <= KM_TANGENT_MC
 KM_WRT = {"qpos": 1, "qvel": 2, "ctrl": 4, "qfrc_applied": 8}     # include/kmanip.h KM_WRT_*: the columns always run in this order
 KM_MAX_LINK_CAPSULES = 24
 KM_COPY_EPISODE, KM_COPY_ENV_PARAMS = 1, 2       # include/kmanip.h: flags of kmanip_copy_envs
@@ -253,6 +270,7 @@ def load():
     lib.kmanip_lqr_backward.argtypes = [vp, C.POINTER(KLqrIn), C.c_int, C.c_int, C.POINTER(KLqrDev), vp]
     lib.kmanip_lqr_backward_box.argtypes = [vp, C.POINTER(KLqrBoxIn), C.c_int, C.c_int, C.POINTER(KLqrBoxDev), vp]
     lib.kmanip_adjoint.argtypes = [vp, C.POINTER(KAdjointIn), C.c_int, C.c_int, C.c_int, C.POINTER(KAdjointDev), vp]
+    lib.kmanip_tangent.argtypes = [vp, C.POINTER(KTangentIn), C.c_int, C.c_int, C.c_int, C.POINTER(KTangentDev), vp]
     lib.kmanip_set_seed.argtypes = [vp, C.c_uint64, C.c_int]
     lib.kmanip_get_diag.argtypes = [vp, C.POINTER(C.c_uint32), i32p, i32p]
     lib.kmanip_timing_summary.argtypes = [vp, f64p, f64p, f64p, i32p]

@@ -3,7 +3,8 @@ adds to the stack of ilqr.trajectory_fd (A_t = d x_{t+1} / d x_t), the adjoint s
 
 trajectory_param_fd   P_t = d x_{t+1} / d p at every step of a trajectory, one param_fd call
 param_grad            the gradient of a rollout loss in the parameters, sum_t P_t' lam_{t+1}
-param_sensitivity     S_t = d x_t / d p, the forward recursion S_{t+1} = (A_t + B_t K_t) S_t + P_t
+param_sensitivity     S_t = d x_t / d p, the forward recursion S_{t+1} = (A_t + B_t K_t) S_t + P_t (env=: one launch, kmanip_tangent)
+gauss_newton_terms    J'J and J'r of the tracking loss from that launch, without S in memory
 TrackingCost          1/2 sum_t dx_t' Q dx_t against an observed trajectory, with its residual
 rollout_param_grad    cost, its gradient in the parameters (and controls, and initial state) in four calls
 identify              Gauss-Newton with Levenberg-Marquardt damping on the parameters of n envs, one trajectory each
@@ -60,10 +61,15 @@ def param_grad(lam, P):
     return torch.einsum("ntxp,ntx->np", P, lam[:, 1:])
 
 
-def param_sensitivity(A, P, B=None, gains=None):
+def param_sensitivity(A, P, B=None, gains=None, env=None, deriv_t=None):
     """S [n, T + 1, 2 nv, npar]: d x_t / d p with x_0 held, S_0 = 0 and S_{t+1} = (A_t + B_t K_t) S_t + P_t (gains [n, T, nu, 2 nv] with
-    B [n, T, 2 nv, nu]: the policy of rollout_feedback; without them the open-loop recursion).  A torch loop over the steps."""
+    B [n, T, 2 nv, nu]: the policy of rollout_feedback; without them the open-loop recursion).  A torch loop over the steps.
+    env: the recursion in ONE launch instead (env.tangent, kmanip_tangent: S_{t+1} = A_t S_t + B_t (K_t S_t) + P_t), on deriv_t
+    (trajectory_fd(fused=True)'s, read where it lies) or on A and B -- B is then needed open loop too -- with P passed by pointer."""
     import torch
+    if env is not None:
+        dyn = dict(deriv_t=deriv_t) if deriv_t is not None else dict(A=A, B=B)
+        return env.tangent(src=P, gains=gains, **dyn)["S"]
     if (B is None) != (gains is None):
         raise ValueError("param_sensitivity: give B and gains together")
     n, T, nx, npar = (int(s) for s in P.shape)
@@ -138,8 +144,21 @@ def _scaled_jacobian(cost, S, scale):
     return J.reshape(n, L * nx, npar), half
 
 
+def gauss_newton_terms(env, fd, P, cost, gains=None, want_S=False):
+    """The Gauss-Newton terms of a tracking loss in the parameters from ONE launch (env.tangent, kmanip_tangent): H [n, npar, npar] =
+    sum_t S_t' W S_t and g [n, npar] = sum_t S_t' W dx_t, with S the sensitivity of param_sensitivity (never written to memory unless
+    want_S), W = cost.Q symmetrised and dx = cost.residual on the trajectory of `fd` (an ilqr.trajectory_fd result: its deriv_t where
+    fused gave one, else A and B), P [n, T, 2 nv, npar] trajectory_param_fd's.  npar <= KM_TANGENT_MC.  Unscaled: column scaling
+    is the caller's, H * (p_a p_b) and g * p_a.  Returns (H, g, S or None)."""
+    dyn = dict(deriv_t=fd["deriv_t"]) if "deriv_t" in fd else dict(A=fd["A"], B=fd["B"])
+    r = env.tangent(src=P, gains=gains, weight=cost.Q, resid=cost.residual(fd["qpos"], fd["qvel"]),
+                    fields=("H", "g") + (("S",) if want_S else ()), **dyn)
+    return r["H"], r["g"], r.get("S")
+
+
 def identify(env, envs, qpos0, qvel0, warm0, ctrl, qpos_obs, qvel_obs, wrt=ENV_PARAMS, iters=8, Q=None, qfrc_applied=None, nsub=None,
-             eps=1e-6, eps_param=1e-4, fused=False, damping=0.1, damping_up=10.0, damping_down=0.1, min_factor=0.5, max_factor=2.0, callback=None):
+             eps=1e-6, eps_param=1e-4, fused=False, damping=0.1, damping_up=10.0, damping_down=0.1, min_factor=0.5, max_factor=2.0, callback=None,
+             device_sensitivity=False):
     """Estimates the parameters `wrt` of envs [n] (no entry repeated) from one observed trajectory each: qpos_obs [n, T + 1, nq],
     qvel_obs [n, T + 1, nv], the states x_0 .. x_T that ctrl [n, T, nu] produced from (qpos0, qvel0, warm0).  Each problem estimates
     the parameters of its own env, starting from the values the handle has in force.
@@ -156,7 +175,10 @@ def identify(env, envs, qpos0, qvel0, warm0, ctrl, qpos_obs, qvel_obs, wrt=ENV_P
     after the last; accepted [iters, n] bool; singular_values [n, npar] of the scaled J at the last iterate, descending -- a ratio
     near zero says that a direction in parameter space is not observable from this trajectory (a cube in flight shows only a combination of its mass
     and friction loss); status [n] the largest rollout / linearisation / param_fd status met.
-    callback(iteration, params [n, npar], loss [n], singular_values [n, npar]) is called with every linearisation."""
+    callback(iteration, params [n, npar], loss [n], singular_values [n, npar]) is called with every linearisation.
+    device_sensitivity: J'J and J'r come from gauss_newton_terms -- the recursion and both products in one launch, scaled by the
+    parameter values in torch -- and the loss from cost.total; S is written and svdvals(J) taken only for a callback and at the last
+    iterate (singular_values keeps its meaning).  The default path is the torch loop, as it was."""
     import torch
     cm = env.cm
     order = _wrt(wrt)
@@ -176,29 +198,31 @@ def identify(env, envs, qpos0, qvel0, warm0, ctrl, qpos_obs, qvel_obs, wrt=ENV_P
         full[idx] = p_rows
         env.set_env_params(**{name: full[:, k].contiguous() for k, name in enumerate(ENV_PARAMS)})
 
-    def linearise():
+    def linearise(want_sv=True):
         fd = trajectory_fd(env, idx.to(torch.int32), qpos0, qvel0, warm0, ctrl, qfrc_applied=qfrc_applied, nsub=nsub, eps=eps, fused=fused)
         info = {}
         P = trajectory_param_fd(env, fd, idx.to(torch.int32), ctrl, qfrc_applied=qfrc_applied, nsub=nsub, eps=eps_param, wrt=order, info=info)
+        st = torch.maximum(torch.maximum(fd["status"], fd["status_fd"]), info["status_fd"])
+        if device_sensitivity:
+            H, g, S = gauss_newton_terms(env, fd, P, cost, want_S=want_sv)
+            scale = p[:, cols]
+            sv = torch.linalg.svdvals(_scaled_jacobian(cost, S, scale)[0]) if want_sv else None
+            return H * (scale[:, :, None] * scale[:, None, :]), g * scale, cost.total(fd["qpos"], fd["qvel"]), st, sv
         S = param_sensitivity(fd["A"], P)
         J, half = _scaled_jacobian(cost, S, p[:, cols])
         r = (cost.residual(fd["qpos"], fd["qvel"]) @ half.transpose(0, 1)).reshape(n, -1)
-        st = torch.maximum(torch.maximum(fd["status"], fd["status_fd"]), info["status_fd"])
-        return J, r, 0.5 * (r * r).sum(dim=1), st
+        return J.transpose(1, 2) @ J, (J.transpose(1, 2) @ r[:, :, None])[:, :, 0], 0.5 * (r * r).sum(dim=1), st, torch.linalg.svdvals(J)
 
     p = full[idx].clone()                                # [n, KM_EP_N]
     mu = torch.full((n,), float(damping), dtype=ctrl.dtype, device=dev)
     losses, accepted = [], []
     status = torch.zeros(n, dtype=torch.uint8, device=dev)
     for it in range(iters):
-        J, r, loss, st = linearise()
+        H, g, loss, st, sv = linearise(want_sv=callback is not None)
         status = torch.maximum(status, st)
-        sv = torch.linalg.svdvals(J)
         if callback is not None:
             callback(it, p[:, cols].clone(), loss.clone(), sv)
         losses.append(loss)
-        H = J.transpose(1, 2) @ J
-        g = (J.transpose(1, 2) @ r[:, :, None])[:, :, 0]
         dg = torch.diagonal(H, dim1=1, dim2=2)
         dg = torch.where(dg > 0, dg, torch.ones_like(dg))
         d = -torch.linalg.solve(H + torch.diag_embed(mu[:, None] * dg), g)
@@ -215,9 +239,8 @@ def identify(env, envs, qpos0, qvel0, warm0, ctrl, qpos_obs, qvel_obs, wrt=ENV_P
         mu = torch.where(ok, mu * damping_down, mu * damping_up)
         if not bool(ok.all()):
             write(p)                                     # the problems that refused their candidate keep their values
-    J, r, loss, st = linearise()
+    H, g, loss, st, sv = linearise()
     status = torch.maximum(status, st)
-    sv = torch.linalg.svdvals(J)
     if callback is not None:
         callback(iters, p[:, cols].clone(), loss.clone(), sv)
     losses.append(loss)

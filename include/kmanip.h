@@ -891,6 +891,55 @@ typedef struct KAdjointDev { /* either field may be NULL */
  * policy (-K' mu: one line for the caller), analytic step derivatives. */
 KMANIP_API int kmanip_adjoint(KHandle h, const KAdjointIn* in, int n, int T, int m, const KAdjointDev* out, void* stream);
 
+/* The FORWARD SENSITIVITY sweep of a rollout -- kmanip_adjoint's forward-mode twin (gym_kmanip_amd/derivatives.py
+ * tangent_pass is the definition; sysid.param_sensitivity / gauss_newton_terms and grad.rollout_jvp build on it): n problems of T
+ * steps and m >= 1 TANGENT COLUMNS per problem in ONE launch, the dynamics addressed exactly as in KLqrIn / KAdjointIn (deriv_t of
+ * kmanip_transition_fd is read where it lies, extra columns skipped by the stride).  Column a of problem e, with s_0 = s0 (NULL: 0):
+ *   du[t]_i  = dU[t]_i + sum_k K_t[i][k] s[t]_k                              (the sum only when gains are given; dU NULL: zeros)
+ *   s[t+1]_j = sum_k A_t[j][k] s[t]_k + sum_i B_t[j][i] du[t]_i + src[t]_j   (src NULL: zeros)
+ * With src = kmanip_param_fd's deriv_t this is S_t = d x_t / d p; with dU a control direction it is the JVP of the rollout (a
+ * Gauss-Newton Hessian-vector product's first half, a line search's predicted change).  Optionally, from the same launch, the
+ * GAUSS-NEWTON terms against a residual r and a weight W shared by all problems and steps (NULL: the identity), y[t] = W s[t]:
+ *   H[a][b] = sum_{t=0..T} sum_j s[t]^a_j y[t]^b_j          g[a] = sum_{t=0..T} sum_j y[t]^a_j r[t]_j
+ * H is computed for a <= b and mirrored: bitwise symmetric (W itself is not symmetrised here: pass a symmetric one).
+ * THE ORDER OF EVERY SUM: du one FMA chain from 0 over k ascending, then ONE add of dU (NULL adds 0.0); s[t+1] one FMA chain from 0
+ * over k ascending (A), continued over i ascending (B), then ONE add of src (NULL adds 0.0); y a chain over k ascending; a step's
+ * term of H and g a chain from 0 over j ascending, added to the accumulator in t ascending.  Open loop without dU the B products are
+ * not formed.  No column reads another column's vector in the recursion: a column's result does not depend on n, on m or on its
+ * place, and with every gain entry zero the values are the open-loop ones.
+ * THE ONE APPROXIMATION is kmanip_adjoint's: with gains, dx is taken as linear in the state. */
+#define KM_TANGENT_MC 16    /* columns a workgroup carries; H and g need m <= KM_TANGENT_MC */
+typedef struct KTangentIn {
+  const double* a_t;        /* KLqrIn::a_t: block (e, t) at a_t + (e*T + t) * a_stride, [nx, nx] TRANSPOSED */
+  const double* b_t;        /* KLqrIn::b_t: block (e, t) at b_t + (e*T + t) * b_stride, [nu, nx] */
+  int64_t a_stride, b_stride; /* in doubles; 0 = dense (nx*nx, nu*nx) */
+  const double* gain_t;     /* [n, T, nx, nu]: KFeedbackIn::gain_t's layout, a trajectory per problem; NULL = open loop */
+  const double* src_t;      /* block (e, t) at src_t + (e*T + t) * src_stride, [m, nx]: column a's source, rows contiguous.  KParamFdDev::
+                               deriv_t over the n*T rows e*T + t is this layout as it lies.  NULL = zeros */
+  int64_t src_stride;       /* in doubles; 0 = dense (m*nx) */
+  const double* du_t;       /* [n, T, m, nu] the open-loop control direction dU, or NULL = zeros */
+  const double* s0_t;       /* [n, m, nx] the initial tangent, or NULL = zeros */
+  const double* r;          /* [n, T+1, nx] the residual g is taken against; NULL only while g is NULL */
+  const double* w;          /* [nx, nx] the weight W, or NULL = the identity */
+} KTangentIn;
+typedef struct KTangentDev { /* any field may be NULL: what is not asked for is not written (H and g alone write no S to memory) */
+  double* s_t;              /* [n, T+1, m, nx]: entry (e, t, a, .) = column a of s[t] */
+  double* du_acted_t;       /* [n, T, m, nu]: du[t], the control change that acted */
+  double* h;                /* [n, m, m] */
+  double* g;                /* [n, m] */
+} KTangentDev;
+/* NO STATUS: nothing is factorised, and a non-finite input propagates as IEEE arithmetic propagates it, into the columns that read it
+ * only: a NaN in column a's src reaches column a of s, row and column a of H and g[a], nothing else; one in A_t reaches every column
+ * of its problem.
+ * ONE kernel launch, asynchronous on `stream`: no allocation, no synchronisation, no host copy.  THE HANDLE IS READ ONLY (it gives
+ * the device, nx and nu).  n == 0, T == 0 or m == 0 succeeds and launches nothing (the fields of `in` are then not looked at).
+ * ERRORS: a NULL handle, `in` or `out`, a NULL a_t or b_t, n < 0, T < 0 or m < 0, a nonzero stride smaller than its block, n * m * T
+ * beyond int, h or g asked for with m > KM_TANGENT_MC, or g asked for with a NULL r return nonzero with kmanip_last_error set,
+ * launch nothing and leave the outputs untouched.
+ * OUT OF SCOPE: normal equations across chunks (m > KM_TANGENT_MC), per-step or per-problem weights, the SVD, sensitivities through
+ * the clamped policy of kmanip_feedback_box, second-order terms, analytic step derivatives. */
+KMANIP_API int kmanip_tangent(KHandle h, const KTangentIn* in, int n, int T, int m, const KTangentDev* out, void* stream);
+
 /* KManipEnv.reset(seed=...) (env_base.py:219-220): re-key the cube-spawn stream.  restart_episodes != 0 also rewinds every
  * env's episode counter so that the next kmanip_reset draws episode 0 of the new seed (reset(seed=s) is then reproducible). */
 KMANIP_API int kmanip_set_seed(KHandle h, uint64_t seed, int restart_episodes);
