@@ -655,6 +655,40 @@ int kmanip_transition_fd(KHandle h, const KTransFdIn* in, int n, int nsub, const
   return 0;
 }
 
+// derivatives.py forward_fd at rows the caller passes (include/kmanip.h KForwardFdIn / KForwardFdDev; kmanip_forward_fd.hip; DESIGN.md
+// section 44).  Two launches ordered by the stream: the nominal rows through kmanip_forward's kernel, then the column pairs, which read
+// the nominal qacc the first wrote.  The handle is only read; Newton handles only.
+int kmanip_forward_fd(KHandle h, const KForwardFdIn* in, int n, const KForwardFdDev* out, void* stream) {
+  if (!h) { g_create_error = "kmanip_forward_fd: null handle"; return -1; }
+  if (row_args(h, "kmanip_forward_fd", "KForwardFdIn", "KForwardFdDev", in, out, n)) return -1;
+  if (n == 0) return 0;                // (first: tensors of no rows have no address, and nothing below is asked of such a call)
+  if (h->desc.solver != KM_SOLVER_NEWTON) { h->err = "kmanip_forward_fd: contact forces need the Newton solver"; return -1; }
+  const int wrt = in->wrt, of = in->of, nv = h->desc.nlink + 6, nu = h->desc.nlink;
+  if (wrt & ~(KM_WRT_QPOS | KM_WRT_QVEL | KM_WRT_CTRL | KM_WRT_FRC)) { h->err = "kmanip_forward_fd: wrt has bits outside KM_WRT_*"; return -1; }
+  if (of & ~(KM_OF_QACC | KM_OF_QFRC_CONSTRAINT | KM_OF_QFRC_ACTUATOR | KM_OF_CONTACT_FORCE)) { h->err = "kmanip_forward_fd: of has bits outside KM_OF_*"; return -1; }
+  if (!(in->eps - in->eps == 0.0) || !(in->eps > 0.0)) { h->err = "kmanip_forward_fd: eps is not a finite positive number"; return -1; }
+  if (!(in->warm_offset - in->warm_offset == 0.0)) { h->err = "kmanip_forward_fd: warm_offset is not finite"; return -1; }
+  if (wrt && !of) { h->err = "kmanip_forward_fd: wrt is set and of names no output"; return -1; }
+  if (wrt && !out->deriv_t) { h->err = "kmanip_forward_fd: wrt is set and KForwardFdDev::deriv_t is NULL"; return -1; }
+  if (wrt && !out->qacc) { h->err = "kmanip_forward_fd: the perturbed rows start from KForwardFdDev::qacc, which is NULL"; return -1; }
+  const int ncol = ((wrt & KM_WRT_QPOS) ? nv : 0) + ((wrt & KM_WRT_QVEL) ? nv : 0) + ((wrt & KM_WRT_CTRL) ? nu : 0) + ((wrt & KM_WRT_FRC) ? nv : 0);
+  if (2LL * ncol * n > 2147483647LL) { h->err = "kmanip_forward_fd: 2 ncol n perturbed rows are more than an int counts"; return -1; }
+  const hipStream_t s = (hipStream_t)stream;
+  const KForwardIn fi = {in->env_index, in->qpos, in->qvel, in->ctrl, in->qacc_warm, in->qfrc_applied};
+  const KForcesDev fo = {out->qacc, out->qfrc_constraint, out->qfrc_actuator, out->contact_force, nullptr, nullptr, nullptr, nullptr,
+                         out->contact_mask, out->status};
+  if (forces_out_empty(fo)) return 0;  // (and then wrt == 0)
+  KM_ENTER(h);
+  kmanip_launch_forward(h->dmodel, h->desc, h->st, fi, n, fo, s);
+  HIPCHK(h, hipGetLastError());
+  if (wrt) {
+    // tangent_perturb's rotation columns: cos and sin of eps / 2, once, on the host
+    kmanip_launch_fwdfd(h->dmodel, h->desc, h->st, *in, n, ncol, cos(0.5 * in->eps), sin(0.5 * in->eps), *out, s);
+    HIPCHK(h, hipGetLastError());
+  }
+  return 0;
+}
+
 // Centred finite differences of ONE step in the per-env physics parameters at rows the caller passes (include/kmanip.h KParamFdIn /
 // KParamFdDev; kmanip_paramfd.hip).  One launch; the handle is only read; the handle's solver; always a
 // per-env parameter build, on a handle without parameters over the compiled model's values.

@@ -605,6 +605,10 @@ void kmanip_launch_boxfb(const KDeviceModel* dm, const KModelDesc& hd, const KDe
 // sh = cos / sin of eps / 2; the applied-force build also while in.wrt has KM_WRT_FRC
 void kmanip_launch_transfd(const KDeviceModel* dm, const KModelDesc& hd, const KDeviceState& st, const KTransFdIn& in, int n, int ncol,
                            int nsub, double ch, double sh, const KTransFdDev& out, hipStream_t stream);
+// kmanip_forward_fd's second launch (Newton handles only: the caller checks): the n * ncol > 0 column pairs of n rows, ch / sh = cos /
+// sin of eps / 2; the builds are picked as kmanip_launch_transfd picks them
+void kmanip_launch_fwdfd(const KDeviceModel* dm, const KModelDesc& hd, const KDeviceState& st, const KForwardFdIn& in, int n, int ncol,
+                         double ch, double sh, const KForwardFdDev& out, hipStream_t stream);
 // the limits every per-env parameter value must meet (kmanip_set_env_params, the ranges' lo and hi, k_paramfd's rows and perturbed values)
 __host__ __device__ static inline bool ep_value_ok(int k, double v) {
   if (!(v - v == 0.0)) return false;           // NaN or infinite (host and device alike)

@@ -26,6 +26,7 @@ typedef void RolloutFn(const KDeviceModel*, const KDeviceState&, const KRolloutI
 typedef void FeedbackFn(const KDeviceModel*, const KDeviceState&, const KFeedbackIn&, int, int, int, const KFeedbackDev&, hipStream_t);
 typedef void BoxFbFn(const KDeviceModel*, const KDeviceState&, const KFeedbackBoxIn&, int, int, int, const KFeedbackDev&, hipStream_t);
 typedef void ParamFdFn(const KDeviceModel*, const KDeviceState&, const KParamFdIn&, const KEnvParamDefaults&, int, int, int, const KParamFdDev&, hipStream_t);
+typedef void FwdFdFn(const KDeviceModel*, const KDeviceState&, const KForwardFdIn&, int, int, double, double, const KForwardFdDev&, hipStream_t);
 typedef void TransFdFn(const KDeviceModel*, const KDeviceState&, const KTransFdIn&, int, int, int, double, double, const KTransFdDev&, hipStream_t);
 
 // kmanip_dyn.hip: step per solver in every build, reset per solver in the parameter builds; observe and prepare are
@@ -50,12 +51,14 @@ typedef void TransFdFn(const KDeviceModel*, const KDeviceState&, const KTransFdI
 #define KM_KIN_ROW(B, NL, G) KM_NAME(kinematics, B, NL, G, ),
 #define KM_INVERSE_ROW(B, NL, G) KM_NAME(inverse, B, NL, G, ),
 #define KM_FORWARD_ROW(B, NL, G) KM_NAME(forward, B, NL, G, ),
+// kmanip_forward_fd.hip: the Newton classes, every build, like kmanip_forward.hip
+#define KM_FWDFD_ROW(B, NL, G) KM_NAME(fwdfd, B, NL, G, ),
 // kmanip_sitekin.hip: two launchers per object, one object per class, the parameter builds
 #define KM_KINROWS_ROW(B, NL, G) KM_NAME(kinrows, B, NL, G, ),
 #define KM_SITECOST_ROW(B, NL, G) KM_NAME(sitecost, B, NL, G, ),
 
 #define KM_DECL_SOLVERS(Fn, kind, B, NL, G) Fn KM_NAME(kind, B, NL, G, _0), KM_NAME(kind, B, NL, G, _1);
-#define KM_DECL_FRC(B, NL, G) KM_DECL_SOLVERS(StepFn, step, B, NL, G) KM_DECL_SOLVERS(RolloutFn, rollout, B, NL, G) KM_DECL_SOLVERS(FeedbackFn, feedback, B, NL, G) KM_DECL_SOLVERS(BoxFbFn, boxfb, B, NL, G) KM_DECL_SOLVERS(TransFdFn, transfd, B, NL, G) ForcesFn KM_NAME(forces, B, NL, G, ); ForwardFn KM_NAME(forward, B, NL, G, );
+#define KM_DECL_FRC(B, NL, G) KM_DECL_SOLVERS(StepFn, step, B, NL, G) KM_DECL_SOLVERS(RolloutFn, rollout, B, NL, G) KM_DECL_SOLVERS(FeedbackFn, feedback, B, NL, G) KM_DECL_SOLVERS(BoxFbFn, boxfb, B, NL, G) KM_DECL_SOLVERS(TransFdFn, transfd, B, NL, G) ForcesFn KM_NAME(forces, B, NL, G, ); ForwardFn KM_NAME(forward, B, NL, G, ); FwdFdFn KM_NAME(fwdfd, B, NL, G, );
 #define KM_DECL_PAR(B, NL, G) KM_DECL_SOLVERS(ResetFn, reset, B, NL, G) KinFn KM_NAME(kinematics, B, NL, G, ); InverseFn KM_NAME(inverse, B, NL, G, ); KinRowsFn KM_NAME(kinrows, B, NL, G, ); SiteCostFn KM_NAME(sitecost, B, NL, G, );
 #define KM_DECL_ONCE(B, NL, G) ObserveFn KM_NAME(observe, B, NL, G, _1); PrepareFn KM_NAME(prepare, B, NL, G, _1);
 #define KM_DECL_EP(B, NL, G) KM_DECL_SOLVERS(ParamFdFn, paramfd, B, NL, G)
@@ -71,6 +74,7 @@ KM_BUILDS(KM_DECL_BUILD_FRC) KM_BUILDS_PAR(KM_DECL_BUILD_PAR) KM_BUILDS_EP(KM_DE
 #define KM_KIN_BUILD(B) {KM_CLASSES(KM_KIN_ROW, B)},
 #define KM_INVERSE_BUILD(B) {KM_CLASSES(KM_INVERSE_ROW, B)},
 #define KM_FORWARD_BUILD(B) {KM_CLASSES(KM_FORWARD_ROW, B)},
+#define KM_FWDFD_BUILD(B) {KM_CLASSES(KM_FWDFD_ROW, B)},
 #define KM_KINROWS_BUILD(B) {KM_CLASSES(KM_KINROWS_ROW, B)},
 #define KM_SITECOST_BUILD(B) {KM_CLASSES(KM_SITECOST_ROW, B)},
 #define KM_ROLLOUT_BUILD(B) {KM_CLASSES(KM_ROLLOUT_ROW, B)},
@@ -86,6 +90,7 @@ static constexpr ForcesFn* forces_tab[4][2] = {KM_BUILDS(KM_FORCES_BUILD)};
 static constexpr KinFn* kin_tab[2][2] = {KM_BUILDS_PAR(KM_KIN_BUILD)};
 static constexpr InverseFn* inverse_tab[2][2] = {KM_BUILDS_PAR(KM_INVERSE_BUILD)};
 static constexpr ForwardFn* forward_tab[4][2] = {KM_BUILDS(KM_FORWARD_BUILD)};
+static constexpr FwdFdFn* fwdfd_tab[4][2] = {KM_BUILDS(KM_FWDFD_BUILD)};
 static constexpr KinRowsFn* kinrows_tab[2][2] = {KM_BUILDS_PAR(KM_KINROWS_BUILD)};
 static constexpr SiteCostFn* sitecost_tab[2][2] = {KM_BUILDS_PAR(KM_SITECOST_BUILD)};
 static constexpr RolloutFn* rollout_tab[4][2][2] = {KM_BUILDS(KM_ROLLOUT_BUILD)};
@@ -154,6 +159,12 @@ void kmanip_launch_transfd(const KDeviceModel* dm, const KModelDesc& hd, const K
                            int nsub, double ch, double sh, const KTransFdDev& out, hipStream_t stream) {
   const int build = par(st) + ((in.qfrc_applied || st.qfrc_applied || (in.wrt & KM_WRT_FRC)) ? 2 : 0);
   transfd_tab[build][cls(hd)][newton(hd)](dm, st, in, n, ncol, nsub, ch, sh, out, stream);
+}
+// (Newton handles only: the caller checks; the force build as kmanip_launch_transfd picks it)
+void kmanip_launch_fwdfd(const KDeviceModel* dm, const KModelDesc& hd, const KDeviceState& st, const KForwardFdIn& in, int n, int ncol,
+                         double ch, double sh, const KForwardFdDev& out, hipStream_t stream) {
+  const int build = par(st) + ((in.qfrc_applied || st.qfrc_applied || (in.wrt & KM_WRT_FRC)) ? 2 : 0);
+  fwdfd_tab[build][cls(hd)](dm, st, in, n, ncol, ch, sh, out, stream);
 }
 // (a parameter build whatever par(st) says: the kernel takes the parameters from its arguments)
 void kmanip_launch_paramfd(const KDeviceModel* dm, const KModelDesc& hd, const KDeviceState& st, const KParamFdIn& in,

@@ -12,6 +12,7 @@ bit-equal rows."""
 import math
 
 WRT = ("qpos", "qvel", "ctrl", "qfrc_applied")
+OF = ("qacc", "qfrc_constraint", "qfrc_actuator", "contact_force")      # what forward_fd differentiates, in the fused kernel's order
 _BLOCK = {"qpos": "dqpos", "qvel": "dqvel", "ctrl": "dctrl", "qfrc_applied": "dfrc"}
 
 
@@ -242,7 +243,7 @@ def gauss_newton_products(S, resid=None, weight=None):
 
 
 def forward_fd(env, envs=None, qpos=None, qvel=None, ctrl=None, qfrc_applied=None, eps=1e-6,
-               wrt=("qpos", "qvel", "ctrl", "qfrc_applied"), warm_offset=1.0):
+               wrt=("qpos", "qvel", "ctrl", "qfrc_applied"), warm_offset=1.0, of=("qacc", "qfrc_constraint"), fused=False):
     """Centred finite differences of env.forward's qacc and qfrc_constraint with respect to the inputs named in `wrt`, at the rows
     (envs, qpos, qvel, ctrl, qfrc_applied) as forward() takes them.  Two launches: the nominal rows, then all 2 ncol n perturbed
     rows at once, each with the nominal qacc + warm_offset (on every dof) as its warm start.
@@ -265,14 +266,25 @@ def forward_fd(env, envs=None, qpos=None, qvel=None, ctrl=None, qfrc_applied=Non
     THE DYNAMICS ARE PIECEWISE SMOOTH.  Across a change of the active set -- a contact opening or closing, a friction-loss row
     saturating, a servo reaching its force or control clamp -- qacc has a kink, and where +eps and -eps fall on different sides
     of one the quotient is a SECANT across it, not a derivative; contact_mask_fd shows the contact part of that.  No smoothing is
-    applied."""
+    applied.
+    `of`: the outputs differentiated, any of OF.  qfrc_actuator adds the nominal qfrc_actuator [n, nu] and dqfrc_actuator_d*
+    [n, nu, w]; contact_force adds contact_force [n, NC, 4] and dcontact_force_d* [n, NC, 4, w], differenced SLOT BY SLOT with an
+    empty slot counting as zeros: where the +eps and -eps rows hold different contact sets an entry is a secant across the change,
+    or the difference of two pairs that share a slot (contact_mask_fd shows it; nothing is matched).  This torch path is THE
+    DEFINITION of those blocks.  fused=True hands the same arguments to env.forward_fd (KManipEnvHip.forward_fd: one library call,
+    the perturbation and the quotient inside the kernel) and returns its dict, which has these keys and a few more."""
     import torch
     cm = env.cm
     nv, nu = cm.nv, cm.nu
-    wrt = tuple(wrt)
+    wrt, of = tuple(wrt), tuple(of)
     unknown = set(wrt) - set(WRT)
     if unknown:
         raise ValueError("unknown wrt name(s) %s" % sorted(unknown))
+    if set(of) - set(OF):
+        raise ValueError("unknown of name(s) %s" % sorted(set(of) - set(OF)))
+    if fused:
+        return env.forward_fd(envs=envs, qpos=qpos, qvel=qvel, ctrl=ctrl, qfrc_applied=qfrc_applied, eps=eps, wrt=wrt, of=of,
+                              warm_offset=warm_offset)
     given = {"qpos": qpos, "qvel": qvel, "ctrl": ctrl, "qfrc_applied": qfrc_applied}
     for name in wrt:
         if given[name] is None and name != "qfrc_applied":
@@ -284,12 +296,14 @@ def forward_fd(env, envs=None, qpos=None, qvel=None, ctrl=None, qfrc_applied=Non
             nominal = env.forward(envs=envs, fields=("qacc",))
             ref = nominal["qacc"]
         given["qfrc_applied"] = torch.zeros((ref.shape[0], nv), dtype=torch.float64, device=ref.device)
-    fields = ("qacc", "qfrc_constraint", "contact_mask", "status")
+    extra = tuple(k for k in OF[2:] if k in of)
+    fields = ("qacc", "qfrc_constraint") + extra + ("contact_mask", "status")
     nominal = env.forward(envs=envs, qpos=given["qpos"], qvel=given["qvel"], ctrl=given["ctrl"], qfrc_applied=given["qfrc_applied"],
                           fields=fields)
     a0 = nominal["qacc"]
     n, dev = int(a0.shape[0]), a0.device
     out = {"qacc": a0, "qfrc_constraint": nominal["qfrc_constraint"], "status": nominal["status"]}
+    out.update((k, nominal[k]) for k in extra)
     width = {"qpos": nv, "qvel": nv, "ctrl": nu, "qfrc_applied": nv}
     ncol = sum(width[name] for name in wrt)
     if ncol == 0 or n == 0:
@@ -311,11 +325,11 @@ def forward_fd(env, envs=None, qpos=None, qvel=None, ctrl=None, qfrc_applied=Non
                        qfrc_applied=big["qfrc_applied"], fields=fields)
     out["status_fd"] = pert["status"].reshape(reps, n).max(dim=0).values
     out["contact_mask_fd"] = pert["contact_mask"].reshape(ncol, 2, n)
-    for key in ("qacc", "qfrc_constraint"):
-        v = pert[key].reshape(ncol, 2, n, nv)
-        d = ((v[:, 0] - v[:, 1]) / (2.0 * eps)).permute(1, 2, 0)          # [n, nv, ncol]
+    for key in (k for k in OF if k in of):
+        v = pert[key].reshape((ncol, 2, n) + tuple(pert[key].shape[1:]))
+        d = ((v[:, 0] - v[:, 1]) / (2.0 * eps)).movedim(0, -1)            # [n, nv, ncol]; contact_force: [n, NC, 4, ncol]
         c = 0
         for name in wrt:
-            out["d%s_%s" % (key, _BLOCK[name])] = d[:, :, c:c + width[name]].contiguous()
+            out["d%s_%s" % (key, _BLOCK[name])] = d[..., c:c + width[name]].contiguous()
             c += width[name]
     return out

@@ -531,6 +531,85 @@ class KManipEnvHip:
             res["contact_mask_fd"] = m.permute(1, 2, 0)
         return res
 
+    # KForwardFdDev field -> (trailing shape in terms of nv / nu / nc / ncol / nout, dtype name)
+    _FWDFD_FIELDS = {"qacc": (("nv",), "float64"), "qfrc_constraint": (("nv",), "float64"), "qfrc_actuator": (("nu",), "float64"),
+                     "contact_force": (("nc", 4), "float64"), "contact_mask": ((), "int32"), "status": ((), "uint8"),
+                     "deriv_t": (("ncol", "nout"), "float64"), "status_cols": (("ncol",), "uint8"), "contact_mask_fd": (("ncol", 2), "int32")}
+
+    def forward_fd(self, envs=None, qpos=None, qvel=None, ctrl=None, qfrc_applied=None, warm=None, eps=1e-6,
+                   wrt=("qpos", "qvel", "ctrl", "qfrc_applied"), of=("qacc", "qfrc_constraint"), warm_offset=1.0):
+        """kmanip_forward_fd: derivatives.forward_fd -- centred finite differences of forward()'s outputs named in `of` (qacc,
+        qfrc_constraint, qfrc_actuator, contact_force) with respect to the inputs named in `wrt` -- in ONE library call of two
+        launches: the nominal rows through forward()'s kernel, then a kernel that perturbs the rows, solves the +eps and -eps copies
+        side by side in one wave and forms the quotients in registers.  No perturbed row and no perturbed output reaches memory, and
+        no torch arithmetic runs.  Rows and their None fields as in forward(): unlike derivatives.forward_fd a differentiated input
+        may stay None (the named env's stored values are then differentiated about); `warm` is the nominal rows' warm start only.
+        Per row the arithmetic is derivatives.forward_fd's, operation for operation: see there for eps, warm_offset and the
+        piecewise-smooth caveat.  Returns its dict:
+          qacc, qfrc_constraint [n, nv], status [n] uint8, and qfrc_actuator [n, nu] / contact_force [n, NC, 4] where `of` names
+          them: the nominal rows
+          dqacc_dqpos [n, nv, nv], dqacc_dqvel, dqacc_dctrl [n, nv, nu], dqacc_dfrc; dqfrc_constraint_d* likewise;
+          dqfrc_actuator_d* [n, nu, w]; dcontact_force_d* [n, NC, 4, w] (slot by slot, an empty slot counting as zeros): the
+          blocks of `wrt` and `of` only, TRANSPOSED VIEWS, no copy, of the one buffer the kernel writes, also returned as deriv_t
+          [n, ncol, nout] with the columns in the order qpos, qvel, ctrl, qfrc_applied and the outputs in the order qacc,
+          qfrc_constraint, qfrc_actuator, contact_force whatever the order of `wrt` and `of`
+          status_cols [n, ncol] uint8 and status_fd [n] = its largest entry per row (nonzero: the column is zeros, not a derivative)
+          contact_mask_fd [ncol, 2, n] int32: the mask of every perturbed row, + then -, columns in `wrt` order
+        A differentiated qfrc_applied left None is rows of zeros, as in derivatives.forward_fd (also while a force is bound: pass its
+        rows to differentiate about it).  Newton handles only."""
+        torch = _torch()
+        from .derivatives import _BLOCK
+        from .model import contact_slots
+        cm = self.cm
+        wrt, of = tuple(wrt), tuple(of)
+        for what, names, known in (("wrt", wrt, _libmod.KM_WRT), ("of", of, _libmod.KM_OF)):
+            if set(names) - set(known):
+                raise ValueError("unknown %s name(s) %s" % (what, sorted(set(names) - set(known))))
+            if len(set(names)) != len(names):
+                raise ValueError("forward_fd: a name is repeated in %s %s" % (what, names))
+        nc = contact_slots(cm.nlink)
+        width = {"qpos": cm.nv, "qvel": cm.nv, "ctrl": cm.nu, "qfrc_applied": cm.nv}
+        owidth = {"qacc": cm.nv, "qfrc_constraint": cm.nv, "qfrc_actuator": cm.nu, "contact_force": 4 * nc}
+        order = [name for name in _libmod.KM_WRT if name in wrt]             # the kernel's column order
+        outs = [name for name in _libmod.KM_OF if name in of]                # ... and its order of the outputs
+        ncol, nout = sum(width[name] for name in order), sum(owidth[name] for name in outs)
+        fi = _libmod.KForwardFdIn()
+        given = [("qpos", qpos, (cm.nq,)), ("qvel", qvel, (cm.nv,)), ("ctrl", ctrl, (cm.nu,)), ("qacc_warm", warm, (cm.nv,)),
+                 ("qfrc_applied", qfrc_applied, (cm.nv,))]
+        n, idx = self._query_rows(envs, given, fi)
+        if "qfrc_applied" in wrt and qfrc_applied is None and self.applied_force is not None and n > 0:
+            qfrc_applied = torch.zeros((n, cm.nv), dtype=torch.float64, device=self.device)
+            fi.qfrc_applied = qfrc_applied.data_ptr()
+        fi.wrt, fi.of = sum(_libmod.KM_WRT[name] for name in order), sum(_libmod.KM_OF[name] for name in outs)
+        fi.eps, fi.warm_offset = float(eps), float(warm_offset)
+        names = ["qacc", "qfrc_constraint"] + [name for name in outs if name not in ("qacc", "qfrc_constraint")] + ["status"]
+        if ncol and n:
+            if not nout:
+                raise ValueError("forward_fd: `of` names no output to differentiate")
+            names += ["deriv_t", "status_cols", "contact_mask_fd"]
+        dims = {"nv": cm.nv, "nu": cm.nu, "nc": nc, "ncol": ncol, "nout": nout}
+        fd = _libmod.KForwardFdDev()
+        res = self._query_out(self._FWDFD_FIELDS, (n,), dims, None, names, fd, "forward_fd")
+        self._check(self.L.kmanip_forward_fd(self.h, C.byref(fi), n, C.byref(fd), self._stream()), "kmanip_forward_fd")
+        if "deriv_t" not in res:
+            return res
+        d = res["deriv_t"].transpose(1, 2)                                   # [n, nout, ncol], a view
+        o = 0
+        for key in outs:
+            c = 0
+            for name in order:
+                blk = d[:, o:o + owidth[key], c:c + width[name]]
+                res["d%s_%s" % (key, _BLOCK[name])] = blk.unflatten(1, (nc, 4)) if key == "contact_force" else blk
+                c += width[name]
+            o += owidth[key]
+        res["status_fd"] = res["status_cols"].amax(dim=1)
+        m = res["contact_mask_fd"]
+        if list(wrt) != order:               # the caller's column order
+            start = {name: sum(width[k] for k in order[:order.index(name)]) for name in order}
+            m = m[:, torch.cat([torch.arange(start[name], start[name] + width[name], device=self.device) for name in wrt])]
+        res["contact_mask_fd"] = m.permute(1, 2, 0)
+        return res
+
     # KParamFdDev field -> (trailing shape in terms of npar / nx = 2 nv, dtype name)
     _PARAMFD_FIELDS = {"deriv_t": (("npar", "nx"), "float64"), "status_cols": (("npar",), "uint8"), "contact_mask_fd": (("npar", 2), "int32")}
 

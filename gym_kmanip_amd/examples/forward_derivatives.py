@@ -2,7 +2,7 @@
 """Linearise the forward dynamics with finite differences (gym_kmanip_amd.derivatives.forward_fd over KManipEnvHip.forward) and test
 the linear model on a small step.  Nothing crosses PCIe until the figures are printed.
 
-    python -m gym_kmanip_amd.examples.forward_derivatives [--env KManipSoloArm] [--num-envs 64] [--steps 8] [--scale 1e-4]
+    python -m gym_kmanip_amd.examples.forward_derivatives [--env KManipSoloArm] [--num-envs 64] [--steps 8] [--scale 1e-4] [--fused]
 
 After `steps` steps of the scripted policy the envs' states are read on the device, forward_fd gives qacc and its derivatives with
 respect to ctrl and the applied force at those states (two forward() launches: the nominal rows, then all perturbed rows), and a
@@ -10,7 +10,11 @@ random dctrl (|.| <= scale rad) and dfrc (|.| <= scale N) are drawn.  forward() 
 prediction  qacc + dqacc_dctrl dctrl + dqacc_dfrc dfrc.  Printed: the worst gap over all envs relative to the size of the change
 the step caused (max |qacc(perturbed) - qacc|), and the worst over the envs whose contact mask did not change.  The dynamics are
 piecewise smooth (a contact opening, a friction-loss row saturating, a servo reaching its clamp), so an env that crosses a kink
-inside the step shows a gap of order one: the derivative there is a secant, and no bar is attached to the figure."""
+inside the step shows a gap of order one: the derivative there is a secant, and no bar is attached to the figure.
+--fused takes the same derivatives from KManipEnvHip.forward_fd: one library call, the perturbation and the quotient inside the kernel.
+Either way the contact forces are differentiated as well, and the record ends with the normal-force sensitivity of a grasping finger
+to its own servo's ctrl: d contact_force[slot of the finger's sphere, normal] / d ctrl[the finger's joint], N / rad, over the right
+arm's fingers that touch the cube in the nominal row and in both perturbed rows."""
 import argparse
 import json
 
@@ -28,6 +32,7 @@ def main(argv=None):
     ap.add_argument("--scale", type=float, default=1e-4)
     ap.add_argument("--eps", type=float, default=1e-6)
     ap.add_argument("--seed", type=int, default=3)
+    ap.add_argument("--fused", action="store_true")
     args = ap.parse_args(argv)
     env = env_hip.make(args.env, num_envs=args.num_envs, seed=args.seed)
     cm, n = env.cm, args.num_envs
@@ -36,7 +41,8 @@ def main(argv=None):
     for _ in range(args.steps):
         env.step_flat(env.scripted_action(generator=gen))
     st = env.state_tensors()
-    d = forward_fd(env, qpos=st["qpos"], qvel=st["qvel"], ctrl=st["ctrl"], eps=args.eps, wrt=("ctrl", "qfrc_applied"))
+    d = forward_fd(env, qpos=st["qpos"], qvel=st["qvel"], ctrl=st["ctrl"], eps=args.eps, wrt=("ctrl", "qfrc_applied"),
+                   of=("qacc", "qfrc_constraint", "contact_force"), fused=args.fused)
     dctrl = (torch.rand((n, cm.nu), dtype=torch.float64, device=env.device, generator=gen) * 2 - 1) * args.scale
     dfrc = (torch.rand((n, cm.nv), dtype=torch.float64, device=env.device, generator=gen) * 2 - 1) * args.scale
     lin = d["qacc"] + torch.bmm(d["dqacc_dctrl"], dctrl[:, :, None])[:, :, 0] + torch.bmm(d["dqacc_dfrc"], dfrc[:, :, None])[:, :, 0]
@@ -48,10 +54,18 @@ def main(argv=None):
     rel = (f["qacc"] - lin).abs().amax(dim=1) / change.clamp(min=1e-300)
     rel = torch.where(ok, rel, torch.zeros_like(rel))
     same = ok & (f["contact_mask"] == f0["contact_mask"])
+    # the right arm's finger spheres are 0 and 1, their cube contacts bits 8 and 9; actuator i drives link i
+    bit = env.forward(qpos=st["qpos"], qvel=st["qvel"], ctrl=st["ctrl"], warm=d["qacc"], fields=("contact_bit",))["contact_bit"]
+    cols = slice(0, cm.nu)                                               # contact_mask_fd's ctrl columns (wrt order: ctrl first)
+    kept = (((d["contact_mask_fd"][cols] >> 8) & 3) == ((f0["contact_mask"] >> 8) & 3)[None, None, :]).all(dim=0).all(dim=0)
+    sens = torch.cat([d["dcontact_force_dctrl"][:, :, 0, cm.desc.sphere_link[s]][(bit == 8 + s) & (ok & kept)[:, None]] for s in (0, 1)])
     out = {"env": args.env, "num_envs": n, "steps": args.steps, "scale": args.scale, "eps": args.eps, "rows_ok": int(ok.sum()),
            "rows_same_contacts": int(same.sum()), "worst_rel_gap": float(rel.max()),
            "worst_rel_gap_same_contacts": float(torch.where(same, rel, torch.zeros_like(rel)).max()),
-           "median_rel_gap": float(rel.median()), "max_qacc_change": float(change.max())}
+           "median_rel_gap": float(rel.median()), "max_qacc_change": float(change.max()),
+           "fused": bool(args.fused), "fingers_grasping": int(sens.numel()),
+           "finger_normal_dctrl_median": float(sens.median()) if sens.numel() else 0.0,
+           "finger_normal_dctrl_max_abs": float(sens.abs().max()) if sens.numel() else 0.0}
     print(json.dumps(out))
     env.k_close()
     return out
