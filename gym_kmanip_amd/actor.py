@@ -1,0 +1,123 @@
+"""A learned state-based policy for the batched env: the MLP kmanip_actor evaluates on the matrix cores (include/kmanip.h KActorDesc;
+DESIGN.md section 45).
+
+`Actor` owns the torch parameter tensors -- w0, b0, w1, b1, w2, b2, log_std: float32, on the env's device, what a torch optimiser
+takes -- and the packed copy the kernel reads; `repack()` rebuilds that copy after the parameters change (three launches, no torch
+arithmetic).  `KManipEnvHip.actor_eval` runs it, `KManipEnvHip.collect` runs it between steps; `reference` is the same network in
+torch float64: the definition.
+"""
+from __future__ import annotations
+
+import ctypes as C
+
+from . import lib as _libmod
+
+_NAMES = ("w0", "b0", "w1", "b1", "w2", "b2")
+
+
+class Actor:
+    def __init__(self, env, hidden=(64, 64), activation="tanh", out_dim=None, in_dim=None, seed=0):
+        """env: the KManipEnvHip the network belongs to (device, library handle).  in_dim / out_dim: None = the env's obs_dim /
+        act_dim.  The weights start as torch.nn.Linear's do, uniform in +-1 / sqrt(fan in), from a generator of their own seeded
+        with `seed`; log_std starts at zero.  obs_mean / obs_inv_std: None, or float64 [in_dim] device tensors the caller sets."""
+        import torch
+        self.env = env
+        self.in_dim = int(env.cm.obs_dim if in_dim is None else in_dim)
+        self.out_dim = int(env.cm.act_dim if out_dim is None else out_dim)
+        self.hidden = tuple(int(v) for v in hidden)
+        if len(self.hidden) != 2 or activation not in _libmod.KM_ACTOR:
+            raise ValueError("Actor: two hidden sizes and an activation of %s" % sorted(_libmod.KM_ACTOR))
+        self.activation = activation
+        self.desc = _libmod.KActorDesc(self.in_dim, (C.c_int32 * 2)(*self.hidden), self.out_dim, _libmod.KM_ACTOR[activation])
+        floats = env.L.kmanip_actor_packed_floats(C.byref(self.desc))
+        if not floats:
+            raise _libmod.KManipError("Actor: %d -> %s -> %d is outside what kmanip_actor takes (in_dim 1..%d, hidden sizes multiples of 16 "
+                                      "in 16..%d, out_dim 1..%d)" % (self.in_dim, self.hidden, self.out_dim, _libmod.KM_ACTOR_MAX_IN,
+                                                                    _libmod.KM_ACTOR_MAX_HIDDEN, _libmod.KM_ACTOR_MAX_OUT))
+        gen = torch.Generator().manual_seed(int(seed))
+        dims = (self.in_dim,) + self.hidden + (self.out_dim,)
+        for l, (i, o) in enumerate(zip(dims, dims[1:])):
+            bound = i ** -0.5
+            setattr(self, "w%d" % l, ((torch.rand((o, i), generator=gen) * 2 - 1) * bound).to(env.device))
+            setattr(self, "b%d" % l, ((torch.rand((o,), generator=gen) * 2 - 1) * bound).to(env.device))
+        self.log_std = torch.zeros((self.out_dim,), dtype=torch.float32, device=env.device)
+        self.obs_mean = self.obs_inv_std = None
+        self.packed = torch.empty((floats,), dtype=torch.float32, device=env.device)
+        self.repack()
+
+    @classmethod
+    def from_module(cls, env, module, **kw):
+        """An Actor with the weights of a torch.nn.Sequential of three Linear layers with a Tanh or a ReLU after the first two."""
+        import torch
+        lin = [m for m in module if isinstance(m, torch.nn.Linear)]
+        acts = {type(m) for m in module if not isinstance(m, torch.nn.Linear)}
+        if len(lin) != 3 or acts not in ({torch.nn.Tanh}, {torch.nn.ReLU}) or any(m.bias is None for m in lin):
+            raise ValueError("Actor.from_module: three biased Linear layers and one kind of activation, Tanh or ReLU")
+        a = cls(env, hidden=(lin[0].out_features, lin[1].out_features), activation="tanh" if acts == {torch.nn.Tanh} else "relu",
+                out_dim=lin[2].out_features, in_dim=lin[0].in_features, **kw)
+        with torch.no_grad():
+            for l, m in enumerate(lin):
+                getattr(a, "w%d" % l).copy_(m.weight)
+                getattr(a, "b%d" % l).copy_(m.bias)
+        a.repack()
+        return a
+
+    def parameters(self):
+        """The tensors a torch optimiser takes (after its step: repack())."""
+        return [getattr(self, nm) for nm in _NAMES] + [self.log_std]
+
+    def repack(self):
+        """kmanip_actor_pack: the parameter tensors as they are now into the buffer the kernel reads, on the current stream."""
+        import torch
+        e, dims = self.env, (self.in_dim,) + self.hidden + (self.out_dim,)
+        wt = _libmod.KActorWeights()
+        for l in range(3):
+            e._check_buf(getattr(self, "w%d" % l), (dims[l + 1], dims[l]), torch.float32, "w%d" % l)
+            e._check_buf(getattr(self, "b%d" % l), (dims[l + 1],), torch.float32, "b%d" % l)
+        for nm in _NAMES:
+            setattr(wt, nm, getattr(self, nm).data_ptr())
+        e._check(e.L.kmanip_actor_pack(e.h, C.byref(self.desc), C.byref(wt), C.c_void_p(self.packed.data_ptr()), e._stream()),
+                 "kmanip_actor_pack")
+
+    def torch_eval(self, obs):
+        """The policy as a torch float32 program on the same parameters -- cast, normalise, three matmuls, sample from torch's global
+        generator, clamp, log-probability: what a training script runs between steps without kmanip_actor, for comparisons of cost
+        (examples/actor_rollout.py --torch, tests/tools/actor_cost.py).  Returns (act, raw, logp), all float32."""
+        import math
+        import torch
+        x = obs.to(torch.float32)
+        if self.obs_mean is not None:
+            x = x - self.obs_mean.to(torch.float32)
+        if self.obs_inv_std is not None:
+            x = x * self.obs_inv_std.to(torch.float32)
+        f = torch.tanh if self.activation == "tanh" else torch.relu
+        mean = torch.addmm(self.b2, f(torch.addmm(self.b1, f(torch.addmm(self.b0, x, self.w0.T)), self.w1.T)), self.w2.T)
+        z = torch.randn_like(mean)
+        raw = mean + self.log_std.exp() * z
+        return raw.clamp(-1.0, 1.0), raw, (-0.5 * z * z - self.log_std - 0.5 * math.log(2.0 * math.pi)).sum(-1)
+
+    def reference(self, obs, noise=None):
+        """The same network in torch float64: float32 weights widened, the normalised input rounded to float32 as the kernel rounds
+        it.  Returns {"mean"}; with `noise` [n, out_dim] (the kernel's, or model.draw_policy_noise's) also raw, act and logp by
+        include/kmanip.h's definition (raw and act in float32, logp in float64)."""
+        import math
+        import torch
+        x = obs.to(torch.float64)
+        if self.obs_mean is not None:
+            x = x - self.obs_mean
+        if self.obs_inv_std is not None:
+            x = x * self.obs_inv_std
+        x = x.to(torch.float32).to(torch.float64)
+        f = torch.tanh if self.activation == "tanh" else torch.relu
+        w = [getattr(self, nm).to(torch.float64) for nm in _NAMES]
+        h = f(x @ w[0].T + w[1])
+        h = f(h @ w[2].T + w[3])
+        out = {"mean": h @ w[4].T + w[5]}
+        if noise is not None:
+            z = noise.to(torch.float32)
+            sd = self.log_std.to(torch.float64).exp().to(torch.float32)
+            out["raw"] = out["mean"].to(torch.float32) + sd * z
+            out["act"] = out["raw"].clamp(-1.0, 1.0)
+            zd = z.to(torch.float64)
+            out["logp"] = (-0.5 * zd * zd - self.log_std.to(torch.float64) - 0.5 * math.log(2.0 * math.pi)).sum(-1)
+        return out

@@ -1156,6 +1156,47 @@ int kmanip_sample_action(KHandle h, float* act_dev, int ahead, void* stream) {
   return 0;
 }
 
+// ---- the learned policy (include/kmanip.h KActorDesc ...; kmanip_actor.hip)
+// what is wrong with a network description, or NULL
+static const char* actor_desc_error(const KActorDesc* d) {
+  if (!d) return "the KActorDesc pointer is NULL";
+  if (d->in_dim < 1 || d->in_dim > KM_ACTOR_MAX_IN) return "in_dim is outside 1 .. KM_ACTOR_MAX_IN";
+  for (int k = 0; k < 2; k++)
+    if (d->hidden[k] < 16 || d->hidden[k] > KM_ACTOR_MAX_HIDDEN || d->hidden[k] % 16) return "a hidden size is no multiple of 16 in 16 .. KM_ACTOR_MAX_HIDDEN";
+  if (d->out_dim < 1 || d->out_dim > KM_ACTOR_MAX_OUT) return "out_dim is outside 1 .. KM_ACTOR_MAX_OUT";
+  if (d->activation != KM_ACTOR_TANH && d->activation != KM_ACTOR_RELU) return "unknown activation";
+  return nullptr;
+}
+
+size_t kmanip_actor_packed_floats(const KActorDesc* desc) { return actor_desc_error(desc) ? 0 : 4 * (size_t)kmanip_actor_plan(*desc).total4; }
+
+int kmanip_actor_pack(KHandle h, const KActorDesc* desc, const KActorWeights* weights, float* packed_dev, void* stream) {
+  if (!h) { g_create_error = "kmanip_actor_pack: null handle"; return -1; }
+  if (const char* e = actor_desc_error(desc)) { h->err = std::string("kmanip_actor_pack: ") + e; return -1; }
+  if (!weights || !weights->w0 || !weights->b0 || !weights->w1 || !weights->b1 || !weights->w2 || !weights->b2) { h->err = "kmanip_actor_pack: a weight or bias pointer is NULL"; return -1; }
+  if (!packed_dev || ((uintptr_t)packed_dev & 15)) { h->err = "kmanip_actor_pack: packed_dev is NULL or not 16-byte aligned"; return -1; }
+  KM_ENTER(h);
+  kmanip_launch_actor_pack(*desc, *weights, packed_dev, (hipStream_t)stream);
+  HIPCHK(h, hipGetLastError());
+  return 0;
+}
+
+int kmanip_actor(KHandle h, const KActorDesc* desc, const float* packed_dev, const KActorIn* in, int n, const KActorDev* out, void* stream) {
+  if (!h) { g_create_error = "kmanip_actor: null handle"; return -1; }
+  if (const char* e = actor_desc_error(desc)) { h->err = std::string("kmanip_actor: ") + e; return -1; }
+  if (!in) { h->err = "kmanip_actor: the KActorIn pointer is NULL"; return -1; }
+  if (!out) { h->err = "kmanip_actor: the KActorDev pointer is NULL"; return -1; }
+  if (n < 0) { h->err = "kmanip_actor: n is negative"; return -1; }
+  if (!in->envs && n > h->st.num_envs) { h->err = "kmanip_actor: more rows than envs need KActorIn::envs"; return -1; }
+  if (!in->obs) { h->err = "kmanip_actor: KActorIn::obs is NULL"; return -1; }
+  if (!packed_dev || ((uintptr_t)packed_dev & 15)) { h->err = "kmanip_actor: packed_dev is NULL or not 16-byte aligned"; return -1; }
+  if (n == 0) return 0;
+  KM_ENTER(h);
+  kmanip_launch_actor(h->st, *desc, packed_dev, *in, n, *out, (hipStream_t)stream);
+  HIPCHK(h, hipGetLastError());
+  return 0;
+}
+
 int kmanip_enable_timing(KHandle h, int enable) {
   if (!h) return -1;
   KM_ENTER(h);

@@ -498,7 +498,7 @@ __device__ __host__ inline double u53(uint32_t hi, uint32_t lo) {
 __device__ __host__ inline float km_action_from_u32(uint32_t r) { return (float)((int32_t)(r >> 8) - 8388608) * (1.0f / 8388608.0f); }
 // counter word 3 of the action stream: the cube spawn uses 0 and 1 (reset_env), the per-env parameter draw of ranges mode
 // KM_EP_CTR3 + 0 and + 1 = 2 and 3 (kmanip.h), the visual parameter draw KM_VP_CTR3 + 0 .. 8 = 0x100 .. 0x108 (km_vp_draw_pair),
-// actions 0x10000 + 4 * step + block
+// actions 0x10000 + 4 * step + block, the Gaussian head of k_actor KM_POL_CTR3(step, block) = 0x40000000 + 4 * step + block (kmanip.h)
 #define KM_ACT_CTR3(step, blk) (0x10000u + 4u * (uint32_t)(step) + (uint32_t)(blk))
 
 // Visual parameters of ranges mode (include/kmanip.h kmanip_set_visual_param_ranges): values 2j and 2j + 1 of global env genv in
@@ -684,6 +684,14 @@ struct KCostWeights { int ik, work, coupled, armtab, cubetab, binw; };
 void kmanip_launch_sort_envs(const KDeviceState& st, int32_t* slot_env, const KCostWeights& w, hipStream_t stream);
 void kmanip_launch_scripted_action(const KDeviceModel* dm, const KDeviceState& st, float* act, hipStream_t stream);
 void kmanip_launch_sample_action(const KDeviceModel* dm, const KDeviceState& st, float* act, int ahead, hipStream_t stream);
+// kmanip_actor / kmanip_actor_pack (kmanip_actor.hip): where a valid network's layers lie in the packed buffer -- per layer the real
+// sizes, the K-blocks (padded to KM_ACTOR_KGROUP) and output tiles, the offsets of its weight blocks and bias in float4s -- and the
+// launches: the three pack launches; one k_actor launch over n > 0 rows
+struct KActorPlan { int in[3], out[3], kb[3], ot[3], w4[3], b4[3], total4; };
+KActorPlan kmanip_actor_plan(const KActorDesc& d);
+void kmanip_launch_actor_pack(const KActorDesc& d, const KActorWeights& w, float* packed, hipStream_t stream);
+void kmanip_launch_actor(const KDeviceState& st, const KActorDesc& d, const float* packed, const KActorIn& in, int n, const KActorDev& out,
+                         hipStream_t stream);
 
 // The env state in and out of a handle on the device (kmanip_state.hip; include/kmanip.h kmanip_get_state_dev / kmanip_set_state_dev /
 // kmanip_copy_envs).  Arguments of their own: no field of KDeviceState / KDeviceModel moves.

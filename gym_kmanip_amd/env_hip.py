@@ -1340,6 +1340,89 @@ class KManipEnvHip:
         self._check(self.L.kmanip_sample_action(self.h, C.c_void_p(act.data_ptr()), int(ahead), self._stream()), "kmanip_sample_action")
         return act
 
+    # KActorDev field -> (trailing shape in terms of od = the actor's out_dim; None: one value per row, dtype name)
+    _ACTOR_FIELDS = {"mean": (("od",), "float32"), "act": (("od",), "float32"), "raw": (("od",), "float32"), "noise": (("od",), "float32"),
+                     "logp": (None, "float64"), "status": (None, "int32")}
+
+    def _actor_launch(self, actor, obs_ptr, envs_ptr, n, head, dev):
+        """One kmanip_actor call on the current stream: raw pointers, checked by the caller."""
+        ai = _libmod.KActorIn(envs_ptr, obs_ptr, None if actor.obs_mean is None else actor.obs_mean.data_ptr(),
+                              None if actor.obs_inv_std is None else actor.obs_inv_std.data_ptr(), actor.log_std.data_ptr() if head else None)
+        self._check(self.L.kmanip_actor(self.h, C.byref(actor.desc), C.c_void_p(actor.packed.data_ptr()), C.byref(ai), n, C.byref(dev),
+                                        self._stream()), "kmanip_actor")
+
+    def _actor_check(self, actor):
+        torch = _torch()
+        for name in ("obs_mean", "obs_inv_std"):
+            if getattr(actor, name) is not None:
+                self._check_buf(getattr(actor, name), (actor.in_dim,), torch.float64, name)
+        self._check_buf(actor.log_std, (actor.out_dim,), torch.float32, "log_std")
+
+    def actor_eval(self, actor, obs, envs=None, deterministic=False, out=None, fields=None):
+        """kmanip_actor: the MLP policy `actor` (gym_kmanip_amd.actor.Actor) at rows the caller passes -- one launch on the current
+        stream, no synchronisation; the handle is only read.  obs: float64 [n, actor.in_dim], row r the observation of env envs[r]
+        (an int32 device tensor or anything torch.as_tensor takes, repeats allowed, more rows than envs allowed; None = row r is
+        env r).  Returns a dict of device tensors: mean [n, out_dim] float32 and status [n] int32 (2: an env index outside the
+        handle, the row's other outputs 0) and, unless `deterministic`, the Gaussian head's act = clamp(raw, -1, 1), raw = mean +
+        exp(log_std) noise, noise [n, out_dim] float32 and logp [n] float64 (include/kmanip.h has the definition).  The noise is a
+        function of (seed, env, the env's episode and step counters): the same call repeated gives the same bytes, a step moves
+        it on.  `fields`: the names wanted (default: all); `out`: a dict of such tensors to fill, returned as given."""
+        torch = _torch()
+        idx, ip, n = self._env_index(envs)
+        if n is None:
+            n = int(obs.shape[0]) if isinstance(obs, torch.Tensor) and obs.dim() else -1
+        self._check_buf(obs, (n, actor.in_dim), torch.float64, "obs")
+        self._actor_check(actor)
+        table = {k: v for k, v in self._ACTOR_FIELDS.items() if not deterministic or k in ("mean", "status")}
+        dev = _libmod.KActorDev()
+        out = self._query_out(table, (n,), {"od": actor.out_dim}, out, fields, dev, "actor")
+        self._actor_launch(actor, obs.data_ptr(), None if idx is None else idx.data_ptr(), n, not deterministic, dev)
+        return out
+
+    def collect(self, actor, nsteps, critic=None, obs0=None, out=None):
+        """The on-policy rollout buffer: for t = 0 .. nsteps-1, kmanip_actor on obs[t] (every env, stochastic), the critic's mean on
+        obs[t] where one is given (an Actor with out_dim 1), then kmanip_step with act[t] writing obs[t + 1], reward[t], done[t];
+        after the last step the critic on obs[nsteps].  All launches go onto the current stream with no host synchronisation and no
+        torch operation in between: exactly the loop actor_eval + step_flat written by hand.  obs[0] is `obs0` (float64
+        [num_envs, obs_dim]) or, for None, observe()'s of the current state.  Returns a dict of device tensors, T = nsteps:
+        obs [T + 1, N, obs_dim] float64, act, raw [T, N, act_dim] float32, logp [T, N] float64, reward [T, N] float64, done [T, N]
+        uint8 and, with a critic, value [T + 1, N] float32.  `out`: such a dict to fill, returned as given."""
+        torch = _torch()
+        T, N, f32, f64 = int(nsteps), self.num_envs, torch.float32, torch.float64
+        if actor.in_dim != self.cm.obs_dim or actor.out_dim != self.cm.act_dim:
+            raise _libmod.KManipError("collect: the actor must map obs_dim to act_dim")
+        if critic is not None and (critic.in_dim != self.cm.obs_dim or critic.out_dim != 1):
+            raise _libmod.KManipError("collect: the critic must map obs_dim to 1")
+        shapes = {"obs": ((T + 1, N, self.cm.obs_dim), f64), "act": ((T, N, self.cm.act_dim), f32), "raw": ((T, N, self.cm.act_dim), f32),
+                  "logp": ((T, N), f64), "reward": ((T, N), f64), "done": ((T, N), torch.uint8)}
+        if critic is not None:
+            shapes["value"] = ((T + 1, N), f32)
+        if out is None:
+            out = {k: torch.empty(s, dtype=dt, device=self.device) for k, (s, dt) in shapes.items()}
+        if set(out) != set(shapes):
+            raise ValueError("collect: out must hold exactly %s" % sorted(shapes))
+        for k, (s, dt) in shapes.items():
+            self._check_buf(out[k], s, dt, k)
+        for a in (actor,) if critic is None else (actor, critic):
+            self._actor_check(a)
+        if obs0 is None:
+            self.observe(out["obs"][0], torch.empty((N,), dtype=f64, device=self.device))
+        else:
+            self._check_buf(obs0, (N, self.cm.obs_dim), f64, "obs0")
+            out["obs"][0].copy_(obs0)
+        at = lambda name, t: out[name][t].data_ptr()          # (a leading-index view of a contiguous tensor: no kernel, no copy)
+        stream = self._stream()
+        for t in range(T + 1):
+            if t < T:
+                self._actor_launch(actor, at("obs", t), None, N, True, _libmod.KActorDev(act=at("act", t), raw=at("raw", t), logp=at("logp", t)))
+            if critic is not None:
+                self._actor_launch(critic, at("obs", t), None, N, False, _libmod.KActorDev(mean=at("value", t)))
+            if t == T:
+                break
+            self._check(self.L.kmanip_step(self.h, C.c_void_p(at("act", t)), C.c_void_p(at("obs", t + 1)), C.c_void_p(at("reward", t)),
+                                           C.c_void_p(at("done", t)), stream), "kmanip_step")
+        return out
+
     def k_render(self, cam):
         """KManipEnvSim.k_render (env_sim.py:187-188): physics.render(cam.h, cam.w, camera_id=cam.name) -> uint8 RGB,
         for every env ([num_envs, h, w, 3], device tensor).  `cam` is a Cam (model.CAMERAS) or a camera name."""

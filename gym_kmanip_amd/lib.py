@@ -20,7 +20,7 @@ _lib = None
 EXPORTS = [
     "kmanip_model_desc_size", "kmanip_create", "kmanip_reset", "kmanip_step", "kmanip_step_chunk", "kmanip_get_state",
     "kmanip_set_state", "kmanip_get_episode", "kmanip_set_episode", "kmanip_get_counters", "kmanip_bind_sim_time", "kmanip_bind_applied_force", "kmanip_bind_reward_done_record", "kmanip_select_reward_done_record", "kmanip_observe", "kmanip_forces", "kmanip_kinematics", "kmanip_inverse", "kmanip_forward", "kmanip_kinematics_rows", "kmanip_site_cost", "kmanip_rollout", "kmanip_feedback", "kmanip_feedback_box", "kmanip_transition_fd", "kmanip_forward_fd", "kmanip_param_fd", "kmanip_lqr_backward", "kmanip_lqr_backward_box", "kmanip_adjoint", "kmanip_tangent", "kmanip_set_seed", "kmanip_get_diag", "kmanip_timing_summary", "kmanip_enable_timing", "kmanip_ik", "kmanip_ik_eval",
-    "kmanip_render_depth", "kmanip_render_rgb", "kmanip_render_rgb_multi", "kmanip_render_labels_multi", "kmanip_render_seg", "kmanip_set_render_links", "kmanip_get_render_links", "kmanip_set_depth_links", "kmanip_get_depth_links", "kmanip_get_camera_poses", "kmanip_render_points", "kmanip_snapshot_render_state", "kmanip_set_render_source", "kmanip_bind_step_depth", "kmanip_scripted_action", "kmanip_sample_action", "kmanip_set_env_params", "kmanip_get_env_params", "kmanip_set_env_param_ranges", "kmanip_set_visual_params", "kmanip_get_visual_params", "kmanip_set_visual_param_ranges",
+    "kmanip_render_depth", "kmanip_render_rgb", "kmanip_render_rgb_multi", "kmanip_render_labels_multi", "kmanip_render_seg", "kmanip_set_render_links", "kmanip_get_render_links", "kmanip_set_depth_links", "kmanip_get_depth_links", "kmanip_get_camera_poses", "kmanip_render_points", "kmanip_snapshot_render_state", "kmanip_set_render_source", "kmanip_bind_step_depth", "kmanip_scripted_action", "kmanip_sample_action", "kmanip_actor_packed_floats", "kmanip_actor_pack", "kmanip_actor", "kmanip_set_env_params", "kmanip_get_env_params", "kmanip_set_env_param_ranges", "kmanip_set_visual_params", "kmanip_get_visual_params", "kmanip_set_visual_param_ranges",
     "kmanip_get_state_dev", "kmanip_set_state_dev", "kmanip_copy_envs", "kmanip_state_index_errors", "kmanip_num_envs", "kmanip_last_error", "kmanip_version", "kmanip_destroy",
 ]
 
@@ -222,6 +222,38 @@ class KTangentDev(C.Structure):
     _fields_ = [("s_t", C.c_void_p), ("du_acted_t", C.c_void_p), ("h", C.c_void_p), ("g", C.c_void_p)]
 
 
+class KActorDesc(C.Structure):
+    """include/kmanip.h KActorDesc: the MLP in_dim -> hidden[0] -> hidden[1] -> out_dim and its activation (KM_ACTOR)."""
+    _fields_ = [("in_dim", C.c_int32), ("hidden", C.c_int32 * 2), ("out_dim", C.c_int32), ("activation", C.c_int32)]
+
+
+class KActorWeights(C.Structure):
+    """include/kmanip.h KActorWeights: DEVICE pointers of the row-major float32 weights and biases kmanip_actor_pack reads."""
+    _fields_ = [(nm, C.c_void_p) for nm in ("w0", "b0", "w1", "b1", "w2", "b2")]
+
+
+class KActorIn(C.Structure):
+    """include/kmanip.h KActorIn: DEVICE pointers of kmanip_actor's inputs; envs NULL = row r is env r, log_std NULL = no head."""
+    _fields_ = [(nm, C.c_void_p) for nm in ("envs", "obs", "obs_mean", "obs_inv_std", "log_std")]
+
+
+class KActorDev(C.Structure):
+    """include/kmanip.h KActorDev: DEVICE pointers of kmanip_actor's outputs, any of them NULL."""
+    _fields_ = [(nm, C.c_void_p) for nm in ("mean", "act", "raw", "noise", "logp", "status")]
+
+
+KM_ACTOR = {"tanh": 0, "relu": 1}      # include/kmanip.h KM_ACTOR_TANH / KM_ACTOR_RELU
+KM_ACTOR_MAX_HIDDEN, KM_ACTOR_MAX_IN, KM_ACTOR_MAX_OUT, KM_ACTOR_KGROUP = 256, 64, 16, 4
+
+
+def actor_packed_floats(in_dim, hidden, out_dim):
+    """include/kmanip.h kmanip_actor_packed_floats, restated: per layer (out tiles of 16) x (K-blocks of 16, padded to a multiple of
+    KM_ACTOR_KGROUP) blocks of 256 floats, then the bias padded to whole tiles."""
+    dims = [in_dim, hidden[0], hidden[1], out_dim]
+    tiles = lambda v: (v + 15) // 16
+    return sum(tiles(o) * (-(-tiles(i) // KM_ACTOR_KGROUP) * KM_ACTOR_KGROUP) * 256 + tiles(o) * 16 for i, o in zip(dims, dims[1:]))
+
+
 KM_TANGENT_MC = 16               # include/kmanip.h: H and g need m <= KM_TANGENT_MC
 KM_WRT = {"qpos": 1, "qvel": 2, "ctrl": 4, "qfrc_applied": 8}     # include/kmanip.h KM_WRT_*: the columns always run in this order
 # include/kmanip.h KM_OF_*: the differentiated outputs of kmanip_forward_fd, always in this order
@@ -310,6 +342,10 @@ def load():
     lib.kmanip_bind_step_depth.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp]
     lib.kmanip_scripted_action.argtypes = [vp, vp, vp]
     lib.kmanip_sample_action.argtypes = [vp, vp, C.c_int, vp]
+    lib.kmanip_actor_packed_floats.argtypes = [C.POINTER(KActorDesc)]
+    lib.kmanip_actor_packed_floats.restype = C.c_size_t
+    lib.kmanip_actor_pack.argtypes = [vp, C.POINTER(KActorDesc), C.POINTER(KActorWeights), vp, vp]
+    lib.kmanip_actor.argtypes = [vp, C.POINTER(KActorDesc), vp, C.POINTER(KActorIn), C.c_int, C.POINTER(KActorDev), vp]
     lib.kmanip_set_env_params.argtypes = [vp, vp, vp]
     lib.kmanip_get_env_params.argtypes = [vp, vp, vp]
     lib.kmanip_set_env_param_ranges.argtypes = [vp, f64p, f64p]

@@ -533,6 +533,27 @@ def draw_env_params(seed: int, genv: int, episode: int, lo, hi) -> np.ndarray:
     return out
 
 
+def KM_POL_CTR3(step: int, blk: int) -> int:
+    """include/kmanip.h KM_POL_CTR3: counter word 3 of the Gaussian head's noise, block `blk` of an env at `step` of its episode."""
+    return (0x40000000 + 4 * int(step) + int(blk)) & 0xFFFFFFFF
+
+
+def draw_policy_noise(seed: int, genv: int, episode: int, step: int, out_dim: int) -> np.ndarray:
+    """The float32 noise kmanip_actor's Gaussian head draws for global env `genv` at (episode, step), by include/kmanip.h's
+    definition in float64: block g = j // 4 of Philox4x32-10 with key = seed and counter (genv lo, genv hi, episode,
+    KM_POL_CTR3(step, g)); Box-Muller on words (0, 1) and on (2, 3), u = ((word >> 8) + 0.5) 2^-24; one cast."""
+    key = (seed & 0xFFFFFFFF, (seed >> 32) & 0xFFFFFFFF)
+    g = int(genv) & 0xFFFFFFFFFFFFFFFF
+    z = np.zeros(4 * ((out_dim + 3) // 4))
+    for blk in range(len(z) // 4):
+        o = _philox4x32_10((g & 0xFFFFFFFF, g >> 32, int(episode) & 0xFFFFFFFF, KM_POL_CTR3(step, blk)), key)
+        u = ((o >> np.uint32(8)).astype(np.float64) + 0.5) / 16777216.0
+        for b in range(2):
+            rho, ang = np.sqrt(-2.0 * np.log(u[2 * b])), 6.283185307179586 * u[2 * b + 1]
+            z[4 * blk + 2 * b], z[4 * blk + 2 * b + 1] = rho * np.cos(ang), rho * np.sin(ang)
+    return z[:out_dim].astype(np.float32)
+
+
 # ---- per-env visual parameters of the camera renders (include/kmanip.h KM_VP_*, DESIGN.md section 12)
 # name -> (first index in the KM_VP_N values, number of components)
 VISUAL_PARAMS = {"cube_rgb": (0, 3), "table_rgb": (3, 3), "robot_rgb": (6, 3), "background_rgb": (9, 3), "ambient": (12, 1),

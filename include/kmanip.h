@@ -22,6 +22,7 @@
 #ifndef KMANIP_H
 #define KMANIP_H
 
+#include <stddef.h>
 #include <stdint.h>
 
 /* The library is built with -fvisibility=hidden: the entry points declared in this header (and the diagnostics of
@@ -1167,6 +1168,61 @@ KMANIP_API int kmanip_scripted_action(KHandle h, float* act_dev, void* stream);
  * `ahead` >= 0 draws the action the env will need `ahead` control steps from now, assuming TimeLimit-only episodes (the
  * reference never terminates early), so the next K actions can be laid out before stepping. */
 KMANIP_API int kmanip_sample_action(KHandle h, float* act_dev, int ahead, void* stream);
+
+/* A LEARNED state-based policy on the device: the MLP  in_dim -> hidden[0] -> hidden[1] -> out_dim  with one
+ * activation after each hidden layer, evaluated for n rows in ONE launch on the matrix cores (float32 weights, float32 accumulation),
+ * optionally with a Gaussian head.  Row r reads obs[r] and belongs to env envs[r] (NULL: env r; rows may repeat and outnumber envs):
+ *   x      = float32((obs[r] - obs_mean) * obs_inv_std)     the difference and the product in float64, each only where its vector is
+ *                                                           given; one cast
+ *   mean   = W2 act(W1 act(W0 x + b0) + b1) + b2            float32; the order of a dot product's terms is the kernel's own
+ * and, when log_std is given, lane group g = 0..3 of the row draws one Philox4x32-10 block keyed by the handle's seed with counter
+ * (global env id lo, hi, episode, KM_POL_CTR3(step, g)) -- the env's STORED episode and step counters, a domain of counter word 3
+ * beside the spawn's, KM_EP_CTR3, KM_VP_CTR3 and the sampled actions' -- whose words give the noise of columns 4 g .. 4 g + 3:
+ *   u      = ((word >> 8) + 0.5) 2^-24;  rho = sqrt(-2 log u1);  z0 = rho cos(2 pi u2), z1 = rho sin(2 pi u2) from words (0, 1), z2, z3
+ *            from words (2, 3), all in float64, then one cast to float32: noise
+ *   raw    = mean + float32(exp(float64(log_std))) * noise  float32, the product rounded before the sum
+ *   act    = min(max(raw, -1), 1)
+ *   logp   = sum_j (-noise_j^2 / 2 - log_std_j - log(2 pi) / 2)   float64, over the out_dim columns: a lane group's columns ascending,
+ *            then group g with g ^ 1, then with g ^ 2
+ * The noise is a function of (seed, env, episode, step) and nothing else; a step or a reset of the env moves it on.  Without log_std
+ * only mean and status are written (a critic is this call with out_dim = 1).  A row's results depend on its env and inputs only,
+ * never on n or on its place. */
+#define KM_POL_CTR3(step, blk) (0x40000000u + 4u * (uint32_t)(step) + (uint32_t)(blk))
+#define KM_ACTOR_MAX_HIDDEN 256   /* hidden sizes: multiples of 16 in 16 .. KM_ACTOR_MAX_HIDDEN */
+#define KM_ACTOR_MAX_IN     64
+#define KM_ACTOR_MAX_OUT    16
+#define KM_ACTOR_KGROUP     4     /* the packed buffer pads a layer's K-blocks (16 inputs each) to a multiple of this */
+#define KM_ACTOR_TANH 0
+#define KM_ACTOR_RELU 1
+typedef struct KActorDesc { int32_t in_dim, hidden[2], out_dim, activation; } KActorDesc;
+typedef struct KActorWeights { /* DEVICE, float32, row-major as torch.nn.Linear holds them: w [out, in], b [out] */
+  const float *w0, *b0, *w1, *b1, *w2, *b2;
+} KActorWeights;
+typedef struct KActorIn {
+  const int32_t* envs;         /* [n] DEVICE or NULL: row r is env r (then n <= num_envs) */
+  const double*  obs;          /* [n, in_dim] */
+  const double  *obs_mean, *obs_inv_std;   /* [in_dim] each, or NULL */
+  const float*   log_std;      /* [out_dim], or NULL: no head */
+} KActorIn;
+typedef struct KActorDev {     /* any field may be NULL: what is not asked for is not written */
+  float  *mean, *act, *raw, *noise;        /* [n, out_dim] */
+  double* logp;                /* [n] */
+  int32_t* status;             /* [n]: 0 ok; 2 an env index outside 0 .. num_envs-1 (never used as an address): every other output of the row is 0 */
+} KActorDev;
+/* The floats of the packed weight buffer of a network: per layer, (out tiles of 16) x (K-blocks of 16, padded to a multiple of
+ * KM_ACTOR_KGROUP) blocks of 256 floats, then the bias padded to whole tiles.  0 for a description kmanip_actor would refuse. */
+KMANIP_API size_t kmanip_actor_packed_floats(const KActorDesc* desc);
+/* The row-major tensors into packed_dev (16-byte aligned, kmanip_actor_packed_floats floats): three launches on `stream`, no host
+ * arithmetic; to be repeated after the weights change. */
+KMANIP_API int kmanip_actor_pack(KHandle h, const KActorDesc* desc, const KActorWeights* weights, float* packed_dev, void* stream);
+/* ONE kernel launch, asynchronous on `stream`: no allocation, no synchronisation.  THE HANDLE IS READ ONLY (seed, env id offset, the
+ * envs' episode and step counters).  in_dim need not be the handle's obs_dim nor out_dim its act_dim.  n == 0 succeeds.
+ * ERRORS: a NULL handle, desc, `in` or `out`, n < 0, more rows than envs without `envs`, a hidden size that is no multiple of 16 or
+ * outside 16 .. KM_ACTOR_MAX_HIDDEN, in_dim outside 1 .. KM_ACTOR_MAX_IN, out_dim outside 1 .. KM_ACTOR_MAX_OUT, an unknown
+ * activation, a NULL obs or packed_dev or a packed_dev that is not 16-byte aligned return nonzero with kmanip_last_error set, launch
+ * nothing and leave the outputs untouched.
+ * OUT OF SCOPE: other weight types, more than two hidden layers, the policy inside the step kernels, backward passes. */
+KMANIP_API int kmanip_actor(KHandle h, const KActorDesc* desc, const float* packed_dev, const KActorIn* in, int n, const KActorDev* out, void* stream);
 
 /* Per-env physics parameters (domain randomisation).  Storage is double[KM_EP_N][num_envs], struct-of-arrays
  * like the state: element (k, env) at k * num_envs + env.  Env e with parameters p behaves exactly like a handle whose KModelDesc is
