@@ -4,7 +4,8 @@ DESIGN.md section 45).
 `Actor` owns the torch parameter tensors -- w0, b0, w1, b1, w2, b2, log_std: float32, on the env's device, what a torch optimiser
 takes -- and the packed copy the kernel reads; `repack()` rebuilds that copy after the parameters change (three launches, no torch
 arithmetic).  `KManipEnvHip.actor_eval` runs it, `KManipEnvHip.collect` runs it between steps; `reference` is the same network in
-torch float64: the definition.
+torch float64: the definition.  `KManipEnvHip.actor_grad` writes the loss gradients of the parameters (kmanip_actor_grad; DESIGN.md
+section 46) from the transposed packed copy repack() also keeps; `loss_reference` is that loss in torch float64 under autograd.
 """
 from __future__ import annotations
 
@@ -43,6 +44,8 @@ class Actor:
         self.log_std = torch.zeros((self.out_dim,), dtype=torch.float32, device=env.device)
         self.obs_mean = self.obs_inv_std = None
         self.packed = torch.empty((floats,), dtype=torch.float32, device=env.device)
+        self.packed_t = torch.empty((env.L.kmanip_actor_grad_packed_floats(C.byref(self.desc)),), dtype=torch.float32, device=env.device)
+        self.grad_workspace = {}                     # n -> kmanip_actor_grad's workspace (KManipEnvHip.actor_grad)
         self.repack()
 
     @classmethod
@@ -67,7 +70,8 @@ class Actor:
         return [getattr(self, nm) for nm in _NAMES] + [self.log_std]
 
     def repack(self):
-        """kmanip_actor_pack: the parameter tensors as they are now into the buffer the kernel reads, on the current stream."""
+        """kmanip_actor_pack and kmanip_actor_grad_pack: the parameter tensors as they are now into the buffers the kernels read (the
+        second holds W2^T and W1^T for the backward), on the current stream."""
         import torch
         e, dims = self.env, (self.in_dim,) + self.hidden + (self.out_dim,)
         wt = _libmod.KActorWeights()
@@ -78,6 +82,8 @@ class Actor:
             setattr(wt, nm, getattr(self, nm).data_ptr())
         e._check(e.L.kmanip_actor_pack(e.h, C.byref(self.desc), C.byref(wt), C.c_void_p(self.packed.data_ptr()), e._stream()),
                  "kmanip_actor_pack")
+        e._check(e.L.kmanip_actor_grad_pack(e.h, C.byref(self.desc), C.byref(wt), C.c_void_p(self.packed_t.data_ptr()), e._stream()),
+                 "kmanip_actor_grad_pack")
 
     def torch_eval(self, obs):
         """The policy as a torch float32 program on the same parameters -- cast, normalise, three matmuls, sample from torch's global
@@ -120,4 +126,45 @@ class Actor:
             out["act"] = out["raw"].clamp(-1.0, 1.0)
             zd = z.to(torch.float64)
             out["logp"] = (-0.5 * zd * zd - self.log_std.to(torch.float64) - 0.5 * math.log(2.0 * math.pi)).sum(-1)
+        return out
+
+    def loss_reference(self, obs, head, g=None, target=None, ppo=None, idx=None, scale=None):
+        """kmanip_actor_grad's loss in torch float64 under autograd: the definition (include/kmanip.h KActorGradIn).  obs: float64
+        [n_records, in_dim]; idx: the records of the rows (None: all, in order); head "given" (g [n_records, out_dim]: the loss is
+        scale sum g . mean), "mse" (target) or "ppo" (a dict of raw, logp_old, adv, clip); scale: None = 1 / n.  Returns {"grads": a
+        dict by parameter name (log_std for "ppo" only), "row_loss" [n] (not for "given"), "logp" [n] ("ppo")}, all float64."""
+        import math
+        import torch
+        rows = torch.arange(obs.shape[0], device=obs.device) if idx is None else torch.as_tensor(idx, device=obs.device).long()
+        scale = 1.0 / max(len(rows), 1) if scale is None else float(scale)
+        x = obs.to(torch.float64)[rows]
+        if self.obs_mean is not None:
+            x = x - self.obs_mean
+        if self.obs_inv_std is not None:
+            x = x * self.obs_inv_std
+        x = x.to(torch.float32).to(torch.float64)
+        f = torch.tanh if self.activation == "tanh" else torch.relu
+        names = _NAMES + (("log_std",) if head == "ppo" else ())
+        w = {nm: getattr(self, nm).to(torch.float64).requires_grad_() for nm in names}
+        mean = f(f(x @ w["w0"].T + w["b0"]) @ w["w1"].T + w["b1"]) @ w["w2"].T + w["b2"]
+        out = {}
+        if head == "given":
+            total = (g.to(torch.float64)[rows] * mean).sum()
+        elif head == "mse":
+            out["row_loss"] = 0.5 * ((mean - target.to(torch.float64)[rows]) ** 2).sum(-1)
+            total = out["row_loss"].sum()
+        elif head == "ppo":
+            ls = w["log_std"]
+            sd = ls.exp()
+            sd = sd + (sd.detach().to(torch.float32).to(torch.float64) - sd.detach())        # the kernel's float32 value, exp's derivative
+            u = (ppo["raw"].to(torch.float64)[rows] - mean) / sd
+            out["logp"] = (-0.5 * u * u - ls - 0.5 * math.log(2.0 * math.pi)).sum(-1)
+            rho, adv, clip = (out["logp"] - ppo["logp_old"].to(torch.float64)[rows]).exp(), ppo["adv"].to(torch.float64)[rows], float(ppo["clip"])
+            out["row_loss"] = -torch.minimum(rho * adv, rho.clamp(1.0 - clip, 1.0 + clip) * adv)
+            total = out["row_loss"].sum()
+        else:
+            raise ValueError("loss_reference: head is 'given', 'mse' or 'ppo'")
+        grads = torch.autograd.grad(scale * total, [w[nm] for nm in names])
+        out = {k: v.detach() for k, v in out.items()}
+        out["grads"] = dict(zip(names, grads))
         return out

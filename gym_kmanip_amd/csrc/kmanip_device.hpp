@@ -692,6 +692,23 @@ KActorPlan kmanip_actor_plan(const KActorDesc& d);
 void kmanip_launch_actor_pack(const KActorDesc& d, const KActorWeights& w, float* packed, hipStream_t stream);
 void kmanip_launch_actor(const KDeviceState& st, const KActorDesc& d, const float* packed, const KActorIn& in, int n, const KActorDev& out,
                          hipStream_t stream);
+// kmanip_actor_grad / kmanip_actor_grad_pack (kmanip_actor_grad.hip): `t` lays out the transposed buffer (layers 0 and 1 of the network
+// out_dim -> hidden[1] -> hidden[0]: W2^T, W1^T; total4 ends there); np the rows padded to 16, `splits` K-splits of `len` rows; off[]
+// the unit-major workspace arrays x h1 h2 dz1 dz2 dz3 and the log_std terms; per work-item layer l (0..2: dW_l, db_l; 3: the log_std
+// row sum) the dz and input arrays, dz tiles, input tiles and groups of four of them, the first item, partial tile and row-sum slot;
+// `part` where the splits' partials (tiles x 256 + biases floats each) begin, `total` the workspace's floats.
+// The launches: two pack launches; per call over n > 0 rows k_actor_bwd, k_actor_wgrad, k_actor_grad_reduce (n == 0: the last only)
+#define KM_AGRAD_ARRAYS 7
+struct KActorGradPlan {
+  KActorPlan t;
+  int np, splits, len;
+  size_t off[KM_AGRAD_ARRAYS], dz[4], h[4], part, total;
+  int ot[4], it[4], itg[4], item0[5], tile0[4], bias0[4], tiles, biases;
+};
+KActorGradPlan kmanip_actor_grad_plan(const KActorDesc& d, int n);
+void kmanip_launch_actor_grad_pack(const KActorDesc& d, const KActorWeights& w, float* packed_t, hipStream_t stream);
+void kmanip_launch_actor_grad(const KActorDesc& d, const float* packed, const float* packed_t, const KActorGradIn& in, int n, float* ws,
+                              const KActorGradDev& out, hipStream_t stream);
 
 // The env state in and out of a handle on the device (kmanip_state.hip; include/kmanip.h kmanip_get_state_dev / kmanip_set_state_dev /
 // kmanip_copy_envs).  Arguments of their own: no field of KDeviceState / KDeviceModel moves.

@@ -1423,6 +1423,61 @@ class KManipEnvHip:
                                            C.c_void_p(at("done", t)), stream), "kmanip_step")
         return out
 
+    def actor_grad(self, actor, obs, *, g=None, target=None, ppo=None, idx=None, scale=None, out=None, set_grad=True):
+        """kmanip_actor_grad: the float32 gradients of a loss over rows of a rollout buffer in `actor`'s parameters -- three launches
+        on the current stream, no synchronisation, no torch arithmetic, the same bytes on every run.  obs: float64 [n_records,
+        actor.in_dim]; idx: the records of the rows (an int32 device tensor or anything torch.as_tensor takes; None = every record,
+        in order), n of them.  Exactly one head: g float32 [n_records, out_dim], the loss scale sum g . mean; target float32
+        [n_records, out_dim], scale / 2 sum |mean - target|^2; ppo = {"raw" float32 [n_records, out_dim], "logp_old" float64
+        [n_records], "adv" float32 [n_records], "clip"}, PPO's clipped surrogate (include/kmanip.h has the definitions).  scale:
+        None = 1 / n.  Returns a dict of device tensors: w0 .. b2 (log_std with ppo) shaped like the parameters, status [n] int32
+        (2: a record index out of range, the row adds nothing), row_loss [n] float64 (target, ppo), logp [n] float64 (ppo); `out`:
+        such a dict to overwrite, returned as given.  With set_grad the gradients become the parameters' .grad: a torch optimiser's
+        step() and actor.repack() then make a training step."""
+        torch = _torch()
+        heads = [k for k, v in (("given", g), ("mse", target), ("ppo", ppo)) if v is not None]
+        if len(heads) != 1:
+            raise ValueError("actor_grad: exactly one of g, target and ppo")
+        head, f32, f64 = heads[0], torch.float32, torch.float64
+        nrec = int(obs.shape[0]) if isinstance(obs, torch.Tensor) and obs.dim() else -1
+        self._check_buf(obs, (nrec, actor.in_dim), f64, "obs")
+        self._actor_check(actor)
+        index, _, n = self._env_index(idx, "idx")
+        n = nrec if n is None else n
+        gi = _libmod.KActorGradIn(head=_libmod.KM_AGRAD[head], n_records=nrec, idx=index.data_ptr() if n and index is not None else None, obs=obs.data_ptr(),
+                                  scale=1.0 / max(n, 1) if scale is None else float(scale))
+        for name in ("obs_mean", "obs_inv_std"):
+            if getattr(actor, name) is not None:
+                setattr(gi, name, getattr(actor, name).data_ptr())
+        given = {"given": {"g": (g, (actor.out_dim,), f32)}, "mse": {"target": (target, (actor.out_dim,), f32)}}.get(head) or {
+            "raw": (ppo["raw"], (actor.out_dim,), f32), "logp_old": (ppo["logp_old"], (), f64), "adv": (ppo["adv"], (), f32)}
+        for name, (t, shp, dt) in given.items():
+            self._check_buf(t, (nrec,) + shp, dt, name)
+            setattr(gi, name, t.data_ptr())
+        if head == "ppo":
+            gi.log_std, gi.clip = actor.log_std.data_ptr(), float(ppo["clip"])
+        params = {nm: getattr(actor, nm) for nm in ("w0", "b0", "w1", "b1", "w2", "b2") + (("log_std",) if head == "ppo" else ())}
+        shapes = {nm: (tuple(p.shape), f32) for nm, p in params.items()}
+        shapes.update({"status": ((n,), torch.int32)}, **({} if head == "given" else {"row_loss": ((n,), f64)}), **({"logp": ((n,), f64)} if head == "ppo" else {}))
+        if out is None:
+            out = {k: torch.empty(s, dtype=dt, device=self.device) for k, (s, dt) in shapes.items()}
+        if set(out) != set(shapes):
+            raise ValueError("actor_grad: out must hold exactly %s" % sorted(shapes))
+        dev = _libmod.KActorGradDev()
+        for k, (s, dt) in shapes.items():
+            self._check_buf(out[k], s, dt, k)
+            setattr(dev, k, out[k].data_ptr())
+        if n not in actor.grad_workspace:
+            floats = self.L.kmanip_actor_grad_workspace_floats(C.byref(actor.desc), n)
+            actor.grad_workspace[n] = torch.empty((floats,), dtype=f32, device=self.device)
+        self._check(self.L.kmanip_actor_grad(self.h, C.byref(actor.desc), C.c_void_p(actor.packed.data_ptr()), C.c_void_p(actor.packed_t.data_ptr()),
+                                             C.byref(gi), n, C.c_void_p(actor.grad_workspace[n].data_ptr()), C.byref(dev), self._stream()),
+                    "kmanip_actor_grad")
+        if set_grad:
+            for nm, p in params.items():
+                p.grad = out[nm]
+        return out
+
     def k_render(self, cam):
         """KManipEnvSim.k_render (env_sim.py:187-188): physics.render(cam.h, cam.w, camera_id=cam.name) -> uint8 RGB,
         for every env ([num_envs, h, w, 3], device tensor).  `cam` is a Cam (model.CAMERAS) or a camera name."""

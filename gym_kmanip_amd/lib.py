@@ -20,7 +20,7 @@ _lib = None
 EXPORTS = [
     "kmanip_model_desc_size", "kmanip_create", "kmanip_reset", "kmanip_step", "kmanip_step_chunk", "kmanip_get_state",
     "kmanip_set_state", "kmanip_get_episode", "kmanip_set_episode", "kmanip_get_counters", "kmanip_bind_sim_time", "kmanip_bind_applied_force", "kmanip_bind_reward_done_record", "kmanip_select_reward_done_record", "kmanip_observe", "kmanip_forces", "kmanip_kinematics", "kmanip_inverse", "kmanip_forward", "kmanip_kinematics_rows", "kmanip_site_cost", "kmanip_rollout", "kmanip_feedback", "kmanip_feedback_box", "kmanip_transition_fd", "kmanip_forward_fd", "kmanip_param_fd", "kmanip_lqr_backward", "kmanip_lqr_backward_box", "kmanip_adjoint", "kmanip_tangent", "kmanip_set_seed", "kmanip_get_diag", "kmanip_timing_summary", "kmanip_enable_timing", "kmanip_ik", "kmanip_ik_eval",
-    "kmanip_render_depth", "kmanip_render_rgb", "kmanip_render_rgb_multi", "kmanip_render_labels_multi", "kmanip_render_seg", "kmanip_set_render_links", "kmanip_get_render_links", "kmanip_set_depth_links", "kmanip_get_depth_links", "kmanip_get_camera_poses", "kmanip_render_points", "kmanip_snapshot_render_state", "kmanip_set_render_source", "kmanip_bind_step_depth", "kmanip_scripted_action", "kmanip_sample_action", "kmanip_actor_packed_floats", "kmanip_actor_pack", "kmanip_actor", "kmanip_set_env_params", "kmanip_get_env_params", "kmanip_set_env_param_ranges", "kmanip_set_visual_params", "kmanip_get_visual_params", "kmanip_set_visual_param_ranges",
+    "kmanip_render_depth", "kmanip_render_rgb", "kmanip_render_rgb_multi", "kmanip_render_labels_multi", "kmanip_render_seg", "kmanip_set_render_links", "kmanip_get_render_links", "kmanip_set_depth_links", "kmanip_get_depth_links", "kmanip_get_camera_poses", "kmanip_render_points", "kmanip_snapshot_render_state", "kmanip_set_render_source", "kmanip_bind_step_depth", "kmanip_scripted_action", "kmanip_sample_action", "kmanip_actor_packed_floats", "kmanip_actor_pack", "kmanip_actor", "kmanip_actor_grad_packed_floats", "kmanip_actor_grad_workspace_floats", "kmanip_actor_grad_pack", "kmanip_actor_grad", "kmanip_set_env_params", "kmanip_get_env_params", "kmanip_set_env_param_ranges", "kmanip_set_visual_params", "kmanip_get_visual_params", "kmanip_set_visual_param_ranges",
     "kmanip_get_state_dev", "kmanip_set_state_dev", "kmanip_copy_envs", "kmanip_state_index_errors", "kmanip_num_envs", "kmanip_last_error", "kmanip_version", "kmanip_destroy",
 ]
 
@@ -254,6 +254,45 @@ def actor_packed_floats(in_dim, hidden, out_dim):
     return sum(tiles(o) * (-(-tiles(i) // KM_ACTOR_KGROUP) * KM_ACTOR_KGROUP) * 256 + tiles(o) * 16 for i, o in zip(dims, dims[1:]))
 
 
+class KActorGradIn(C.Structure):
+    """include/kmanip.h KActorGradIn: the head (KM_AGRAD), the record count, DEVICE pointers of kmanip_actor_grad's inputs (those the
+    head does not read may be NULL), PPO's clip and the factor on every row's loss."""
+    _fields_ = ([("head", C.c_int32), ("n_records", C.c_int32)]
+                + [(nm, C.c_void_p) for nm in ("idx", "obs", "obs_mean", "obs_inv_std", "log_std", "g", "target", "raw", "logp_old", "adv")]
+                + [("clip", C.c_double), ("scale", C.c_double)])
+
+
+class KActorGradDev(C.Structure):
+    """include/kmanip.h KActorGradDev: DEVICE pointers of the seven gradient tensors and of the per-row outputs (each of those or NULL)."""
+    _fields_ = [(nm, C.c_void_p) for nm in ("w0", "b0", "w1", "b1", "w2", "b2", "log_std", "row_loss", "logp", "status")]
+
+
+KM_AGRAD = {"given": 0, "mse": 1, "ppo": 2}      # include/kmanip.h KM_AGRAD_GIVEN / _MSE / _PPO_CLIP
+
+
+def actor_grad_packed_floats(in_dim, hidden, out_dim):
+    """include/kmanip.h kmanip_actor_grad_packed_floats, restated: W2^T and W1^T as layers out_dim -> hidden[1] -> hidden[0] of
+    actor_packed_floats' layout."""
+    tiles = lambda v: (v + 15) // 16
+    layer = lambda i, o: tiles(o) * (-(-tiles(i) // KM_ACTOR_KGROUP) * KM_ACTOR_KGROUP) * 256 + tiles(o) * 16
+    return layer(out_dim, hidden[1]) + layer(hidden[1], hidden[0])
+
+
+def actor_grad_splits(n):
+    """(rows padded to 16, K-splits, rows per split) of a kmanip_actor_grad call over n rows."""
+    tiles = max(1, -(-n // 16))
+    splits = 0 if n == 0 else min(64, -(-16 * tiles // 256))
+    return 16 * tiles, splits, 16 * -(-tiles // max(splits, 1))
+
+
+def actor_grad_workspace_floats(in_dim, hidden, out_dim, n):
+    """include/kmanip.h kmanip_actor_grad_workspace_floats, restated: x, h1, h2, dz1, dz2, dz3 and the log_std terms [units padded to
+    16][rows padded to 16], then per K-split the partial 16 x 16 tiles of the three weight gradients and the row sums."""
+    np_, splits, _ = actor_grad_splits(n)
+    ti, t1, t2 = (in_dim + 15) // 16, hidden[0] // 16, hidden[1] // 16
+    return 16 * (ti + 2 * t1 + 2 * t2 + 2) * np_ + splits * (256 * (t1 * ti + t2 * t1 + t2) + 16 * (t1 + t2 + 2))
+
+
 KM_TANGENT_MC = 16               # include/kmanip.h: H and g need m <= KM_TANGENT_MC
 KM_WRT = {"qpos": 1, "qvel": 2, "ctrl": 4, "qfrc_applied": 8}     # include/kmanip.h KM_WRT_*: the columns always run in this order
 # include/kmanip.h KM_OF_*: the differentiated outputs of kmanip_forward_fd, always in this order
@@ -346,6 +385,12 @@ def load():
     lib.kmanip_actor_packed_floats.restype = C.c_size_t
     lib.kmanip_actor_pack.argtypes = [vp, C.POINTER(KActorDesc), C.POINTER(KActorWeights), vp, vp]
     lib.kmanip_actor.argtypes = [vp, C.POINTER(KActorDesc), vp, C.POINTER(KActorIn), C.c_int, C.POINTER(KActorDev), vp]
+    lib.kmanip_actor_grad_packed_floats.argtypes = [C.POINTER(KActorDesc)]
+    lib.kmanip_actor_grad_packed_floats.restype = C.c_size_t
+    lib.kmanip_actor_grad_workspace_floats.argtypes = [C.POINTER(KActorDesc), C.c_int]
+    lib.kmanip_actor_grad_workspace_floats.restype = C.c_size_t
+    lib.kmanip_actor_grad_pack.argtypes = [vp, C.POINTER(KActorDesc), C.POINTER(KActorWeights), vp, vp]
+    lib.kmanip_actor_grad.argtypes = [vp, C.POINTER(KActorDesc), vp, vp, C.POINTER(KActorGradIn), C.c_int, vp, C.POINTER(KActorGradDev), vp]
     lib.kmanip_set_env_params.argtypes = [vp, vp, vp]
     lib.kmanip_get_env_params.argtypes = [vp, vp, vp]
     lib.kmanip_set_env_param_ranges.argtypes = [vp, f64p, f64p]

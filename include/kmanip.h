@@ -1221,8 +1221,69 @@ KMANIP_API int kmanip_actor_pack(KHandle h, const KActorDesc* desc, const KActor
  * outside 16 .. KM_ACTOR_MAX_HIDDEN, in_dim outside 1 .. KM_ACTOR_MAX_IN, out_dim outside 1 .. KM_ACTOR_MAX_OUT, an unknown
  * activation, a NULL obs or packed_dev or a packed_dev that is not 16-byte aligned return nonzero with kmanip_last_error set, launch
  * nothing and leave the outputs untouched.
- * OUT OF SCOPE: other weight types, more than two hidden layers, the policy inside the step kernels, backward passes. */
+ * OUT OF SCOPE: other weight types, more than two hidden layers, the policy inside the step kernels. */
 KMANIP_API int kmanip_actor(KHandle h, const KActorDesc* desc, const float* packed_dev, const KActorIn* in, int n, const KActorDev* out, void* stream);
+
+/* THE LOSS GRADIENTS of that network: for n rows of a rollout buffer of n_records records, the float32 gradients
+ * of  L = sum_r loss_r  in w0, b0, w1, b1, w2, b2 (and log_std), in the shapes of the KActorWeights tensors, ready to be a torch .grad.
+ * Row r reads record i = idx ? idx[r] : r (a minibatch is an index list: nothing is gathered).  The forward is kmanip_actor's to the
+ * bit (the same code on the same packed buffer): x = float32((obs[i] - obs_mean) * obs_inv_std), h1 = act(W0 x + b0), h2 = act(W1 h1
+ * + b1), mean = W2 h2 + b2.  A head turns mean into gmean[r][j] = dL/dmean, in float64 per row, rounded to float32 once:
+ *   KM_AGRAD_GIVEN     gmean = scale g[i]
+ *   KM_AGRAD_MSE       gmean = scale (mean - target[i]);  row_loss[r] = 1/2 sum_j (mean_j - target_j)^2      (value loss, cloning)
+ *   KM_AGRAD_PPO_CLIP  sd_j = float32(exp(float64(log_std_j)));  u_j = (raw[i][j] - mean_j) / sd_j;
+ *                      logp = sum_j (-u_j^2 / 2 - log_std_j - log(2 pi) / 2)     (summed as kmanip_actor sums it);
+ *                      rho = exp(logp - logp_old[i]);  s = rho adv[i];  c = min(max(rho, 1 - clip), 1 + clip) adv[i];
+ *                      row_loss = -min(s, c);  coef = (s <= c) ? -scale adv[i] rho : 0;
+ *                      gmean_j = coef u_j / sd_j;  glog_std_j = sum_r float32(coef_r (u_rj^2 - 1))
+ * and the backward is  dz3 = gmean;  dW2 = sum_r dz3 h2^T, db2 = sum_r dz3;  dz2 = (W2^T dz3) act'(h2);  dW1, db1 likewise from dz2 and
+ * h1;  dz1 = (W1^T dz2) act'(h1);  dW0 = sum_r dz1 x^T, db0 = sum_r dz1,  with act' from the activated value (1 - h^2 for tanh, h > 0
+ * for relu): float32 on the matrix cores with float32 accumulation.  The order of every sum is the kernels' own and a function of
+ * (desc, n) only; no atomics: the same call gives the same bytes.  The gradient tensors are OVERWRITTEN, not accumulated; log_std's is
+ * written by the PPO head only.  A row whose record index is outside 0 .. n_records-1 has status 2, reads nothing through the index
+ * and adds exact zeros to every sum: the gradients are those of the call with the other rows in the same places. */
+#define KM_AGRAD_GIVEN    0
+#define KM_AGRAD_MSE      1
+#define KM_AGRAD_PPO_CLIP 2
+typedef struct KActorGradIn {        /* pointers DEVICE; the arrays a head does not read may be NULL */
+  int32_t head, n_records;           /* KM_AGRAD_*; the records the arrays below hold */
+  const int32_t* idx;                /* [n] or NULL: row r is record r (then n <= n_records) */
+  const double*  obs;                /* [n_records, in_dim] */
+  const double  *obs_mean, *obs_inv_std;   /* [in_dim] each, or NULL */
+  const float*   log_std;            /* [out_dim]: PPO */
+  const float*   g;                  /* [n_records, out_dim]: GIVEN */
+  const float*   target;             /* [n_records, out_dim]: MSE */
+  const float*   raw;                /* [n_records, out_dim]: PPO -- raw, logp_old, adv in the dtypes collect() writes */
+  const double*  logp_old;           /* [n_records]: PPO */
+  const float*   adv;                /* [n_records]: PPO */
+  double clip, scale;                /* PPO's clip in (0, 1); the factor on every row's loss, e.g. 1 / n */
+} KActorGradIn;
+typedef struct KActorGradDev {
+  float *w0, *b0, *w1, *b1, *w2, *b2;      /* row-major, as KActorWeights; all required */
+  float *log_std;                    /* [out_dim]: required and written with the PPO head, untouched otherwise */
+  double* row_loss;                  /* [n] or NULL: MSE and PPO */
+  double* logp;                      /* [n] or NULL: PPO */
+  int32_t* status;                   /* [n] or NULL: 0 ok; 2 a record index outside 0 .. n_records-1: row_loss and logp of the row are 0 */
+} KActorGradDev;
+/* The floats of the transposed packed buffer (W2^T and W1^T in kmanip_actor_pack's layout, each with a bias of zeros) and of the
+ * workspace of a call over n rows: with np = n rounded up to 16 (at least 16), the arrays x, h1, h2, dz1, dz2, dz3 and the log_std
+ * terms unit-major [units padded to 16][np], then per K-split the partial tiles and row sums; there are min(64, ceil(np / 256)) splits.
+ * Both are 0 for a description kmanip_actor would refuse, the second also for n < 0. */
+KMANIP_API size_t kmanip_actor_grad_packed_floats(const KActorDesc* desc);
+KMANIP_API size_t kmanip_actor_grad_workspace_floats(const KActorDesc* desc, int n);
+/* W2 and W1 into packed_t_dev (16-byte aligned): two launches on `stream`; to be repeated with kmanip_actor_pack after the weights change. */
+KMANIP_API int kmanip_actor_grad_pack(KHandle h, const KActorDesc* desc, const KActorWeights* weights, float* packed_t_dev, void* stream);
+/* THREE launches, asynchronous on `stream` (recompute and data gradients; weight-gradient partials; their sum): no allocation, no
+ * synchronisation, no atomics.  The handle is not read beyond its error slot.  n == 0 succeeds and writes zeros to the gradients (one launch).
+ * ERRORS: a NULL handle, desc, `in` or `out`; a desc kmanip_actor would refuse; n < 0, n_records < 1, n > n_records without idx; an
+ * unknown head; a NULL obs or array the head reads (GIVEN: g; MSE: target; PPO: log_std, raw, logp_old, adv); clip outside (0, 1) with
+ * the PPO head; a NULL gradient pointer (log_std's with the PPO head only); a NULL or not 16-byte aligned packed_dev, packed_t_dev or
+ * workspace_dev (their sizes are the caller's to keep: the call cannot see them) return nonzero with kmanip_last_error set and launch
+ * nothing.
+ * OUT OF SCOPE: the gradient in obs, an entropy bonus (its log_std gradient is a constant the caller adds), GAE and advantage
+ * normalisation, the optimiser step, other weight types, more than two hidden layers. */
+KMANIP_API int kmanip_actor_grad(KHandle h, const KActorDesc* desc, const float* packed_dev, const float* packed_t_dev, const KActorGradIn* in, int n,
+                                 float* workspace_dev, const KActorGradDev* out, void* stream);
 
 /* Per-env physics parameters (domain randomisation).  Storage is double[KM_EP_N][num_envs], struct-of-arrays
  * like the state: element (k, env) at k * num_envs + env.  Env e with parameters p behaves exactly like a handle whose KModelDesc is
