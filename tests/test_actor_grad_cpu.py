@@ -34,8 +34,10 @@ def inputs(net, in_dim, out_dim, activation):
                 raw=raw, logp_old=logp - np.log(np.array(RHO)[i % 4]), adv=(rng.uniform(0.5, 1.5, NREC) * np.where(i // 4 % 2, -1.0, 1.0)).astype(np.float32))
 
 
-def grads_of(net, rec, activation, head, rows, dtype):
-    """include/kmanip.h's gradients in `dtype`: the head in float64 on the dtype's mean, the GEMMs in dtype."""
+def grads_of(net, rec, activation, head, rows, dtype, rowsum=None):
+    """include/kmanip.h's gradients in `dtype`: the head in float64 on the dtype's mean, the GEMMs in dtype.  rowsum(a, b=None): the
+    sum over the rows of a[n, p] (b given: of the outer products a[r] b[r]) -- None: NumPy's own, a.sum(0) and a.T @ b."""
+    rowsum = rowsum or (lambda a, b=None: a.sum(0) if b is None else a.T @ b)
     rows = np.arange(NREC) if rows is None else np.array(rows)
     f = np.tanh if activation == "tanh" else (lambda v: np.maximum(v, 0))
     df = (lambda h: 1 - h * h) if activation == "tanh" else (lambda h: (h > 0).astype(dtype))
@@ -54,10 +56,10 @@ def grads_of(net, rec, activation, head, rows, dtype):
         rho = np.exp((-0.5 * u * u - net["log_std"] - 0.5 * np.log(2.0 * np.pi)).sum(-1) - rec["logp_old"][rows])
         adv = rec["adv"][rows].astype(np.float64)
         coef = np.where(rho * adv <= np.clip(rho, 1 - CLIP, 1 + CLIP) * adv, -scale * adv * rho, 0.0)[:, None]
-        gm, out["log_std"] = coef * u / sd, (coef * (u * u - 1)).astype(dtype).sum(0)
+        gm, out["log_std"] = coef * u / sd, rowsum((coef * (u * u - 1)).astype(dtype))
     dz = gm.astype(dtype)
     for l, h in ((2, h2), (1, h1), (0, x)):
-        out["w%d" % l], out["b%d" % l] = dz.T @ h, dz.sum(0)
+        out["w%d" % l], out["b%d" % l] = rowsum(dz, h), rowsum(dz)
         dz = (dz @ w["w%d" % l]) * df(h) if l else None
     return out
 
