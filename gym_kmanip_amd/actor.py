@@ -6,6 +6,8 @@ takes -- and the packed copy the kernel reads; `repack()` rebuilds that copy aft
 arithmetic).  `KManipEnvHip.actor_eval` runs it, `KManipEnvHip.collect` runs it between steps; `reference` is the same network in
 torch float64: the definition.  `KManipEnvHip.actor_grad` writes the loss gradients of the parameters (kmanip_actor_grad; DESIGN.md
 section 46) from the transposed packed copy repack() also keeps; `loss_reference` is that loss in torch float64 under autograd.
+`KManipEnvHip.actor_adam` (kmanip_actor_adam) is the optimiser step on these tensors: it keeps its moments in
+`adam_state` and its step count in `adam_step`, and rewrites both packed copies itself -- no repack() after it.
 """
 from __future__ import annotations
 
@@ -46,6 +48,7 @@ class Actor:
         self.packed = torch.empty((floats,), dtype=torch.float32, device=env.device)
         self.packed_t = torch.empty((env.L.kmanip_actor_grad_packed_floats(C.byref(self.desc)),), dtype=torch.float32, device=env.device)
         self.grad_workspace = {}                     # n -> kmanip_actor_grad's workspace (KManipEnvHip.actor_grad)
+        self.adam_state, self.adam_step = None, 0    # kmanip_actor_adam's moments and step count (KManipEnvHip.actor_adam)
         self.repack()
 
     @classmethod

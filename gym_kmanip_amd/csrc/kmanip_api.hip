@@ -1241,6 +1241,52 @@ int kmanip_actor_grad(KHandle h, const KActorDesc* desc, const float* packed_dev
   return 0;
 }
 
+// ---- advantages and returns (include/kmanip.h KGaeIn ...; kmanip_gae.hip)
+size_t kmanip_gae_workspace_doubles(int N) { return N < 1 ? 0 : 2 * (((size_t)N + KM_GAE_BLOCK - 1) / KM_GAE_BLOCK); }
+
+int kmanip_gae(KHandle h, const KGaeIn* in, int T, int N, double* workspace_dev, const KGaeDev* out, void* stream) {
+  if (!h) { g_create_error = "kmanip_gae: null handle"; return -1; }
+  auto refuse = [&](const char* what) { h->err = std::string("kmanip_gae: ") + what; return -1; };
+  if (!in) return refuse("the KGaeIn pointer is NULL");
+  if (!out) return refuse("the KGaeDev pointer is NULL");
+  if (!in->reward || !in->done || !in->value) return refuse("reward, done or value is NULL");
+  if (!out->adv || !out->ret) return refuse("adv or ret is NULL");
+  if (!workspace_dev) return refuse("workspace_dev is NULL");
+  if (T < 1 || N < 1) return refuse("T or N is below 1");
+  if (!(in->gamma >= 0.0 && in->gamma <= 1.0) || !(in->lambda >= 0.0 && in->lambda <= 1.0)) return refuse("gamma or lambda is not in [0, 1]");
+  KM_ENTER(h);
+  kmanip_launch_gae(*in, T, N, workspace_dev, *out, (hipStream_t)stream);
+  HIPCHK(h, hipGetLastError());
+  return 0;
+}
+
+// ---- the optimiser step (include/kmanip.h KActorAdamIn ...; kmanip_actor_opt.hip)
+size_t kmanip_actor_adam_state_floats(const KActorDesc* desc) { return actor_desc_error(desc) ? 0 : 2 * (size_t)kmanip_actor_adam_plan(*desc, true).total; }
+
+int kmanip_actor_adam(KHandle h, const KActorDesc* desc, const KActorAdamIn* in, const KActorParams* params, float* state_dev, float* packed_dev,
+                      float* packed_t_dev, double* workspace_dev, double* gnorm_dev, void* stream) {
+  if (!h) { g_create_error = "kmanip_actor_adam: null handle"; return -1; }
+  auto refuse = [&](const char* what) { h->err = std::string("kmanip_actor_adam: ") + what; return -1; };
+  if (const char* e = actor_desc_error(desc)) return refuse(e);
+  if (!in) return refuse("the KActorAdamIn pointer is NULL");
+  if (!params) return refuse("the KActorParams pointer is NULL");
+  if (!in->gw0 || !in->gb0 || !in->gw1 || !in->gb1 || !in->gw2 || !in->gb2) return refuse("a gradient pointer is NULL");
+  if (!params->w0 || !params->b0 || !params->w1 || !params->b1 || !params->w2 || !params->b2) return refuse("a parameter pointer is NULL");
+  if (!in->glog_std != !params->log_std) return refuse("glog_std and params->log_std must both be NULL or both be set");
+  if (in->step < 1) return refuse("step is below 1");
+  if (!std::isfinite(in->lr) || !std::isfinite(in->max_grad_norm)) return refuse("lr or max_grad_norm is not finite");
+  if (!(in->beta1 >= 0.0 && in->beta1 < 1.0) || !(in->beta2 >= 0.0 && in->beta2 < 1.0)) return refuse("a beta is not in [0, 1)");
+  if (!(in->eps > 0.0) || !std::isfinite(in->eps)) return refuse("eps is not a finite value above 0");
+  if (!state_dev || ((uintptr_t)state_dev & 15)) return refuse("state_dev is NULL or not 16-byte aligned");
+  if (!packed_dev || ((uintptr_t)packed_dev & 15)) return refuse("packed_dev is NULL or not 16-byte aligned");
+  if (!packed_t_dev || ((uintptr_t)packed_t_dev & 15)) return refuse("packed_t_dev is NULL or not 16-byte aligned");
+  if ((in->max_grad_norm > 0.0 || gnorm_dev) && !workspace_dev) return refuse("workspace_dev is NULL where the norm is taken");
+  KM_ENTER(h);
+  kmanip_launch_actor_adam(*desc, *in, *params, state_dev, packed_dev, packed_t_dev, workspace_dev, gnorm_dev, (hipStream_t)stream);
+  HIPCHK(h, hipGetLastError());
+  return 0;
+}
+
 int kmanip_enable_timing(KHandle h, int enable) {
   if (!h) return -1;
   KM_ENTER(h);

@@ -709,6 +709,21 @@ KActorGradPlan kmanip_actor_grad_plan(const KActorDesc& d, int n);
 void kmanip_launch_actor_grad_pack(const KActorDesc& d, const KActorWeights& w, float* packed_t, hipStream_t stream);
 void kmanip_launch_actor_grad(const KActorDesc& d, const float* packed, const float* packed_t, const KActorGradIn& in, int n, float* ws,
                               const KActorGradDev& out, hipStream_t stream);
+// kmanip_gae (kmanip_gae.hip): k_gae over ceil(N / KM_GAE_BLOCK) blocks, then k_gae_finish where the call normalises or reports stats
+void kmanip_launch_gae(const KGaeIn& in, int T, int N, double* ws, const KGaeDev& out, hipStream_t stream);
+// kmanip_actor_adam (kmanip_actor_opt.hip): `p` and `t` lay out the two packed buffers; rkb[l] the REAL K-blocks of layer l (the work
+// items: the padding blocks are never touched); item0[] the first work item of the tiles of layers 0..2, of the three biases [3..5], of
+// log_std [6], and the item count [7]; off[] where the seven tensors begin in each half of the state, `total` that half's floats (and
+// the elements the norm runs over, less out_dim where there is no log_std gradient); `nb` blocks of `per` elements take the norm.
+// hyper: what the host works out in double.  The launches: k_actor_gradnorm where the norm is wanted, then k_actor_adam
+struct KActorAdamPlan {
+  KActorPlan p, t;
+  int rkb[3], item0[8], off[7], total, nb, per;
+};
+struct KActorAdamHyper { double beta1, omb1, beta2, omb2, step_size, sqrt_bc2, eps, max_norm; };
+KActorAdamPlan kmanip_actor_adam_plan(const KActorDesc& d, bool with_log_std);
+void kmanip_launch_actor_adam(const KActorDesc& d, const KActorAdamIn& in, const KActorParams& params, float* state, float* packed, float* packed_t,
+                              double* ws, double* gnorm, hipStream_t stream);
 
 // The env state in and out of a handle on the device (kmanip_state.hip; include/kmanip.h kmanip_get_state_dev / kmanip_set_state_dev /
 // kmanip_copy_envs).  Arguments of their own: no field of KDeviceState / KDeviceModel moves.

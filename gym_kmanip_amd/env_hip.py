@@ -1478,6 +1478,71 @@ class KManipEnvHip:
                 p.grad = out[nm]
         return out
 
+    def gae(self, buf, gamma=0.99, lam=0.95, normalize=True, timeout_value=None, out=None):
+        """kmanip_gae: the advantages and value targets of a collect() buffer `buf` (which must hold `value`: collect with a critic) --
+        two launches on the current stream, no synchronisation, the same bytes on every run.  A done step cuts the recursion and
+        bootstraps from 0, or from timeout_value[t] (float32 [T, N]) where the step is truncated and did not diverge.  Returns a dict
+        of device tensors: adv [T, N] float32 (normalised over the whole buffer with `normalize`), ret [T, N] float32 (never
+        normalised), stats [2] float64 (mean and population std of the unnormalised advantages); adv.view(-1) and ret.view(-1, 1)
+        are what actor_grad takes.  `out`: such a dict to overwrite, returned as given."""
+        torch = _torch()
+        if "value" not in buf:
+            raise _libmod.KManipError("gae: the buffer holds no value (collect with a critic)")
+        T, N = (int(v) for v in buf["reward"].shape) if isinstance(buf["reward"], torch.Tensor) and buf["reward"].dim() == 2 else (-1, -1)
+        self._check_buf(buf["reward"], (T, N), torch.float64, "reward")
+        self._check_buf(buf["done"], (T, N), torch.uint8, "done")
+        self._check_buf(buf["value"], (T + 1, N), torch.float32, "value")
+        gi = _libmod.KGaeIn(reward=buf["reward"].data_ptr(), done=buf["done"].data_ptr(), value=buf["value"].data_ptr(), gamma=float(gamma),
+                            normalize=1 if normalize else 0)
+        setattr(gi, "lambda", float(lam))
+        if timeout_value is not None:
+            self._check_buf(timeout_value, (T, N), torch.float32, "timeout_value")
+            gi.timeout_value = timeout_value.data_ptr()
+        shapes = {"adv": ((T, N), torch.float32), "ret": ((T, N), torch.float32), "stats": ((2,), torch.float64)}
+        if out is None:
+            out = {k: torch.empty(s, dtype=dt, device=self.device) for k, (s, dt) in shapes.items()}
+        if set(out) != set(shapes):
+            raise ValueError("gae: out must hold exactly %s" % sorted(shapes))
+        dev = _libmod.KGaeDev()
+        for k, (s, dt) in shapes.items():
+            self._check_buf(out[k], s, dt, k)
+            setattr(dev, k, out[k].data_ptr())
+        ws = getattr(self, "_gae_ws", None)          # the blocks' partial sums: kept on the env, grown when a wider buffer comes
+        if ws is None or ws.numel() < _libmod.gae_workspace_doubles(N):
+            ws = self._gae_ws = torch.empty((max(2, _libmod.gae_workspace_doubles(N)),), dtype=torch.float64, device=self.device)
+        self._check(self.L.kmanip_gae(self.h, C.byref(gi), T, N, C.c_void_p(ws.data_ptr()), C.byref(dev), self._stream()), "kmanip_gae")
+        return out
+
+    def actor_adam(self, actor, lr, betas=(0.9, 0.999), eps=1e-8, max_grad_norm=None, grads=None, log_std=True):
+        """kmanip_actor_adam: one Adam step of `actor`'s parameters from their .grad (or from `grads`, a dict by parameter name such
+        as actor_grad returns), with the gradients clipped to the norm max_grad_norm as torch's clip_grad_norm_ does (None: no
+        clipping), and BOTH packed copies rewritten in the same pass: actor.repack() is not needed afterwards.  Two launches on the
+        current stream, no synchronisation, the same bytes on every run.  The moments live in actor.adam_state (zeros before the
+        first step), the step count in actor.adam_step.  log_std=False leaves log_std alone (critics, the heads without one).
+        Returns the gradients' norm before clipping, a float64 device scalar."""
+        torch = _torch()
+        names = ("w0", "b0", "w1", "b1", "w2", "b2") + (("log_std",) if log_std else ())
+        ai, pr = _libmod.KActorAdamIn(lr=float(lr), beta1=float(betas[0]), beta2=float(betas[1]), eps=float(eps),
+                                      max_grad_norm=0.0 if max_grad_norm is None else float(max_grad_norm)), _libmod.KActorParams()
+        for nm in names:
+            p = getattr(actor, nm)
+            g = p.grad if grads is None else grads[nm]
+            self._check_buf(p, tuple(p.shape), torch.float32, nm)
+            self._check_buf(g, tuple(p.shape), torch.float32, "the gradient of " + nm)
+            setattr(ai, "g" + nm, g.data_ptr())
+            setattr(pr, nm, p.data_ptr())
+        if actor.adam_state is None:
+            actor.adam_state = torch.zeros((self.L.kmanip_actor_adam_state_floats(C.byref(actor.desc)),), dtype=torch.float32, device=self.device)
+            actor.adam_workspace = torch.empty((_libmod.KM_ACTOR_ADAM_WS_DOUBLES,), dtype=torch.float64, device=self.device)
+        ai.step = actor.adam_step + 1
+        gnorm = torch.empty((), dtype=torch.float64, device=self.device)
+        self._check(self.L.kmanip_actor_adam(self.h, C.byref(actor.desc), C.byref(ai), C.byref(pr), C.c_void_p(actor.adam_state.data_ptr()),
+                                             C.c_void_p(actor.packed.data_ptr()), C.c_void_p(actor.packed_t.data_ptr()),
+                                             C.c_void_p(actor.adam_workspace.data_ptr()), C.c_void_p(gnorm.data_ptr()), self._stream()),
+                    "kmanip_actor_adam")
+        actor.adam_step += 1
+        return gnorm
+
     def k_render(self, cam):
         """KManipEnvSim.k_render (env_sim.py:187-188): physics.render(cam.h, cam.w, camera_id=cam.name) -> uint8 RGB,
         for every env ([num_envs, h, w, 3], device tensor).  `cam` is a Cam (model.CAMERAS) or a camera name."""

@@ -20,7 +20,7 @@ _lib = None
 EXPORTS = [
     "kmanip_model_desc_size", "kmanip_create", "kmanip_reset", "kmanip_step", "kmanip_step_chunk", "kmanip_get_state",
     "kmanip_set_state", "kmanip_get_episode", "kmanip_set_episode", "kmanip_get_counters", "kmanip_bind_sim_time", "kmanip_bind_applied_force", "kmanip_bind_reward_done_record", "kmanip_select_reward_done_record", "kmanip_observe", "kmanip_forces", "kmanip_kinematics", "kmanip_inverse", "kmanip_forward", "kmanip_kinematics_rows", "kmanip_site_cost", "kmanip_rollout", "kmanip_feedback", "kmanip_feedback_box", "kmanip_transition_fd", "kmanip_forward_fd", "kmanip_param_fd", "kmanip_lqr_backward", "kmanip_lqr_backward_box", "kmanip_adjoint", "kmanip_tangent", "kmanip_set_seed", "kmanip_get_diag", "kmanip_timing_summary", "kmanip_enable_timing", "kmanip_ik", "kmanip_ik_eval",
-    "kmanip_render_depth", "kmanip_render_rgb", "kmanip_render_rgb_multi", "kmanip_render_labels_multi", "kmanip_render_seg", "kmanip_set_render_links", "kmanip_get_render_links", "kmanip_set_depth_links", "kmanip_get_depth_links", "kmanip_get_camera_poses", "kmanip_render_points", "kmanip_snapshot_render_state", "kmanip_set_render_source", "kmanip_bind_step_depth", "kmanip_scripted_action", "kmanip_sample_action", "kmanip_actor_packed_floats", "kmanip_actor_pack", "kmanip_actor", "kmanip_actor_grad_packed_floats", "kmanip_actor_grad_workspace_floats", "kmanip_actor_grad_pack", "kmanip_actor_grad", "kmanip_set_env_params", "kmanip_get_env_params", "kmanip_set_env_param_ranges", "kmanip_set_visual_params", "kmanip_get_visual_params", "kmanip_set_visual_param_ranges",
+    "kmanip_render_depth", "kmanip_render_rgb", "kmanip_render_rgb_multi", "kmanip_render_labels_multi", "kmanip_render_seg", "kmanip_set_render_links", "kmanip_get_render_links", "kmanip_set_depth_links", "kmanip_get_depth_links", "kmanip_get_camera_poses", "kmanip_render_points", "kmanip_snapshot_render_state", "kmanip_set_render_source", "kmanip_bind_step_depth", "kmanip_scripted_action", "kmanip_sample_action", "kmanip_actor_packed_floats", "kmanip_actor_pack", "kmanip_actor", "kmanip_actor_grad_packed_floats", "kmanip_actor_grad_workspace_floats", "kmanip_actor_grad_pack", "kmanip_actor_grad", "kmanip_gae_workspace_doubles", "kmanip_gae", "kmanip_actor_adam_state_floats", "kmanip_actor_adam", "kmanip_set_env_params", "kmanip_get_env_params", "kmanip_set_env_param_ranges", "kmanip_set_visual_params", "kmanip_get_visual_params", "kmanip_set_visual_param_ranges",
     "kmanip_get_state_dev", "kmanip_set_state_dev", "kmanip_copy_envs", "kmanip_state_index_errors", "kmanip_num_envs", "kmanip_last_error", "kmanip_version", "kmanip_destroy",
 ]
 
@@ -293,7 +293,45 @@ def actor_grad_workspace_floats(in_dim, hidden, out_dim, n):
     return 16 * (ti + 2 * t1 + 2 * t2 + 2) * np_ + splits * (256 * (t1 * ti + t2 * t1 + t2) + 16 * (t1 + t2 + 2))
 
 
-KM_TANGENT_MC = 16               # include/kmanip.h: H and g need m <= KM_TANGENT_MC
+class KGaeIn(C.Structure):
+    """include/kmanip.h KGaeIn: DEVICE pointers of a collect() buffer's reward, done, value (and the values truncated steps bootstrap
+    from, or NULL), the discount, GAE's lambda (the header's name, a Python keyword: set it with setattr) and whether adv is normalised."""
+    _fields_ = ([(nm, C.c_void_p) for nm in ("reward", "done", "value", "timeout_value")]
+                + [("gamma", C.c_double), ("lambda", C.c_double), ("normalize", C.c_int32)])
+
+
+class KGaeDev(C.Structure):
+    """include/kmanip.h KGaeDev: DEVICE pointers of kmanip_gae's outputs adv, ret [T, N] float32 and stats [2] float64 (or NULL)."""
+    _fields_ = [(nm, C.c_void_p) for nm in ("adv", "ret", "stats")]
+
+
+class KActorAdamIn(C.Structure):
+    """include/kmanip.h KActorAdamIn: DEVICE pointers of the seven gradient tensors (glog_std or NULL), Adam's constants, the norm the
+    gradients are clipped to (<= 0: none) and the step count from 1."""
+    _fields_ = ([(nm, C.c_void_p) for nm in ("gw0", "gb0", "gw1", "gb1", "gw2", "gb2", "glog_std")]
+                + [(nm, C.c_double) for nm in ("lr", "beta1", "beta2", "eps", "max_grad_norm")] + [("step", C.c_int32)])
+
+
+class KActorParams(C.Structure):
+    """include/kmanip.h KActorParams: DEVICE pointers of the parameter tensors kmanip_actor_adam updates in place (log_std or NULL)."""
+    _fields_ = [(nm, C.c_void_p) for nm in ("w0", "b0", "w1", "b1", "w2", "b2", "log_std")]
+
+
+KM_GAE_BLOCK, KM_GAE_CHUNK, KM_ACTOR_ADAM_WS_DOUBLES = 256, 8, 64      # include/kmanip.h
+
+
+def gae_workspace_doubles(n):
+    """include/kmanip.h kmanip_gae_workspace_doubles, restated: a pair of partial sums per block of KM_GAE_BLOCK envs."""
+    return 0 if n < 1 else 2 * -(-n // KM_GAE_BLOCK)
+
+
+def actor_adam_state_floats(in_dim, hidden, out_dim):
+    """include/kmanip.h kmanip_actor_adam_state_floats, restated: m and v of every parameter, log_std's slot included."""
+    dims = [in_dim, hidden[0], hidden[1], out_dim]
+    return 2 * (sum(o * (i + 1) for i, o in zip(dims, dims[1:])) + out_dim)
+
+
+KM_TANGENT_MC = 16              # include/kmanip.h: H and g need m <= KM_TANGENT_MC
 KM_WRT = {"qpos": 1, "qvel": 2, "ctrl": 4, "qfrc_applied": 8}     # include/kmanip.h KM_WRT_*: the columns always run in this order
 # include/kmanip.h KM_OF_*: the differentiated outputs of kmanip_forward_fd, always in this order
 KM_OF = {"qacc": 1, "qfrc_constraint": 2, "qfrc_actuator": 4, "contact_force": 8}
@@ -391,6 +429,12 @@ def load():
     lib.kmanip_actor_grad_workspace_floats.restype = C.c_size_t
     lib.kmanip_actor_grad_pack.argtypes = [vp, C.POINTER(KActorDesc), C.POINTER(KActorWeights), vp, vp]
     lib.kmanip_actor_grad.argtypes = [vp, C.POINTER(KActorDesc), vp, vp, C.POINTER(KActorGradIn), C.c_int, vp, C.POINTER(KActorGradDev), vp]
+    lib.kmanip_gae_workspace_doubles.argtypes = [C.c_int]
+    lib.kmanip_gae_workspace_doubles.restype = C.c_size_t
+    lib.kmanip_gae.argtypes = [vp, C.POINTER(KGaeIn), C.c_int, C.c_int, vp, C.POINTER(KGaeDev), vp]
+    lib.kmanip_actor_adam_state_floats.argtypes = [C.POINTER(KActorDesc)]
+    lib.kmanip_actor_adam_state_floats.restype = C.c_size_t
+    lib.kmanip_actor_adam.argtypes = [vp, C.POINTER(KActorDesc), C.POINTER(KActorAdamIn), C.POINTER(KActorParams), vp, vp, vp, vp, vp, vp]
     lib.kmanip_set_env_params.argtypes = [vp, vp, vp]
     lib.kmanip_get_env_params.argtypes = [vp, vp, vp]
     lib.kmanip_set_env_param_ranges.argtypes = [vp, f64p, f64p]

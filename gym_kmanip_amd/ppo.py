@@ -1,0 +1,62 @@
+"""PPO on the device: a small driver over the library's five training calls.  One iteration is a fixed sequence
+of launches on the current stream -- collect, gae, then per epoch and minibatch actor_grad (the clipped surrogate) + actor_adam for
+the policy and actor_grad (the squared error on the returns) + actor_adam for the critic -- with no torch arithmetic on the parameters
+and no host synchronisation: the same seeds give the same bytes.
+
+PPO          the driver: buffers allocated once, iterate() runs one iteration and returns device tensors
+
+Out of scope, as in include/kmanip.h: running observation statistics, an entropy bonus, value-loss clipping, per-minibatch advantage
+normalisation, learning-rate schedules (set .lr between iterations)."""
+
+
+class PPO:
+    def __init__(self, env, actor, critic, nsteps=16, epochs=4, minibatches=4, lr=3e-4, gamma=0.99, lam=0.95, clip=0.2, max_grad_norm=0.5,
+                 betas=(0.9, 0.999), eps=1e-8, seed=0):
+        """env: a KManipEnvHip; actor, critic: Actors mapping obs_dim to act_dim and to 1.  Each iteration collects nsteps steps of
+        every env and makes `epochs` passes over the nsteps * num_envs records in `minibatches` index lists each, drawn from a host
+        generator seeded with `seed` (a permutation per epoch)."""
+        import torch
+        self.env, self.actor, self.critic = env, actor, critic
+        self.nsteps, self.epochs, self.minibatches = int(nsteps), int(epochs), int(minibatches)
+        self.lr, self.gamma, self.lam, self.clip, self.max_grad_norm, self.betas, self.eps = lr, gamma, lam, clip, max_grad_norm, betas, eps
+        self.n = self.nsteps * env.num_envs
+        if not 1 <= self.minibatches <= self.n:
+            raise ValueError("PPO: between 1 and nsteps * num_envs minibatches")
+        self.gen = torch.Generator().manual_seed(int(seed))
+        self.idx = torch.empty((self.epochs, self.n), dtype=torch.int32, device=env.device)
+        self.buf = self.adv = None
+        self.grads = [{}, {}]                        # actor_grad's outputs by minibatch size, policy and critic: allocated once each
+        self.iterations = 0
+
+    def _step(self, which, net, obs, rows, **head):
+        env, n = self.env, int(rows.numel())
+        out = env.actor_grad(net, obs, idx=rows, out=self.grads[which].get(n), set_grad=False, **head)
+        self.grads[which][n] = out
+        env.actor_adam(net, self.lr, self.betas, self.eps, self.max_grad_norm, grads=out, log_std=which == 0)
+        return out["row_loss"].mean()
+
+    def iterate(self):
+        """One iteration.  Returns {"policy_loss", "value_loss": the mean row_loss of every update [epochs, minibatches], "reward": the
+        mean reward of the rollout, "adv_stats": kmanip_gae's mean and std}, all device tensors: nothing is read back here."""
+        import torch
+        env, T, n = self.env, self.nsteps, self.n
+        # the index lists: drawn on the host and uploaded before the first launch, from pinned memory of their own (torch keeps the block
+        # until the copy has run: the host never waits for it and never writes over it)
+        host = torch.stack([torch.randperm(n, generator=self.gen) for _ in range(self.epochs)]).to(torch.int32).pin_memory()
+        self.idx.copy_(host, non_blocking=True)
+        self.buf = env.collect(self.actor, T, critic=self.critic, out=self.buf)
+        self.adv = env.gae(self.buf, self.gamma, self.lam, normalize=True, out=self.adv)
+        obs = self.buf["obs"][:T].view(n, -1)
+        ppo = dict(raw=self.buf["raw"].view(n, -1), logp_old=self.buf["logp"].view(n), adv=self.adv["adv"].view(n), clip=self.clip)
+        ret = self.adv["ret"].view(n, 1)
+        cuts = [n * k // self.minibatches for k in range(self.minibatches + 1)]
+        losses = [[], []]
+        for e in range(self.epochs):
+            for lo, hi in zip(cuts, cuts[1:]):
+                rows = self.idx[e, lo:hi]
+                losses[0].append(self._step(0, self.actor, obs, rows, ppo=ppo))
+                losses[1].append(self._step(1, self.critic, obs, rows, target=ret))
+        self.iterations += 1
+        shape = (self.epochs, self.minibatches)
+        return {"policy_loss": torch.stack(losses[0]).view(shape), "value_loss": torch.stack(losses[1]).view(shape),
+                "reward": self.buf["reward"].mean(), "adv_stats": self.adv["stats"]}

@@ -1280,10 +1280,76 @@ KMANIP_API int kmanip_actor_grad_pack(KHandle h, const KActorDesc* desc, const K
  * the PPO head; a NULL gradient pointer (log_std's with the PPO head only); a NULL or not 16-byte aligned packed_dev, packed_t_dev or
  * workspace_dev (their sizes are the caller's to keep: the call cannot see them) return nonzero with kmanip_last_error set and launch
  * nothing.
- * OUT OF SCOPE: the gradient in obs, an entropy bonus (its log_std gradient is a constant the caller adds), GAE and advantage
- * normalisation, the optimiser step, other weight types, more than two hidden layers. */
+ * OUT OF SCOPE: the gradient in obs, an entropy bonus (its log_std gradient is a constant the caller adds), other weight types, more
+ * than two hidden layers.  (Advantages: kmanip_gae below; the optimiser step: kmanip_actor_adam.) */
 KMANIP_API int kmanip_actor_grad(KHandle h, const KActorDesc* desc, const float* packed_dev, const float* packed_t_dev, const KActorGradIn* in, int n,
                                  float* workspace_dev, const KActorGradDev* out, void* stream);
+
+/* ADVANTAGES AND RETURNS of a collect() buffer: generalised advantage estimation over T steps of N envs, time-major
+ * as the step kernels write reward and done.  A DONE STEP CUTS THE RECURSION: with auto_reset the step kernel resets a done env inside
+ * the same step and writes the NEW episode's first observation as obs[t + 1], so value[t + 1] after a done step belongs to another
+ * episode and is never read; the terminal observation of the old episode is not kept.  What a done step bootstraps from is therefore 0,
+ * or, for a step that is TRUNCATED and not DIVERGED, timeout_value[t][e] where the caller has one.  Per env e, in float64, no fused
+ * multiply-add, backward from A_T = 0:
+ *   d     = done[t][e] != 0
+ *   nv    = d ? ((done & KM_DONE_TRUNCATED) && !(done & KM_DONE_DIVERGED) && timeout_value ? timeout_value[t][e] : 0) : value[t + 1][e]
+ *   delta = (reward[t][e] + gamma nv) - value[t][e]
+ *   A_t   = d ? delta : delta + (gamma lambda) A_(t+1)
+ *   a_t   = float32(A_t);   ret[t][e] = float32(A_t + value[t][e])
+ * Without `normalize`, adv = a_t.  With it, adv = float32((double(a_t) - mean) / (std + 1e-8)), mean and std (population form) of all
+ * T N ROUNDED values a_t in float64: mean = S1 / (T N), std = sqrt(max(S2 / (T N) - mean^2, 0)) from the sums S1 of a and S2 of a^2,
+ * taken in a fixed order (per lane backward in time, then the lanes of a block, then the blocks ascending).  stats = {mean, std} of the
+ * unnormalised a_t either way.  ret is never normalised.  No atomics: the same call gives the same bytes. */
+typedef struct KGaeIn {            /* DEVICE pointers, time-major as collect() writes them */
+  const double*  reward;           /* [T, N] */
+  const uint8_t* done;             /* [T, N], KM_DONE_* bits */
+  const float*   value;            /* [T + 1, N] */
+  const float*   timeout_value;    /* [T, N] or NULL: what a TRUNCATED (and not DIVERGED) step bootstraps from; NULL = 0 */
+  double gamma, lambda;            /* each in [0, 1] */
+  int32_t normalize;               /* 0 / 1 */
+} KGaeIn;
+typedef struct KGaeDev { float* adv; float* ret; double* stats; } KGaeDev;   /* adv, ret [T, N]; stats [2] or NULL */
+/* The doubles of the workspace of a call over N envs: one pair of partial sums per block of KM_GAE_BLOCK envs.  0 for N < 1. */
+#define KM_GAE_BLOCK 256
+#define KM_GAE_CHUNK 8             /* the time steps whose loads are in flight before their dependent chain starts */
+KMANIP_API size_t kmanip_gae_workspace_doubles(int N);
+/* ONE launch, or TWO with normalize or stats (the recursion and the blocks' partial sums; their sum and the normalisation in place),
+ * asynchronous on `stream`: no allocation, no synchronisation.  The handle is not read beyond its error slot.
+ * ERRORS: a NULL handle, `in`, `out`, reward, done, value, adv, ret or workspace_dev; T < 1 or N < 1; gamma or lambda outside [0, 1] or
+ * not finite return nonzero with kmanip_last_error set and launch nothing.
+ * OUT OF SCOPE: a parallel scan over T, the terminal observation under auto_reset, per-minibatch normalisation. */
+KMANIP_API int kmanip_gae(KHandle h, const KGaeIn* in, int T, int N, double* workspace_dev, const KGaeDev* out, void* stream);
+
+/* THE OPTIMISER STEP of that network: gradient-norm clipping as torch's clip_grad_norm_, Adam as torch.optim.Adam
+ * (no weight decay, no amsgrad), and BOTH PACKED BUFFERS rewritten in the same pass: after the call packed_dev and packed_t_dev hold
+ * exactly the bytes kmanip_actor_pack and kmanip_actor_grad_pack would write from the updated tensors.  Per element, in float64, no fused
+ * multiply-add, each stored value rounded to float32 once:
+ *   norm = sqrt(sum g^2) over all tensors given;   c = max_grad_norm > 0 ? min(1, max_grad_norm / (norm + 1e-6)) : 1;   g' = c g
+ *   m = float32(beta1 m + (1 - beta1) g');   v = float32(beta2 v + (1 - beta2) g' g')          (products left to right)
+ *   p = float32(p - (lr / bc1) (m / (sqrt(v) / sqrt(bc2) + eps)))      with the ROUNDED m and v, bc1 = 1 - beta1^step, bc2 = 1 - beta2^step,
+ *                                                                      lr / bc1 and sqrt(bc2) computed on the host in double
+ * The sum of g^2 is taken in float64 in a fixed order (a function of desc and of glog_std's presence only); no atomics.
+ * state_dev: m and then v, each the seven tensors row-major, concatenated in the order w0, b0, w1, b1, w2, b2, log_std (log_std's slot
+ * is there whether or not it is updated); the caller zeroes it once, before step 1. */
+typedef struct KActorAdamIn {
+  const float *gw0, *gb0, *gw1, *gb1, *gw2, *gb2, *glog_std;   /* the shapes kmanip_actor_grad writes; glog_std may be NULL */
+  double lr, beta1, beta2, eps, max_grad_norm;                 /* max_grad_norm <= 0: no clipping */
+  int32_t step;                                                /* >= 1: the bias corrections' exponent */
+} KActorAdamIn;
+typedef struct KActorParams { float *w0, *b0, *w1, *b1, *w2, *b2, *log_std; } KActorParams;   /* updated IN PLACE; log_std NULL iff glog_std is */
+#define KM_ACTOR_ADAM_WS_DOUBLES 64   /* the doubles of workspace_dev: at most this many partial sums of the norm */
+/* 2 * (the network's parameter count + out_dim) floats of state_dev; 0 for a description kmanip_actor would refuse. */
+KMANIP_API size_t kmanip_actor_adam_state_floats(const KActorDesc* desc);
+/* TWO launches (the norm's partial sums; the update), or ONE when max_grad_norm <= 0 and gnorm_dev is NULL, asynchronous on `stream`:
+ * no allocation, no synchronisation.  gnorm_dev: NULL, or one double that receives norm.  The zero blocks that pad a layer of
+ * packed_dev / packed_t_dev to KM_ACTOR_KGROUP and packed_t_dev's zero biases are NOT written: both buffers must have been packed once.
+ * ERRORS: a NULL handle, desc, `in` or params; a desc kmanip_actor would refuse; a NULL gradient or parameter pointer (glog_std and
+ * params->log_std both NULL or both set); step < 1; lr, beta1, beta2, eps or max_grad_norm not finite, a beta outside [0, 1), eps <= 0;
+ * a NULL or not 16-byte aligned state_dev, packed_dev or packed_t_dev; a NULL workspace_dev where the norm is taken return nonzero with
+ * kmanip_last_error set and launch nothing.
+ * OUT OF SCOPE: weight decay, other optimisers, learning-rate schedules (pass lr per call). */
+KMANIP_API int kmanip_actor_adam(KHandle h, const KActorDesc* desc, const KActorAdamIn* in, const KActorParams* params, float* state_dev,
+                                 float* packed_dev, float* packed_t_dev, double* workspace_dev, double* gnorm_dev, void* stream);
 
 /* Per-env physics parameters (domain randomisation).  Storage is double[KM_EP_N][num_envs], struct-of-arrays
  * like the state: element (k, env) at k * num_envs + env.  Env e with parameters p behaves exactly like a handle whose KModelDesc is
