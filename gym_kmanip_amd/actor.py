@@ -8,6 +8,9 @@ torch float64: the definition.  `KManipEnvHip.actor_grad` writes the loss gradie
 section 46) from the transposed packed copy repack() also keeps; `loss_reference` is that loss in torch float64 under autograd.
 `KManipEnvHip.actor_adam` (kmanip_actor_adam) is the optimiser step on these tensors: it keeps its moments in
 `adam_state` and its step count in `adam_step`, and rewrites both packed copies itself -- no repack() after it.
+`repack_bf16()` keeps a third copy, `packed_bf16`: the weights rounded to bf16 for kmanip_actor_bf16, which
+`actor_eval` and `collect` run with precision="bf16".  Neither repack() nor actor_adam touches it: whoever changes the parameters calls
+repack_bf16() before the next bf16 evaluation (PPO with collect_precision="bf16" does, once per iteration).
 """
 from __future__ import annotations
 
@@ -16,6 +19,14 @@ import ctypes as C
 from . import lib as _libmod
 
 _NAMES = ("w0", "b0", "w1", "b1", "w2", "b2")
+
+
+def round_bf16(t):
+    """A float64 tensor rounded to the nearest bf16, ties to even, in ONE rounding (through float32 it would be two): the value keeps
+    its 8 leading significand bits.  Exact for zeros and for every magnitude in bf16's normal range."""
+    import torch
+    bits = t.contiguous().view(torch.int64)
+    return ((bits + ((1 << 44) - 1) + ((bits >> 45) & 1)) & ~((1 << 45) - 1)).view(torch.float64)
 
 
 class Actor:
@@ -47,6 +58,7 @@ class Actor:
         self.obs_mean = self.obs_inv_std = None
         self.packed = torch.empty((floats,), dtype=torch.float32, device=env.device)
         self.packed_t = torch.empty((env.L.kmanip_actor_grad_packed_floats(C.byref(self.desc)),), dtype=torch.float32, device=env.device)
+        self.packed_bf16 = None                      # kmanip_actor_bf16's buffer: repack_bf16() allocates and fills it
         self.grad_workspace = {}                     # n -> kmanip_actor_grad's workspace (KManipEnvHip.actor_grad)
         self.adam_state, self.adam_step = None, 0    # kmanip_actor_adam's moments and step count (KManipEnvHip.actor_adam)
         self.repack()
@@ -77,16 +89,32 @@ class Actor:
         second holds W2^T and W1^T for the backward), on the current stream."""
         import torch
         e, dims = self.env, (self.in_dim,) + self.hidden + (self.out_dim,)
-        wt = _libmod.KActorWeights()
         for l in range(3):
             e._check_buf(getattr(self, "w%d" % l), (dims[l + 1], dims[l]), torch.float32, "w%d" % l)
             e._check_buf(getattr(self, "b%d" % l), (dims[l + 1],), torch.float32, "b%d" % l)
-        for nm in _NAMES:
-            setattr(wt, nm, getattr(self, nm).data_ptr())
+        wt = self._weights()
         e._check(e.L.kmanip_actor_pack(e.h, C.byref(self.desc), C.byref(wt), C.c_void_p(self.packed.data_ptr()), e._stream()),
                  "kmanip_actor_pack")
         e._check(e.L.kmanip_actor_grad_pack(e.h, C.byref(self.desc), C.byref(wt), C.c_void_p(self.packed_t.data_ptr()), e._stream()),
                  "kmanip_actor_grad_pack")
+
+    def _weights(self):
+        wt = _libmod.KActorWeights()
+        for nm in _NAMES:
+            setattr(wt, nm, getattr(self, nm).data_ptr())
+        return wt
+
+    def repack_bf16(self):
+        """kmanip_actor_bf16_pack: the parameter tensors as they are now, rounded to bf16 (nearest-even), into `packed_bf16` (allocated on
+        first use), on the current stream.  repack() and KManipEnvHip.actor_adam do not refresh this copy: call this after the
+        parameters change and before the next evaluation with precision="bf16"."""
+        import torch
+        e = self.env
+        if self.packed_bf16 is None:
+            self.packed_bf16 = torch.empty((e.L.kmanip_actor_bf16_packed_bytes(C.byref(self.desc)),), dtype=torch.uint8, device=e.device)
+        wt = self._weights()
+        e._check(e.L.kmanip_actor_bf16_pack(e.h, C.byref(self.desc), C.byref(wt), C.c_void_p(self.packed_bf16.data_ptr()), e._stream()),
+                 "kmanip_actor_bf16_pack")
 
     def torch_eval(self, obs):
         """The policy as a torch float32 program on the same parameters -- cast, normalise, three matmuls, sample from torch's global
@@ -105,9 +133,11 @@ class Actor:
         raw = mean + self.log_std.exp() * z
         return raw.clamp(-1.0, 1.0), raw, (-0.5 * z * z - self.log_std - 0.5 * math.log(2.0 * math.pi)).sum(-1)
 
-    def reference(self, obs, noise=None):
+    def reference(self, obs, noise=None, precision="f32"):
         """The same network in torch float64: float32 weights widened, the normalised input rounded to float32 as the kernel rounds
-        it.  Returns {"mean"}; with `noise` [n, out_dim] (the kernel's, or model.draw_policy_noise's) also raw, act and logp by
+        it.  precision="bf16" is kmanip_actor_bf16's definition: the same float64 program with the weights, that float32 input and each
+        hidden layer's output rounded to bf16 (nearest-even) before the next product; biases and the last layer's output are not
+        rounded.  Returns {"mean"}; with `noise` [n, out_dim] (the kernel's, or model.draw_policy_noise's) also raw, act and logp by
         include/kmanip.h's definition (raw and act in float32, logp in float64)."""
         import math
         import torch
@@ -116,12 +146,15 @@ class Actor:
             x = x - self.obs_mean
         if self.obs_inv_std is not None:
             x = x * self.obs_inv_std
-        x = x.to(torch.float32).to(torch.float64)
+        if precision not in ("f32", "bf16"):
+            raise ValueError("reference: precision is 'f32' or 'bf16'")
+        q = round_bf16 if precision == "bf16" else (lambda v: v)
+        x = q(x.to(torch.float32).to(torch.float64))
         f = torch.tanh if self.activation == "tanh" else torch.relu
         w = [getattr(self, nm).to(torch.float64) for nm in _NAMES]
-        h = f(x @ w[0].T + w[1])
-        h = f(h @ w[2].T + w[3])
-        out = {"mean": h @ w[4].T + w[5]}
+        h = q(f(x @ q(w[0]).T + w[1]))
+        h = q(f(h @ q(w[2]).T + w[3]))
+        out = {"mean": h @ q(w[4]).T + w[5]}
         if noise is not None:
             z = noise.to(torch.float32)
             sd = self.log_std.to(torch.float64).exp().to(torch.float32)

@@ -22,7 +22,7 @@
 // layer, two layers live).  Every tile loop is fully unrolled -- the accumulators are registers, never indexed at run time -- and
 // guarded by wave-uniform tests against the layer's real tile counts.
 // A row's results depend on that row's env and inputs only: a column of the product never meets another column.
-#include "kmanip_actor_layer.hpp"   // f4, actor_activate, actor_layer: shared with k_actor_bwd
+#include "kmanip_actor_head.hpp"    // actor_row, actor_obs, actor_head: shared with k_actor_bf16; f4, actor_layer: with k_actor_bwd
 
 KActorPlan kmanip_actor_plan(const KActorDesc& d) {
   KActorPlan p;
@@ -77,93 +77,22 @@ __global__ __launch_bounds__(64) void k_actor(KDeviceState st, KActorDesc d, KAc
                                               KActorDev out) {
   static_assert(NT >= 4, "the first layer reads up to 64 inputs: four tiles");
   const f4* pk = (const f4*)packed;
-  const int lane = threadIdx.x, g = lane >> 4, row = blockIdx.x * 16 + (lane & 15);
-  const int id = d.in_dim, od = d.out_dim;
-  // ---- the row's env: an index outside the handle is status 2 and never an address
-  const bool live = row < n;
-  int env = 0, status = 0;
-  if (live) {
-    env = in.envs ? in.envs[row] : row;
-    if (env < 0 || env >= st.num_envs) status = 2;
-  }
-  const bool ok = live && status == 0;
+  const int lane = threadIdx.x, g = lane >> 4;
+  const int id = d.in_dim;
+  const ActorRow rw = actor_row(st, in, n, lane);                    // the row's env: kmanip_actor_head.hpp
   // ---- the first layer's B operand: obs[row][16 t + 4 g + 0..3], normalised in float64, cast once
   f4 x[4];
 #pragma unroll
   for (int t = 0; t < 4; t++) {
-    x[t] = f4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-    for (int c = 0; c < 4; c++) {
-      const int k = 16 * t + 4 * g + c;
-      if (ok && k < id) {
-        double v = in.obs[(size_t)row * id + k];
-        if (in.obs_mean) v = v - in.obs_mean[k];
-        if (in.obs_inv_std) v = v * in.obs_inv_std[k];
-        x[t][c] = (float)v;
-      }
-    }
+    for (int c = 0; c < 4; c++) x[t][c] = actor_obs(in, rw, id, 16 * t + 4 * g + c);
   }
   f4 h1[NT], h2[NT], y[1];
   actor_layer<4, NT, true>(pk, p.w4[0], p.b4[0], p.kb[0], p.ot[0], d.activation, x, h1, lane);
   actor_layer<NT, NT, true>(pk, p.w4[1], p.b4[1], p.kb[1], p.ot[1], d.activation, h1, h2, lane);
   actor_layer<NT, 1, false>(pk, p.w4[2], p.b4[2], p.kb[2], 1, d.activation, h2, y, lane);
-  // ---- lane (g, n): outputs 4 g .. 4 g + 3 of its row
-  const f4 mean = ok ? y[0] : f4{0.f, 0.f, 0.f, 0.f};
-  if (live && out.mean) {
-#pragma unroll
-    for (int c = 0; c < 4; c++)
-      if (4 * g + c < od) out.mean[(size_t)row * od + 4 * g + c] = mean[c];
-  }
-  if (live && g == 0 && out.status) out.status[row] = status;
-  if (!in.log_std) return;                                           // (wave-uniform: every lane reaches the shuffles below or none)
-  // ---- the Gaussian head
-  {
-#pragma clang fp contract(off)
-    f4 z = {0.f, 0.f, 0.f, 0.f}, raw = z, act = z;
-    double lp = 0.0;
-    if (ok) {
-      const int64_t genv = st.env_id_offset + env;
-      const uint32_t key[2] = {(uint32_t)st.seed, (uint32_t)(st.seed >> 32)};
-      const uint32_t ctr[4] = {(uint32_t)genv, (uint32_t)((uint64_t)genv >> 32), (uint32_t)st.episode[env], KM_POL_CTR3(st.step_idx[env], g)};
-      uint32_t o[4];
-      philox4x32_10(ctr, key, o);
-#pragma unroll
-      for (int b = 0; b < 2; b++) {                                  // Box-Muller in float64 on words (0, 1), then (2, 3)
-        const double u1 = ((double)(o[2 * b] >> 8) + 0.5) * (1.0 / 16777216.0), u2 = ((double)(o[2 * b + 1] >> 8) + 0.5) * (1.0 / 16777216.0);
-        const double rho = sqrt(-2.0 * log(u1)), ang = 6.283185307179586 * u2;
-        z[2 * b] = (float)(rho * cos(ang));
-        z[2 * b + 1] = (float)(rho * sin(ang));
-      }
-#pragma unroll
-      for (int c = 0; c < 4; c++) {
-        const int j = 4 * g + c;
-        if (j < od) {
-          const float ls = in.log_std[j];
-          const float sd = (float)exp((double)ls);                   // exp in float64, rounded once: the same float32 on every host
-          const float pr = sd * z[c];
-          raw[c] = mean[c] + pr;
-          act[c] = fminf(fmaxf(raw[c], -1.f), 1.f);
-          const double zd = (double)z[c];
-          lp = lp + (((-0.5 * (zd * zd)) - (double)ls) - 0.9189385332046727);
-        } else z[c] = 0.f;
-      }
-    }
-    // the four lane groups of a row, a fixed order: (g ^ 1) first, then (g ^ 2); every lane ends with the same bits
-    lp = lp + __shfl_xor(lp, 16, 64);
-    lp = lp + __shfl_xor(lp, 32, 64);
-    if (!live) return;
-#pragma unroll
-    for (int c = 0; c < 4; c++) {
-      const int j = 4 * g + c;
-      if (j < od) {
-        const size_t at = (size_t)row * od + j;
-        if (out.noise) out.noise[at] = z[c];
-        if (out.raw) out.raw[at] = raw[c];
-        if (out.act) out.act[at] = act[c];
-      }
-    }
-    if (g == 0 && out.logp) out.logp[row] = lp;
-  }
+  // ---- lane (g, n): outputs 4 g .. 4 g + 3 of its row: the mean, the status and the Gaussian head
+  actor_head(st, in, out, d.out_dim, rw, g, y[0]);
 }
 
 void kmanip_launch_actor(const KDeviceState& st, const KActorDesc& d, const float* packed, const KActorIn& in, int n, const KActorDev& out,

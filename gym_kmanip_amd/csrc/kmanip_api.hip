@@ -1197,6 +1197,38 @@ int kmanip_actor(KHandle h, const KActorDesc* desc, const float* packed_dev, con
   return 0;
 }
 
+// ---- the same network on the bf16 matrix cores (include/kmanip.h kmanip_actor_bf16; kmanip_actor_bfloat.hip)
+size_t kmanip_actor_bf16_packed_bytes(const KActorDesc* desc) { return actor_desc_error(desc) ? 0 : 16 * (size_t)kmanip_actor_bf16_plan(*desc).total16; }
+
+int kmanip_actor_bf16_pack(KHandle h, const KActorDesc* desc, const KActorWeights* weights, void* packed_dev, void* stream) {
+  if (!h) { g_create_error = "kmanip_actor_bf16_pack: null handle"; return -1; }
+  auto refuse = [&](const char* what) { h->err = std::string("kmanip_actor_bf16_pack: ") + what; return -1; };
+  if (const char* e = actor_desc_error(desc)) return refuse(e);
+  if (!weights || !weights->w0 || !weights->b0 || !weights->w1 || !weights->b1 || !weights->w2 || !weights->b2) return refuse("a weight or bias pointer is NULL");
+  if (!packed_dev || ((uintptr_t)packed_dev & 15)) return refuse("packed_dev is NULL or not 16-byte aligned");
+  KM_ENTER(h);
+  kmanip_launch_actor_bf16_pack(*desc, *weights, packed_dev, (hipStream_t)stream);
+  HIPCHK(h, hipGetLastError());
+  return 0;
+}
+
+int kmanip_actor_bf16(KHandle h, const KActorDesc* desc, const void* packed_dev, const KActorIn* in, int n, const KActorDev* out, void* stream) {
+  if (!h) { g_create_error = "kmanip_actor_bf16: null handle"; return -1; }
+  auto refuse = [&](const char* what) { h->err = std::string("kmanip_actor_bf16: ") + what; return -1; };
+  if (const char* e = actor_desc_error(desc)) return refuse(e);
+  if (!in) return refuse("the KActorIn pointer is NULL");
+  if (!out) return refuse("the KActorDev pointer is NULL");
+  if (n < 0) return refuse("n is negative");
+  if (!in->envs && n > h->st.num_envs) return refuse("more rows than envs need KActorIn::envs");
+  if (!in->obs) return refuse("KActorIn::obs is NULL");
+  if (!packed_dev || ((uintptr_t)packed_dev & 15)) return refuse("packed_dev is NULL or not 16-byte aligned");
+  if (n == 0) return 0;
+  KM_ENTER(h);
+  kmanip_launch_actor_bf16(h->st, *desc, packed_dev, *in, n, *out, (hipStream_t)stream);
+  HIPCHK(h, hipGetLastError());
+  return 0;
+}
+
 // ---- its loss gradients (include/kmanip.h KActorGradIn ...; kmanip_actor_grad.hip)
 size_t kmanip_actor_grad_packed_floats(const KActorDesc* desc) { return actor_desc_error(desc) ? 0 : 4 * (size_t)kmanip_actor_grad_plan(*desc, 0).t.total4; }
 

@@ -692,6 +692,15 @@ KActorPlan kmanip_actor_plan(const KActorDesc& d);
 void kmanip_launch_actor_pack(const KActorDesc& d, const KActorWeights& w, float* packed, hipStream_t stream);
 void kmanip_launch_actor(const KDeviceState& st, const KActorDesc& d, const float* packed, const KActorIn& in, int n, const KActorDev& out,
                          hipStream_t stream);
+// kmanip_actor_bf16 / kmanip_actor_bf16_pack (kmanip_actor_bfloat.hip): the same network in a bf16 packed buffer, addressed in 16-byte
+// entries -- per layer the real sizes, the K-steps of 32 inputs (padded to KM_ACTOR_BF16_KGROUP) and output tiles, the offsets of its
+// weight blocks (64 entries of eight bf16 each) and of its float32 bias -- and the launches: three pack launches; one k_actor_bf16
+// launch over n > 0 rows
+struct KActorBf16Plan { int in[3], out[3], ks[3], ot[3], w16[3], b16[3], total16; };
+KActorBf16Plan kmanip_actor_bf16_plan(const KActorDesc& d);
+void kmanip_launch_actor_bf16_pack(const KActorDesc& d, const KActorWeights& w, void* packed, hipStream_t stream);
+void kmanip_launch_actor_bf16(const KDeviceState& st, const KActorDesc& d, const void* packed, const KActorIn& in, int n, const KActorDev& out,
+                              hipStream_t stream);
 // kmanip_actor_grad / kmanip_actor_grad_pack (kmanip_actor_grad.hip): `t` lays out the transposed buffer (layers 0 and 1 of the network
 // out_dim -> hidden[1] -> hidden[0]: W2^T, W1^T; total4 ends there); np the rows padded to 16, `splits` K-splits of `len` rows; off[]
 // the unit-major workspace arrays x h1 h2 dz1 dz2 dz3 and the log_std terms; per work-item layer l (0..2: dW_l, db_l; 3: the log_std

@@ -1344,21 +1344,29 @@ class KManipEnvHip:
     _ACTOR_FIELDS = {"mean": (("od",), "float32"), "act": (("od",), "float32"), "raw": (("od",), "float32"), "noise": (("od",), "float32"),
                      "logp": (None, "float64"), "status": (None, "int32")}
 
-    def _actor_launch(self, actor, obs_ptr, envs_ptr, n, head, dev):
-        """One kmanip_actor call on the current stream: raw pointers, checked by the caller."""
+    def _actor_launch(self, actor, obs_ptr, envs_ptr, n, head, dev, precision="f32"):
+        """One kmanip_actor (precision "f32") or kmanip_actor_bf16 ("bf16") call on the current stream: raw pointers, checked by the caller."""
         ai = _libmod.KActorIn(envs_ptr, obs_ptr, None if actor.obs_mean is None else actor.obs_mean.data_ptr(),
                               None if actor.obs_inv_std is None else actor.obs_inv_std.data_ptr(), actor.log_std.data_ptr() if head else None)
+        if precision == "bf16":
+            self._check(self.L.kmanip_actor_bf16(self.h, C.byref(actor.desc), C.c_void_p(actor.packed_bf16.data_ptr()), C.byref(ai), n,
+                                                 C.byref(dev), self._stream()), "kmanip_actor_bf16")
+            return
         self._check(self.L.kmanip_actor(self.h, C.byref(actor.desc), C.c_void_p(actor.packed.data_ptr()), C.byref(ai), n, C.byref(dev),
                                         self._stream()), "kmanip_actor")
 
-    def _actor_check(self, actor):
+    def _actor_check(self, actor, precision="f32"):
         torch = _torch()
+        if precision not in ("f32", "bf16"):
+            raise ValueError("precision is 'f32' or 'bf16'")
+        if precision == "bf16" and actor.packed_bf16 is None:
+            actor.repack_bf16()
         for name in ("obs_mean", "obs_inv_std"):
             if getattr(actor, name) is not None:
                 self._check_buf(getattr(actor, name), (actor.in_dim,), torch.float64, name)
         self._check_buf(actor.log_std, (actor.out_dim,), torch.float32, "log_std")
 
-    def actor_eval(self, actor, obs, envs=None, deterministic=False, out=None, fields=None):
+    def actor_eval(self, actor, obs, envs=None, deterministic=False, out=None, fields=None, precision="f32"):
         """kmanip_actor: the MLP policy `actor` (gym_kmanip_amd.actor.Actor) at rows the caller passes -- one launch on the current
         stream, no synchronisation; the handle is only read.  obs: float64 [n, actor.in_dim], row r the observation of env envs[r]
         (an int32 device tensor or anything torch.as_tensor takes, repeats allowed, more rows than envs allowed; None = row r is
@@ -1366,27 +1374,30 @@ class KManipEnvHip:
         handle, the row's other outputs 0) and, unless `deterministic`, the Gaussian head's act = clamp(raw, -1, 1), raw = mean +
         exp(log_std) noise, noise [n, out_dim] float32 and logp [n] float64 (include/kmanip.h has the definition).  The noise is a
         function of (seed, env, the env's episode and step counters): the same call repeated gives the same bytes, a step moves
-        it on.  `fields`: the names wanted (default: all); `out`: a dict of such tensors to fill, returned as given."""
+        it on.  `fields`: the names wanted (default: all); `out`: a dict of such tensors to fill, returned as given.
+        precision="bf16" is kmanip_actor_bf16 on actor.packed_bf16 (filled on first use; after the parameters change the caller runs
+        actor.repack_bf16()): the mean of the bf16 network, the same noise and logp, raw and act on that mean."""
         torch = _torch()
         idx, ip, n = self._env_index(envs)
         if n is None:
             n = int(obs.shape[0]) if isinstance(obs, torch.Tensor) and obs.dim() else -1
         self._check_buf(obs, (n, actor.in_dim), torch.float64, "obs")
-        self._actor_check(actor)
+        self._actor_check(actor, precision)
         table = {k: v for k, v in self._ACTOR_FIELDS.items() if not deterministic or k in ("mean", "status")}
         dev = _libmod.KActorDev()
         out = self._query_out(table, (n,), {"od": actor.out_dim}, out, fields, dev, "actor")
-        self._actor_launch(actor, obs.data_ptr(), None if idx is None else idx.data_ptr(), n, not deterministic, dev)
+        self._actor_launch(actor, obs.data_ptr(), None if idx is None else idx.data_ptr(), n, not deterministic, dev, precision)
         return out
 
-    def collect(self, actor, nsteps, critic=None, obs0=None, out=None):
+    def collect(self, actor, nsteps, critic=None, obs0=None, out=None, precision="f32"):
         """The on-policy rollout buffer: for t = 0 .. nsteps-1, kmanip_actor on obs[t] (every env, stochastic), the critic's mean on
         obs[t] where one is given (an Actor with out_dim 1), then kmanip_step with act[t] writing obs[t + 1], reward[t], done[t];
         after the last step the critic on obs[nsteps].  All launches go onto the current stream with no host synchronisation and no
         torch operation in between: exactly the loop actor_eval + step_flat written by hand.  obs[0] is `obs0` (float64
         [num_envs, obs_dim]) or, for None, observe()'s of the current state.  Returns a dict of device tensors, T = nsteps:
         obs [T + 1, N, obs_dim] float64, act, raw [T, N, act_dim] float32, logp [T, N] float64, reward [T, N] float64, done [T, N]
-        uint8 and, with a critic, value [T + 1, N] float32.  `out`: such a dict to fill, returned as given."""
+        uint8 and, with a critic, value [T + 1, N] float32.  `out`: such a dict to fill, returned as given.  precision="bf16" runs
+        the ACTOR as actor_eval(precision="bf16") does (logp is then the bf16 policy's density); the critic stays float32."""
         torch = _torch()
         T, N, f32, f64 = int(nsteps), self.num_envs, torch.float32, torch.float64
         if actor.in_dim != self.cm.obs_dim or actor.out_dim != self.cm.act_dim:
@@ -1403,8 +1414,9 @@ class KManipEnvHip:
             raise ValueError("collect: out must hold exactly %s" % sorted(shapes))
         for k, (s, dt) in shapes.items():
             self._check_buf(out[k], s, dt, k)
-        for a in (actor,) if critic is None else (actor, critic):
-            self._actor_check(a)
+        self._actor_check(actor, precision)
+        if critic is not None:
+            self._actor_check(critic)
         if obs0 is None:
             self.observe(out["obs"][0], torch.empty((N,), dtype=f64, device=self.device))
         else:
@@ -1414,7 +1426,8 @@ class KManipEnvHip:
         stream = self._stream()
         for t in range(T + 1):
             if t < T:
-                self._actor_launch(actor, at("obs", t), None, N, True, _libmod.KActorDev(act=at("act", t), raw=at("raw", t), logp=at("logp", t)))
+                self._actor_launch(actor, at("obs", t), None, N, True, _libmod.KActorDev(act=at("act", t), raw=at("raw", t), logp=at("logp", t)),
+                                   precision)
             if critic is not None:
                 self._actor_launch(critic, at("obs", t), None, N, False, _libmod.KActorDev(mean=at("value", t)))
             if t == T:

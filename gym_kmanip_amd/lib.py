@@ -20,7 +20,7 @@ _lib = None
 EXPORTS = [
     "kmanip_model_desc_size", "kmanip_create", "kmanip_reset", "kmanip_step", "kmanip_step_chunk", "kmanip_get_state",
     "kmanip_set_state", "kmanip_get_episode", "kmanip_set_episode", "kmanip_get_counters", "kmanip_bind_sim_time", "kmanip_bind_applied_force", "kmanip_bind_reward_done_record", "kmanip_select_reward_done_record", "kmanip_observe", "kmanip_forces", "kmanip_kinematics", "kmanip_inverse", "kmanip_forward", "kmanip_kinematics_rows", "kmanip_site_cost", "kmanip_rollout", "kmanip_feedback", "kmanip_feedback_box", "kmanip_transition_fd", "kmanip_forward_fd", "kmanip_param_fd", "kmanip_lqr_backward", "kmanip_lqr_backward_box", "kmanip_adjoint", "kmanip_tangent", "kmanip_set_seed", "kmanip_get_diag", "kmanip_timing_summary", "kmanip_enable_timing", "kmanip_ik", "kmanip_ik_eval",
-    "kmanip_render_depth", "kmanip_render_rgb", "kmanip_render_rgb_multi", "kmanip_render_labels_multi", "kmanip_render_seg", "kmanip_set_render_links", "kmanip_get_render_links", "kmanip_set_depth_links", "kmanip_get_depth_links", "kmanip_get_camera_poses", "kmanip_render_points", "kmanip_snapshot_render_state", "kmanip_set_render_source", "kmanip_bind_step_depth", "kmanip_scripted_action", "kmanip_sample_action", "kmanip_actor_packed_floats", "kmanip_actor_pack", "kmanip_actor", "kmanip_actor_grad_packed_floats", "kmanip_actor_grad_workspace_floats", "kmanip_actor_grad_pack", "kmanip_actor_grad", "kmanip_gae_workspace_doubles", "kmanip_gae", "kmanip_actor_adam_state_floats", "kmanip_actor_adam", "kmanip_set_env_params", "kmanip_get_env_params", "kmanip_set_env_param_ranges", "kmanip_set_visual_params", "kmanip_get_visual_params", "kmanip_set_visual_param_ranges",
+    "kmanip_render_depth", "kmanip_render_rgb", "kmanip_render_rgb_multi", "kmanip_render_labels_multi", "kmanip_render_seg", "kmanip_set_render_links", "kmanip_get_render_links", "kmanip_set_depth_links", "kmanip_get_depth_links", "kmanip_get_camera_poses", "kmanip_render_points", "kmanip_snapshot_render_state", "kmanip_set_render_source", "kmanip_bind_step_depth", "kmanip_scripted_action", "kmanip_sample_action", "kmanip_actor_packed_floats", "kmanip_actor_pack", "kmanip_actor", "kmanip_actor_bf16_packed_bytes", "kmanip_actor_bf16_pack", "kmanip_actor_bf16", "kmanip_actor_grad_packed_floats", "kmanip_actor_grad_workspace_floats", "kmanip_actor_grad_pack", "kmanip_actor_grad", "kmanip_gae_workspace_doubles", "kmanip_gae", "kmanip_actor_adam_state_floats", "kmanip_actor_adam", "kmanip_set_env_params", "kmanip_get_env_params", "kmanip_set_env_param_ranges", "kmanip_set_visual_params", "kmanip_get_visual_params", "kmanip_set_visual_param_ranges",
     "kmanip_get_state_dev", "kmanip_set_state_dev", "kmanip_copy_envs", "kmanip_state_index_errors", "kmanip_num_envs", "kmanip_last_error", "kmanip_version", "kmanip_destroy",
 ]
 
@@ -254,6 +254,17 @@ def actor_packed_floats(in_dim, hidden, out_dim):
     return sum(tiles(o) * (-(-tiles(i) // KM_ACTOR_KGROUP) * KM_ACTOR_KGROUP) * 256 + tiles(o) * 16 for i, o in zip(dims, dims[1:]))
 
 
+KM_ACTOR_BF16_KGROUP = 2      # include/kmanip.h
+
+
+def actor_bf16_packed_bytes(in_dim, hidden, out_dim):
+    """include/kmanip.h kmanip_actor_bf16_packed_bytes, restated: per layer (out tiles of 16) x (K-steps of 32, padded to a multiple of
+    KM_ACTOR_BF16_KGROUP: 2 ceil(in / 64)) blocks of 64 entries of 16 bytes, then the float32 bias padded to whole tiles."""
+    dims = (in_dim,) + tuple(hidden) + (out_dim,)
+    steps = lambda i: -(-(-(-i // 32)) // KM_ACTOR_BF16_KGROUP) * KM_ACTOR_BF16_KGROUP
+    return sum(-(-o // 16) * steps(i) * 1024 + -(-o // 16) * 64 for i, o in zip(dims, dims[1:]))
+
+
 class KActorGradIn(C.Structure):
     """include/kmanip.h KActorGradIn: the head (KM_AGRAD), the record count, DEVICE pointers of kmanip_actor_grad's inputs (those the
     head does not read may be NULL), PPO's clip and the factor on every row's loss."""
@@ -423,6 +434,10 @@ def load():
     lib.kmanip_actor_packed_floats.restype = C.c_size_t
     lib.kmanip_actor_pack.argtypes = [vp, C.POINTER(KActorDesc), C.POINTER(KActorWeights), vp, vp]
     lib.kmanip_actor.argtypes = [vp, C.POINTER(KActorDesc), vp, C.POINTER(KActorIn), C.c_int, C.POINTER(KActorDev), vp]
+    lib.kmanip_actor_bf16_packed_bytes.argtypes = [C.POINTER(KActorDesc)]
+    lib.kmanip_actor_bf16_packed_bytes.restype = C.c_size_t
+    lib.kmanip_actor_bf16_pack.argtypes = [vp, C.POINTER(KActorDesc), C.POINTER(KActorWeights), vp, vp]
+    lib.kmanip_actor_bf16.argtypes = [vp, C.POINTER(KActorDesc), vp, C.POINTER(KActorIn), C.c_int, C.POINTER(KActorDev), vp]
     lib.kmanip_actor_grad_packed_floats.argtypes = [C.POINTER(KActorDesc)]
     lib.kmanip_actor_grad_packed_floats.restype = C.c_size_t
     lib.kmanip_actor_grad_workspace_floats.argtypes = [C.POINTER(KActorDesc), C.c_int]

@@ -11,13 +11,18 @@ normalisation, learning-rate schedules (set .lr between iterations)."""
 
 class PPO:
     def __init__(self, env, actor, critic, nsteps=16, epochs=4, minibatches=4, lr=3e-4, gamma=0.99, lam=0.95, clip=0.2, max_grad_norm=0.5,
-                 betas=(0.9, 0.999), eps=1e-8, seed=0):
+                 betas=(0.9, 0.999), eps=1e-8, seed=0, collect_precision="f32"):
         """env: a KManipEnvHip; actor, critic: Actors mapping obs_dim to act_dim and to 1.  Each iteration collects nsteps steps of
         every env and makes `epochs` passes over the nsteps * num_envs records in `minibatches` index lists each, drawn from a host
-        generator seeded with `seed` (a permutation per epoch)."""
+        generator seeded with `seed` (a permutation per epoch).  collect_precision="bf16" collects with kmanip_actor_bf16: the behaviour
+        policy is the bf16 network and logp_old its density, against which actor_grad (float32, unchanged) forms the exact importance
+        ratio; iterate() then refreshes the bf16 copy with actor.repack_bf16() before each collect, after the previous Adam steps."""
         import torch
         self.env, self.actor, self.critic = env, actor, critic
         self.nsteps, self.epochs, self.minibatches = int(nsteps), int(epochs), int(minibatches)
+        if collect_precision not in ("f32", "bf16"):
+            raise ValueError("PPO: collect_precision is 'f32' or 'bf16'")
+        self.collect_precision = collect_precision
         self.lr, self.gamma, self.lam, self.clip, self.max_grad_norm, self.betas, self.eps = lr, gamma, lam, clip, max_grad_norm, betas, eps
         self.n = self.nsteps * env.num_envs
         if not 1 <= self.minibatches <= self.n:
@@ -44,7 +49,9 @@ class PPO:
         # until the copy has run: the host never waits for it and never writes over it)
         host = torch.stack([torch.randperm(n, generator=self.gen) for _ in range(self.epochs)]).to(torch.int32).pin_memory()
         self.idx.copy_(host, non_blocking=True)
-        self.buf = env.collect(self.actor, T, critic=self.critic, out=self.buf)
+        if self.collect_precision == "bf16":
+            self.actor.repack_bf16()
+        self.buf = env.collect(self.actor, T, critic=self.critic, out=self.buf, precision=self.collect_precision)
         self.adv = env.gae(self.buf, self.gamma, self.lam, normalize=True, out=self.adv)
         obs = self.buf["obs"][:T].view(n, -1)
         ppo = dict(raw=self.buf["raw"].view(n, -1), logp_old=self.buf["logp"].view(n), adv=self.adv["adv"].view(n), clip=self.clip)

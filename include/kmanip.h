@@ -1224,6 +1224,26 @@ KMANIP_API int kmanip_actor_pack(KHandle h, const KActorDesc* desc, const KActor
  * OUT OF SCOPE: other weight types, more than two hidden layers, the policy inside the step kernels. */
 KMANIP_API int kmanip_actor(KHandle h, const KActorDesc* desc, const float* packed_dev, const KActorIn* in, int n, const KActorDev* out, void* stream);
 
+/* THE SAME NETWORK ON THE bf16 MATRIX CORES: kmanip_actor with bf16 weights and bf16 activations between the
+ * layers (v_mfma_f32_16x16x32_bf16), float32 biases, float32 accumulation and a float32 mean.  THE DEFINITION, every rounding to bf16
+ * to nearest, ties to even:
+ *   x      = bf16(float32((obs[r] - obs_mean) * obs_inv_std))        the float32 input of kmanip_actor, rounded once more
+ *   h1     = bf16(act(bf16(W0) x + b0)),  h2 = bf16(act(bf16(W1) h1 + b1)),  mean = bf16(W2) h2 + b2
+ * The biases and the last layer's output are not rounded.  Rows, envs, status and the Gaussian head are kmanip_actor's, compiled from
+ * the same source: at the same handle state noise and logp are kmanip_actor's bits, raw and act its float32 arithmetic on this call's
+ * mean.  The float32 tensors stay the master weights: kmanip_actor_grad and kmanip_actor_adam neither read nor write the bf16 buffer,
+ * which is refreshed by kmanip_actor_bf16_pack alone.
+ * THE BUFFER, in 16-byte entries: per layer (out tiles of 16) x (K-steps of 32 inputs, padded to a multiple of KM_ACTOR_BF16_KGROUP:
+ * 2 ceil(in / 64)) blocks of 64 entries, then the float32 bias padded to whole tiles (4 entries a tile).  Entry l of block (t2, s) holds
+ * W[16 t2 + l % 16][32 s + 4 (l / 16) + 0..3], then W[16 t2 + l % 16][32 s + 16 + 4 (l / 16) + 0..3]; zero beyond the real rows and columns. */
+#define KM_ACTOR_BF16_KGROUP 2    /* the bf16 buffer pads a layer's K-steps (32 inputs each) to a multiple of this: 64 inputs, as KM_ACTOR_KGROUP */
+/* The bytes of that buffer; 0 for a description kmanip_actor would refuse. */
+KMANIP_API size_t kmanip_actor_bf16_packed_bytes(const KActorDesc* desc);
+/* The row-major float32 tensors into packed_dev (16-byte aligned): three launches on `stream`; to be repeated after the weights change. */
+KMANIP_API int kmanip_actor_bf16_pack(KHandle h, const KActorDesc* desc, const KActorWeights* weights, void* packed_dev, void* stream);
+/* ONE launch, as kmanip_actor, with kmanip_actor's ERRORS (a NULL packed_dev or one that is not 16-byte aligned among them). */
+KMANIP_API int kmanip_actor_bf16(KHandle h, const KActorDesc* desc, const void* packed_dev, const KActorIn* in, int n, const KActorDev* out, void* stream);
+
 /* THE LOSS GRADIENTS of that network: for n rows of a rollout buffer of n_records records, the float32 gradients
  * of  L = sum_r loss_r  in w0, b0, w1, b1, w2, b2 (and log_std), in the shapes of the KActorWeights tensors, ready to be a torch .grad.
  * Row r reads record i = idx ? idx[r] : r (a minibatch is an index list: nothing is gathered).  The forward is kmanip_actor's to the
