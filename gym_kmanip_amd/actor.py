@@ -11,6 +11,9 @@ section 46) from the transposed packed copy repack() also keeps; `loss_reference
 `repack_bf16()` keeps a third copy, `packed_bf16`: the weights rounded to bf16 for kmanip_actor_bf16, which
 `actor_eval` and `collect` run with precision="bf16".  Neither repack() nor actor_adam touches it: whoever changes the parameters calls
 repack_bf16() before the next bf16 evaluation (PPO with collect_precision="bf16" does, once per iteration).
+`KManipEnvHip.actor_grad(..., precision="bf16")` (kmanip_actor_grad_bf16) is the gradient of that bf16 network with
+bf16 operands, from `packed_bf16` and a fourth copy, `packed_bf16_t`, which repack_bf16() refreshes once it exists;
+`loss_reference(precision="bf16")` is its definition, `grad_bf16_definition` the program over plain tensors.
 """
 from __future__ import annotations
 
@@ -27,6 +30,57 @@ def round_bf16(t):
     import torch
     bits = t.contiguous().view(torch.int64)
     return ((bits + ((1 << 44) - 1) + ((bits >> 45) & 1)) & ~((1 << 45) - 1)).view(torch.float64)
+
+
+def grad_bf16_definition(w, x, activation, head, rec, scale, sum_dtype=None):
+    """kmanip_actor_grad_bf16's definition (include/kmanip.h) as a program over plain tensors.  w: the float32 parameters by name,
+    widened to float64 (log_std with "ppo"); x: float64 [n, in_dim], the normalised input already rounded to float32; rec: the rows'
+    float64 head inputs -- {"g"} | {"target"} | {"raw", "logp_old", "adv", "clip"}.  Every product's operands are rounded to bf16
+    (round_bf16: one rounding) and summed in `sum_dtype` (None: float64, the reference; torch.float32: the arithmetic of the matrix
+    cores, which bounds the device's distance from the reference); the head is float64 per row on the mean.  Returns {"grads",
+    "row_loss" (not "given"), "logp" ("ppo"), "inter": x, h1, h2, dz3, dz2, dz1 as they are BEFORE their rounding to bf16}."""
+    import math
+    import torch
+    f64, sd_ = torch.float64, sum_dtype or torch.float64
+    q = round_bf16
+    f = torch.tanh if activation == "tanh" else torch.relu
+    dact = (lambda h: 1.0 - h * h) if activation == "tanh" else (lambda h: (h > 0).to(sd_))
+    mm = lambda a, b: a.to(sd_) @ b.to(sd_)
+    wq = [q(w[nm]) for nm in ("w0", "w1", "w2")]
+    inter, hs = {"x": x}, [q(x)]
+    for l in range(2):
+        inter["h%d" % (l + 1)] = f(mm(hs[l], wq[l].T) + w["b%d" % l].to(sd_)).to(f64)
+        hs.append(q(inter["h%d" % (l + 1)]))
+    mean = (mm(hs[2], wq[2].T) + w["b2"].to(sd_)).to(f64)
+    out, lt = {}, None
+    if head == "given":
+        gm = scale * rec["g"]
+    elif head == "mse":
+        e = mean - rec["target"]
+        gm, out["row_loss"] = scale * e, 0.5 * (e * e).sum(-1)
+    elif head == "ppo":
+        ls = w["log_std"]
+        sd = ls.exp().to(torch.float32).to(f64)
+        u = (rec["raw"] - mean) / sd
+        out["logp"] = (-0.5 * u * u - ls - 0.5 * math.log(2.0 * math.pi)).sum(-1)
+        rho, adv, clip = (out["logp"] - rec["logp_old"]).exp(), rec["adv"], float(rec["clip"])
+        s, cl = rho * adv, rho.clamp(1.0 - clip, 1.0 + clip) * adv
+        coef = torch.where(s <= cl, -scale * adv * rho, torch.zeros_like(rho))[:, None]
+        out["row_loss"] = -torch.minimum(s, cl)
+        gm, lt = coef * u / sd, (coef * (u * u - 1.0)).to(torch.float32)
+    else:
+        raise ValueError("grad_bf16_definition: head is 'given', 'mse' or 'ppo'")
+    grads, dz = {}, gm.to(torch.float32).to(f64)
+    for l in (2, 1, 0):
+        inter["dz%d" % (l + 1)] = dz
+        dz = q(dz)
+        grads["w%d" % l], grads["b%d" % l] = mm(dz.T, hs[l]).to(f64), dz.to(sd_).sum(0).to(f64)
+        if l:
+            dz = (mm(dz, wq[l]) * dact(hs[l].to(sd_))).to(f64)
+    if lt is not None:
+        grads["log_std"] = lt.to(sd_).sum(0).to(f64)
+    out.update(grads=grads, inter=inter)
+    return out
 
 
 class Actor:
@@ -59,7 +113,8 @@ class Actor:
         self.packed = torch.empty((floats,), dtype=torch.float32, device=env.device)
         self.packed_t = torch.empty((env.L.kmanip_actor_grad_packed_floats(C.byref(self.desc)),), dtype=torch.float32, device=env.device)
         self.packed_bf16 = None                      # kmanip_actor_bf16's buffer: repack_bf16() allocates and fills it
-        self.grad_workspace = {}                     # n -> kmanip_actor_grad's workspace (KManipEnvHip.actor_grad)
+        self.packed_bf16_t = None                    # kmanip_actor_grad_bf16's: actor_grad(precision="bf16") allocates it, repack_bf16() refreshes it
+        self.grad_workspace = {}                     # (n, precision) -> the gradient call's workspace (KManipEnvHip.actor_grad)
         self.adam_state, self.adam_step = None, 0    # kmanip_actor_adam's moments and step count (KManipEnvHip.actor_adam)
         self.repack()
 
@@ -104,17 +159,23 @@ class Actor:
             setattr(wt, nm, getattr(self, nm).data_ptr())
         return wt
 
-    def repack_bf16(self):
+    def repack_bf16(self, with_t=False):
         """kmanip_actor_bf16_pack: the parameter tensors as they are now, rounded to bf16 (nearest-even), into `packed_bf16` (allocated on
         first use), on the current stream.  repack() and KManipEnvHip.actor_adam do not refresh this copy: call this after the
-        parameters change and before the next evaluation with precision="bf16"."""
+        parameters change and before the next evaluation with precision="bf16".  Once `packed_bf16_t` exists (with_t, or a first
+        actor_grad with precision="bf16") kmanip_actor_grad_bf16_pack refreshes that transposed copy here too: two more launches."""
         import torch
         e = self.env
         if self.packed_bf16 is None:
             self.packed_bf16 = torch.empty((e.L.kmanip_actor_bf16_packed_bytes(C.byref(self.desc)),), dtype=torch.uint8, device=e.device)
+        if with_t and self.packed_bf16_t is None:
+            self.packed_bf16_t = torch.empty((e.L.kmanip_actor_grad_bf16_packed_bytes(C.byref(self.desc)),), dtype=torch.uint8, device=e.device)
         wt = self._weights()
         e._check(e.L.kmanip_actor_bf16_pack(e.h, C.byref(self.desc), C.byref(wt), C.c_void_p(self.packed_bf16.data_ptr()), e._stream()),
                  "kmanip_actor_bf16_pack")
+        if self.packed_bf16_t is not None:
+            e._check(e.L.kmanip_actor_grad_bf16_pack(e.h, C.byref(self.desc), C.byref(wt), C.c_void_p(self.packed_bf16_t.data_ptr()), e._stream()),
+                     "kmanip_actor_grad_bf16_pack")
 
     def torch_eval(self, obs):
         """The policy as a torch float32 program on the same parameters -- cast, normalise, three matmuls, sample from torch's global
@@ -164,11 +225,13 @@ class Actor:
             out["logp"] = (-0.5 * zd * zd - self.log_std.to(torch.float64) - 0.5 * math.log(2.0 * math.pi)).sum(-1)
         return out
 
-    def loss_reference(self, obs, head, g=None, target=None, ppo=None, idx=None, scale=None):
+    def loss_reference(self, obs, head, g=None, target=None, ppo=None, idx=None, scale=None, precision="f32"):
         """kmanip_actor_grad's loss in torch float64 under autograd: the definition (include/kmanip.h KActorGradIn).  obs: float64
         [n_records, in_dim]; idx: the records of the rows (None: all, in order); head "given" (g [n_records, out_dim]: the loss is
         scale sum g . mean), "mse" (target) or "ppo" (a dict of raw, logp_old, adv, clip); scale: None = 1 / n.  Returns {"grads": a
-        dict by parameter name (log_std for "ppo" only), "row_loss" [n] (not for "given"), "logp" [n] ("ppo")}, all float64."""
+        dict by parameter name (log_std for "ppo" only), "row_loss" [n] (not for "given"), "logp" [n] ("ppo")}, all float64.
+        precision="bf16" is kmanip_actor_grad_bf16's definition, grad_bf16_definition with float64 sums: explicit formulas, since
+        act' from the rounded activation and the roundings of dz are no forward program's autograd (it also returns "inter")."""
         import math
         import torch
         rows = torch.arange(obs.shape[0], device=obs.device) if idx is None else torch.as_tensor(idx, device=obs.device).long()
@@ -179,8 +242,14 @@ class Actor:
         if self.obs_inv_std is not None:
             x = x * self.obs_inv_std
         x = x.to(torch.float32).to(torch.float64)
-        f = torch.tanh if self.activation == "tanh" else torch.relu
         names = _NAMES + (("log_std",) if head == "ppo" else ())
+        if precision == "bf16":
+            rec = {"given": {"g": g}, "mse": {"target": target}}.get(head) or {k: ppo[k] for k in ("raw", "logp_old", "adv")}
+            rec = dict({k: v.to(torch.float64)[rows] for k, v in rec.items()}, **({"clip": ppo["clip"]} if head == "ppo" else {}))
+            return grad_bf16_definition({nm: getattr(self, nm).to(torch.float64) for nm in names}, x, self.activation, head, rec, scale)
+        if precision != "f32":
+            raise ValueError("loss_reference: precision is 'f32' or 'bf16'")
+        f = torch.tanh if self.activation == "tanh" else torch.relu
         w = {nm: getattr(self, nm).to(torch.float64).requires_grad_() for nm in names}
         mean = f(f(x @ w["w0"].T + w["b0"]) @ w["w1"].T + w["b1"]) @ w["w2"].T + w["b2"]
         out = {}

@@ -21,7 +21,7 @@
 //
 // k_actor_grad_reduce: one thread per element of the seven gradient tensors sums the partials in ascending split order and writes
 // the row-major tensors without the tile padding.  With no splits (n == 0) it writes zeros.
-#include "kmanip_actor_layer.hpp"
+#include "kmanip_actor_grad_head.hpp"   // agrad_row, agrad_obs, agrad_head: shared with k_actor_bwd_bf16; f4, actor_layer: with k_actor
 
 #define KM_AGRAD_SPLIT_ROWS 256   // a K-split holds at least this many rows ...
 #define KM_AGRAD_MAX_SPLITS 64    // ... and there are at most this many
@@ -107,89 +107,26 @@ __global__ __launch_bounds__(64) void k_actor_bwd(KActorDesc d, KActorPlan p, KA
                                                   const float* __restrict__ packed_t, KActorGradIn in, int n, float* __restrict__ ws, KActorGradDev out) {
   static_assert(NT >= 4, "the first layer reads up to 64 inputs: four tiles");
   const f4 *pk = (const f4*)packed, *pkt = (const f4*)packed_t;
-  const int lane = threadIdx.x, g = lane >> 4, row = blockIdx.x * 16 + (lane & 15);
+  const int lane = threadIdx.x, g = lane >> 4;
   const int id = d.in_dim, od = d.out_dim;
-  const size_t np = gp.np, rowpos = row;                             // (row < np: the grid is np / 16 waves)
-  // ---- the row's record: an index outside the buffer is status 2 and never an address
-  const bool live = row < n;
-  int rec = 0, status = 0;
-  if (live) {
-    rec = in.idx ? in.idx[row] : row;
-    if (rec < 0 || rec >= in.n_records) status = 2;
-  }
-  const bool ok = live && status == 0;
+  const AgradRow rw = agrad_row(in, n, lane);
+  const size_t np = gp.np, rowpos = rw.row;                          // (row < np: the grid is np / 16 waves)
   // ---- the forward, as k_actor has it
   f4 x[4];
 #pragma unroll
   for (int t = 0; t < 4; t++) {
-    x[t] = f4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-    for (int c = 0; c < 4; c++) {
-      const int k = 16 * t + 4 * g + c;
-      if (ok && k < id) {
-        double v = in.obs[(size_t)rec * id + k];
-        if (in.obs_mean) v = v - in.obs_mean[k];
-        if (in.obs_inv_std) v = v * in.obs_inv_std[k];
-        x[t][c] = (float)v;
-      }
-    }
+    for (int c = 0; c < 4; c++) x[t][c] = agrad_obs(in, rw, id, 16 * t + 4 * g + c);
   }
   f4 h1[NT], h2[NT], y[1];
   actor_layer<4, NT, true>(pk, p.w4[0], p.b4[0], p.kb[0], p.ot[0], d.activation, x, h1, lane);
   agrad_store<4>(ws + gp.off[0], np, rowpos, gp.it[0], x, g);
   actor_layer<NT, NT, true>(pk, p.w4[1], p.b4[1], p.kb[1], p.ot[1], d.activation, h1, h2, lane);
   actor_layer<NT, 1, false>(pk, p.w4[2], p.b4[2], p.kb[2], 1, d.activation, h2, y, lane);
-  // ---- the head: lane (g, n) has outputs 4 g .. 4 g + 3 of its row; float64, gmean rounded once
+  // ---- the head (kmanip_actor_grad_head.hpp): dL/dmean and the log_std terms coef (u^2 - 1)
   const f4 zero = {0.f, 0.f, 0.f, 0.f};
-  f4 gm[1] = {zero}, lt[1] = {zero};                                 // dL/dmean and the log_std terms coef (u^2 - 1)
-  {
-#pragma clang fp contract(off)
-    const f4 mean = y[0];
-    const size_t at = (size_t)rec * od + 4 * g;
-    double part = 0.0, u[4] = {0.0, 0.0, 0.0, 0.0}, isd[4] = {0.0, 0.0, 0.0, 0.0};
-    if (ok) {
-#pragma unroll
-      for (int c = 0; c < 4; c++) {
-        if (4 * g + c < od) {
-          if (in.head == KM_AGRAD_GIVEN) gm[0][c] = (float)(in.scale * (double)in.g[at + c]);
-          else if (in.head == KM_AGRAD_MSE) {
-            const double e = (double)mean[c] - (double)in.target[at + c];
-            gm[0][c] = (float)(in.scale * e);
-            part = part + e * e;
-          } else {
-            const float ls = in.log_std[4 * g + c];
-            const float sd = (float)exp((double)ls);                 // as k_actor: float64, rounded once
-            isd[c] = 1.0 / (double)sd;
-            u[c] = ((double)in.raw[at + c] - (double)mean[c]) / (double)sd;
-            part = part + (((-0.5 * (u[c] * u[c])) - (double)ls) - 0.9189385332046727);
-          }
-        }
-      }
-    }
-    if (in.head != KM_AGRAD_GIVEN) {                                 // (wave-uniform: every lane reaches the shuffles or none)
-      // the four lane groups of a row, a fixed order: (g ^ 1) first, then (g ^ 2); every lane ends with the same bits
-      part = part + __shfl_xor(part, 16, 64);
-      part = part + __shfl_xor(part, 32, 64);
-      double loss = 0.5 * part;
-      if (in.head == KM_AGRAD_PPO_CLIP && ok) {
-        const double adv = (double)in.adv[rec], rho = exp(part - in.logp_old[rec]);
-        const double s = rho * adv, cl = fmin(fmax(rho, 1.0 - in.clip), 1.0 + in.clip) * adv;
-        const double coef = s <= cl ? -in.scale * adv * rho : 0.0;
-        loss = -fmin(s, cl);
-#pragma unroll
-        for (int c = 0; c < 4; c++)
-          if (4 * g + c < od) {
-            gm[0][c] = (float)(coef * u[c] * isd[c]);
-            lt[0][c] = (float)(coef * (u[c] * u[c] - 1.0));
-          }
-      }
-      if (live && g == 0) {
-        if (out.row_loss) out.row_loss[row] = ok ? loss : 0.0;
-        if (out.logp && in.head == KM_AGRAD_PPO_CLIP) out.logp[row] = ok ? part : 0.0;
-      }
-    }
-  }
-  if (live && g == 0 && out.status) out.status[row] = status;
+  f4 gm[1], lt[1];
+  agrad_head(in, out, od, rw, g, y[0], gm[0], lt[0]);
   agrad_store<1>(ws + gp.off[5], np, rowpos, 1, gm, g);
   agrad_store<1>(ws + gp.off[6], np, rowpos, 1, lt, g);
   const f4 dz3[4] = {gm[0], zero, zero, zero};                       // one K group: the tile and three of zeros against the zero blocks
@@ -293,6 +230,11 @@ void kmanip_launch_actor_grad(const KActorDesc& d, const float* packed, const fl
     const int items = in.head == KM_AGRAD_PPO_CLIP ? gp.item0[4] : gp.item0[3];
     hipLaunchKernelGGL(k_actor_wgrad, dim3(items, gp.splits), block, 0, stream, gp, ws);
   }
+  kmanip_launch_actor_grad_reduce(d, gp, in.head, ws, out, stream);
+}
+
+void kmanip_launch_actor_grad_reduce(const KActorDesc& d, const KActorGradPlan& gp, int head, const float* ws, const KActorGradDev& out,
+                                     hipStream_t stream) {
   const int elems = d.hidden[0] * (d.in_dim + 1) + d.hidden[1] * (d.hidden[0] + 1) + d.out_dim * (d.hidden[1] + 2);
-  hipLaunchKernelGGL(k_actor_grad_reduce, dim3((elems + 255) / 256), dim3(256), 0, stream, d, gp, in.head, ws, out);
+  hipLaunchKernelGGL(k_actor_grad_reduce, dim3((elems + 255) / 256), dim3(256), 0, stream, d, gp, head, ws, out);
 }

@@ -1245,30 +1245,67 @@ int kmanip_actor_grad_pack(KHandle h, const KActorDesc* desc, const KActorWeight
   return 0;
 }
 
+// what kmanip_actor_grad and kmanip_actor_grad_bf16 refuse alike in (desc, in, out, n), or NULL
+static const char* actor_grad_args_error(const KActorDesc* desc, const KActorGradIn* in, const KActorGradDev* out, int n) {
+  if (const char* e = actor_desc_error(desc)) return e;
+  if (!in) return "the KActorGradIn pointer is NULL";
+  if (!out) return "the KActorGradDev pointer is NULL";
+  if (n < 0) return "n is negative";
+  if (in->n_records < 1) return "n_records is below 1";
+  if (!in->idx && n > in->n_records) return "more rows than records need KActorGradIn::idx";
+  if (!in->obs) return "KActorGradIn::obs is NULL";
+  const bool ppo = in->head == KM_AGRAD_PPO_CLIP;
+  if (in->head == KM_AGRAD_GIVEN) { if (!in->g) return "the GIVEN head needs KActorGradIn::g"; }
+  else if (in->head == KM_AGRAD_MSE) { if (!in->target) return "the MSE head needs KActorGradIn::target"; }
+  else if (ppo) {
+    if (!in->log_std || !in->raw || !in->logp_old || !in->adv) return "the PPO head needs log_std, raw, logp_old and adv";
+    if (!(in->clip > 0.0 && in->clip < 1.0)) return "clip is not in (0, 1)";
+  } else return "unknown head";
+  if (!out->w0 || !out->b0 || !out->w1 || !out->b1 || !out->w2 || !out->b2 || (ppo && !out->log_std)) return "a gradient pointer is NULL";
+  return nullptr;
+}
+
 int kmanip_actor_grad(KHandle h, const KActorDesc* desc, const float* packed_dev, const float* packed_t_dev, const KActorGradIn* in, int n,
                       float* workspace_dev, const KActorGradDev* out, void* stream) {
   if (!h) { g_create_error = "kmanip_actor_grad: null handle"; return -1; }
   auto refuse = [&](const char* what) { h->err = std::string("kmanip_actor_grad: ") + what; return -1; };
-  if (const char* e = actor_desc_error(desc)) return refuse(e);
-  if (!in) return refuse("the KActorGradIn pointer is NULL");
-  if (!out) return refuse("the KActorGradDev pointer is NULL");
-  if (n < 0) return refuse("n is negative");
-  if (in->n_records < 1) return refuse("n_records is below 1");
-  if (!in->idx && n > in->n_records) return refuse("more rows than records need KActorGradIn::idx");
-  if (!in->obs) return refuse("KActorGradIn::obs is NULL");
-  const bool ppo = in->head == KM_AGRAD_PPO_CLIP;
-  if (in->head == KM_AGRAD_GIVEN) { if (!in->g) return refuse("the GIVEN head needs KActorGradIn::g"); }
-  else if (in->head == KM_AGRAD_MSE) { if (!in->target) return refuse("the MSE head needs KActorGradIn::target"); }
-  else if (ppo) {
-    if (!in->log_std || !in->raw || !in->logp_old || !in->adv) return refuse("the PPO head needs log_std, raw, logp_old and adv");
-    if (!(in->clip > 0.0 && in->clip < 1.0)) return refuse("clip is not in (0, 1)");
-  } else return refuse("unknown head");
-  if (!out->w0 || !out->b0 || !out->w1 || !out->b1 || !out->w2 || !out->b2 || (ppo && !out->log_std)) return refuse("a gradient pointer is NULL");
+  if (const char* e = actor_grad_args_error(desc, in, out, n)) return refuse(e);
   if (!packed_dev || ((uintptr_t)packed_dev & 15)) return refuse("packed_dev is NULL or not 16-byte aligned");
   if (!packed_t_dev || ((uintptr_t)packed_t_dev & 15)) return refuse("packed_t_dev is NULL or not 16-byte aligned");
   if (!workspace_dev || ((uintptr_t)workspace_dev & 15)) return refuse("workspace_dev is NULL or not 16-byte aligned");
   KM_ENTER(h);
   kmanip_launch_actor_grad(*desc, packed_dev, packed_t_dev, *in, n, workspace_dev, *out, (hipStream_t)stream);
+  HIPCHK(h, hipGetLastError());
+  return 0;
+}
+
+// ---- the gradients of the bf16 network (include/kmanip.h kmanip_actor_grad_bf16; kmanip_actor_grad_bfloat.hip)
+size_t kmanip_actor_grad_bf16_packed_bytes(const KActorDesc* desc) { return actor_desc_error(desc) ? 0 : 16 * (size_t)kmanip_actor_grad_bf16_plan(*desc, 0).t.total16; }
+
+size_t kmanip_actor_grad_bf16_workspace_bytes(const KActorDesc* desc, int n) { return actor_desc_error(desc) || n < 0 ? 0 : 4 * kmanip_actor_grad_bf16_plan(*desc, n).g.total; }
+
+int kmanip_actor_grad_bf16_pack(KHandle h, const KActorDesc* desc, const KActorWeights* weights, void* packed_t_bf16_dev, void* stream) {
+  if (!h) { g_create_error = "kmanip_actor_grad_bf16_pack: null handle"; return -1; }
+  auto refuse = [&](const char* what) { h->err = std::string("kmanip_actor_grad_bf16_pack: ") + what; return -1; };
+  if (const char* e = actor_desc_error(desc)) return refuse(e);
+  if (!weights || !weights->w1 || !weights->w2) return refuse("a weight pointer is NULL");
+  if (!packed_t_bf16_dev || ((uintptr_t)packed_t_bf16_dev & 15)) return refuse("packed_t_bf16_dev is NULL or not 16-byte aligned");
+  KM_ENTER(h);
+  kmanip_launch_actor_grad_bf16_pack(*desc, *weights, packed_t_bf16_dev, (hipStream_t)stream);
+  HIPCHK(h, hipGetLastError());
+  return 0;
+}
+
+int kmanip_actor_grad_bf16(KHandle h, const KActorDesc* desc, const void* packed_bf16_dev, const void* packed_t_bf16_dev, const KActorGradIn* in,
+                           int n, void* workspace_dev, const KActorGradDev* out, void* stream) {
+  if (!h) { g_create_error = "kmanip_actor_grad_bf16: null handle"; return -1; }
+  auto refuse = [&](const char* what) { h->err = std::string("kmanip_actor_grad_bf16: ") + what; return -1; };
+  if (const char* e = actor_grad_args_error(desc, in, out, n)) return refuse(e);
+  if (!packed_bf16_dev || ((uintptr_t)packed_bf16_dev & 15)) return refuse("packed_bf16_dev is NULL or not 16-byte aligned");
+  if (!packed_t_bf16_dev || ((uintptr_t)packed_t_bf16_dev & 15)) return refuse("packed_t_bf16_dev is NULL or not 16-byte aligned");
+  if (!workspace_dev || ((uintptr_t)workspace_dev & 15)) return refuse("workspace_dev is NULL or not 16-byte aligned");
+  KM_ENTER(h);
+  kmanip_launch_actor_grad_bf16(*desc, packed_bf16_dev, packed_t_bf16_dev, *in, n, workspace_dev, *out, (hipStream_t)stream);
   HIPCHK(h, hipGetLastError());
   return 0;
 }

@@ -718,6 +718,20 @@ KActorGradPlan kmanip_actor_grad_plan(const KActorDesc& d, int n);
 void kmanip_launch_actor_grad_pack(const KActorDesc& d, const KActorWeights& w, float* packed_t, hipStream_t stream);
 void kmanip_launch_actor_grad(const KActorDesc& d, const float* packed, const float* packed_t, const KActorGradIn& in, int n, float* ws,
                               const KActorGradDev& out, hipStream_t stream);
+// kmanip_actor_grad_bf16 / kmanip_actor_grad_bf16_pack (kmanip_actor_grad_bfloat.hip): `t` lays out the transposed bf16 buffer (layers 0
+// and 1 of kmanip_actor_bf16_plan for out_dim -> hidden[1] -> hidden[0]; total16 ends there); `g` is KActorGradPlan with the rows padded
+// to 32, `len` a multiple of 32, itg[] groups of EIGHT input tiles, and every offset in 4-byte words of the workspace: the six bf16
+// arrays x h1 h2 dz1 dz2 dz3 take half a word an element, the log_std terms and the partials stay float32 (g.t is not used).
+// k_actor_grad_reduce reads `g` as it reads kmanip_actor_grad's plan.  The launches: two pack launches; per call over n > 0 rows
+// k_actor_bwd_bf16, k_actor_wgrad_bf16, k_actor_grad_reduce (n == 0: the last only)
+struct KActorGradBf16Plan { KActorBf16Plan t; KActorGradPlan g; };
+KActorGradBf16Plan kmanip_actor_grad_bf16_plan(const KActorDesc& d, int n);
+void kmanip_launch_actor_grad_bf16_pack(const KActorDesc& d, const KActorWeights& w, void* packed_t, hipStream_t stream);
+void kmanip_launch_actor_grad_bf16(const KActorDesc& d, const void* packed, const void* packed_t, const KActorGradIn& in, int n, void* ws,
+                                   const KActorGradDev& out, hipStream_t stream);
+// k_actor_grad_reduce (kmanip_actor_grad.hip), launched by both gradient calls: the partials of `gp` summed into the seven tensors
+void kmanip_launch_actor_grad_reduce(const KActorDesc& d, const KActorGradPlan& gp, int head, const float* ws, const KActorGradDev& out,
+                                     hipStream_t stream);
 // kmanip_gae (kmanip_gae.hip): k_gae over ceil(N / KM_GAE_BLOCK) blocks, then k_gae_finish where the call normalises or reports stats
 void kmanip_launch_gae(const KGaeIn& in, int T, int N, double* ws, const KGaeDev& out, hipStream_t stream);
 // kmanip_actor_adam (kmanip_actor_opt.hip): `p` and `t` lay out the two packed buffers; rkb[l] the REAL K-blocks of layer l (the work

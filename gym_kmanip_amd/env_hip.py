@@ -1436,7 +1436,7 @@ class KManipEnvHip:
                                            C.c_void_p(at("done", t)), stream), "kmanip_step")
         return out
 
-    def actor_grad(self, actor, obs, *, g=None, target=None, ppo=None, idx=None, scale=None, out=None, set_grad=True):
+    def actor_grad(self, actor, obs, *, g=None, target=None, ppo=None, idx=None, scale=None, out=None, set_grad=True, precision="f32"):
         """kmanip_actor_grad: the float32 gradients of a loss over rows of a rollout buffer in `actor`'s parameters -- three launches
         on the current stream, no synchronisation, no torch arithmetic, the same bytes on every run.  obs: float64 [n_records,
         actor.in_dim]; idx: the records of the rows (an int32 device tensor or anything torch.as_tensor takes; None = every record,
@@ -1446,7 +1446,10 @@ class KManipEnvHip:
         None = 1 / n.  Returns a dict of device tensors: w0 .. b2 (log_std with ppo) shaped like the parameters, status [n] int32
         (2: a record index out of range, the row adds nothing), row_loss [n] float64 (target, ppo), logp [n] float64 (ppo); `out`:
         such a dict to overwrite, returned as given.  With set_grad the gradients become the parameters' .grad: a torch optimiser's
-        step() and actor.repack() then make a training step."""
+        step() and actor.repack() then make a training step.  precision="bf16" is kmanip_actor_grad_bf16: the gradients of the bf16
+        network actor_eval(precision="bf16") runs, with bf16 operands and float32 sums (include/kmanip.h has the definition), from
+        actor.packed_bf16 and actor.packed_bf16_t -- both filled on first use; after the parameters change the caller runs
+        actor.repack_bf16(), which refreshes both.  The outputs keep their dtypes; a workspace is kept per (n, precision)."""
         torch = _torch()
         heads = [k for k, v in (("given", g), ("mse", target), ("ppo", ppo)) if v is not None]
         if len(heads) != 1:
@@ -1454,7 +1457,9 @@ class KManipEnvHip:
         head, f32, f64 = heads[0], torch.float32, torch.float64
         nrec = int(obs.shape[0]) if isinstance(obs, torch.Tensor) and obs.dim() else -1
         self._check_buf(obs, (nrec, actor.in_dim), f64, "obs")
-        self._actor_check(actor)
+        self._actor_check(actor, precision)
+        if precision == "bf16" and actor.packed_bf16_t is None:
+            actor.repack_bf16(with_t=True)
         index, _, n = self._env_index(idx, "idx")
         n = nrec if n is None else n
         gi = _libmod.KActorGradIn(head=_libmod.KM_AGRAD[head], n_records=nrec, idx=index.data_ptr() if n and index is not None else None, obs=obs.data_ptr(),
@@ -1480,12 +1485,18 @@ class KManipEnvHip:
         for k, (s, dt) in shapes.items():
             self._check_buf(out[k], s, dt, k)
             setattr(dev, k, out[k].data_ptr())
-        if n not in actor.grad_workspace:
-            floats = self.L.kmanip_actor_grad_workspace_floats(C.byref(actor.desc), n)
-            actor.grad_workspace[n] = torch.empty((floats,), dtype=f32, device=self.device)
-        self._check(self.L.kmanip_actor_grad(self.h, C.byref(actor.desc), C.c_void_p(actor.packed.data_ptr()), C.c_void_p(actor.packed_t.data_ptr()),
-                                             C.byref(gi), n, C.c_void_p(actor.grad_workspace[n].data_ptr()), C.byref(dev), self._stream()),
-                    "kmanip_actor_grad")
+        if (n, precision) not in actor.grad_workspace:
+            nbytes = (self.L.kmanip_actor_grad_bf16_workspace_bytes(C.byref(actor.desc), n) if precision == "bf16"
+                      else 4 * self.L.kmanip_actor_grad_workspace_floats(C.byref(actor.desc), n))
+            actor.grad_workspace[(n, precision)] = torch.empty((nbytes // 4,), dtype=f32, device=self.device)
+        ws = C.c_void_p(actor.grad_workspace[(n, precision)].data_ptr())
+        if precision == "bf16":
+            self._check(self.L.kmanip_actor_grad_bf16(self.h, C.byref(actor.desc), C.c_void_p(actor.packed_bf16.data_ptr()),
+                                                      C.c_void_p(actor.packed_bf16_t.data_ptr()), C.byref(gi), n, ws, C.byref(dev), self._stream()),
+                        "kmanip_actor_grad_bf16")
+        else:
+            self._check(self.L.kmanip_actor_grad(self.h, C.byref(actor.desc), C.c_void_p(actor.packed.data_ptr()), C.c_void_p(actor.packed_t.data_ptr()),
+                                                 C.byref(gi), n, ws, C.byref(dev), self._stream()), "kmanip_actor_grad")
         if set_grad:
             for nm, p in params.items():
                 p.grad = out[nm]

@@ -20,7 +20,7 @@ _lib = None
 EXPORTS = [
     "kmanip_model_desc_size", "kmanip_create", "kmanip_reset", "kmanip_step", "kmanip_step_chunk", "kmanip_get_state",
     "kmanip_set_state", "kmanip_get_episode", "kmanip_set_episode", "kmanip_get_counters", "kmanip_bind_sim_time", "kmanip_bind_applied_force", "kmanip_bind_reward_done_record", "kmanip_select_reward_done_record", "kmanip_observe", "kmanip_forces", "kmanip_kinematics", "kmanip_inverse", "kmanip_forward", "kmanip_kinematics_rows", "kmanip_site_cost", "kmanip_rollout", "kmanip_feedback", "kmanip_feedback_box", "kmanip_transition_fd", "kmanip_forward_fd", "kmanip_param_fd", "kmanip_lqr_backward", "kmanip_lqr_backward_box", "kmanip_adjoint", "kmanip_tangent", "kmanip_set_seed", "kmanip_get_diag", "kmanip_timing_summary", "kmanip_enable_timing", "kmanip_ik", "kmanip_ik_eval",
-    "kmanip_render_depth", "kmanip_render_rgb", "kmanip_render_rgb_multi", "kmanip_render_labels_multi", "kmanip_render_seg", "kmanip_set_render_links", "kmanip_get_render_links", "kmanip_set_depth_links", "kmanip_get_depth_links", "kmanip_get_camera_poses", "kmanip_render_points", "kmanip_snapshot_render_state", "kmanip_set_render_source", "kmanip_bind_step_depth", "kmanip_scripted_action", "kmanip_sample_action", "kmanip_actor_packed_floats", "kmanip_actor_pack", "kmanip_actor", "kmanip_actor_bf16_packed_bytes", "kmanip_actor_bf16_pack", "kmanip_actor_bf16", "kmanip_actor_grad_packed_floats", "kmanip_actor_grad_workspace_floats", "kmanip_actor_grad_pack", "kmanip_actor_grad", "kmanip_gae_workspace_doubles", "kmanip_gae", "kmanip_actor_adam_state_floats", "kmanip_actor_adam", "kmanip_set_env_params", "kmanip_get_env_params", "kmanip_set_env_param_ranges", "kmanip_set_visual_params", "kmanip_get_visual_params", "kmanip_set_visual_param_ranges",
+    "kmanip_render_depth", "kmanip_render_rgb", "kmanip_render_rgb_multi", "kmanip_render_labels_multi", "kmanip_render_seg", "kmanip_set_render_links", "kmanip_get_render_links", "kmanip_set_depth_links", "kmanip_get_depth_links", "kmanip_get_camera_poses", "kmanip_render_points", "kmanip_snapshot_render_state", "kmanip_set_render_source", "kmanip_bind_step_depth", "kmanip_scripted_action", "kmanip_sample_action", "kmanip_actor_packed_floats", "kmanip_actor_pack", "kmanip_actor", "kmanip_actor_bf16_packed_bytes", "kmanip_actor_bf16_pack", "kmanip_actor_bf16", "kmanip_actor_grad_packed_floats", "kmanip_actor_grad_workspace_floats", "kmanip_actor_grad_pack", "kmanip_actor_grad", "kmanip_actor_grad_bf16_packed_bytes", "kmanip_actor_grad_bf16_workspace_bytes", "kmanip_actor_grad_bf16_pack", "kmanip_actor_grad_bf16", "kmanip_gae_workspace_doubles", "kmanip_gae", "kmanip_actor_adam_state_floats", "kmanip_actor_adam", "kmanip_set_env_params", "kmanip_get_env_params", "kmanip_set_env_param_ranges", "kmanip_set_visual_params", "kmanip_get_visual_params", "kmanip_set_visual_param_ranges",
     "kmanip_get_state_dev", "kmanip_set_state_dev", "kmanip_copy_envs", "kmanip_state_index_errors", "kmanip_num_envs", "kmanip_last_error", "kmanip_version", "kmanip_destroy",
 ]
 
@@ -304,6 +304,28 @@ def actor_grad_workspace_floats(in_dim, hidden, out_dim, n):
     return 16 * (ti + 2 * t1 + 2 * t2 + 2) * np_ + splits * (256 * (t1 * ti + t2 * t1 + t2) + 16 * (t1 + t2 + 2))
 
 
+def actor_grad_bf16_packed_bytes(in_dim, hidden, out_dim):
+    """include/kmanip.h kmanip_actor_grad_bf16_packed_bytes, restated: W2^T and W1^T as layers out_dim -> hidden[1] -> hidden[0] of
+    actor_bf16_packed_bytes' layout."""
+    steps = lambda i: -(-(-(-i // 32)) // KM_ACTOR_BF16_KGROUP) * KM_ACTOR_BF16_KGROUP
+    return sum(o // 16 * (steps(i) * 1024 + 64) for i, o in ((out_dim, hidden[1]), (hidden[1], hidden[0])))
+
+
+def actor_grad_bf16_splits(n):
+    """(rows padded to 32, K-splits, rows per split) of a kmanip_actor_grad_bf16 call over n rows."""
+    steps = max(1, -(-n // 32))
+    splits = 0 if n == 0 else min(64, -(-32 * steps // 256))
+    return 32 * steps, splits, 32 * -(-steps // max(splits, 1))
+
+
+def actor_grad_bf16_workspace_bytes(in_dim, hidden, out_dim, n):
+    """include/kmanip.h kmanip_actor_grad_bf16_workspace_bytes, restated: x, h1, h2, dz1, dz2, dz3 in bf16 and the log_std terms in
+    float32 [units padded to 16][rows padded to 32], then per K-split the float32 partials of actor_grad_workspace_floats."""
+    np_, splits, _ = actor_grad_bf16_splits(n)
+    ti, t1, t2 = (in_dim + 15) // 16, hidden[0] // 16, hidden[1] // 16
+    return 2 * 16 * (ti + 2 * t1 + 2 * t2 + 1) * np_ + 4 * 16 * np_ + 4 * splits * (256 * (t1 * ti + t2 * t1 + t2) + 16 * (t1 + t2 + 2))
+
+
 class KGaeIn(C.Structure):
     """include/kmanip.h KGaeIn: DEVICE pointers of a collect() buffer's reward, done, value (and the values truncated steps bootstrap
     from, or NULL), the discount, GAE's lambda (the header's name, a Python keyword: set it with setattr) and whether adv is normalised."""
@@ -444,6 +466,12 @@ def load():
     lib.kmanip_actor_grad_workspace_floats.restype = C.c_size_t
     lib.kmanip_actor_grad_pack.argtypes = [vp, C.POINTER(KActorDesc), C.POINTER(KActorWeights), vp, vp]
     lib.kmanip_actor_grad.argtypes = [vp, C.POINTER(KActorDesc), vp, vp, C.POINTER(KActorGradIn), C.c_int, vp, C.POINTER(KActorGradDev), vp]
+    lib.kmanip_actor_grad_bf16_packed_bytes.argtypes = [C.POINTER(KActorDesc)]
+    lib.kmanip_actor_grad_bf16_packed_bytes.restype = C.c_size_t
+    lib.kmanip_actor_grad_bf16_workspace_bytes.argtypes = [C.POINTER(KActorDesc), C.c_int]
+    lib.kmanip_actor_grad_bf16_workspace_bytes.restype = C.c_size_t
+    lib.kmanip_actor_grad_bf16_pack.argtypes = [vp, C.POINTER(KActorDesc), C.POINTER(KActorWeights), vp, vp]
+    lib.kmanip_actor_grad_bf16.argtypes = [vp, C.POINTER(KActorDesc), vp, vp, C.POINTER(KActorGradIn), C.c_int, vp, C.POINTER(KActorGradDev), vp]
     lib.kmanip_gae_workspace_doubles.argtypes = [C.c_int]
     lib.kmanip_gae_workspace_doubles.restype = C.c_size_t
     lib.kmanip_gae.argtypes = [vp, C.POINTER(KGaeIn), C.c_int, C.c_int, vp, C.POINTER(KGaeDev), vp]

@@ -11,18 +11,23 @@ normalisation, learning-rate schedules (set .lr between iterations)."""
 
 class PPO:
     def __init__(self, env, actor, critic, nsteps=16, epochs=4, minibatches=4, lr=3e-4, gamma=0.99, lam=0.95, clip=0.2, max_grad_norm=0.5,
-                 betas=(0.9, 0.999), eps=1e-8, seed=0, collect_precision="f32"):
+                 betas=(0.9, 0.999), eps=1e-8, seed=0, collect_precision="f32", update_precision="f32"):
         """env: a KManipEnvHip; actor, critic: Actors mapping obs_dim to act_dim and to 1.  Each iteration collects nsteps steps of
         every env and makes `epochs` passes over the nsteps * num_envs records in `minibatches` index lists each, drawn from a host
         generator seeded with `seed` (a permutation per epoch).  collect_precision="bf16" collects with kmanip_actor_bf16: the behaviour
         policy is the bf16 network and logp_old its density, against which actor_grad (float32, unchanged) forms the exact importance
-        ratio; iterate() then refreshes the bf16 copy with actor.repack_bf16() before each collect, after the previous Adam steps."""
+        ratio; iterate() then refreshes the bf16 copy with actor.repack_bf16() before each collect, after the previous Adam steps.
+        update_precision="bf16" (it needs collect_precision="bf16") runs the POLICY's actor_grad as kmanip_actor_grad_bf16 (DESIGN.md
+        section 50): the learner's forward is the behaviour policy's to the bit, so the ratio of the first minibatch starts at 1;
+        actor.repack_bf16() then follows every policy Adam step.  The critic stays float32."""
         import torch
         self.env, self.actor, self.critic = env, actor, critic
         self.nsteps, self.epochs, self.minibatches = int(nsteps), int(epochs), int(minibatches)
         if collect_precision not in ("f32", "bf16"):
             raise ValueError("PPO: collect_precision is 'f32' or 'bf16'")
-        self.collect_precision = collect_precision
+        if update_precision not in ("f32", "bf16") or (update_precision == "bf16" and collect_precision != "bf16"):
+            raise ValueError("PPO: update_precision is 'f32' or 'bf16', and 'bf16' needs collect_precision='bf16'")
+        self.collect_precision, self.update_precision = collect_precision, update_precision
         self.lr, self.gamma, self.lam, self.clip, self.max_grad_norm, self.betas, self.eps = lr, gamma, lam, clip, max_grad_norm, betas, eps
         self.n = self.nsteps * env.num_envs
         if not 1 <= self.minibatches <= self.n:
@@ -35,9 +40,12 @@ class PPO:
 
     def _step(self, which, net, obs, rows, **head):
         env, n = self.env, int(rows.numel())
-        out = env.actor_grad(net, obs, idx=rows, out=self.grads[which].get(n), set_grad=False, **head)
+        bf16 = which == 0 and self.update_precision == "bf16"
+        out = env.actor_grad(net, obs, idx=rows, out=self.grads[which].get(n), set_grad=False, precision="bf16" if bf16 else "f32", **head)
         self.grads[which][n] = out
         env.actor_adam(net, self.lr, self.betas, self.eps, self.max_grad_norm, grads=out, log_std=which == 0)
+        if bf16:
+            net.repack_bf16()
         return out["row_loss"].mean()
 
     def iterate(self):

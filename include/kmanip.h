@@ -1305,6 +1305,35 @@ KMANIP_API int kmanip_actor_grad_pack(KHandle h, const KActorDesc* desc, const K
 KMANIP_API int kmanip_actor_grad(KHandle h, const KActorDesc* desc, const float* packed_dev, const float* packed_t_dev, const KActorGradIn* in, int n,
                                  float* workspace_dev, const KActorGradDev* out, void* stream);
 
+/* THE LOSS GRADIENTS OF THE bf16 NETWORK: kmanip_actor_grad for the network kmanip_actor_bf16 evaluates, with
+ * bf16 operands in every product (v_mfma_f32_16x16x32_bf16) and float32 accumulation.  Float32 stays the master precision: the
+ * gradients are float32 tensors in the shapes above, KActorGradIn and KActorGradDev are used as they are.  THE DEFINITION (mixed
+ * precision, straight-through: every rounding has derivative 1).  Write v^ for v rounded to bf16, nearest-even, in one rounding.
+ *   forward   kmanip_actor_bf16's, to the bit (the same code on the same packed_bf16 buffer): x^, h1^, h2^ and a float32 mean
+ *   head      kmanip_actor_grad's three heads unchanged on that mean: float64 per row, gmean rounded to float32 once; row_loss, logp
+ *             and status as there.  With PPO and a buffer collected by kmanip_actor_bf16 from the same weights, logp recomputes
+ *             logp_old's mean exactly: the importance ratio starts at 1 up to the rounding of raw
+ *   data      dz3^ = bf16(gmean);  dz2 = (W2^T^ dz3^) act'(h2^), then dz2^;  dz1 = (W1^T^ dz2^) act'(h1^), then dz1^;  float32
+ *             accumulation; act' from the ROUNDED activation widened to float32 (1 - h^2 for tanh, h^ > 0 for relu)
+ *   weights   dW_l = sum_r dz_(l+1)^ h_l^T (h_0 = x^),  db_l = sum_r dz_(l+1)^: bf16 operands, float32 accumulation, float32 partials
+ *             and results;  glog_std_j = sum_r float32(coef_r (u_rj^2 - 1)): float32 terms, summed in float32
+ * bf16 has float32's exponent range: scale = 1 / n needs NO LOSS SCALING (a gradient underflows in bf16 where it would in float32).
+ * The order of every sum is a function of (desc, n) only; no atomics: the same call gives the same bytes.  A row with a bad index has
+ * status 2 and adds exact zeros, as in kmanip_actor_grad.
+ * THE TRANSPOSED BUFFER: W2^T and W1^T rounded to bf16 in kmanip_actor_bf16's layout for the network out_dim -> hidden[1] ->
+ * hidden[0], each followed by a float32 bias block of zeros.  THE WORKSPACE of a call over n rows, np = n rounded up to 32 (at least
+ * 32): x^, h1^, h2^, dz1^, dz2^, dz3^ unit-major [units padded to 16][np] in bf16, the log_std terms [16][np] in float32, then per
+ * K-split the float32 partial tiles and row sums of kmanip_actor_grad; min(64, ceil(np / 256)) splits of a multiple of 32 rows.
+ * Both sizes are 0 for a description kmanip_actor would refuse, the second also for n < 0. */
+KMANIP_API size_t kmanip_actor_grad_bf16_packed_bytes(const KActorDesc* desc);
+KMANIP_API size_t kmanip_actor_grad_bf16_workspace_bytes(const KActorDesc* desc, int n);
+/* W2 and W1 into packed_t_bf16_dev (16-byte aligned): two launches on `stream`; to be repeated with kmanip_actor_bf16_pack after the weights change. */
+KMANIP_API int kmanip_actor_grad_bf16_pack(KHandle h, const KActorDesc* desc, const KActorWeights* weights, void* packed_t_bf16_dev, void* stream);
+/* THREE launches, as kmanip_actor_grad (n == 0: one, writing zeros), with kmanip_actor_grad's ERRORS; packed_bf16_dev is
+ * kmanip_actor_bf16_pack's buffer.  OUT OF SCOPE: fp8, bf16 moments or master weights, the optimiser writing the bf16 buffers. */
+KMANIP_API int kmanip_actor_grad_bf16(KHandle h, const KActorDesc* desc, const void* packed_bf16_dev, const void* packed_t_bf16_dev,
+                                      const KActorGradIn* in, int n, void* workspace_dev, const KActorGradDev* out, void* stream);
+
 /* ADVANTAGES AND RETURNS of a collect() buffer: generalised advantage estimation over T steps of N envs, time-major
  * as the step kernels write reward and done.  A DONE STEP CUTS THE RECURSION: with auto_reset the step kernel resets a done env inside
  * the same step and writes the NEW episode's first observation as obs[t + 1], so value[t + 1] after a done step belongs to another
