@@ -1356,6 +1356,51 @@ int kmanip_actor_adam(KHandle h, const KActorDesc* desc, const KActorAdamIn* in,
   return 0;
 }
 
+// ---- running observation statistics and reward scaling (include/kmanip.h KObsStatsIn, KRewardScaleIn; kmanip_normalize.hip)
+size_t kmanip_obs_stats_workspace_doubles(int n_rows, int dim) {
+  if (dim < 1 || dim > KM_ACTOR_MAX_IN || n_rows < 1) return 0;
+  const size_t rows = kmanip_obs_stats_block_rows(n_rows, dim);
+  return 2 * (size_t)dim * (((size_t)n_rows + rows - 1) / rows);
+}
+
+int kmanip_obs_stats(KHandle h, const KObsStatsIn* in, double* state_dev, double* workspace_dev, double* obs_mean_dev, double* obs_inv_std_dev,
+                     void* stream) {
+  if (!h) { g_create_error = "kmanip_obs_stats: null handle"; return -1; }
+  auto refuse = [&](const char* what) { h->err = std::string("kmanip_obs_stats: ") + what; return -1; };
+  auto odd = [](const void* p) { return ((uintptr_t)p & 7) != 0; };
+  if (!in) return refuse("the KObsStatsIn pointer is NULL");
+  if (in->dim < 1 || in->dim > KM_ACTOR_MAX_IN) return refuse("dim is outside 1 .. KM_ACTOR_MAX_IN");
+  if (in->n_rows < 0) return refuse("n_rows is negative");
+  if (!(in->eps > 0.0) || !std::isfinite(in->eps)) return refuse("eps is not a finite value above 0");
+  if (!state_dev) return refuse("state_dev is NULL");
+  if (in->n_rows > 0 && (!in->obs || !workspace_dev)) return refuse("obs or workspace_dev is NULL with n_rows > 0");
+  if (odd(in->obs) || odd(state_dev) || odd(workspace_dev) || odd(obs_mean_dev) || odd(obs_inv_std_dev)) return refuse("a pointer is not 8-byte aligned");
+  KM_ENTER(h);
+  kmanip_launch_obs_stats(*in, state_dev, workspace_dev, obs_mean_dev, obs_inv_std_dev, (hipStream_t)stream);
+  HIPCHK(h, hipGetLastError());
+  return 0;
+}
+
+size_t kmanip_reward_scale_workspace_doubles(int N) { return N < 1 ? 0 : 4 + 2 * (((size_t)N + KM_GAE_BLOCK - 1) / KM_GAE_BLOCK) + (size_t)N; }
+
+int kmanip_reward_scale(KHandle h, const KRewardScaleIn* in, double* state_dev, double* workspace_dev, double* scaled_dev, double* stats_dev,
+                        void* stream) {
+  if (!h) { g_create_error = "kmanip_reward_scale: null handle"; return -1; }
+  auto refuse = [&](const char* what) { h->err = std::string("kmanip_reward_scale: ") + what; return -1; };
+  auto odd = [](const void* p) { return ((uintptr_t)p & 7) != 0; };
+  if (!in) return refuse("the KRewardScaleIn pointer is NULL");
+  if (!in->reward || !in->done) return refuse("reward or done is NULL");
+  if (!state_dev || !workspace_dev || !scaled_dev) return refuse("state_dev, workspace_dev or scaled_dev is NULL");
+  if (in->T < 1 || in->N < 1) return refuse("T or N is below 1");
+  if (!(in->gamma >= 0.0 && in->gamma <= 1.0)) return refuse("gamma is not in [0, 1]");
+  if (!(in->eps > 0.0) || !std::isfinite(in->eps)) return refuse("eps is not a finite value above 0");
+  if (odd(in->reward) || odd(state_dev) || odd(workspace_dev) || odd(scaled_dev) || odd(stats_dev)) return refuse("a pointer is not 8-byte aligned");
+  KM_ENTER(h);
+  kmanip_launch_reward_scale(*in, state_dev, workspace_dev, scaled_dev, stats_dev, (hipStream_t)stream);
+  HIPCHK(h, hipGetLastError());
+  return 0;
+}
+
 int kmanip_enable_timing(KHandle h, int enable) {
   if (!h) return -1;
   KM_ENTER(h);

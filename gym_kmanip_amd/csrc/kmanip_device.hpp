@@ -734,6 +734,11 @@ void kmanip_launch_actor_grad_reduce(const KActorDesc& d, const KActorGradPlan& 
                                      hipStream_t stream);
 // kmanip_gae (kmanip_gae.hip): k_gae over ceil(N / KM_GAE_BLOCK) blocks, then k_gae_finish where the call normalises or reports stats
 void kmanip_launch_gae(const KGaeIn& in, int T, int N, double* ws, const KGaeDev& out, hipStream_t stream);
+// kmanip_obs_stats / kmanip_reward_scale (kmanip_normalize.hip): k_obs_stats over ceil(n_rows / block_rows) blocks (none for n_rows == 0),
+// then k_obs_stats_finish; k_return_stats over ceil(N / KM_GAE_BLOCK) blocks, then k_reward_scale_finish over ceil(T N / 256)
+size_t kmanip_obs_stats_block_rows(int n_rows, int dim);      // include/kmanip.h's formula; dim in 1 .. KM_ACTOR_MAX_IN, n_rows >= 0
+void kmanip_launch_obs_stats(const KObsStatsIn& in, double* state, double* ws, double* obs_mean, double* obs_inv_std, hipStream_t stream);
+void kmanip_launch_reward_scale(const KRewardScaleIn& in, double* state, double* ws, double* scaled, double* stats, hipStream_t stream);
 // kmanip_actor_adam (kmanip_actor_opt.hip): `p` and `t` lay out the two packed buffers; rkb[l] the REAL K-blocks of layer l (the work
 // items: the padding blocks are never touched); item0[] the first work item of the tiles of layers 0..2, of the three biases [3..5], of
 // log_std [6], and the item count [7]; off[] where the seven tensors begin in each half of the state, `total` that half's floats (and

@@ -20,7 +20,7 @@ _lib = None
 EXPORTS = [
     "kmanip_model_desc_size", "kmanip_create", "kmanip_reset", "kmanip_step", "kmanip_step_chunk", "kmanip_get_state",
     "kmanip_set_state", "kmanip_get_episode", "kmanip_set_episode", "kmanip_get_counters", "kmanip_bind_sim_time", "kmanip_bind_applied_force", "kmanip_bind_reward_done_record", "kmanip_select_reward_done_record", "kmanip_observe", "kmanip_forces", "kmanip_kinematics", "kmanip_inverse", "kmanip_forward", "kmanip_kinematics_rows", "kmanip_site_cost", "kmanip_rollout", "kmanip_feedback", "kmanip_feedback_box", "kmanip_transition_fd", "kmanip_forward_fd", "kmanip_param_fd", "kmanip_lqr_backward", "kmanip_lqr_backward_box", "kmanip_adjoint", "kmanip_tangent", "kmanip_set_seed", "kmanip_get_diag", "kmanip_timing_summary", "kmanip_enable_timing", "kmanip_ik", "kmanip_ik_eval",
-    "kmanip_render_depth", "kmanip_render_rgb", "kmanip_render_rgb_multi", "kmanip_render_labels_multi", "kmanip_render_seg", "kmanip_set_render_links", "kmanip_get_render_links", "kmanip_set_depth_links", "kmanip_get_depth_links", "kmanip_get_camera_poses", "kmanip_render_points", "kmanip_snapshot_render_state", "kmanip_set_render_source", "kmanip_bind_step_depth", "kmanip_scripted_action", "kmanip_sample_action", "kmanip_actor_packed_floats", "kmanip_actor_pack", "kmanip_actor", "kmanip_actor_bf16_packed_bytes", "kmanip_actor_bf16_pack", "kmanip_actor_bf16", "kmanip_actor_grad_packed_floats", "kmanip_actor_grad_workspace_floats", "kmanip_actor_grad_pack", "kmanip_actor_grad", "kmanip_actor_grad_bf16_packed_bytes", "kmanip_actor_grad_bf16_workspace_bytes", "kmanip_actor_grad_bf16_pack", "kmanip_actor_grad_bf16", "kmanip_gae_workspace_doubles", "kmanip_gae", "kmanip_actor_adam_state_floats", "kmanip_actor_adam", "kmanip_set_env_params", "kmanip_get_env_params", "kmanip_set_env_param_ranges", "kmanip_set_visual_params", "kmanip_get_visual_params", "kmanip_set_visual_param_ranges",
+    "kmanip_render_depth", "kmanip_render_rgb", "kmanip_render_rgb_multi", "kmanip_render_labels_multi", "kmanip_render_seg", "kmanip_set_render_links", "kmanip_get_render_links", "kmanip_set_depth_links", "kmanip_get_depth_links", "kmanip_get_camera_poses", "kmanip_render_points", "kmanip_snapshot_render_state", "kmanip_set_render_source", "kmanip_bind_step_depth", "kmanip_scripted_action", "kmanip_sample_action", "kmanip_actor_packed_floats", "kmanip_actor_pack", "kmanip_actor", "kmanip_actor_bf16_packed_bytes", "kmanip_actor_bf16_pack", "kmanip_actor_bf16", "kmanip_actor_grad_packed_floats", "kmanip_actor_grad_workspace_floats", "kmanip_actor_grad_pack", "kmanip_actor_grad", "kmanip_actor_grad_bf16_packed_bytes", "kmanip_actor_grad_bf16_workspace_bytes", "kmanip_actor_grad_bf16_pack", "kmanip_actor_grad_bf16", "kmanip_gae_workspace_doubles", "kmanip_gae", "kmanip_actor_adam_state_floats", "kmanip_actor_adam", "kmanip_obs_stats_workspace_doubles", "kmanip_obs_stats", "kmanip_reward_scale_workspace_doubles", "kmanip_reward_scale", "kmanip_set_env_params", "kmanip_get_env_params", "kmanip_set_env_param_ranges", "kmanip_set_visual_params", "kmanip_get_visual_params", "kmanip_set_visual_param_ranges",
     "kmanip_get_state_dev", "kmanip_set_state_dev", "kmanip_copy_envs", "kmanip_state_index_errors", "kmanip_num_envs", "kmanip_last_error", "kmanip_version", "kmanip_destroy",
 ]
 
@@ -364,6 +364,37 @@ def actor_adam_state_floats(in_dim, hidden, out_dim):
     return 2 * (sum(o * (i + 1) for i, o in zip(dims, dims[1:])) + out_dim)
 
 
+class KObsStatsIn(C.Structure):
+    """include/kmanip.h KObsStatsIn: the DEVICE pointer of n_rows contiguous float64 rows of dim columns, and the eps under the root."""
+    _fields_ = [("obs", C.c_void_p), ("n_rows", C.c_int32), ("dim", C.c_int32), ("eps", C.c_double)]
+
+
+class KRewardScaleIn(C.Structure):
+    """include/kmanip.h KRewardScaleIn: DEVICE pointers of a collect() buffer's reward and done [T, N], the discount and the eps."""
+    _fields_ = [("reward", C.c_void_p), ("done", C.c_void_p), ("T", C.c_int32), ("N", C.c_int32), ("gamma", C.c_double), ("eps", C.c_double)]
+
+
+KM_OBS_STATS_BLOCK, KM_OBS_STATS_UNROLL, KM_OBS_STATS_PASSES, KM_OBS_STATS_MAX_BLOCKS = 256, 4, 64, 1024      # include/kmanip.h
+
+
+def obs_stats_block_rows(n_rows, dim):
+    """include/kmanip.h's block_rows, restated: floor(KM_OBS_STATS_BLOCK / dim) rows a pass, KM_OBS_STATS_PASSES passes, times the least
+    integer that keeps the blocks at KM_OBS_STATS_MAX_BLOCKS or fewer."""
+    q = KM_OBS_STATS_BLOCK // dim * KM_OBS_STATS_PASSES
+    return q * max(1, -(-n_rows // (q * KM_OBS_STATS_MAX_BLOCKS)))
+
+
+def obs_stats_workspace_doubles(n_rows, dim):
+    """include/kmanip.h kmanip_obs_stats_workspace_doubles, restated: 2 dim partial sums per block."""
+    return 0 if not 1 <= dim <= KM_ACTOR_MAX_IN or n_rows < 1 else 2 * dim * -(-n_rows // obs_stats_block_rows(n_rows, dim))
+
+
+def reward_scale_workspace_doubles(n):
+    """include/kmanip.h kmanip_reward_scale_workspace_doubles, restated: the moments and the shift as read, a pair per block of
+    KM_GAE_BLOCK envs, the new carried returns."""
+    return 0 if n < 1 else 4 + 2 * -(-n // KM_GAE_BLOCK) + n
+
+
 KM_TANGENT_MC = 16              # include/kmanip.h: H and g need m <= KM_TANGENT_MC
 KM_WRT = {"qpos": 1, "qvel": 2, "ctrl": 4, "qfrc_applied": 8}     # include/kmanip.h KM_WRT_*: the columns always run in this order
 # include/kmanip.h KM_OF_*: the differentiated outputs of kmanip_forward_fd, always in this order
@@ -478,6 +509,12 @@ def load():
     lib.kmanip_actor_adam_state_floats.argtypes = [C.POINTER(KActorDesc)]
     lib.kmanip_actor_adam_state_floats.restype = C.c_size_t
     lib.kmanip_actor_adam.argtypes = [vp, C.POINTER(KActorDesc), C.POINTER(KActorAdamIn), C.POINTER(KActorParams), vp, vp, vp, vp, vp, vp]
+    lib.kmanip_obs_stats_workspace_doubles.argtypes = [C.c_int, C.c_int]
+    lib.kmanip_obs_stats_workspace_doubles.restype = C.c_size_t
+    lib.kmanip_obs_stats.argtypes = [vp, C.POINTER(KObsStatsIn), vp, vp, vp, vp, vp]
+    lib.kmanip_reward_scale_workspace_doubles.argtypes = [C.c_int]
+    lib.kmanip_reward_scale_workspace_doubles.restype = C.c_size_t
+    lib.kmanip_reward_scale.argtypes = [vp, C.POINTER(KRewardScaleIn), vp, vp, vp, vp, vp]
     lib.kmanip_set_env_params.argtypes = [vp, vp, vp]
     lib.kmanip_get_env_params.argtypes = [vp, vp, vp]
     lib.kmanip_set_env_param_ranges.argtypes = [vp, f64p, f64p]

@@ -1400,6 +1400,73 @@ KMANIP_API size_t kmanip_actor_adam_state_floats(const KActorDesc* desc);
 KMANIP_API int kmanip_actor_adam(KHandle h, const KActorDesc* desc, const KActorAdamIn* in, const KActorParams* params, float* state_dev,
                                  float* packed_dev, float* packed_t_dev, double* workspace_dev, double* gnorm_dev, void* stream);
 
+/* RUNNING OBSERVATION STATISTICS: the column moments of a block of rows, folded into a running state, and from
+ * it the two vectors KActorIn / KActorGradIn take as obs_mean / obs_inv_std.  THE STATE: double[1 + 2 dim] = count n, mean[dim],
+ * M2[dim] (the sum of squared distances from the mean); all zeros is the empty state.  Per column, in float64, no fused multiply-add,
+ * with R = n_rows and (na, ma, M2a) the state before the call:
+ *   c    = na > 0 ? ma : x[0]                       the shift: the state's mean, for an empty state row 0 of the batch
+ *   s1   = sum (x - c);   s2 = sum (x - c) (x - c)   in a fixed order, below
+ *   mb   = c + s1 / R;    M2b = max(s2 - (s1 s1) / R, 0)
+ *   na == 0:  n = R, mean = mb, M2 = M2b            an empty state takes the batch's moments as they are
+ *   else      n = na + R;  delta = mb - ma;  mean = ma + (delta R) / n;  M2 = (M2a + M2b) + (((delta delta) na) R) / n      (Chan's merge)
+ *   obs_mean = mean;   obs_inv_std = 1 / sqrt(M2 / n + eps)
+ * n_rows == 0 leaves the state unchanged and still writes the two vectors from it: for an EMPTY state mean 0 and inv_std 1 (what a
+ * network without normalisation computes), not 1 / sqrt(eps).
+ * THE ORDER.  A block of KM_OBS_STATS_BLOCK lanes reads p = floor(KM_OBS_STATS_BLOCK / dim) whole rows a pass: lane t < p dim owns column
+ * t % dim and row offset t / dim and adds its rows in ascending order.  Block b owns the block_rows rows from
+ * b block_rows on: p KM_OBS_STATS_PASSES rows, times the least integer that keeps the blocks at KM_OBS_STATS_MAX_BLOCKS or fewer (the
+ * formula stands with the workspace size below).  A column's lanes are added in ascending row offset, then the blocks in ascending order.  No atomics: the same call on the
+ * same state gives the same bytes. */
+typedef struct KObsStatsIn {
+  const double* obs;               /* DEVICE [n_rows, dim], rows contiguous; may be NULL when n_rows == 0 */
+  int32_t n_rows, dim;             /* n_rows >= 0; dim in 1 .. KM_ACTOR_MAX_IN */
+  double eps;                      /* > 0, finite */
+} KObsStatsIn;
+#define KM_OBS_STATS_BLOCK 256
+#define KM_OBS_STATS_UNROLL 4       /* the passes whose loads are in flight before their dependent adds */
+#define KM_OBS_STATS_PASSES 64      /* the passes of a block (a multiple of the unroll) */
+#define KM_OBS_STATS_MAX_BLOCKS 1024
+/* With p = floor(KM_OBS_STATS_BLOCK / dim) and q = p KM_OBS_STATS_PASSES:
+ *   block_rows = q max(1, ceil(n_rows / (q KM_OBS_STATS_MAX_BLOCKS)));   blocks = ceil(n_rows / block_rows)
+ * The doubles of the workspace: 2 dim partial sums per block, block-major (s1[dim], then s2[dim]).  0 for dim outside 1 ..
+ * KM_ACTOR_MAX_IN or n_rows < 0; n_rows == 0 needs no workspace. */
+KMANIP_API size_t kmanip_obs_stats_workspace_doubles(int n_rows, int dim);
+/* TWO launches (the blocks' partial sums; their sum, the merge and the vectors), ONE when n_rows == 0, asynchronous on `stream`: no
+ * allocation, no synchronisation.  The handle is not read beyond its error slot.  obs_mean_dev / obs_inv_std_dev: [dim], either NULL.
+ * ERRORS: a NULL handle or `in`; dim outside 1 .. KM_ACTOR_MAX_IN; n_rows < 0; eps not finite or not > 0; a NULL state_dev; with n_rows
+ * > 0 a NULL obs or workspace_dev; any pointer given that is not 8-byte aligned return nonzero with kmanip_last_error set and launch
+ * nothing.
+ * OUT OF SCOPE: clipping the normalised observation, updates inside collect(), the terminal observation under auto_reset. */
+KMANIP_API int kmanip_obs_stats(KHandle h, const KObsStatsIn* in, double* state_dev, double* workspace_dev, double* obs_mean_dev,
+                                double* obs_inv_std_dev, void* stream);
+
+/* REWARD SCALING by the running standard deviation of the discounted return.  THE STATE: double[3 + N] = count n,
+ * mean, M2 of every return seen so far, then each env's carried return; all zeros is the empty state.  Per env e, in float64, no fused
+ * multiply-add, G starting at the carried return, for t = 0 .. T-1:
+ *   G = gamma G + reward[t][e];   fold G into the batch's sums s1 = sum (G - c), s2 = sum (G - c)(G - c);   done[t][e] != 0: G = 0 after the fold
+ * with the common shift c = na > 0 ? ma : gamma carried[0] + reward[0][0] (for an empty state the first return of env 0).  The batch of
+ * R = T N returns merges into the state exactly as in kmanip_obs_stats; then, with the NEW moments,
+ *   scaled[t][e] = reward[t][e] / sqrt(M2 / n + eps)          (the mean is not subtracted);   stats = { mean, sqrt(M2 / n) }
+ * and the carried returns are written back.  THE ORDER: one lane per env adds its returns forward in time; the lanes of a block of
+ * KM_GAE_BLOCK envs and then the blocks are added as kmanip_gae adds its pairs.  No atomics: the same call on the same state gives the
+ * same bytes. */
+typedef struct KRewardScaleIn {    /* DEVICE pointers, time-major as collect() writes them */
+  const double*  reward;           /* [T, N] */
+  const uint8_t* done;             /* [T, N], any nonzero byte ends the return */
+  int32_t T, N;                    /* each >= 1 */
+  double gamma, eps;               /* gamma in [0, 1]; eps > 0, finite */
+} KRewardScaleIn;
+/* The doubles of the workspace: the state's moments and the shift as the first launch read them (4), a pair of partial sums per block
+ * of KM_GAE_BLOCK envs, then the N new carried returns.  0 for N < 1. */
+KMANIP_API size_t kmanip_reward_scale_workspace_doubles(int N);
+/* TWO launches (the returns and the blocks' partial sums; their sum, the merge, the state and the scaling), asynchronous on `stream`:
+ * no allocation, no synchronisation.  scaled_dev: [T, N], it may alias nothing.  stats_dev: [2] or NULL.
+ * ERRORS: a NULL handle, `in`, reward, done, state_dev, workspace_dev or scaled_dev; T < 1 or N < 1; gamma outside [0, 1]; eps not
+ * finite or not > 0; a double pointer that is not 8-byte aligned return nonzero with kmanip_last_error set and launch nothing.
+ * OUT OF SCOPE: clipping the scaled reward, subtracting the mean, per-step updates inside collect(). */
+KMANIP_API int kmanip_reward_scale(KHandle h, const KRewardScaleIn* in, double* state_dev, double* workspace_dev, double* scaled_dev,
+                                   double* stats_dev, void* stream);
+
 /* Per-env physics parameters (domain randomisation).  Storage is double[KM_EP_N][num_envs], struct-of-arrays
  * like the state: element (k, env) at k * num_envs + env.  Env e with parameters p behaves exactly like a handle whose KModelDesc is
  * the compiled one with these fields and their derived constants replaced (gym_kmanip_amd/model.py with_env_params):
